@@ -1,9 +1,9 @@
 #!/usr/bin/env python
 """Benchmark of the MI355X LoRa demod hot path: Msymbols/s demodulated (dechirp + FFT + argmax), per SF.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-        --master-port P bench.py --gpus N --steps K --warmup W
+        --master-port P bench.py --gpus N --steps K --warmup W [--full]
 
 A "step" is one pass of the hot path (one lorahip_detect_batch launch) over one batch of synthetic IQ already resident
 in HBM: `channels` channels x `symbols` symbol windows of 2^SF cf32 samples. The headline workload (value / config /
@@ -11,6 +11,12 @@ roofline) is BASELINE.json configs[1]: 4096 channels SF7 (N=128 FFT) x 256 windo
 With N > 1 every rank demodulates its own channels (independent units, no data-path collective): weak scaling; every
 value is the whole-job aggregate. The CPU legs (cpu_baseline, the oracle checks) run on rank 0, on its own shard, after the timed
 regions, while the other ranks wait at a host-side (gloo) barrier; every rank also holds a sample of its shard to the oracle.
+
+A plain run does only what the headline figure needs: it sets up, warms up, times exactly K steps and prints the line (the contract
+keys, config, and the roofline of the K timed launches). Everything else -- the symbol error rate against the sent symbols, the CPU
+baseline, the oracle checks, the PCIe-inclusive rates and the per-SF / BASELINE-config sections listed below -- runs with --full.
+--dump-outputs DIR writes what the last timed step computed (sym, power, powerAvg, fIndex: the arrays a caller of the detect path
+receives) as DIR/<name>.npy in float32; the inputs are seeded, so two builds can be compared output for output.
 
 Rank 0 prints ONE JSON line -- the COMPACT form of the result (compact_line: under LINE_LIMIT = 8000 bytes; round 5's 20.8 KB line was lost by the
 driver's reader): the contract keys, roofline, cpu_baseline and oracle as they are, one short row per SF of every sweep (level3 by columns). The FULL
@@ -72,6 +78,11 @@ def parse():
                     help="A/B: read the fine-tune table in HBM (round-1 path) instead of the split tables (lorahip_set_fine_gather)")
     ap.add_argument("--traffic", type=float, default=None,
                     help="HBM bytes per launch from a separate rocprofv3 --pmc pass (profiles/), if known")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: symbol error rate, CPU baseline, oracle checks, PCIe-inclusive rates and (default shape) "
+                         "the per-SF / BASELINE-config sections")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs to DIR/<name>.npy (float32)")
     return ap.parse_args()
 
 
@@ -402,6 +413,29 @@ class Shape:
 
     def close(self):
         self.ctx.close()
+
+
+DUMP_MAX_WINDOWS = 1 << 21      # 4 float32 arrays of 8 MiB and the float64 index of a sample: 48 MiB, under the 64 MB a dump may take
+
+
+def dump_outputs(path, out, rank):
+    """The outputs of the last timed step, as a caller of the detect path receives them, to path/<name>.npy in float32 (sym: the bin,
+    exact). A batch of more than DUMP_MAX_WINDOWS windows is written at a fixed seeded sample of windows, listed in window_index.npy.
+    Ranks after the first write their own shard's outputs as <name>_rank<r>.npy."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    W = out["sym"].numel()
+    sfx = "" if rank == 0 else "_rank%d" % rank
+    idx = None
+    if W > DUMP_MAX_WINDOWS:
+        idx = np.sort(np.random.default_rng(0).choice(W, DUMP_MAX_WINDOWS, replace=False))
+        np.save(os.path.join(path, "window_index%s.npy" % sfx), idx.astype(np.float64))
+        idx = torch.from_numpy(idx).to(out["sym"].device)
+    for name, v in out.items():
+        if name == "sym":
+            v = v.to(torch.int32) & 0xffff
+        v = v.reshape(-1) if idx is None else v.reshape(-1)[idx]
+        np.save(os.path.join(path, "%s%s.npy" % (name, sfx)), v.to(torch.float32).cpu().numpy())
 
 
 def host_cpu_info():
@@ -1237,13 +1271,18 @@ def respawn_under_torchrun(a):
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stderr.write("bench.py: --gpus %d without WORLD_SIZE: re-launching as %s\n" % (a.gpus, " ".join(cmd)))
     sys.stderr.flush()
-    os.execv(sys.executable, cmd)
+    import subprocess
+    raise SystemExit(subprocess.call(cmd))           # a child process, its exit status ours
 
 
 def main():
     a = parse()
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs and a.config == "mixed":
+        raise SystemExit("--dump-outputs writes the outputs of the batch path; --config mixed does not take it")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         respawn_under_torchrun(a)                       # does not return
     env = Env(a)
@@ -1276,9 +1315,8 @@ def main():
     if a.fine_gather:
         sh.ctx.set_fine_gather(True)
     elapsed, kernel_ms = sh.measure(a.steps, a.warmup, a.ramp_seconds, moving=a.moving, alias=a.alias_windows)
-    ser, off = sh.ser_vs_sent(sh.out_moving if a.moving else None) if not a.alias_windows else (None, None)
-    if ser is not None:
-        (ser,) = env.max_over_ranks(ser)                # every rank's recovered symbols against the ones it sent: the worst rank
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, sh.out_moving if a.moving else sh.out, env.rank)
     line = None
     threads = min(os.cpu_count() or 1, 64)
     if rank0:
@@ -1292,12 +1330,19 @@ def main():
                        "noise_sigma": a.noise_sigma, "parallelism": "channels sharded, %d rank(s), no data-path collective" % env.world,
                        "kernel_variant": a.variant, "alias_windows": bool(a.alias_windows), "moving_fine_index": bool(a.moving),
                        "fine_gather": bool(a.fine_gather), "ramp_seconds": a.ramp_seconds},
-            "symbol_error_rate_vs_sent": ser, "bin_offset": off,
             "roofline": roofline_obj(sf0, sh.W, launch_s, None if (a.moving or a.alias_windows) else traffic_for(sf0, a), L,
                                      shape="moving" if a.moving else "steady", default_geometry=a.channels is None and a.symbols is None and not a.alias_windows),
         }
         if env.rccl_ranks is not None:
             line["rccl_ranks"] = env.rccl_ranks
+    if not a.full:
+        emit(env, line)
+        return
+    ser, off = sh.ser_vs_sent(sh.out_moving if a.moving else None) if not a.alias_windows else (None, None)
+    if ser is not None:
+        (ser,) = env.max_over_ranks(ser)                # every rank's recovered symbols against the ones it sent: the worst rank
+    if rank0:
+        line["symbol_error_rate_vs_sent"], line["bin_offset"] = ser, off
     # (rank 0's CPU legs: with several ranks the others are waiting at the host barrier below, which must be reached whatever happens here --
     # an exception is recorded in the line in place of the object, and one rank fails loudly at the end instead of all hanging)
     cpu_leg_error = None

@@ -2,7 +2,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
 for rep in 1 2 3 4 5; do
   for lib in cur m10a m10c; do
     path=$R/lora_sdr_amd/liblorahip_$lib.so; [[ $lib == cur ]] && path=$R/lora_sdr_amd/liblorahip.so
-    LORAHIP_LIB=$path timeout 200 python bench.py --sf 10 --no-cpu-baseline --moving 2>/dev/null | python -c "
+    LORAHIP_LIB=$path timeout 200 python bench.py --full --sf 10 --no-cpu-baseline --moving 2>/dev/null | python -c "
 import json, sys
 for line in sys.stdin:
     if line.startswith('{'):

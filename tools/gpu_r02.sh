@@ -33,7 +33,7 @@ fi
 if [[ $what == *l2* ]]; then
   # L1/L2/SQ counters of the locked-receiver batch shape (bench.py --moving) and of the streaming demodulator
   for sf in ${L2SF:-7 10 12}; do
-    timeout 200 python bench.py --sf $sf --no-cpu-baseline --moving > $O/${TAG}_moving_sf$sf.json 2> $O/${TAG}_moving_sf$sf.err
+    timeout 200 python bench.py --full --sf $sf --no-cpu-baseline --moving > $O/${TAG}_moving_sf$sf.json 2> $O/${TAG}_moving_sf$sf.err
     pmc_run ${TAG}_l2_mov_sf$sf python $R/bench.py --sf $sf --moving --steps 3 --warmup 1 --ramp-seconds 0 --no-cpu-baseline
     python tools/pmc_kernels.py "$O/${TAG}_l2_mov_sf${sf}_set*" detect "bench.py --sf $sf --moving" | tee $O/${TAG}_l2_mov_sf$sf.txt
     case $sf in 7) CH=16384;; 8|9) CH=8192;; 10) CH=4096;; *) CH=1024;; esac
@@ -64,9 +64,9 @@ EOP
 if [[ $what == *after* ]]; then
   # the locked-receiver shape with the split tables (default) and with the round-1 table gather (A/B), then the L1/L2 counters
   for sf in ${L2SF:-7 10 12}; do
-    timeout 200 python bench.py --sf $sf --no-cpu-baseline --moving > $O/${TAG}_moving_sf$sf.json 2> $O/${TAG}_moving_sf$sf.err
+    timeout 200 python bench.py --full --sf $sf --no-cpu-baseline --moving > $O/${TAG}_moving_sf$sf.json 2> $O/${TAG}_moving_sf$sf.err
     line $O/${TAG}_moving_sf$sf.json "SF$sf moving, split tables"
-    timeout 200 python bench.py --sf $sf --no-cpu-baseline --moving --fine-gather > $O/${TAG}_moving_gather_sf$sf.json 2> $O/${TAG}_moving_gather_sf$sf.err
+    timeout 200 python bench.py --full --sf $sf --no-cpu-baseline --moving --fine-gather > $O/${TAG}_moving_gather_sf$sf.json 2> $O/${TAG}_moving_gather_sf$sf.err
     line $O/${TAG}_moving_gather_sf$sf.json "SF$sf moving, table gather"
   done
   for sf in ${PMCSF:-7 10}; do
@@ -86,7 +86,7 @@ if [[ $what == *movvar* ]]; then
   # A/B of option sets on the locked-receiver shape (needs a library built with --all-variants)
   for spec in ${MOVVARS:-7:0 7:3 7:5 7:10 10:0 10:16 10:10 12:0 12:2 12:10}; do
     sf=${spec%%:*}; v=${spec##*:}
-    timeout 200 python bench.py --sf $sf --no-cpu-baseline --moving --variant $v > $O/${TAG}_movvar_sf${sf}_v$v.json 2> $O/${TAG}_movvar_sf${sf}_v$v.err
+    timeout 200 python bench.py --full --sf $sf --no-cpu-baseline --moving --variant $v > $O/${TAG}_movvar_sf${sf}_v$v.json 2> $O/${TAG}_movvar_sf${sf}_v$v.err
     line $O/${TAG}_movvar_sf${sf}_v$v.json "SF$sf moving variant $v"
   done
 fi
@@ -126,6 +126,6 @@ if [[ $what == *final* ]]; then
 fi
 
 if [[ $what == *bench* ]]; then
-  timeout 900 python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+  timeout 900 python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
   echo "bench exit $?"; tail -c 3000 $O/${TAG}_bench.json; tail -5 $O/${TAG}_bench.err
 fi

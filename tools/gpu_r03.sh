@@ -12,7 +12,7 @@ if [[ $what == *loopback* ]]; then
   timeout 600 python tools/loopback_probe.py 21 22 27 28 > $O/loopback_probe.txt 2>&1; tail -20 $O/loopback_probe.txt
 fi
 if [[ $what == *bench* ]]; then
-  timeout 1500 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench exit $?"; tail -c 6000 $O/bench_default.json; tail -25 $O/bench_default.err
+  timeout 1500 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench exit $?"; tail -c 6000 $O/bench_default.json; tail -25 $O/bench_default.err
 fi
 if [[ $what == *quicktests* ]]; then
   timeout 900 python -m pytest tests/test_gpu_demod.py tests/test_gpu_dropin.py tests/test_gpu_codec.py tests/test_gpu_bench.py -m gpu -x -q > $O/pytest_quick.log 2>&1; echo "pytest exit $?" >> $O/pytest_quick.log; tail -4 $O/pytest_quick.log
@@ -48,7 +48,7 @@ if [[ $what == *geo64* ]]; then
   # the two-phase geometries of 64 points per lane (variants 40 / 41 of an --all-variants build) against the defaults
   for sf in 10 11 12; do
     for v in 0 25 26; do
-      LORAHIP_LIB=$R/lora_sdr_amd/liblorahip_AV.so timeout 200 python bench.py --sf $sf --variant $v --no-cpu-baseline > $O/geo64_sf${sf}_v$v.json 2> $O/geo64_sf${sf}_v$v.err
+      LORAHIP_LIB=$R/lora_sdr_amd/liblorahip_AV.so timeout 200 python bench.py --full --sf $sf --variant $v --no-cpu-baseline > $O/geo64_sf${sf}_v$v.json 2> $O/geo64_sf${sf}_v$v.err
       python - <<EOF2 | tee -a $O/geo64.txt
 import json
 try:

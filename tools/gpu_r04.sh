@@ -46,7 +46,7 @@ EOP
   done
 fi
 if [[ $what == *bench* ]]; then
-  timeout 600 python bench.py > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err; tail -c 600 $O/${TAG}_bench_default.err
+  timeout 600 python bench.py --full > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err; tail -c 600 $O/${TAG}_bench_default.err
   python tools/bench_digest.py $O/${TAG}_bench_default.json
 fi
 if [[ $what == *smoke* ]]; then

@@ -9,7 +9,7 @@ if [[ $what == *tests* ]]; then
 fi
 if [[ $what == *tworank* ]]; then
   # the --gpus 2 code path on one device over gloo: the line must carry cpu_baseline + oracle like the N = 1 line
-  LORA_BENCH_BACKEND=gloo LORA_BENCH_ONE_DEVICE=1 timeout 900 python bench.py --gpus 2 ${TWORANK_ARGS:-} > $O/${TAG}_bench_two_ranks_one_device_gloo.json 2> $O/${TAG}_bench_two_ranks.err
+  LORA_BENCH_BACKEND=gloo LORA_BENCH_ONE_DEVICE=1 timeout 900 python bench.py --full --gpus 2 ${TWORANK_ARGS:-} > $O/${TAG}_bench_two_ranks_one_device_gloo.json 2> $O/${TAG}_bench_two_ranks.err
   tail -c 400 $O/${TAG}_bench_two_ranks.err
   python tools/bench_digest.py $O/${TAG}_bench_two_ranks_one_device_gloo.json
 fi
@@ -24,7 +24,7 @@ if [[ $what == *scaling* ]]; then
 fi
 if [[ $what == *moving* ]]; then
   for sf in ${MVSFS:-7 8 9 10 11 12}; do
-    timeout 200 python bench.py --sf $sf --no-cpu-baseline --moving > $O/${TAG}_moving_sf$sf.json 2> $O/${TAG}_moving_sf$sf.err
+    timeout 200 python bench.py --full --sf $sf --no-cpu-baseline --moving > $O/${TAG}_moving_sf$sf.json 2> $O/${TAG}_moving_sf$sf.err
     python - $O/${TAG}_moving_sf$sf.json $sf <<'EOP'
 import json, sys
 try:
@@ -49,7 +49,7 @@ EOP
   done
 fi
 if [[ $what == *bench* ]]; then
-  timeout 700 python bench.py > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err; tail -c 600 $O/${TAG}_bench_default.err
+  timeout 700 python bench.py --full > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err; tail -c 600 $O/${TAG}_bench_default.err
   python tools/bench_digest.py $O/${TAG}_bench_default.json
 fi
 if [[ $what == *smoke* ]]; then

@@ -9,7 +9,7 @@ if [[ $what == *tests* ]]; then
 fi
 if [[ $what == *tworank* ]]; then
   # the --gpus 2 code path on one device over gloo: the line must carry cpu_baseline + oracle like the N = 1 line
-  LORA_BENCH_BACKEND=gloo LORA_BENCH_ONE_DEVICE=1 timeout 900 python bench.py --gpus 2 ${TWORANK_ARGS:-} > $O/${TAG}_bench_two_ranks_one_device_gloo.json 2> $O/${TAG}_bench_two_ranks.err
+  LORA_BENCH_BACKEND=gloo LORA_BENCH_ONE_DEVICE=1 timeout 900 python bench.py --full --gpus 2 ${TWORANK_ARGS:-} > $O/${TAG}_bench_two_ranks_one_device_gloo.json 2> $O/${TAG}_bench_two_ranks.err
   tail -c 400 $O/${TAG}_bench_two_ranks.err
   python tools/bench_digest.py $O/${TAG}_bench_two_ranks_one_device_gloo.json
 fi
@@ -17,7 +17,7 @@ if [[ $what == *eightrank* ]]; then
   # the --gpus 8 code path (what the driver's SCALE run launches) on the ONE device of this box over gloo: a code-path check -- the line's
   # size, its keys and the wall time (rank 0 runs every CPU leg; the driver's limit is 1800 s) -- not a scaling measurement
   t0=$(date +%s)
-  LORA_BENCH_BACKEND=gloo LORA_BENCH_ONE_DEVICE=1 timeout 1500 python bench.py --gpus 8 --steps 20 --warmup 5 > $O/${TAG}_bench_eight_ranks_one_device_gloo.json 2> $O/${TAG}_bench_eight_ranks.err
+  LORA_BENCH_BACKEND=gloo LORA_BENCH_ONE_DEVICE=1 timeout 1500 python bench.py --full --gpus 8 --steps 20 --warmup 5 > $O/${TAG}_bench_eight_ranks_one_device_gloo.json 2> $O/${TAG}_bench_eight_ranks.err
   echo "eight ranks on one device: rc $? wall $(( $(date +%s) - t0 )) s" | tee $O/${TAG}_bench_eight_ranks_wall.txt
   tail -c 300 $O/${TAG}_bench_eight_ranks.err
   python tools/bench_digest.py $O/${TAG}_bench_eight_ranks_one_device_gloo.json | head -30
@@ -33,7 +33,7 @@ if [[ $what == *scaling* ]]; then
 fi
 if [[ $what == *moving* ]]; then
   for sf in ${MVSFS:-7 8 9 10 11 12}; do
-    timeout 200 python bench.py --sf $sf --no-cpu-baseline --moving > $O/${TAG}_moving_sf$sf.json 2> $O/${TAG}_moving_sf$sf.err
+    timeout 200 python bench.py --full --sf $sf --no-cpu-baseline --moving > $O/${TAG}_moving_sf$sf.json 2> $O/${TAG}_moving_sf$sf.err
     python - $O/${TAG}_moving_sf$sf.json $sf <<'EOP'
 import json, sys
 try:
@@ -58,7 +58,7 @@ EOP
   done
 fi
 if [[ $what == *bench* ]]; then
-  timeout 700 python bench.py > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err; tail -c 600 $O/${TAG}_bench_default.err
+  timeout 700 python bench.py --full > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err; tail -c 600 $O/${TAG}_bench_default.err
   python tools/bench_digest.py $O/${TAG}_bench_default.json
 fi
 if [[ $what == *smoke* ]]; then
@@ -133,7 +133,7 @@ if [[ $what == *abfine* ]]; then
     for sf in ${ABSF:-10 11 12}; do
       for lib in ${ABLIBS:-cur pow2 skew}; do
         path=$R/lora_sdr_amd/liblorahip_$lib.so; [[ $lib == cur ]] && path=$R/lora_sdr_amd/liblorahip.so
-        LORAHIP_LIB=$path timeout 200 python bench.py --sf $sf --no-cpu-baseline --moving 2>/dev/null | python -c "
+        LORAHIP_LIB=$path timeout 200 python bench.py --full --sf $sf --no-cpu-baseline --moving 2>/dev/null | python -c "
 import json, sys
 for line in sys.stdin:
     if line.startswith('{'):

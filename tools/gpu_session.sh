@@ -17,10 +17,10 @@ if [[ $what == *tests* ]]; then
 fi
 
 if [[ $what == *bench* ]]; then
-  timeout 600 python bench.py > $O/bench_sf7.json 2> $O/bench_sf7.err
+  timeout 600 python bench.py --full > $O/bench_sf7.json 2> $O/bench_sf7.err
   tail -c 2500 $O/bench_sf7.json
   for sf in 8 9 10 11 12; do
-    timeout 300 python bench.py --sf $sf --cpu-seconds 3 > $O/bench_sf$sf.json 2> $O/bench_sf$sf.err
+    timeout 300 python bench.py --full --sf $sf --cpu-seconds 3 > $O/bench_sf$sf.json 2> $O/bench_sf$sf.err
     python - <<EOF
 import json
 try:
@@ -60,7 +60,7 @@ fi
 if [[ $what == *variants* ]]; then
   for sf in ${VSF:-11 12}; do
     for v in ${VARS:-0 2 3 4 5}; do
-      timeout 200 python bench.py --sf $sf --variant $v --no-cpu-baseline > $O/var_sf${sf}_v$v.json 2> $O/var_sf${sf}_v$v.err
+      timeout 200 python bench.py --full --sf $sf --variant $v --no-cpu-baseline > $O/var_sf${sf}_v$v.json 2> $O/var_sf${sf}_v$v.err
       python - <<EOF2
 import json
 try:
@@ -121,7 +121,7 @@ fi
 
 if [[ $what == *quick* ]]; then
   for sf in ${QSF:-7 8 9 10 11 12}; do
-    timeout 200 python bench.py --sf $sf --no-cpu-baseline > $O/q_sf$sf.json 2> $O/q_sf$sf.err
+    timeout 200 python bench.py --full --sf $sf --no-cpu-baseline > $O/q_sf$sf.json 2> $O/q_sf$sf.err
     python - <<EOF2
 import json
 try:
@@ -152,7 +152,7 @@ fi
 if [[ $what == *multi* ]]; then
   # the N > 1 path of bench.py on the one GPU that is here: 2 ranks over gloo, both on device 0 (halved batch so both fit)
   LORA_BENCH_BACKEND=gloo LORA_BENCH_ONE_DEVICE=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 \
-      bench.py --gpus 2 --steps 100 --warmup 10 --channels 2048 > $O/multi2.json 2> $O/multi2.err
+      bench.py --full --gpus 2 --steps 100 --warmup 10 --channels 2048 > $O/multi2.json 2> $O/multi2.err
   tail -c 1200 $O/multi2.json; tail -3 $O/multi2.err
 fi
 

@@ -8,7 +8,7 @@ vars() { case $1 in 7) echo "0 4 15 17 3";; 8) echo "0 15 17 30";; 9) echo "0 11
 for sf in ${SFS:-7 8 9 10 11 12}; do
   for v in $(vars $sf); do
     for shape in "" ${MOVING:+--moving}; do
-      timeout 120 python bench.py --sf $sf --variant $v --no-cpu-baseline $shape > $O/retune.json 2> $O/retune.err
+      timeout 120 python bench.py --full --sf $sf --variant $v --no-cpu-baseline $shape > $O/retune.json 2> $O/retune.err
       python - $sf $v "$shape" <<'EOP'
 import json, sys
 try:
