@@ -62,8 +62,97 @@ struct Signal
     float power, snr;
 };
 
+static size_t align256(const size_t x) { return (x + 255) & ~size_t(255); }
+
+//! where the pieces of one streaming launch live inside dm->sDev (device) / dm->sHost (host mirror of the head)
+struct StreamLayout
+{
+    size_t B, cap, capPkt, symStride;
+    bool tracing, signals;
+    size_t oBase, oLen, oState, oN, oNSym, oNPkt, oNSig, oNear, oSum, oEnd, oPkt, oSym, oSig, oCalls, total;
+    void make(const size_t B_, const size_t cap_, const size_t capPkt_, const bool tracing_, const size_t carryCap_ = 0, const bool signals_ = false)
+    {
+        B = B_; cap = cap_; capPkt = capPkt_; tracing = tracing_; signals = signals_;
+        symStride = cap_ + carryCap_;                    // a channel's symbol row: what the launch may add behind what it was handed
+        size_t cur = 0;
+        auto carve = [&cur](const size_t bytes) { const size_t o = cur; cur += align256(bytes); return o; };
+        oBase = carve(B * sizeof(long long)); oLen = carve(B * sizeof(long long));
+        oState = carve(B * sizeof(StreamState));
+        oN = carve(B * sizeof(int)); oNSym = carve(B * sizeof(int)); oNPkt = carve(B * sizeof(int)); oNSig = carve(B * sizeof(int));
+        oNear = carve(2 * sizeof(unsigned));
+        oSum = carve(sizeof(StreamSummary));
+        oEnd = carve(B * sizeof(int2));
+        oPkt = carve(B * capPkt * sizeof(StreamPacket));
+        oSym = carve(B * symStride * sizeof(short));
+        oSig = carve(signals ? B * capPkt * sizeof(StreamSignal) : 0);
+        oCalls = carve(tracing ? B * cap * sizeof(lorahip_work_result) : 0);
+        total = cur;
+    }
+};
+
+//! The records of the LAST streaming launch of a run stay on the device until somebody needs them on the host: a receive chain
+//! that hands the packets to the batched decoder (lorahip_demod_packets_to_device) never does, and then nothing but the
+//! per-channel state and counts (52 B per channel) crosses PCIe per run.
+struct PendingLaunch
+{
+    bool valid;
+    StreamLayout lay;
+    size_t firstNewPacket;          // index in dm->packets of the first packet of the run this launch belongs to
+    int64_t rounds;
+    size_t packets, packetSyms;     // what draining will append
+    size_t signals;
+    bool anyCarryIn, anyOpen;       // a channel entered the launch inside a packet / leaves it inside one
+    double drainMs;                 // LORAHIP_DEMOD_TIMING
+};
+
+//! the PIPELINED receiver (lorahip_demod_receive, async = 2; see pipeStep): two record sets, their summaries and events
+struct Pipe
+{
+    bool active;                    // steps are in flight: only receive / flush may touch the object
+    unsigned k;                     // steps launched since the pipeline was entered
+    char *dev[2]; size_t bytes[2];  // record sets (a StreamLayout each; the state and the carry rows are the object's own)
+    StreamLayout lay[2];
+    StreamSummary *hSum;            // [2] pinned and mapped: the summary kernel writes here directly (no copy to enqueue)
+    hipEvent_t ev[2];
+    bool pending[2];                // the set's kernel has been launched, its summary not read yet
+    bool held[2];                   // the set's summary has been read, its packets are still in the set (rows too small: nothing is lost)
+    size_t nPk[2]; int64_t nCalls[2];   // ... what that summary said
+    size_t nSig[2]; bool sigs[2];       // ... and the signals kept in the set (the step ran with lorahip_demod_set_signals on)
+    hipStream_t side;               // step k's packets are packed HERE while step k + 1's kernel runs on the launch stream
+    hipEvent_t packDone;            // ... which waits for this before anything later (the next kernel reuses the record set, the caller reads the rows)
+    hipEvent_t entry;               // ... and the side stream for this: where the launch stream stood when the call began (the caller's
+                                    // consumer of the rows handed out by the call before, earlier packing on the launch stream)
+};
+
+//! the RESIDENT receiver (lorahip_demod_receive, async = 3): one launch across the steps, lorahip_streamkernel.h (RES)
+struct Resident
+{
+    bool active;                    // the kernel is on the device: only receive (async = 3) / flush may touch the object
+    bool unavailable;               // tried and refused for this object (no instance, the grid not resident at once, a step timed out)
+    unsigned seq;                   // steps rung
+    unsigned reported;              // steps whose report the caller has had
+    ResidentCtl *ctl;               // device: the mirror of the ring, the steps' counters
+    ResidentHost *host;             // pinned and mapped: the ring the host writes, the steps' reports, the abort flag
+    char *rec; size_t recBytes;     // the channels' records of a step (a StreamLayout; the state and the carry rows are the object's own)
+    StreamLayout lay;
+    hipStream_t run;                // the kernel's stream
+    hipEvent_t ev;
+    unsigned grid;
+    size_t lastValid;
+    bool lastMore;                  // the last reported step left a channel with samples it could not record
+    bool sigs;                      // the launch keeps signal records
+    bool tail;                      // the last step left fewer than 16 valid samples per row untouched (the flush's ordinary step takes them)
+    unsigned nRep; size_t repPk[RES_DEPTH_MAX + 1], repSg[RES_DEPTH_MAX + 1];   // the steps the last call reported, oldest first (lorahip_demod_receive_steps)
+    unsigned depth;                 // steps the caller lets the receiver run ahead of the last report (1 .. RES_DEPTH_MAX): it has depth + 1 sets of rows
+    // LORAHIP_RESIDENT_DEBUG prints these at the flush: where the host's share of a step goes
+    uint64_t dbgReports, dbgImmediate, dbgCalls;
+    double dbgWaitNs, dbgBetweenNs;
+    std::chrono::steady_clock::time_point dbgLast;
+};
+
 } // namespace
 
+// Made by `new lorahip_demod()`, which value-initialises: a member without a default below starts at zero, false or null.
 struct lorahip_demod
 {
     int streamGrid;                  // lorahip_demod_set_stream_grid: 0 default, < 0 one workgroup per channel set, > 0 at most that many workgroups
@@ -73,9 +162,9 @@ struct lorahip_demod
     lorahip::Composite *comp;        // non-null: the handle is a container of (device, SF) parts (lorahip_rx.cpp); nothing below is used then
     lorahip_ctx *ctx;
     size_t N, B;
-    unsigned char sync;
-    float thresh;
-    size_t mtu;
+    unsigned char sync = 0x12;       // LoRaDemod.cpp:71-73
+    float thresh = -30.0f;
+    size_t mtu = 256;
     bool tracing;
     int64_t workCalls;
     std::vector<Channel> ch;
@@ -113,24 +202,27 @@ struct lorahip_demod
     bool uniform; size_t uniSpc;     // the streams of the current run are n_channels x uniSpc samples, uniStride apart (lorahip_demod_run_device[_append])
     size_t uniStride;
     bool append;                     // the current run continues every channel's stream where the last append run left it
-    bool appendFresh;                // ... unless nothing has been appended yet (create, rewind, any other kind of run in between)
+    bool appendFresh = true;         // ... unless nothing has been appended yet (create, rewind, any other kind of run in between)
     size_t appendPrev;               // samples per channel the last append run was given
     bool headStale;                  // the pinned copy of the per-channel state and counts (sHost) lags the device: ensureHead() fetches it
     StreamSummary lastSum;           // of the last streaming launch (valid while devStateFresh)
     unsigned nearSeen[2];            // the kernels' running near-threshold counters as last read
-    bool geomApplied;                // ch[].base / len / pos hold the current run's placement
+    bool geomApplied = true;         // ch[].base / len / pos hold the current run's placement
     bool posOnDevice;                // the pinned state copy's `pos` belongs to the CURRENT placement (a streaming run filled it; a new
                                      // lorahip_demod_run[_device] call invalidates it: its streams start at sample 0)
-    bool portCountsDirty;            // ch[].portFft / portDec / portRaw may be non-zero
+    bool portCountsDirty = true;     // ch[].portFft / portDec / portRaw may be non-zero
     // The symbols of the packet a channel is INSIDE when a streaming run ends stay on the device too: the kernel leaves them in dCarry
     // and copies them to the head of the channel's symbol row at the start of the next run, then appends behind them -- a packet
     // that spans runs is assembled without the host (the running receiver: lorahip_demod_run_device_segments + packets_to_device).
     short *dCarry; size_t carryCap;  // [B][carryCap]
     bool devCarryValid;              // dCarry holds the open packets of the state on the device
     bool hostCarryStale;             // ch[].outSymbols lack what the runs since the last drain received (implies devCarryValid)
-    size_t callsPerWindowQ8;         // streaming runs: work() calls per N samples the record buffers are sized for, in 1/256 (adapts, see runStream)
-    void *pipe;                      // Pipe: the two record sets and events of the pipelined receiver (lorahip_demod_receive, async = 2)
-    void *pending;                   // PendingLaunch (records of the last streaming launch still on the device)
+    size_t callsPerWindowQ8 = 288;   // streaming runs: work() calls per N samples the record buffers are sized for, in 1/256 (adapts, see runStream;
+                                     // 1.125 to begin with)
+    PendingLaunch pending;           // records of the last streaming launch still on the device
+    Pipe pipe;                       // the pipelined receiver (lorahip_demod_receive, async = 2) ...
+    Resident res;                    // ... and the resident one (async = 3): at most one of them is active
+    const float *stepIq; size_t stepStride;   // the rows the steps of either read (a flush that has to resume a full channel continues on them)
     std::vector<size_t> carry;       // per channel: symbols of a packet begun before the launch being drained
 };
 
@@ -142,8 +234,6 @@ struct Round
     uint16_t *sym; float *power; float *pavg; float *fidx; int32_t *idxOut; // outputs
     size_t inBytes, total;
 };
-
-static size_t align256(const size_t x) { return (x + 255) & ~size_t(255); }
 
 static Round carve(char *p, const size_t B)
 {
@@ -209,6 +299,37 @@ static void applyGeometry(lorahip_demod *dm)
         if (!cont) { dm->ch[c].pos = 0; dm->ch[c].callCount = 0; }
     }
     dm->geomApplied = true;
+}
+
+//! the next run's streams: n_channels x spc samples, `stride` apart. An append run continues every channel's stream where the last
+//! append run left it (unless there was none: create, rewind, any other kind of run in between); any other run begins new streams.
+static void placeUniform(lorahip_demod *dm, const size_t spc, const size_t stride, const bool append)
+{
+    dm->uniform = true; dm->uniSpc = spc; dm->uniStride = stride; dm->geomApplied = false;
+    if (!append || dm->appendFresh) dm->posOnDevice = false;
+    if (!append) dm->appendFresh = true;
+    dm->append = append;
+}
+
+//! the next run's streams: channel c's n[c] samples from sample baseOf(c) of the device buffer on, each a new stream
+template <class BaseOf> static void placeSegments(lorahip_demod *dm, const size_t *n, const BaseOf &baseOf)
+{
+    dm->uniform = false; dm->geomApplied = true; dm->posOnDevice = false;
+    dm->append = false; dm->appendFresh = true;
+    for (size_t c = 0; c < dm->B; c++)
+    {
+        Channel &k = dm->ch[c];
+        k.base = baseOf(c); k.len = n[c]; k.pos = 0; k.callCount = 0;
+    }
+}
+
+//! the owned upload buffer of lorahip_demod_run / lorahip_demod_run_host_rows, regrown to hold `samples` (callers grow it only)
+static int regrowIq(lorahip_demod *dm, const size_t samples)
+{
+    if (dm->dIq) { (void)hipFree(dm->dIq); dm->dIq = nullptr; dm->dIqSamples = 0; }
+    LORAHIP_TRY(hipMalloc((void **)&dm->dIq, samples * sizeof(cf32)));
+    dm->dIqSamples = samples;
+    return LORAHIP_OK;
 }
 
 static int syncMirrors(lorahip_demod *dm);
@@ -419,57 +540,15 @@ static int growDense(lorahip_demod *dm, const size_t bytes)
     return LORAHIP_OK;
 }
 
-//! where the pieces of one streaming launch live inside dm->sDev (device) / dm->sHost (host mirror of the head)
-struct StreamLayout
-{
-    size_t B, cap, capPkt, symStride;
-    bool tracing, signals;
-    size_t oBase, oLen, oState, oN, oNSym, oNPkt, oNSig, oNear, oSum, oEnd, oPkt, oSym, oSig, oCalls, total;
-    void make(const size_t B_, const size_t cap_, const size_t capPkt_, const bool tracing_, const size_t carryCap_ = 0, const bool signals_ = false)
-    {
-        B = B_; cap = cap_; capPkt = capPkt_; tracing = tracing_; signals = signals_;
-        symStride = cap_ + carryCap_;                    // a channel's symbol row: what the launch may add behind what it was handed
-        size_t cur = 0;
-        auto carve = [&cur](const size_t bytes) { const size_t o = cur; cur += align256(bytes); return o; };
-        oBase = carve(B * sizeof(long long)); oLen = carve(B * sizeof(long long));
-        oState = carve(B * sizeof(StreamState));
-        oN = carve(B * sizeof(int)); oNSym = carve(B * sizeof(int)); oNPkt = carve(B * sizeof(int)); oNSig = carve(B * sizeof(int));
-        oNear = carve(2 * sizeof(unsigned));
-        oSum = carve(sizeof(StreamSummary));
-        oEnd = carve(B * sizeof(int2));
-        oPkt = carve(B * capPkt * sizeof(StreamPacket));
-        oSym = carve(B * symStride * sizeof(short));
-        oSig = carve(signals ? B * capPkt * sizeof(StreamSignal) : 0);
-        oCalls = carve(tracing ? B * cap * sizeof(lorahip_work_result) : 0);
-        total = cur;
-    }
-};
-
-//! The records of the LAST streaming launch of a run stay on the device until somebody needs them on the host: a receive chain
-//! that hands the packets to the batched decoder (lorahip_demod_packets_to_device) never does, and then nothing but the
-//! per-channel state and counts (52 B per channel) crosses PCIe per run.
-struct PendingLaunch
-{
-    bool valid;
-    StreamLayout lay;
-    size_t firstNewPacket;          // index in dm->packets of the first packet of the run this launch belongs to
-    int64_t rounds;
-    size_t packets, packetSyms;     // what draining will append
-    size_t signals;
-    bool anyCarryIn, anyOpen;       // a channel entered the launch inside a packet / leaves it inside one
-    double drainMs;                 // LORAHIP_DEMOD_TIMING
-};
-
-static PendingLaunch &pendingOf(lorahip_demod *dm) { return *static_cast<PendingLaunch *>(dm->pending); }
-//! a pipelined receiver step is in flight (lorahip_demod_receive with async = 2): only receive / receive_flush may touch the object
-static bool pipeBusy(const lorahip_demod *dm);
+//! a pipelined or resident receiver step is in flight (lorahip_demod_receive with async = 2 / 3): only receive / receive_flush may touch
+//! the object
+static bool pipeBusy(const lorahip_demod *dm) { return dm->pipe.active || dm->res.active; }
 static int refuseWhilePiped(const lorahip_demod *dm)
 {
     if (!pipeBusy(dm)) return LORAHIP_OK;
     setLastError("a pipelined receiver step is in flight: lorahip_demod_receive_flush first");
     return LORAHIP_E_INVALID;
 }
-static std::vector<size_t> &carryOf(lorahip_demod *dm) { return dm->carry; }
 
 //! packets of one run in the order the host-driven path posts them: round by round, channels ascending inside a round
 static void orderNewPackets(lorahip_demod *dm, const size_t firstNewPacket, const int64_t rounds)
@@ -529,7 +608,7 @@ static int drainLaunch(lorahip_demod *dm, const StreamLayout &L)
     { const int rc = ensureHead(dm); if (rc != LORAHIP_OK) return rc; }
     char *h = dm->sHost, *d = dm->sDev;
     const int *hN = reinterpret_cast<int *>(h + L.oN), *hNSym = reinterpret_cast<int *>(h + L.oNSym), *hNPkt = reinterpret_cast<int *>(h + L.oNPkt);
-    std::vector<size_t> &carry = carryOf(dm);
+    std::vector<size_t> &carry = dm->carry;
     // only as many columns of the [channel][capacity] record arrays as the fullest channel used cross PCIe: the capacities are
     // worst-case bounds, several times what a run fills
     const int *hNSig = reinterpret_cast<int *>(h + L.oNSig);
@@ -603,7 +682,7 @@ static int drainLaunch(lorahip_demod *dm, const StreamLayout &L)
 //! bring a pending launch's records to the host (any accessor of the queue / traces does this first)
 static int drainPending(lorahip_demod *dm)
 {
-    PendingLaunch &P = pendingOf(dm);
+    PendingLaunch &P = dm->pending;
     if (!P.valid) return LORAHIP_OK;
     const DeviceGuard guard(dm->ctx->device);
     typedef std::chrono::steady_clock Clock;
@@ -693,6 +772,70 @@ static int lanesArg(const lorahip_demod *dm)
     return l == dm->ctx->sf - 4 ? -1 : l;
 }
 
+static bool usesStreamKernel(const lorahip_demod *dm) { return dm->mode == 1 || (dm->mode == 0 && streamAvailable(dm->ctx->sf)); }
+
+//! per-launch record capacity (work() calls per channel) and packet capacity for streams of at most maxLen samples
+static void streamCapacity(const lorahip_demod *dm, const size_t maxLen, size_t &cap, size_t &capPkt)
+{
+    // work() calls per channel per launch: enough for a clean stream in one launch, bounded so that the
+    // per-launch buffers stay moderate (the launch is resumable)
+    const size_t perCall = sizeof(short) + (dm->tracing ? sizeof(lorahip_work_result) : 0) + sizeof(StreamPacket) / 4 + 1 + (dm->wantSignals ? sizeof(StreamSignal) / 4 : 0);
+    // A call consumes N samples except around a frame's sync (N - value, N/4 + error/2: LoRaDemod.cpp:219, :278) -- a handful of short
+    // calls per frame -- and in an unsquelched FRAMESYNC window that does not sync (N - value every call: a receiver idling on noise
+    // above its threshold makes about two calls per N samples). A launch whose record buffers fill is resumed, but the records have
+    // to be drained in between (measured: 9.7 ms instead of 7.0 ms per run at SF7, 16384 channels x 16 frames), so the capacity
+    // starts with an eighth of headroom and follows what the runs of this receiver actually needed (never shrinks).
+    cap = (maxLen / dm->N) * dm->callsPerWindowQ8 / 256 + 64;
+    if (cap > 65536) cap = 65536;
+    const size_t capMem = (size_t(1) << 30) / (dm->B * perCall);
+    if (cap > capMem) cap = capMem;
+    if (cap < 8) cap = 8;
+    // lorahip_demod_set_record_capacity: a bound on the per-launch record capacity (tests force the resume path with it)
+    if (dm->streamCapMax != 0 && cap > dm->streamCapMax) cap = dm->streamCapMax;
+    capPkt = cap / 4 + 2;                            // a packet costs at least 5 calls (3 sync, quarter, 1 symbol)
+}
+
+//! the kernels' running near-threshold counters, as read now, into the object's counts: the counters only add, so what is new is
+//! the difference to the last read
+static void foldNear(lorahip_demod *dm, const unsigned squelch, const unsigned step)
+{
+    dm->nNearSquelch += int64_t(unsigned(squelch - dm->nearSeen[0]));
+    dm->nNearStep += int64_t(unsigned(step - dm->nearSeen[1]));
+    dm->nearSeen[0] = squelch; dm->nearSeen[1] = step;
+}
+
+/*! What every streaming launch of this object shares: its tables and settings, the head of dm->sDev (the per-channel state and the
+ * near-threshold counters, which every launch continues), the carry rows, the record arrays of layout L at `rec`, and the grid. The
+ * caller sets the placement (uniformLen; base / len for per-channel streams) and the flags; what nobody sets stays zero. */
+static StreamArgs makeStreamArgs(const lorahip_demod *dm, const float *iqDev, const StreamLayout &L, char *rec)
+{
+    const lorahip_ctx *ctx = dm->ctx;
+    const StreamLayout H = headLayout(dm);
+    StreamArgs a{};
+    a.iq = reinterpret_cast<const float2 *>(iqDev);
+    a.uniformStride = (long long)dm->uniStride;
+    a.state = reinterpret_cast<StreamState *>(dm->sDev + H.oState);
+    a.near = reinterpret_cast<unsigned *>(dm->sDev + H.oNear);
+    a.carry = dm->dCarry; a.carryCap = int(dm->carryCap);
+    a.nCalls = reinterpret_cast<int *>(rec + L.oN); a.nSym = reinterpret_cast<int *>(rec + L.oNSym); a.nPkt = reinterpret_cast<int *>(rec + L.oNPkt);
+    a.nSig = reinterpret_cast<int *>(rec + L.oNSig); a.end = reinterpret_cast<int2 *>(rec + L.oEnd);
+    a.pktOut = reinterpret_cast<StreamPacket *>(rec + L.oPkt); a.symOut = reinterpret_cast<short *>(rec + L.oSym);
+    a.sigOut = L.signals ? reinterpret_cast<StreamSignal *>(rec + L.oSig) : nullptr;
+    a.calls = L.tracing ? reinterpret_cast<lorahip_work_result *>(rec + L.oCalls) : nullptr;
+    a.down = ctx->dDown; a.fine = ctx->dFine; a.twStage = ctx->dTwStage;
+    a.fineA = ctx->fineGather ? nullptr : ctx->dFineA; a.fineB = ctx->fineGather ? nullptr : ctx->dFineB;
+    a.nChannels = unsigned(L.B); a.cap = int(L.cap); a.symStride = int(L.symStride); a.capPkt = int(L.capPkt);
+    a.powerScale = ctx->powerScale; a.thresh = dm->thresh; a.sync = dm->sync;
+    a.mtu = dm->mtu > 0xffffffffu ? 0xffffffffu : unsigned(dm->mtu);
+    // The grid (lorahip_demod_set_stream_grid; 0 = the kernels' own default). One workgroup per channel set, however many there are,
+    // at every SF but 11: the dispatcher hands a free slot the next set. A PERSISTENT grid (the resident number of workgroups, each
+    // looping over sets) lost there even with the alternating priority (profiles/r04/s22_*: SF7 32768 channels 0.34 against 0.44,
+    // SF9 0.36 against 0.40; SF8 / 10 / 12 equal) -- the loop costs the wave-per-channel-set kernels registers -- and is the default
+    // only where one-by-one placement leaves slots unusable: SF11 (lorahip_wide.hip::launchStreamWideCfg).
+    a.maxBlocks = dm->streamGrid; a.lanes = lanesArg(dm); a.lastRoundFrom = 0;
+    return a;
+}
+
 static int runStream(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
 {
     lorahip_ctx *ctx = dm->ctx;
@@ -709,22 +852,8 @@ static int runStream(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
     // an append run works through what is new since the last one plus what that one left (fewer than 2N samples per channel)
     size_t maxLen = dm->uniform ? (cont && dm->appendPrev <= dm->uniSpc ? dm->uniSpc - dm->appendPrev + 2 * N : dm->uniSpc) : 0;
     if (!dm->uniform) for (size_t c = 0; c < B; c++) if (dm->ch[c].len - dm->ch[c].pos > maxLen) maxLen = dm->ch[c].len - dm->ch[c].pos;
-    // work() calls per channel per launch: enough for a clean stream in one launch, bounded so that the
-    // per-launch buffers stay moderate (the launch is resumable)
-    const size_t perCall = sizeof(short) + (dm->tracing ? sizeof(lorahip_work_result) : 0) + sizeof(StreamPacket) / 4 + 1 + (dm->wantSignals ? sizeof(StreamSignal) / 4 : 0);
-    // A call consumes N samples except around a frame's sync (N - value, N/4 + error/2: LoRaDemod.cpp:219, :278) -- a handful of short
-    // calls per frame -- and in an unsquelched FRAMESYNC window that does not sync (N - value every call: a receiver idling on noise
-    // above its threshold makes about two calls per N samples). A launch whose record buffers fill is resumed, but the records have
-    // to be drained in between (measured: 9.7 ms instead of 7.0 ms per run at SF7, 16384 channels x 16 frames), so the capacity
-    // starts with an eighth of headroom and follows what the runs of this receiver actually needed (never shrinks).
-    size_t cap = (maxLen / N) * dm->callsPerWindowQ8 / 256 + 64;
-    if (cap > 65536) cap = 65536;
-    const size_t capMem = (size_t(1) << 30) / (B * perCall);
-    if (cap > capMem) cap = capMem;
-    if (cap < 8) cap = 8;
-    // lorahip_demod_set_record_capacity: a bound on the per-launch record capacity (tests force the resume path with it)
-    if (dm->streamCapMax != 0 && cap > dm->streamCapMax) cap = dm->streamCapMax;
-    const size_t capPkt = cap / 4 + 2;               // a packet costs at least 5 calls (3 sync, quarter, 1 symbol)
+    size_t cap, capPkt;
+    streamCapacity(dm, maxLen, cap, capPkt);
 
     // open packets on the device (dCarry): rows of mtu + 1 symbols; receivers with longer packets than this keep the host path
     // (the carry rows and their share of the symbol rows stay inside the memory bound of the record buffers above)
@@ -769,7 +898,7 @@ static int runStream(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
     long long *hBase = reinterpret_cast<long long *>(h + L.oBase), *hLen = reinterpret_cast<long long *>(h + L.oLen);
     StreamState *hState = reinterpret_cast<StreamState *>(h + L.oState);
     const StreamSummary *hSum = reinterpret_cast<const StreamSummary *>(h + L.oSum);
-    std::vector<size_t> &carry = carryOf(dm);
+    std::vector<size_t> &carry = dm->carry;
     carry.assign(B, 0);
     bool anyCarryIn = false;
     size_t maxCarry = 0;
@@ -845,47 +974,16 @@ static int runStream(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
         LORAHIP_TRY(hipMemcpyAsync(d, h, L.oState, hipMemcpyHostToDevice, ctx->stream));       // base, len
     }
 
-    StreamArgs a;
-    a.iq = reinterpret_cast<const float2 *>(iqDev);
+    StreamArgs a = makeStreamArgs(dm, iqDev, L, d);
     a.base = reinterpret_cast<const long long *>(d + L.oBase);
     a.len = reinterpret_cast<const long long *>(d + L.oLen);
     a.uniformLen = dm->uniform ? (long long)dm->uniSpc : -1;
-    a.uniformStride = (long long)dm->uniStride;
     // first launch of the run: every channel starts at sample 0, call 0 (unless the run continues the streams), behind its open packet's
     // symbols, and leaves the packet it is inside at the end in the carry rows
     a.flags = (cont ? 0 : 1) | (activate ? 2 : 0) | (useDevCarry ? 4 | 8 : 0);
-    a.carry = dm->dCarry; a.carryCap = int(dm->carryCap);
-    // The grid (lorahip_demod_set_stream_grid; 0 = the kernels' own default). One workgroup per channel set, however many there are,
-    // at every SF but 11: the dispatcher hands a free slot the next set. A PERSISTENT grid (the resident number of workgroups, each
-    // looping over sets) lost there even with the alternating priority (profiles/r04/s22_*: SF7 32768 channels 0.34 against 0.44,
-    // SF9 0.36 against 0.40; SF8 / 10 / 12 equal) -- the loop costs the wave-per-channel-set kernels registers -- and is the default
-    // only where one-by-one placement leaves slots unusable: SF11 (lorahip_wide.hip::launchStreamWideCfg).
-    a.maxBlocks = dm->streamGrid; a.lanes = lanesArg(dm); a.lastRoundFrom = 0;
 #if defined(LORAHIP_ALL_VARIANTS) || defined(LORAHIP_STREAM_PERSIST)
     if (const char *e = std::getenv("LORAHIP_STREAM_BLOCKS")) a.maxBlocks = std::atoi(e);        // e.g. 512: two workgroups of 256 threads per CU
 #endif
-    a.state = reinterpret_cast<StreamState *>(d + L.oState);
-    a.nCalls = reinterpret_cast<int *>(d + L.oN);
-    a.nSym = reinterpret_cast<int *>(d + L.oNSym);
-    a.nPkt = reinterpret_cast<int *>(d + L.oNPkt);
-    a.pktOut = reinterpret_cast<StreamPacket *>(d + L.oPkt);
-    a.symOut = reinterpret_cast<short *>(d + L.oSym);
-    a.sigOut = dm->wantSignals ? reinterpret_cast<StreamSignal *>(d + L.oSig) : nullptr;
-    a.nSig = reinterpret_cast<int *>(d + L.oNSig);
-    a.end = reinterpret_cast<int2 *>(d + L.oEnd);
-    a.calls = dm->tracing ? reinterpret_cast<lorahip_work_result *>(d + L.oCalls) : nullptr;
-    a.down = ctx->dDown; a.fine = ctx->dFine; a.twStage = ctx->dTwStage;
-    a.fineA = ctx->fineGather ? nullptr : ctx->dFineA;
-    a.fineB = ctx->fineGather ? nullptr : ctx->dFineB;
-    a.nChannels = unsigned(B);
-    a.cap = int(cap);
-    a.symStride = int(L.symStride);
-    a.capPkt = int(capPkt);
-    a.powerScale = ctx->powerScale;
-    a.thresh = dm->thresh;
-    a.sync = dm->sync;
-    a.mtu = dm->mtu > 0xffffffffu ? 0xffffffffu : unsigned(dm->mtu);
-    a.near = reinterpret_cast<unsigned *>(d + L.oNear);
     if (activate) dm->activatePending = false;        // applied by the kernel when it loads the state
     dm->devStateFresh = false;                        // until the run has completed
     dm->mirrorsStale = true;
@@ -919,10 +1017,7 @@ static int runStream(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
         const Clock::time_point tb = Clock::now();
         tDev += std::chrono::duration<double>(tb - ta).count();
         sum = *hSum;
-        // the kernels' counters run on (they only add): what this launch added
-        dm->nNearSquelch += int64_t(unsigned(sum.nearSquelch - dm->nearSeen[0]));
-        dm->nNearStep += int64_t(unsigned(sum.nearStep - dm->nearSeen[1]));
-        dm->nearSeen[0] = sum.nearSquelch; dm->nearSeen[1] = sum.nearStep;
+        foldNear(dm, sum.nearSquelch, sum.nearStep);
         const bool more = sum.more != 0;
         dm->workCalls += sum.calls;
         runCalls += size_t(sum.fullest);
@@ -963,7 +1058,7 @@ static int runStream(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
         dm->hostCarryStale = lastPending;             // a drain (traced runs) has brought the mirrors' outSymbols up to date already
     }
     else { dm->devCarryValid = false; dm->hostCarryStale = false; }      // a resumed run: its launches handed the symbols on through the mirrors
-    PendingLaunch &P = pendingOf(dm);
+    PendingLaunch &P = dm->pending;
     if (lastPending)
     {
         P.valid = true;
@@ -996,78 +1091,65 @@ static int runStream(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
  * device, in stream order; a channel that filled its record buffer in step k-1 is simply continued by kernel k (the kernels are
  * resumable by design). The per-launch record arrays exist twice (kernel k writes one set while step k-1's are packed from the other).
  **********************************************************************/
-struct Pipe
+/*! What a pipelined or resident step needs in place, beside its own terms: the streaming kernel, no trace / ports / deferred
+ * activate(), a continuing append stream over the same rows (no fewer valid samples than the step before), carry rows long enough
+ * for a packet. Anything else takes the ordinary step (which establishes exactly that). */
+static bool steadyAppend(const lorahip_demod *dm, const size_t rowStride, const size_t nValid)
 {
-    bool active;                    // steps are in flight: only receive / flush may touch the object
-    unsigned k;                     // steps launched since the pipeline was entered
-    char *dev[2]; size_t bytes[2];  // record sets (a StreamLayout each; the state and the carry rows are the object's own)
-    StreamLayout lay[2];
-    StreamSummary *hSum;            // [2] pinned and mapped: the summary kernel writes here directly (no copy to enqueue)
-    hipEvent_t ev[2];
-    bool pending[2];                // the set's kernel has been launched, its summary not read yet
-    bool held[2];                   // the set's summary has been read, its packets are still in the set (rows too small: nothing is lost)
-    size_t nPk[2]; int64_t nCalls[2];   // ... what that summary said
-    size_t nSig[2]; bool sigs[2];       // ... and the signals kept in the set (the step ran with lorahip_demod_set_signals on)
-    hipStream_t side;               // step k's packets are packed HERE while step k + 1's kernel runs on the launch stream
-    hipEvent_t packDone;            // ... which waits for this before anything later (the next kernel reuses the record set, the caller reads the rows)
-    hipEvent_t entry;               // ... and the side stream for this: where the launch stream stood when the call began (the caller's
-                                    // consumer of the rows handed out by the call before, earlier packing on the launch stream)
-    const float *iq; size_t rowStride;  // the rows the steps read (a flush that has to resume a full channel continues on them)
-    // ---- the RESIDENT receiver (lorahip_demod_receive, async = 3): one launch across the steps, lorahip_streamkernel.h (RES) ----
-    struct Resident
-    {
-        bool active;                    // the kernel is on the device: only receive (async = 3) / flush may touch the object
-        bool unavailable;               // tried and refused for this object (no instance, the grid not resident at once, a step timed out)
-        unsigned seq;                   // steps rung
-        unsigned reported;              // steps whose report the caller has had
-        ResidentCtl *ctl;               // device: the mirror of the ring, the steps' counters
-        ResidentHost *host;             // pinned and mapped: the ring the host writes, the steps' reports, the abort flag
-        char *rec; size_t recBytes;     // the channels' records of a step (a StreamLayout; the state and the carry rows are the object's own)
-        StreamLayout lay;
-        hipStream_t run;                // the kernel's stream
-        hipEvent_t ev;
-        unsigned grid;
-        size_t lastValid;
-        bool lastMore;                  // the last reported step left a channel with samples it could not record
-        bool sigs;                      // the launch keeps signal records
-        bool tail;                      // the last step left fewer than 16 valid samples per row untouched (the flush's ordinary step takes them)
-        unsigned nRep; size_t repPk[RES_DEPTH_MAX + 1], repSg[RES_DEPTH_MAX + 1];   // the steps the last call reported, oldest first (lorahip_demod_receive_steps)
-        unsigned depth;                 // steps the caller lets the receiver run ahead of the last report (1 .. RES_DEPTH_MAX): it has depth + 1 sets of rows
-        // LORAHIP_RESIDENT_DEBUG prints these at the flush: where the host's share of a step goes
-        uint64_t dbgReports, dbgImmediate, dbgCalls;
-        double dbgWaitNs, dbgBetweenNs;
-        std::chrono::steady_clock::time_point dbgLast;
-    } res;
-};
-static Pipe &pipeOf(lorahip_demod *dm) { return *static_cast<Pipe *>(dm->pipe); }
-static bool pipeBusy(const lorahip_demod *dm)
-{
-    return dm->pipe != nullptr && (static_cast<const Pipe *>(dm->pipe)->active || static_cast<const Pipe *>(dm->pipe)->res.active);
+    return usesStreamKernel(dm) && !dm->tracing && !dm->portsOn && !dm->activatePending && dm->sDev != nullptr && dm->append && !dm->appendFresh &&
+           dm->uniStride == rowStride && nValid >= dm->appendPrev && dm->dCarry != nullptr && dm->mtu + 1 <= dm->carryCap;
 }
 
-//! per-launch record capacity (work() calls per channel) for streams of at most maxLen samples: see runStream
-static void streamCapacity(const lorahip_demod *dm, const size_t maxLen, size_t &cap, size_t &capPkt)
+//! ... and to enter either mode: the state and the open packets' symbols on the device, no records of a launch left there
+static bool stateOnDevice(const lorahip_demod *dm) { return dm->devStateFresh && (dm->devCarryValid || !dm->lastSum.anyOpen) && !dm->pending.valid; }
+
+//! a pipelined or resident step has been given the first nValid samples of rows rowStride apart: an append run over those rows, after
+//! which the pinned copy of the state and the mirrors lag behind the device
+static void noteSteadyStep(lorahip_demod *dm, const size_t rowStride, const size_t nValid)
 {
-    const size_t perCall = sizeof(short) + (dm->tracing ? sizeof(lorahip_work_result) : 0) + sizeof(StreamPacket) / 4 + 1 + (dm->wantSignals ? sizeof(StreamSignal) / 4 : 0);
-    cap = (maxLen / dm->N) * dm->callsPerWindowQ8 / 256 + 64;
-    if (cap > 65536) cap = 65536;
-    const size_t capMem = (size_t(1) << 30) / (dm->B * perCall);
-    if (cap > capMem) cap = capMem;
-    if (cap < 8) cap = 8;
-    if (dm->streamCapMax != 0 && cap > dm->streamCapMax) cap = dm->streamCapMax;      // lorahip_demod_set_record_capacity (tests: resumed launches)
-    capPkt = cap / 4 + 2;
+    placeUniform(dm, nValid, rowStride, true);
+    dm->appendPrev = nValid;
+    dm->mirrorsStale = true; dm->headStale = true;
+}
+
+//! a pipelined or resident receiver has been left: the object is as a streaming run leaves it -- the state (and the open packets'
+//! symbols) on the device, the pinned copy and the mirrors behind. (Its steps are not timed one by one: an event pair per step is two
+//! more calls.)
+static void leaveStateOnDevice(lorahip_demod *dm)
+{
+    dm->kernelMs = 0.0;
+    dm->devStateFresh = true; dm->posOnDevice = true; dm->mirrorsStale = true; dm->headStale = true;
+    dm->devCarryValid = true; dm->hostCarryStale = true;
+    dm->pending.valid = false;
+}
+
+//! the n packets of a record set of layout L at `rec` into rows (stream-ordered on `st`, no wait; the rows are numbered on the device,
+//! channels ascending). The scratch (growDense) has been sized by the caller.
+static hipError_t packPackets(const lorahip_demod *dm, const StreamLayout &L, const char *rec, const size_t n, uint16_t *syms, const size_t symStride,
+                              int32_t *nsyms, int32_t *chan, hipStream_t st)
+{
+    const size_t nbRow = align256(L.B * sizeof(int));
+    return launchPackPackets(reinterpret_cast<const StreamPacket *>(rec + L.oPkt), reinterpret_cast<const int *>(rec + L.oNPkt),
+                             reinterpret_cast<const short *>(rec + L.oSym), reinterpret_cast<int *>(dm->dDense), L.B, int(L.symStride), int(L.capPkt), n,
+                             reinterpret_cast<long long *>(dm->dDense + nbRow), syms, int(symStride), nsyms, chan, st);
+}
+
+//! the signals of a record set of layout L at `rec` into the registered signal rows from row `first` on (stream-ordered on `st`, no wait)
+static hipError_t packSignals(const lorahip_demod *dm, const StreamLayout &L, const char *rec, const size_t first, hipStream_t st)
+{
+    const lorahip_signal_rows &R = dm->sigRows;
+    return launchPackSignals(reinterpret_cast<const StreamSignal *>(rec + L.oSig), reinterpret_cast<const int *>(rec + L.oNSig), L.B, int(L.capPkt),
+                             R.channel, R.error, R.power, R.snr, first, R.cap, st);
 }
 
 //! summary of record set `set` into the object's books (waits for that step's kernel); its packets stay in the set until packed
 static int pipeRead(lorahip_demod *dm, const int set)
 {
-    Pipe &P = pipeOf(dm);
+    Pipe &P = dm->pipe;
     LORAHIP_TRY(hipEventSynchronize(P.ev[set]));
     P.pending[set] = false;
     const StreamSummary sum = P.hSum[set];
-    dm->nNearSquelch += int64_t(unsigned(sum.nearSquelch - dm->nearSeen[0]));
-    dm->nNearStep += int64_t(unsigned(sum.nearStep - dm->nearSeen[1]));
-    dm->nearSeen[0] = sum.nearSquelch; dm->nearSeen[1] = sum.nearStep;
+    foldNear(dm, sum.nearSquelch, sum.nearStep);
     dm->workCalls += sum.calls;
     dm->lastSum = sum;
     P.nPk[set] = size_t(sum.packets);
@@ -1090,13 +1172,11 @@ static bool sigRowsHold(const lorahip_demod *dm, const size_t n) { return !dm->s
 //! (stream-ordered; no wait); the set is free afterwards. The scratch (growDense) has been sized by the caller.
 static int pipePack(lorahip_demod *dm, const int set, const lorahip_packet_rows *rows, const size_t firstRow, const size_t firstSig, const bool beside)
 {
-    Pipe &P = pipeOf(dm);
+    Pipe &P = dm->pipe;
     lorahip_ctx *ctx = dm->ctx;
     const size_t n = P.nPk[set], ns = dm->sigRowsOn ? P.nSig[set] : 0;
     if (n == 0 && ns == 0) { P.held[set] = false; return LORAHIP_OK; }
     const StreamLayout &L = P.lay[set];
-    const size_t nbRow = align256(L.B * sizeof(int));
-    char *d = P.dev[set];
     // `beside`: packed on the side stream WHILE the step just launched runs (the host has just waited for this step's summary: its
     // kernel is complete). The side stream first waits for where the launch stream stood when this call began -- whatever the caller
     // queued there to read the rows of the call before (a decoder) and any earlier packing, which shares the scratch -- and the launch
@@ -1106,13 +1186,9 @@ static int pipePack(lorahip_demod *dm, const int set, const lorahip_packet_rows 
     hipStream_t packStream = beside ? P.side : ctx->stream;
     if (beside) LORAHIP_TRY(hipStreamWaitEvent(P.side, P.entry, 0));
     if (n)
-        LORAHIP_TRY(launchPackPackets(reinterpret_cast<const StreamPacket *>(d + L.oPkt), reinterpret_cast<const int *>(d + L.oNPkt),
-                                      reinterpret_cast<const short *>(d + L.oSym), reinterpret_cast<int *>(dm->dDense), L.B, int(L.symStride), int(L.capPkt), n,
-                                      reinterpret_cast<long long *>(dm->dDense + nbRow), rows->syms_dev + firstRow * rows->sym_stride, int(rows->sym_stride),
-                                      rows->nsyms_dev + firstRow, rows->channel_dev ? rows->channel_dev + firstRow : nullptr, packStream));
-    if (ns)
-        LORAHIP_TRY(launchPackSignals(reinterpret_cast<const StreamSignal *>(d + L.oSig), reinterpret_cast<const int *>(d + L.oNSig), L.B, int(L.capPkt),
-                                      dm->sigRows.channel, dm->sigRows.error, dm->sigRows.power, dm->sigRows.snr, firstSig, dm->sigRows.cap, packStream));
+        LORAHIP_TRY(packPackets(dm, L, P.dev[set], n, rows->syms_dev + firstRow * rows->sym_stride, rows->sym_stride, rows->nsyms_dev + firstRow,
+                                rows->channel_dev ? rows->channel_dev + firstRow : nullptr, packStream));
+    if (ns) LORAHIP_TRY(packSignals(dm, L, P.dev[set], firstSig, packStream));
     if (beside)
     {
         LORAHIP_TRY(hipEventRecord(P.packDone, P.side));
@@ -1128,7 +1204,7 @@ static int pipePack(lorahip_demod *dm, const int set, const lorahip_packet_rows 
  * rows registered for them (lorahip_demod_receive_signal_rows): all or nothing, lorahip_demod_receive_num_signals() = what is due. */
 static int pipeDeliverHeld(lorahip_demod *dm, const int older, const int sets, const lorahip_packet_rows *rows, size_t *nPackets, int64_t *calls, const bool beside)
 {
-    Pipe &P = pipeOf(dm);
+    Pipe &P = dm->pipe;
     size_t need = 0, needSig = 0, most = 0;
     for (int i = 0; i < sets; i++)
         if (P.held[older ^ i]) { need += P.nPk[older ^ i]; needSig += P.nSig[older ^ i]; if (P.nPk[older ^ i] > most) most = P.nPk[older ^ i]; }
@@ -1165,7 +1241,7 @@ static int pipeDeliverHeld(lorahip_demod *dm, const int older, const int sets, c
 //! leave the pipeline: the packets not delivered yet into `rows` (nullable: they are dropped), the object back in the state a streaming run leaves
 static int pipeFlush(lorahip_demod *dm, const lorahip_packet_rows *rows, size_t *nPackets, int64_t *calls)
 {
-    Pipe &P = pipeOf(dm);
+    Pipe &P = dm->pipe;
     if (nPackets) *nPackets = 0;
     if (calls) *calls = 0;
     if (!P.active) return LORAHIP_OK;
@@ -1187,11 +1263,7 @@ static int pipeFlush(lorahip_demod *dm, const lorahip_packet_rows *rows, size_t 
     if (calls) *calls = c1;
     LORAHIP_TRY(hipStreamSynchronize(dm->ctx->stream));
     P.active = false;
-    dm->kernelMs = 0.0;                               // (the pipelined steps are not timed one by one: an event pair per step is two more calls)
-    // what a streaming run leaves: the state (and the open packets' symbols) on the device, the pinned copy and the mirrors behind
-    dm->devStateFresh = true; dm->posOnDevice = true; dm->mirrorsStale = true; dm->headStale = true;
-    dm->devCarryValid = true; dm->hostCarryStale = true;
-    pendingOf(dm).valid = false;
+    leaveStateOnDevice(dm);
     return LORAHIP_OK;
 }
 
@@ -1199,16 +1271,11 @@ static int pipeStep(lorahip_demod *dm, const float *iqDev, const size_t rowStrid
                     int64_t *calls, bool &handled)
 {
     handled = false;
-    Pipe &P = pipeOf(dm);
+    Pipe &P = dm->pipe;
     lorahip_ctx *ctx = dm->ctx;
     const size_t N = dm->N, B = dm->B;
-    const bool stream = dm->mode == 1 || (dm->mode == 0 && streamAvailable(ctx->sf));
-    // What the pipeline needs in place: the streaming mode, no trace / ports, the state and the open packets on the device
-    // with carry rows long enough, a continuing append stream. Anything else takes the ordinary step (which establishes exactly that).
-    const bool compatible = stream && !dm->tracing && !dm->portsOn && !dm->activatePending && dm->sDev != nullptr &&
-                            dm->append && !dm->appendFresh && dm->uniStride == rowStride && nValid >= dm->appendPrev &&
-                            dm->dCarry != nullptr && dm->mtu + 1 <= dm->carryCap;
-    const bool ready = compatible && dm->devStateFresh && (dm->devCarryValid || !dm->lastSum.anyOpen) && !pendingOf(dm).valid;
+    const bool compatible = steadyAppend(dm, rowStride, nValid);
+    const bool ready = compatible && stateOnDevice(dm);
     if (!P.active && !ready) return LORAHIP_OK;
     if (P.active && !compatible) { setLastError("lorahip_demod_receive (pipelined): a setting or the rows changed under a running pipeline (lorahip_demod_receive_flush first)"); return LORAHIP_E_INVALID; }
     handled = true;
@@ -1260,27 +1327,11 @@ static int pipeStep(lorahip_demod *dm, const float *iqDev, const size_t rowStrid
         P.bytes[set] = want;
     }
     P.lay[set] = L;
-    const StreamLayout H = headLayout(dm);
-    char *d = P.dev[set];
-    StreamArgs a;
-    a.iq = reinterpret_cast<const float2 *>(iqDev);
-    a.base = nullptr; a.len = nullptr;
-    a.uniformLen = (long long)nValid; a.uniformStride = (long long)rowStride;
+    StreamArgs a = makeStreamArgs(dm, iqDev, L, P.dev[set]);
+    a.uniformLen = (long long)nValid;
     a.flags = 4 | 8;                                  // continue the streams; open packets in from / out to the carry rows
-    a.carry = dm->dCarry; a.carryCap = int(dm->carryCap); a.maxBlocks = dm->streamGrid; a.lanes = lanesArg(dm); a.lastRoundFrom = 0;
-    a.state = reinterpret_cast<StreamState *>(dm->sDev + H.oState);          // the object's own: every launch continues it
-    a.nCalls = reinterpret_cast<int *>(d + L.oN); a.nSym = reinterpret_cast<int *>(d + L.oNSym); a.nPkt = reinterpret_cast<int *>(d + L.oNPkt);
-    a.nSig = reinterpret_cast<int *>(d + L.oNSig); a.end = reinterpret_cast<int2 *>(d + L.oEnd);
-    a.pktOut = reinterpret_cast<StreamPacket *>(d + L.oPkt); a.symOut = reinterpret_cast<short *>(d + L.oSym);
     // the block's signals (:267-269), kept per step like the packets and delivered with them one step late
-    a.sigOut = dm->wantSignals ? reinterpret_cast<StreamSignal *>(d + L.oSig) : nullptr; a.calls = nullptr;
     P.sigs[set] = dm->wantSignals;
-    a.down = ctx->dDown; a.fine = ctx->dFine; a.twStage = ctx->dTwStage;
-    a.fineA = ctx->fineGather ? nullptr : ctx->dFineA; a.fineB = ctx->fineGather ? nullptr : ctx->dFineB;
-    a.nChannels = unsigned(B); a.cap = int(cap); a.symStride = int(L.symStride); a.capPkt = int(capPkt);
-    a.powerScale = ctx->powerScale; a.thresh = dm->thresh; a.sync = dm->sync;
-    a.mtu = dm->mtu > 0xffffffffu ? 0xffffffffu : unsigned(dm->mtu);
-    a.near = reinterpret_cast<unsigned *>(dm->sDev + H.oNear);
     // four calls per step: the kernel, its summary (written straight into pinned host memory), the event the next call waits on -- and
     // the previous step's packing below. (The summary on a stream of its own, behind the kernel's event and beside the NEXT step's kernel
     // -- it reads only this record set's counts and end words -- was measured: two more API calls and the hand-over between the streams
@@ -1290,9 +1341,8 @@ static int pipeStep(lorahip_demod *dm, const float *iqDev, const size_t rowStrid
     LORAHIP_TRY(hipEventRecord(P.ev[set], ctx->stream));
     P.pending[set] = true;
     P.k++;
-    P.iq = iqDev; P.rowStride = rowStride;
-    dm->uniform = true; dm->uniSpc = nValid; dm->uniStride = rowStride; dm->appendPrev = nValid; dm->geomApplied = false;
-    dm->mirrorsStale = true; dm->headStale = true;
+    dm->stepIq = iqDev; dm->stepStride = rowStride;
+    noteSteadyStep(dm, rowStride, nValid);
     // ... and while it runs: the step before
     if (delivered || P.k < 2 || !P.pending[set ^ 1]) return LORAHIP_OK;
     { const int rc = pipeRead(dm, set ^ 1); if (rc != LORAHIP_OK) return rc; }
@@ -1310,7 +1360,7 @@ static const unsigned long long kResidentWatchdog = 800000000ull;   // device: 8
 
 static int residentRing(lorahip_demod *dm, const size_t nValid, const lorahip_packet_rows *rows, const unsigned flags)
 {
-    Pipe::Resident &R = pipeOf(dm).res;
+    Resident &R = dm->res;
     const unsigned seq = R.seq + 1;
     ResidentMsg m;
     std::memset(&m, 0, sizeof(m));
@@ -1340,7 +1390,7 @@ static int residentRing(lorahip_demod *dm, const size_t nValid, const lorahip_pa
 //! wait for step `k`'s report (bounded); *packets / *signals = what the step produced (dropped ones included), *flags = RES_F_*
 static int residentReport(lorahip_demod *dm, const unsigned k, size_t *packets, size_t *signals, int64_t *calls, unsigned *flags)
 {
-    Pipe::Resident &R = pipeOf(dm).res;
+    Resident &R = dm->res;
     volatile unsigned long long *h = R.host->sum + 2 * (k & 7);
     typedef std::chrono::steady_clock Clock;
     const Clock::time_point t0 = Clock::now();
@@ -1369,7 +1419,7 @@ static int residentReport(lorahip_demod *dm, const unsigned k, size_t *packets, 
 //! get the kernel off the device whatever state the steps are in (error paths, destroy)
 static void residentAbort(lorahip_demod *dm)
 {
-    Pipe::Resident &R = pipeOf(dm).res;
+    Resident &R = dm->res;
     if (!R.active) return;
     __atomic_store_n(&R.host->abort, 1u, __ATOMIC_RELEASE);
     (void)hipStreamSynchronize(R.run);
@@ -1379,7 +1429,7 @@ static void residentAbort(lorahip_demod *dm)
 
 static int residentFlush(lorahip_demod *dm, size_t *nPackets, int64_t *calls)
 {
-    Pipe::Resident &R = pipeOf(dm).res;
+    Resident &R = dm->res;
     if (nPackets) *nPackets = 0;
     if (calls) *calls = 0;
     dm->lastSignals = 0;
@@ -1409,10 +1459,7 @@ static int residentFlush(lorahip_demod *dm, size_t *nPackets, int64_t *calls)
     if (nPackets) *nPackets = pk;
     if (calls) *calls = cl;
     dm->lastSignals = dm->sigRowsOn ? sg : 0;
-    dm->kernelMs = 0.0;
-    dm->devStateFresh = true; dm->posOnDevice = true; dm->mirrorsStale = true; dm->headStale = true;
-    dm->devCarryValid = true; dm->hostCarryStale = true;
-    pendingOf(dm).valid = false;
+    leaveStateOnDevice(dm);
     std::memset(&dm->lastSum, 0, sizeof(dm->lastSum));
     dm->lastSum.anyOpen = 1;                          // (not tracked per step: the carry rows are valid, which is all `anyOpen` guards)
     dm->lastSum.more = (R.lastMore || R.tail) ? 1 : 0;
@@ -1470,8 +1517,7 @@ static int residentFlush(lorahip_demod *dm, size_t *nPackets, int64_t *calls)
         const StreamLayout H = headLayout(dm);
         unsigned near[2] = {0, 0};
         LORAHIP_TRY(hipMemcpy(near, dm->sDev + H.oNear, sizeof(near), hipMemcpyDeviceToHost));
-        dm->nNearSquelch += int64_t(unsigned(near[0] - dm->nearSeen[0])); dm->nNearStep += int64_t(unsigned(near[1] - dm->nearSeen[1]));
-        dm->nearSeen[0] = near[0]; dm->nearSeen[1] = near[1];
+        foldNear(dm, near[0], near[1]);
     }
     if (lost)
     {
@@ -1488,24 +1534,20 @@ static int residentStep(lorahip_demod *dm, const float *iqDev, const size_t rowS
                         int64_t *calls, bool &handled)
 {
     handled = false;
-    Pipe &P = pipeOf(dm);
-    Pipe::Resident &R = P.res;
+    Resident &R = dm->res;
     lorahip_ctx *ctx = dm->ctx;
     const size_t N = dm->N, B = dm->B;
-    const bool stream = dm->mode == 1 || (dm->mode == 0 && streamAvailable(ctx->sf));
-    const bool compatible = stream && ctx->sf >= 7 && ctx->sf <= 12 && !dm->tracing && !dm->portsOn && !dm->activatePending && dm->sDev != nullptr &&
-                            dm->append && !dm->appendFresh && dm->uniStride == rowStride && nValid >= dm->appendPrev && dm->dCarry != nullptr &&
-                            dm->mtu + 1 <= dm->carryCap && !P.active && rowsHold(rows, 1) &&
+    const bool compatible = steadyAppend(dm, rowStride, nValid) && ctx->sf >= 7 && ctx->sf <= 12 && !dm->pipe.active && rowsHold(rows, 1) &&
                             // rows of whole 128-byte lines: a step then never reads a line that holds samples which arrive later (no cache to invalidate)
                             (rowStride & 15u) == 0 && (reinterpret_cast<uintptr_t>(iqDev) & 127u) == 0;
-    if (R.active && (!compatible || iqDev != P.iq))
+    if (R.active && (!compatible || iqDev != dm->stepIq))
     {
         setLastError("lorahip_demod_receive (resident): a setting or the rows changed under the resident kernel (lorahip_demod_receive_flush first)");
         return LORAHIP_E_INVALID;
     }
     if (!R.active)
     {
-        const bool ready = compatible && !R.unavailable && dm->devStateFresh && (dm->devCarryValid || !dm->lastSum.anyOpen) && !pendingOf(dm).valid;
+        const bool ready = compatible && !R.unavailable && stateOnDevice(dm);
         if (!ready) return LORAHIP_OK;
         const DeviceGuard guard(ctx->device);
         if (R.ctl == nullptr)
@@ -1533,25 +1575,10 @@ static int residentStep(lorahip_demod *dm, const float *iqDev, const size_t rowS
         LORAHIP_TRY(hipHostGetDevicePointer(&hostDev, R.host, 0));
         std::memset(R.host, 0, sizeof(ResidentHost));
         LORAHIP_TRY(hipMemsetAsync(R.ctl, 0, std::getenv("LORAHIP_RESIDENT_DEBUG") ? sizeof(ResidentCtl) : offsetof(ResidentCtl, dbgWave), ctx->stream));
-        const StreamLayout H = headLayout(dm);
-        char *d = R.rec;
-        StreamArgs a;
-        a.iq = reinterpret_cast<const float2 *>(iqDev);
-        a.base = nullptr; a.len = nullptr;
-        a.uniformLen = 0; a.uniformStride = (long long)rowStride;       // (the length of a step comes with its message)
+        StreamArgs a = makeStreamArgs(dm, iqDev, L, R.rec);
+        a.uniformLen = 0;                             // (the length of a step comes with its message)
         a.flags = 4 | 8;
-        a.carry = dm->dCarry; a.carryCap = int(dm->carryCap); a.maxBlocks = 0; a.lanes = -1; a.lastRoundFrom = 0;
-        a.state = reinterpret_cast<StreamState *>(dm->sDev + H.oState);
-        a.nCalls = reinterpret_cast<int *>(d + L.oN); a.nSym = reinterpret_cast<int *>(d + L.oNSym); a.nPkt = reinterpret_cast<int *>(d + L.oNPkt);
-        a.nSig = reinterpret_cast<int *>(d + L.oNSig); a.end = reinterpret_cast<int2 *>(d + L.oEnd);
-        a.pktOut = reinterpret_cast<StreamPacket *>(d + L.oPkt); a.symOut = reinterpret_cast<short *>(d + L.oSym);
-        a.sigOut = dm->wantSignals ? reinterpret_cast<StreamSignal *>(d + L.oSig) : nullptr; a.calls = nullptr;
-        a.down = ctx->dDown; a.fine = ctx->dFine; a.twStage = ctx->dTwStage;
-        a.fineA = ctx->fineGather ? nullptr : ctx->dFineA; a.fineB = ctx->fineGather ? nullptr : ctx->dFineB;
-        a.nChannels = unsigned(B); a.cap = int(cap); a.symStride = int(L.symStride); a.capPkt = int(capPkt);
-        a.powerScale = ctx->powerScale; a.thresh = dm->thresh; a.sync = dm->sync;
-        a.mtu = dm->mtu > 0xffffffffu ? 0xffffffffu : unsigned(dm->mtu);
-        a.near = reinterpret_cast<unsigned *>(dm->sDev + H.oNear);
+        a.maxBlocks = 0; a.lanes = -1;
         a.res = R.ctl; a.resHost = static_cast<ResidentHost *>(hostDev); a.resWatchdog = kResidentWatchdog; a.resRecStride = L.total;
         if (const char *e = std::getenv("LORAHIP_RESIDENT_DEBUG")) a.resDebug = unsigned(std::atoi(e));     // (the step whose stamps every wavefront leaves)
         if (const char *e = std::getenv("LORAHIP_RESIDENT_SLEEP")) a.resSleep = std::atoi(e);             // (measurements: profiles/r06)
@@ -1577,7 +1604,7 @@ static int residentStep(lorahip_demod *dm, const float *iqDev, const size_t rowS
                 return LORAHIP_OK;
             }
         }
-        P.iq = iqDev; P.rowStride = rowStride;
+        dm->stepIq = iqDev; dm->stepStride = rowStride;
         dm->devStateFresh = false;                    // until the kernel has left, only it knows where the state stands
     }
     handled = true;
@@ -1595,8 +1622,7 @@ static int residentStep(lorahip_demod *dm, const float *iqDev, const size_t rowS
     { const int rc = residentRing(dm, nValid & ~size_t(15), rows, 0u); if (rc != LORAHIP_OK) { residentAbort(dm); return rc; } }
     R.lastValid = nValid & ~size_t(15);
     R.tail = (nValid & 15u) != 0;
-    dm->uniform = true; dm->uniSpc = nValid; dm->uniStride = rowStride; dm->appendPrev = nValid; dm->geomApplied = false;
-    dm->mirrorsStale = true; dm->headStale = true;
+    noteSteadyStep(dm, rowStride, nValid);
     if (R.seq <= R.depth) return LORAHIP_OK;
     // ... and while it runs: the step `depth` calls back
     size_t pk = 0, sg = 0;
@@ -1774,7 +1800,7 @@ static int fillPorts(lorahip_demod *dm, const float *iqDev)
 
 static int runAny(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
 {
-    const bool stream = dm->mode == 1 || (dm->mode == 0 && streamAvailable(dm->ctx->sf));
+    const bool stream = usesStreamKernel(dm);
     if (stream && !streamAvailable(dm->ctx->sf)) { setLastError("no streaming kernel for this SF"); return LORAHIP_E_INVALID; }
     { const int rc = refuseWhilePiped(dm); if (rc != LORAHIP_OK) return rc; }
     { const int rc = drainPending(dm); if (rc != LORAHIP_OK) return rc; }       // the previous run's records, if still on the device
@@ -1813,41 +1839,12 @@ int lorahip_demod_create(lorahip_demod **out, const int device, const int sf, co
     *out = nullptr;
     lorahip_demod *dm = new (std::nothrow) lorahip_demod();
     if (dm == nullptr) return LORAHIP_E_NOMEM;
-    dm->comp = nullptr;
-    dm->ctx = nullptr; dm->h = nullptr; dm->d = nullptr; dm->dIq = nullptr; dm->dIqSamples = 0;
-    dm->evK0 = nullptr; dm->evK1 = nullptr; dm->evJoin = nullptr; dm->kernelMs = 0.0; dm->dSumScratch = nullptr;
-    dm->pending = new (std::nothrow) PendingLaunch();
-    dm->pipe = new (std::nothrow) Pipe();
-    if (dm->pending == nullptr || dm->pipe == nullptr) { delete static_cast<PendingLaunch *>(dm->pending); delete static_cast<Pipe *>(dm->pipe); delete dm; return LORAHIP_E_NOMEM; }
-    pendingOf(dm).valid = false;
-    std::memset(dm->pipe, 0, sizeof(Pipe));
-    std::memset(&dm->ports, 0, sizeof(dm->ports)); dm->portsOn = false; dm->userTracing = false; dm->dPort = nullptr; dm->dPortBytes = 0;
-    std::memset(&dm->hostPorts, 0, sizeof(dm->hostPorts)); dm->ownFft = dm->ownDec = dm->ownRaw = nullptr;
-    dm->mode = 0; dm->sDev = nullptr; dm->sHost = nullptr; dm->sBytes = 0; dm->dDense = nullptr; dm->hDense = nullptr; dm->denseBytes = 0;
     int rc = lorahip_create(&dm->ctx, device, sf);
     if (rc != LORAHIP_OK) { const std::string e = lorahip_last_error(); lorahip_demod_destroy(dm); setLastError(e); return rc; }
     dm->N = size_t(1) << sf;
     dm->B = n_channels;
-    dm->sync = 0x12; dm->thresh = -30.0f; dm->mtu = 256;        // LoRaDemod.cpp:71-73
-    dm->tracing = false;
-    dm->workCalls = 0;
-    dm->nNearSquelch = dm->nNearStep = 0;
-    dm->devStateFresh = false; dm->mirrorsStale = false; dm->activatePending = false;
-    dm->uniform = false; dm->uniSpc = 0; dm->uniStride = 0; dm->geomApplied = true; dm->portCountsDirty = true; dm->posOnDevice = false;
-    dm->append = false; dm->appendFresh = true; dm->appendPrev = 0; dm->headStale = false; dm->nearSeen[0] = dm->nearSeen[1] = 0;
-    std::memset(&dm->lastSum, 0, sizeof(dm->lastSum));
-    dm->wantSignals = false;
-    std::memset(&dm->sigRows, 0, sizeof(dm->sigRows)); dm->sigRowsOn = false; dm->lastSignals = 0;
-    dm->streamGrid = 0;
-    dm->streamCapMax = 0;
-    dm->streamLanes = 0;
-    dm->coWaves = 0;
-    dm->lastLaunches = 0;
-    dm->dCarry = nullptr; dm->carryCap = 0; dm->devCarryValid = false; dm->hostCarryStale = false;
-    dm->callsPerWindowQ8 = 288;                                 // 1.125 calls per N samples to begin with
-    try { dm->ch.resize(n_channels); }
+    try { dm->ch.resize(n_channels); }                              // (value-initialised too: every count and position zero)
     catch (const std::bad_alloc &) { lorahip_demod_destroy(dm); return LORAHIP_E_NOMEM; }
-    for (auto &k : dm->ch) { k.traceStart = 0; k.traceSymCount0 = 0; k.portFft = k.portDec = k.portRaw = 0; k.callCount = 0; k.runStart = 0; }
     dm->stageBytes = carve(nullptr, n_channels).total;
     bool staged;
     {
@@ -1937,29 +1934,25 @@ void lorahip_demod_destroy(lorahip_demod *dm)
     if (dm->evK1) (void)hipEventDestroy(dm->evK1);
     if (dm->evJoin) (void)hipEventDestroy(dm->evJoin);
     if (dm->dSumScratch) (void)hipFree(dm->dSumScratch);
-    if (dm->pipe)
+    residentAbort(dm);                                        // (a resident kernel must leave before its memory goes)
+    const Resident &R = dm->res;
+    if (R.ctl) (void)hipFree(R.ctl);
+    if (R.host) (void)hipHostFree(R.host);
+    if (R.rec) (void)hipFree(R.rec);
+    if (R.run) (void)hipStreamDestroy(R.run);
+    if (R.ev) (void)hipEventDestroy(R.ev);
+    const Pipe &P = dm->pipe;
+    for (int i = 0; i < 2; i++)
     {
-        Pipe &P = pipeOf(dm);
-        residentAbort(dm);                                        // (a resident kernel must leave before its memory goes)
-        if (P.res.ctl) (void)hipFree(P.res.ctl);
-        if (P.res.host) (void)hipHostFree(P.res.host);
-        if (P.res.rec) (void)hipFree(P.res.rec);
-        if (P.res.run) (void)hipStreamDestroy(P.res.run);
-        if (P.res.ev) (void)hipEventDestroy(P.res.ev);
-        for (int i = 0; i < 2; i++)
-        {
-            if (P.dev[i]) (void)hipFree(P.dev[i]);
-            if (P.hSum) (void)hipEventDestroy(P.ev[i]);
-        }
-        if (P.side) { (void)hipStreamSynchronize(P.side); (void)hipStreamDestroy(P.side); }
-        if (P.packDone) (void)hipEventDestroy(P.packDone);
-        if (P.entry) (void)hipEventDestroy(P.entry);
-        if (P.hSum) (void)hipHostFree(P.hSum);
+        if (P.dev[i]) (void)hipFree(P.dev[i]);
+        if (P.hSum) (void)hipEventDestroy(P.ev[i]);
     }
+    if (P.side) { (void)hipStreamSynchronize(P.side); (void)hipStreamDestroy(P.side); }
+    if (P.packDone) (void)hipEventDestroy(P.packDone);
+    if (P.entry) (void)hipEventDestroy(P.entry);
+    if (P.hSum) (void)hipHostFree(P.hSum);
     }
     lorahip_destroy(dm->ctx);
-    delete static_cast<PendingLaunch *>(dm->pending);
-    delete static_cast<Pipe *>(dm->pipe);
     delete dm;
 }
 
@@ -2131,8 +2124,7 @@ int lorahip_demod_run_device(lorahip_demod *dm, const float *iq_dev, const size_
     { const int rc = refuseWhilePiped(dm); if (rc != LORAHIP_OK) return rc; }         // before anything of the object changes
     // n_channels streams of equal length back to back: the placement is two numbers, not 3 * n_channels (ch[].base / len / pos are
     // filled only for the paths that read them, applyGeometry)
-    dm->uniform = true; dm->uniSpc = dm->uniStride = samples_per_channel; dm->geomApplied = false; dm->posOnDevice = false;
-    dm->append = false; dm->appendFresh = true;
+    placeUniform(dm, samples_per_channel, samples_per_channel, false);
     return runAny(dm, iq_dev, rounds);
 }
 
@@ -2144,9 +2136,7 @@ int lorahip_demod_run_device_append(lorahip_demod *dm, const float *iq_dev, cons
     if (!dm->appendFresh && n_valid < dm->appendPrev) { setLastError("an append run was given fewer samples than the one before it (lorahip_demod_rewind starts a new stream)"); return LORAHIP_E_INVALID; }
     // every channel's stream is the first n_valid samples of its row; a channel continues at its own read position (the device's
     // copy of the state holds it: nothing is uploaded per run)
-    dm->uniform = true; dm->uniSpc = n_valid; dm->uniStride = row_stride; dm->geomApplied = false;
-    if (dm->appendFresh) dm->posOnDevice = false;
-    dm->append = true;
+    placeUniform(dm, n_valid, row_stride, true);
     return runAny(dm, iq_dev, rounds);
 }
 
@@ -2172,14 +2162,7 @@ int lorahip_demod_run_device_segments(lorahip_demod *dm, const float *iq_dev, co
     }
     if (any && iq_dev == nullptr) return LORAHIP_E_INVALID;
     const DeviceGuard guard(dm->ctx->device);
-    dm->uniform = false; dm->geomApplied = true; dm->posOnDevice = false;
-    dm->append = false; dm->appendFresh = true;
-    for (size_t c = 0; c < dm->B; c++)
-    {
-        dm->ch[c].base = size_t(first_sample[c]);
-        dm->ch[c].len = n_samples[c];
-        dm->ch[c].pos = 0; dm->ch[c].callCount = 0;
-    }
+    placeSegments(dm, n_samples, [&](const size_t c) { return size_t(first_sample[c]); });
     return runAny(dm, iq_dev, rounds);
 }
 
@@ -2198,22 +2181,9 @@ int lorahip_demod_run(lorahip_demod *dm, const float *const *streams, const size
         if ((n_samples[c] && streams[c] == nullptr) || n_samples[c] > (size_t(1) << 48)) return LORAHIP_E_INVALID;
     size_t total = 0;
     for (size_t c = 0; c < dm->B; c++) total += n_samples[c];
-    if (total > dm->dIqSamples)
-    {
-        if (dm->dIq) { (void)hipFree(dm->dIq); dm->dIq = nullptr; dm->dIqSamples = 0; }
-        LORAHIP_TRY(hipMalloc((void **)&dm->dIq, (total ? total : 1) * sizeof(cf32)));
-        dm->dIqSamples = total;
-    }
-    dm->uniform = false; dm->geomApplied = true; dm->posOnDevice = false;
-    dm->append = false; dm->appendFresh = true;
+    if (total > dm->dIqSamples) { const int rc = regrowIq(dm, total); if (rc != LORAHIP_OK) return rc; }
     total = 0;
-    for (size_t c = 0; c < dm->B; c++)
-    {
-        dm->ch[c].base = total;
-        dm->ch[c].len = n_samples[c];
-        dm->ch[c].pos = 0; dm->ch[c].callCount = 0;
-        total += n_samples[c];
-    }
+    placeSegments(dm, n_samples, [&](const size_t c) { const size_t at = total; total += n_samples[c]; return at; });     // back to back
     {
         // the channels' buffers gathered into one device array back to back (base = running total): pinned double-buffered upload
         std::vector<const void *> src(dm->B);
@@ -2263,24 +2233,11 @@ int lorahip_demod_run_host_rows(lorahip_demod *dm, const float *rows, const size
     if (width && rows == nullptr) return LORAHIP_E_INVALID;
     if (width > (size_t(1) << 40) / (dm->B ? dm->B : 1)) return LORAHIP_E_INVALID;
     const DeviceGuard guard(dm->ctx->device);
-    const size_t total = dm->B * width;
-    if (total > dm->dIqSamples)
-    {
-        if (dm->dIq) { (void)hipFree(dm->dIq); dm->dIq = nullptr; dm->dIqSamples = 0; }
-        LORAHIP_TRY(hipMalloc((void **)&dm->dIq, (total ? total : 1) * sizeof(cf32)));
-        dm->dIqSamples = total;
-    }
+    if (dm->B * width > dm->dIqSamples) { const int rc = regrowIq(dm, dm->B * width); if (rc != LORAHIP_OK) return rc; }
     if (width)
         LORAHIP_TRY(hipMemcpy2DAsync(dm->dIq, width * sizeof(cf32), rows + 2 * lo, row_stride * sizeof(cf32), width * sizeof(cf32), dm->B, hipMemcpyHostToDevice,
                                      dm->ctx->stream));
-    dm->uniform = false; dm->geomApplied = true; dm->posOnDevice = false;
-    dm->append = false; dm->appendFresh = true;
-    for (size_t c = 0; c < dm->B; c++)
-    {
-        dm->ch[c].base = n_samples[c] ? c * width + (size_t(first_sample[c]) - lo) : 0;
-        dm->ch[c].len = n_samples[c];
-        dm->ch[c].pos = 0; dm->ch[c].callCount = 0;
-    }
+    placeSegments(dm, n_samples, [&](const size_t c) { return n_samples[c] ? c * width + (size_t(first_sample[c]) - lo) : 0; });
     return runAny(dm, dm->dIq, rounds);               // (in stream order behind the copy; returns with the stream drained: the rows are the caller's again)
 }
 
@@ -2307,7 +2264,7 @@ size_t lorahip_demod_num_packets(const lorahip_demod *dm)
 {
     if (dm == nullptr) return 0;
     if (dm->comp) return dm->comp->numPackets();
-    const PendingLaunch &P = pendingOf(const_cast<lorahip_demod *>(dm));
+    const PendingLaunch &P = dm->pending;
     return dm->packets.size() + (P.valid ? P.packets : 0);      // known from the per-channel counts: no drain needed
 }
 
@@ -2333,7 +2290,7 @@ size_t lorahip_demod_num_packet_symbols(const lorahip_demod *dm)
 {
     if (dm == nullptr) return 0;
     if (dm->comp) return dm->comp->numPacketSymbols();
-    const PendingLaunch &P = pendingOf(const_cast<lorahip_demod *>(dm));
+    const PendingLaunch &P = dm->pending;
     return dm->pktSyms.size() + (P.valid ? P.packetSyms : 0);
 }
 
@@ -2366,7 +2323,7 @@ static int packetsToDevice(lorahip_demod *dm, uint16_t *syms_dev, const size_t s
         // (rows: channels ascending, time ascending inside a channel). A channel that entered the launch inside a packet found
         // its symbols at the head of its row (carryLoad); only a run that had to take them from the mirrors (anyCarryIn: packets
         // longer than the carry rows, launches of a resumed run) takes the queue path below.
-        PendingLaunch &Q = pendingOf(dm);
+        PendingLaunch &Q = dm->pending;
         if (Q.valid && dm->packets.empty() && !Q.anyCarryIn)
         {
             const size_t n = Q.packets;
@@ -2374,16 +2331,11 @@ static int packetsToDevice(lorahip_demod *dm, uint16_t *syms_dev, const size_t s
             if (n == 0) return LORAHIP_OK;
             if (syms_dev == nullptr || nsyms_dev == nullptr || sym_stride == 0 || sym_stride > 0x7fffffffu || cap_packets < n) return LORAHIP_E_INVALID;
             const DeviceGuard guard(dm->ctx->device);
-            const StreamLayout &L = Q.lay;
-            const size_t nbRow = align256(L.B * sizeof(int));
-            { const int grc = growDense(dm, nbRow + n * sizeof(long long)); if (grc != LORAHIP_OK) return grc; }
+            { const int grc = growDense(dm, align256(Q.lay.B * sizeof(int)) + n * sizeof(long long)); if (grc != LORAHIP_OK) return grc; }
             hipStream_t st = dm->ctx->stream;
             // the rows are numbered on the device (scanDescribe: exclusive prefix sum of the per-channel packet counts): nothing is
             // uploaded, and nothing on the host is reused, so the caller decides whether to wait
-            LORAHIP_TRY(launchPackPackets(reinterpret_cast<const StreamPacket *>(dm->sDev + L.oPkt), reinterpret_cast<const int *>(dm->sDev + L.oNPkt),
-                                          reinterpret_cast<const short *>(dm->sDev + L.oSym), reinterpret_cast<int *>(dm->dDense), L.B, int(L.symStride),
-                                          int(L.capPkt), n, reinterpret_cast<long long *>(dm->dDense + nbRow), syms_dev, int(sym_stride), nsyms_dev,
-                                          channel_dev, st));
+            LORAHIP_TRY(packPackets(dm, Q.lay, dm->sDev, n, syms_dev, sym_stride, nsyms_dev, channel_dev, st));
             if (sync) LORAHIP_TRY(hipStreamSynchronize(st));
             return LORAHIP_OK;
         }
@@ -2430,16 +2382,14 @@ static int signalsToRows(lorahip_demod *dm, const size_t first, size_t *n, const
     const lorahip_signal_rows &R = dm->sigRows;
     const DeviceGuard guard(dm->ctx->device);
     hipStream_t st = dm->ctx->stream;
-    PendingLaunch &Q = pendingOf(dm);
+    PendingLaunch &Q = dm->pending;
     if (Q.valid && dm->signals.empty())
     {
         *n = Q.signals;
         if (*n == 0) return LORAHIP_OK;
         if (first + *n > R.cap) { setLastError("lorahip_demod_receive: the signal rows cannot hold the signals that are due"); return LORAHIP_E_INVALID; }
-        const StreamLayout &L = Q.lay;
-        if (!L.signals) { *n = 0; return LORAHIP_OK; }
-        LORAHIP_TRY(launchPackSignals(reinterpret_cast<const StreamSignal *>(dm->sDev + L.oSig), reinterpret_cast<const int *>(dm->sDev + L.oNSig), L.B,
-                                      int(L.capPkt), R.channel, R.error, R.power, R.snr, first, R.cap, st));
+        if (!Q.lay.signals) { *n = 0; return LORAHIP_OK; }
+        LORAHIP_TRY(packSignals(dm, Q.lay, dm->sDev, first, st));
         if (sync) LORAHIP_TRY(hipStreamSynchronize(st));
         return LORAHIP_OK;
     }
@@ -2476,8 +2426,8 @@ size_t lorahip_demod_receive_num_signals(const lorahip_demod *dm) { return dm &&
 
 size_t lorahip_demod_receive_steps(const lorahip_demod *dm, size_t *packets, size_t *signals, const size_t cap)
 {
-    if (dm == nullptr || dm->comp || dm->pipe == nullptr) return 0;
-    const Pipe::Resident &R = static_cast<const Pipe *>(dm->pipe)->res;
+    if (dm == nullptr || dm->comp) return 0;
+    const Resident &R = dm->res;
     for (unsigned i = 0; i < R.nRep && i < cap; i++)
     {
         if (packets) packets[i] = R.repPk[i];
@@ -2488,7 +2438,7 @@ size_t lorahip_demod_receive_steps(const lorahip_demod *dm, size_t *packets, siz
 
 int lorahip_demod_resident_active(const lorahip_demod *dm)
 {
-    return dm && !dm->comp && dm->pipe && static_cast<const Pipe *>(dm->pipe)->res.active ? 1 : 0;
+    return dm && !dm->comp && dm->res.active ? 1 : 0;
 }
 
 int lorahip_demod_receive(lorahip_demod *dm, const float *iq_dev, const size_t row_stride, const size_t n_valid, const lorahip_packet_rows *rows,
@@ -2504,13 +2454,13 @@ int lorahip_demod_receive(lorahip_demod *dm, const float *iq_dev, const size_t r
         bool handled = false;
         if (rows->async == 3)
         {
-            if (pipeOf(dm).active) { setLastError("a pipelined step is in flight: lorahip_demod_receive_flush first"); return LORAHIP_E_INVALID; }
+            if (dm->pipe.active) { setLastError("a pipelined step is in flight: lorahip_demod_receive_flush first"); return LORAHIP_E_INVALID; }
             const int prc = residentStep(dm, iq_dev, row_stride, n_valid, rows, n_packets, work_calls, handled);
             if (handled || prc != LORAHIP_OK) return prc;
         }
         else
         {
-            if (pipeOf(dm).res.active) { setLastError("the resident kernel is on the device: lorahip_demod_receive_flush first"); return LORAHIP_E_INVALID; }
+            if (dm->res.active) { setLastError("the resident kernel is on the device: lorahip_demod_receive_flush first"); return LORAHIP_E_INVALID; }
             const int prc = pipeStep(dm, iq_dev, row_stride, n_valid, rows, n_packets, work_calls, handled);
             if (handled || prc != LORAHIP_OK) return prc;
         }
@@ -2532,6 +2482,34 @@ int lorahip_demod_receive(lorahip_demod *dm, const float *iq_dev, const size_t r
     return LORAHIP_OK;
 }
 
+/*! The LAST step of a pipelined or resident receiver filled a channel's record or packet capacity (lastSum.more): that channel still
+ * holds >= 2N samples nobody would look at again. An ordinary step over the same rows resumes it until dry (the receiver has been
+ * left: this is lorahip_demod_receive's own path), its packets into `rows` from row `row` on, its signals into the signal rows from
+ * row `sig` on. If THEY do not fit they stay queued like any ordinary step's (LORAHIP_E_INVALID, *nPackets = all rows needed; the
+ * first rows are filled; lorahip_demod_packets_to_device / the next receive delivers the rest). The counts add to the flush's own:
+ * n0 packets, c0 work() calls, lastSignals. */
+static int flushResume(lorahip_demod *dm, const lorahip_packet_rows *rows, const size_t row, const size_t sig, const size_t n0, const int64_t c0,
+                       size_t *nPackets, int64_t *calls)
+{
+    const int64_t calls0 = dm->workCalls;
+    int rc = lorahip_demod_run_device_append(dm, dm->stepIq, dm->stepStride, dm->appendPrev, nullptr);
+    if (rc != LORAHIP_OK) return rc;
+    if (calls) *calls = c0 + (dm->workCalls - calls0);
+    if (rows == nullptr) { lorahip_demod_clear_packets(dm); return LORAHIP_OK; }
+    size_t n2 = 0;
+    rc = packetsToDevice(dm, rows->syms_dev ? rows->syms_dev + row * rows->sym_stride : nullptr, rows->sym_stride, rows->nsyms_dev ? rows->nsyms_dev + row : nullptr,
+                         rows->channel_dev ? rows->channel_dev + row : nullptr, rows->cap_packets - row, &n2, true);
+    if (nPackets) *nPackets = n0 + n2;
+    if (rc != LORAHIP_OK) return rc;
+    const size_t s1 = dm->lastSignals;
+    size_t s2 = 0;
+    rc = signalsToRows(dm, sig, &s2, true);
+    dm->lastSignals = s1 + s2;
+    if (rc != LORAHIP_OK) return rc;
+    lorahip_demod_clear_packets(dm);
+    return LORAHIP_OK;
+}
+
 int lorahip_demod_receive_flush(lorahip_demod *dm, const lorahip_packet_rows *rows, size_t *n_packets, int64_t *work_calls)
 {
     if (dm == nullptr || (rows != nullptr && rows->struct_size != sizeof(lorahip_packet_rows))) return LORAHIP_E_INVALID;
@@ -2539,67 +2517,27 @@ int lorahip_demod_receive_flush(lorahip_demod *dm, const lorahip_packet_rows *ro
     if (work_calls) *work_calls = 0;
     if (dm->comp) return LORAHIP_OK;
     dm->lastSignals = 0;                                    // (a flush with nothing in flight delivers nothing: not the count of the call before)
-    pipeOf(dm).res.nRep = 0;
-    if (pipeOf(dm).res.active)
+    dm->res.nRep = 0;
+    if (dm->res.active)
     {
         // the resident receiver: every step's rows came with its own call; what is left to report are the counts of the last step(s)
         size_t n0 = 0; int64_t c0 = 0;
-        int rc0 = residentFlush(dm, &n0, &c0);
+        const int rc0 = residentFlush(dm, &n0, &c0);
         if (n_packets) *n_packets = n0;
         if (work_calls) *work_calls = c0;
         if (rc0 != LORAHIP_OK || dm->lastSum.more == 0) return rc0;
-        // a channel still holds samples its last step could not record: an ordinary step over the same rows takes them (as below)
-        const Pipe &P0 = pipeOf(dm);
-        const int64_t calls0 = dm->workCalls;
-        rc0 = lorahip_demod_run_device_append(dm, P0.iq, P0.rowStride, dm->appendPrev, nullptr);
-        if (rc0 != LORAHIP_OK) return rc0;
-        if (work_calls) *work_calls = c0 + (dm->workCalls - calls0);
-        if (rows == nullptr) { lorahip_demod_clear_packets(dm); return LORAHIP_OK; }
-        size_t n2 = 0;
-        rc0 = packetsToDevice(dm, rows->syms_dev, rows->sym_stride, rows->nsyms_dev, rows->channel_dev, rows->cap_packets, &n2, true);
-        if (n_packets) *n_packets = n0 + n2;                  // (n0 of them in the rows of their own calls, n2 in these)
-        if (rc0 != LORAHIP_OK) return rc0;
-        {
-            const size_t s1 = dm->lastSignals;
-            size_t s2 = 0;
-            rc0 = signalsToRows(dm, 0, &s2, true);            // (into the rows registered now, from row 0: the steps' signals are in their own)
-            dm->lastSignals = s1 + s2;
-            if (rc0 != LORAHIP_OK) return rc0;
-        }
-        lorahip_demod_clear_packets(dm);
-        return LORAHIP_OK;
+        // packets and signals of the resumed channels into these rows from row 0 on (the steps' are in the rows of their own calls)
+        return flushResume(dm, rows, 0, 0, n0, c0, n_packets, work_calls);
     }
     const bool wasPiped = pipeBusy(dm);
     size_t n1 = 0;
     int64_t c1 = 0;
-    int rc = pipeFlush(dm, rows, &n1, &c1);
+    const int rc = pipeFlush(dm, rows, &n1, &c1);
     if (n_packets) *n_packets = n1;
     if (work_calls) *work_calls = c1;
     if (rc != LORAHIP_OK || !wasPiped || dm->lastSum.more == 0) return rc;
-    // The LAST step filled a channel's record or packet capacity: that channel still holds >= 2N samples nobody would look at again.
-    // An ordinary step over the same rows resumes it until dry (the pipeline is left: this is lorahip_demod_receive's own path), its
-    // packets behind the ones above. If THEY do not fit they stay queued like any ordinary step's (LORAHIP_E_INVALID, *n_packets =
-    // all rows needed; the first rows are filled; lorahip_demod_packets_to_device / the next receive delivers the rest).
-    const Pipe &P = pipeOf(dm);
-    const int64_t calls0 = dm->workCalls;
-    rc = lorahip_demod_run_device_append(dm, P.iq, P.rowStride, dm->appendPrev, nullptr);
-    if (rc != LORAHIP_OK) return rc;
-    if (work_calls) *work_calls = c1 + (dm->workCalls - calls0);
-    if (rows == nullptr) { lorahip_demod_clear_packets(dm); return LORAHIP_OK; }
-    size_t n2 = 0;
-    rc = packetsToDevice(dm, rows->syms_dev ? rows->syms_dev + n1 * rows->sym_stride : nullptr, rows->sym_stride, rows->nsyms_dev ? rows->nsyms_dev + n1 : nullptr,
-                         rows->channel_dev ? rows->channel_dev + n1 : nullptr, rows->cap_packets - n1, &n2, true);
-    if (n_packets) *n_packets = n1 + n2;
-    if (rc != LORAHIP_OK) return rc;
-    {
-        const size_t s1 = dm->lastSignals;
-        size_t s2 = 0;
-        rc = signalsToRows(dm, s1, &s2, true);
-        dm->lastSignals = s1 + s2;
-        if (rc != LORAHIP_OK) return rc;
-    }
-    lorahip_demod_clear_packets(dm);
-    return LORAHIP_OK;
+    // packets and signals of the resumed channels behind the ones just delivered
+    return flushResume(dm, rows, n1, dm->lastSignals, n1, c1, n_packets, work_calls);
 }
 
 int lorahip_demod_set_signals(lorahip_demod *dm, const int enable)
@@ -2614,7 +2552,7 @@ size_t lorahip_demod_num_signals(const lorahip_demod *dm)
 {
     if (dm == nullptr) return 0;
     if (dm->comp) return dm->comp->numSignals();
-    const PendingLaunch &P = pendingOf(const_cast<lorahip_demod *>(dm));
+    const PendingLaunch &P = dm->pending;
     return dm->signals.size() + (P.valid ? P.signals : 0);
 }
 
@@ -2639,7 +2577,7 @@ void lorahip_demod_clear_packets(lorahip_demod *dm)
 {
     if (dm == nullptr) return;
     if (dm->comp) { dm->comp->clearPackets(); return; }
-    PendingLaunch &P = pendingOf(dm);
+    PendingLaunch &P = dm->pending;
     if (P.valid)
     {
         // records still on the device: they can simply be dropped unless a channel is inside a packet -- the symbols it has
@@ -2685,7 +2623,7 @@ int lorahip_demod_consumed_all(const lorahip_demod *dm, int64_t *out)
     if (dm == nullptr || out == nullptr) return LORAHIP_E_INVALID;
     if (dm->comp) return dm->comp->consumedAll(out);
     // (while the resident kernel is on the device the positions live in its steps; a copy queued behind it could wait for the flush)
-    if (dm->pipe && static_cast<const Pipe *>(dm->pipe)->res.active)
+    if (dm->res.active)
     {
         setLastError("the resident kernel is on the device: lorahip_demod_receive_flush first");
         return LORAHIP_E_INVALID;
