@@ -628,6 +628,9 @@ int lorahip_decode_max_data_length(void);
  * run(): consumes n_in samples, writes *n_out = lorahip_channelizer_out_count(c, n_in) samples per channel at
  * out_dev + k*out_stride (complex64, out_stride in samples >= *n_out). decim*(256 + n_taps/decim) samples must
  * fit the LDS (decim <= 64 for short filters).
+ * Limits of one call (run and run_captures alike; a longer stream is fed in several calls): at most 2^30 outputs per channel
+ * (8 GiB a row), and channel groups x tiles = ceil(n_channels / 8) * (outputs / 256 + 1) at most 2^31 - 1 (the launch grid). A call beyond either is refused with
+ * LORAHIP_E_INVALID and consumes nothing. Rows, strides and the stream position are addressed with 64 bits.
  * ------------------------------------------------------------------------------------- */
 typedef struct lorahip_channelizer lorahip_channelizer;
 uint64_t lorahip_channelizer_phase_inc(double freq);          /* floor(frac(freq) * 2^64) */

@@ -261,21 +261,24 @@ __global__ __launch_bounds__(CHAN_THREADS) void channelize(const ChanArgs a)
     const v2f mine = mixerPhase(unsigned((a.w[chBase + (t & (CHAN_KG - 1))] * (unsigned long long)((mTile + 1) * D - 1)) >> 32));
     int mineRe = __float_as_int(mine.x), mineIm = __float_as_int(mine.y);
     asm volatile("" : "+v"(mineRe), "+v"(mineIm));             // two separate registers for the lane reads below
-    const int mLoc = int(mTile - a.mLo) + t;                    // this call's output index (a call makes < 2^30 outputs)
+    const long long mTileLoc = mTile - a.mLo;                   // the tile's first output in this call (< 0: the call starts inside the tile)
+    const int mLoc = int(mTileLoc) + t;                         // this call's output index (a call makes <= 2^30 outputs)
 #pragma unroll
     for (int k = 0; k < CHAN_KG; k++)
     {
         const int ch = chBase + k;                              // w, step, laneRot are padded to whole groups
         const v2f base = {__int_as_float(__builtin_amdgcn_readlane(mineRe, k)), __int_as_float(__builtin_amdgcn_readlane(mineIm, k))};
         v2f rot = cmulF(a.laneRot[ch * CHAN_THREADS + t], base);
-        char *o = reinterpret_cast<char *>(a.out + (size_t)blockIdx.y * a.captureOut + (size_t)ch * a.outStride);     // uniform; + 32-bit byte offset per lane
+        // uniform 64-bit address of the tile's first output in row ch (2^30 outputs are 2^33 bytes: a 32-bit byte offset from the
+        // start of the row would wrap at output 2^29); + a 32-bit byte offset per lane inside the tile
+        char *o = reinterpret_cast<char *>(uintptr_t(a.out) + ((long long)blockIdx.y * a.captureOut + (long long)ch * a.outStride + mTileLoc) * 8);
 #pragma unroll
         for (int r = 0; r < RM; r++)
         {
             if (r) rot = cmulF(rot, a.step[ch]);                // the output 256 places on: phase advanced by w*256*D
             const v2f y = cmulF(acc[r][k], rot);
             const int ml = mLoc + r * CHAN_THREADS;
-            if (ch < a.K && ml >= 0 && ml < int(a.nOut)) *reinterpret_cast<float2 *>(o + unsigned(ml) * 8u) = make_float2(y.x, y.y);
+            if (ch < a.K && ml >= 0 && ml < int(a.nOut)) *reinterpret_cast<float2 *>(o + unsigned(t + r * CHAN_THREADS) * 8u) = make_float2(y.x, y.y);
         }
     }
 }
