@@ -613,6 +613,58 @@ int lorahip_decode_max_symbols(void);
 int lorahip_decode_max_data_length(void);
 
 /* -------------------------------------------------------------------------------------
+ * Batched encoder (the first block of the chain): what the LoRaEncoder block does with one message of bytes
+ * (LoRaEncoder.cpp:161-233 on LoRaCodes.hpp), for n_packets messages of different lengths at once. Parameters and defaults are
+ * the block's (LoRaEncoder.cpp:78-85, setters :101-133): coding rate "4/4".."4/8" = rdd 0..4.
+ *   packet p: nbytes_dev[p] payload bytes at bytes_dev + p*byte_stride (byte_stride <= lorahip_encode_max_bytes() = 4096)
+ *   nsyms_dev[p]: the number of symbols written at syms_dev + p*sym_stride (sym_stride <= lorahip_decode_max_symbols()), or
+ *       -1 where the reference has no defined result: an empty payload without crc and without header (its symbol count
+ *          `8 + (numCodewords / PPM - 1) * (4 + rdd)` wraps for numCodewords == 0), or a negative nbytes_dev[p];
+ *       -2 where a row is too short: nbytes_dev[p] > byte_stride, or the packet's symbols > sym_stride.
+ *   The symbols of a row behind the packet's own are written as 0 up to sym_stride (the whole row for -1 / -2), nothing behind the row.
+ *   PAD NIBBLES ARE ZERO. Where 2 * bytes + header codewords is not a multiple of PPM the reference's encodeFec reads up to
+ *   (PPM - 1) / 2 bytes past the end of its byte vector (LoRaEncoder.cpp:202,206), i.e. whatever the heap holds. This encoder
+ *   defines the pad nibbles as 0, then FEC-encoded and whitened like any data nibble: the symbols equal the reference's wherever
+ *   the reference is defined, and equal the reference's for the payload extended by zero bytes where it is not. The decoder never
+ *   reads pad codewords. A payload of more than 255 bytes with an explicit header is encoded as the reference does it: all the
+ *   bytes, length field & 0xff.
+ *   LORAHIP_E_INVALID: struct_size mismatch, sf outside 1..12, ppm > sf (the reference throws), rdd outside 0..4, explicit header
+ *   with PPM < 5 (the reference's `PPM - cOfs` wraps), byte_stride or sym_stride beyond the limits above. ctx supplies the device
+ *   and the stream only (any SF).
+ * ------------------------------------------------------------------------------------- */
+typedef struct lorahip_encoder_cfg {
+    size_t struct_size;     /* = sizeof(lorahip_encoder_cfg) */
+    int32_t sf;             /* setSpreadFactor      default 10 */
+    int32_t ppm;            /* setSymbolSize        default 0 = sf */
+    int32_t rdd;            /* setCodingRate        default 4 ("4/8") */
+    int32_t explicit_hdr;   /* enableExplicit       default 1 */
+    int32_t crc;            /* enableCrc            default 1 */
+    int32_t whitening;      /* enableWhitening      default 1 */
+} lorahip_encoder_cfg;
+/* host only: the symbols of a packet of n_bytes payload bytes; -1 for the undefined case above, for a configuration that
+ * lorahip_encode_packets refuses and for n_bytes > lorahip_encode_max_bytes(). Never decreases with n_bytes. */
+long lorahip_encode_num_symbols(const lorahip_encoder_cfg *cfg, size_t n_bytes);
+/* the longest payload (4096 bytes, = lorahip_decode_max_data_length()): byte_stride <= this */
+int lorahip_encode_max_bytes(void);
+int lorahip_encode_packets(lorahip_ctx *ctx, const lorahip_encoder_cfg *cfg, const uint8_t *bytes_dev, size_t byte_stride,
+                           const int32_t *nbytes_dev, size_t n_packets, uint16_t *syms_dev, size_t sym_stride, int32_t *nsyms_dev);
+/* The same with every buffer in HOST memory (staged through the context's pinned buffer; synchronous). */
+int lorahip_encode_packets_host(lorahip_ctx *ctx, const lorahip_encoder_cfg *cfg, const uint8_t *bytes, size_t byte_stride,
+                                const int32_t *nbytes, size_t n_packets, uint16_t *syms, size_t sym_stride, int32_t *nsyms);
+
+/* -------------------------------------------------------------------------------------
+ * The batched modulator for frames of DIFFERENT lengths (the encoder's rows): frame f has nsyms_dev[f] symbols at
+ * syms_dev + f*sym_stride (max_nsyms <= sym_stride) and is walked like a frame of lorahip_mod_frames, then continued with zero
+ * chirps to the common length lorahip_mod_frame_len(sf, max_nsyms, padding) <= frame_stride: row f equals the frame
+ * lorahip_mod_frames (and the LoRaMod block) produces for the same symbols with padding + max_nsyms - nsyms_dev[f]
+ * (padding 0 counts as 1, as there). A frame with nsyms_dev[f] < 0 -- a packet the encoder refused -- or > max_nsyms is written as
+ * all zeros. No host round trip between lorahip_encode_packets and this call: max_nsyms = lorahip_encode_num_symbols(cfg, byte_stride)
+ * bounds every packet of the launch.
+ * ------------------------------------------------------------------------------------- */
+int lorahip_mod_frames_var(lorahip_ctx *ctx, float *iq_dev, size_t frame_stride, const uint16_t *syms_dev, size_t sym_stride,
+                           const int32_t *nsyms_dev, size_t n_frames, size_t max_nsyms, unsigned char sync, float ampl, size_t padding);
+
+/* -------------------------------------------------------------------------------------
  * Front-end channeliser (the step before the path: SURVEY.md section 8f #4). NOT a reference component: the
  * reference's topologies put Pothos' /comms/rotate and a decimating FIR in front of every LoRaDemod block; this
  * does that for K channels of one wideband stream at once and writes the [channel][time] layout

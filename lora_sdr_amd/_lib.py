@@ -39,6 +39,11 @@ class DecoderCfg(C.Structure):
                                                                           "explicit_hdr", "hdr", "data_length")]
 
 
+class EncoderCfg(C.Structure):
+    """struct lorahip_encoder_cfg"""
+    _fields_ = [("struct_size", C.c_size_t)] + [(n, C.c_int32) for n in ("sf", "ppm", "rdd", "explicit_hdr", "crc", "whitening")]
+
+
 class DemodPorts(C.Structure):
     """struct lorahip_demod_ports"""
     _fields_ = [("struct_size", C.c_size_t), ("fft_dev", C.c_void_p), ("fft_cap_frames", C.c_size_t), ("dec_dev", C.c_void_p),
@@ -153,6 +158,12 @@ SIGNATURES = {
                                              C.c_void_p, C.c_void_p]),
     "lorahip_decode_max_symbols": (C.c_int, []),
     "lorahip_decode_max_data_length": (C.c_int, []),
+    "lorahip_encode_num_symbols": (C.c_long, [C.c_void_p, C.c_size_t]),
+    "lorahip_encode_max_bytes": (C.c_int, []),
+    "lorahip_encode_packets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "lorahip_encode_packets_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "lorahip_mod_frames_var": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_ubyte,
+                                        C.c_float, C.c_size_t]),
     "lorahip_channelizer_phase_inc": (C.c_uint64, [C.c_double]),
     "lorahip_channelizer_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "lorahip_channelizer_destroy": (None, [C.c_void_p]),

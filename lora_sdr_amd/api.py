@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import Batch, DecoderCfg, WorkResult, check, load, CHIRP_UP, CHIRP_DOWN, CHIRP_NONE  # noqa: F401
+from ._lib import Batch, DecoderCfg, EncoderCfg, WorkResult, check, load, CHIRP_UP, CHIRP_DOWN, CHIRP_NONE  # noqa: F401
 
 
 # lorahip_work_result as a numpy record (include/lorahip.h)
@@ -245,9 +245,13 @@ class Context:
     def mod_frame_len(self, nsyms, padding=1):
         return int(self._lib.lorahip_mod_frame_len(self.sf, int(nsyms), int(padding)))
 
-    def mod_frames(self, syms, sync=0x12, ampl=1.0, padding=1, frame_stride=None, lead=0, tail=0):
+    def mod_frames(self, syms, sync=0x12, ampl=1.0, padding=1, frame_stride=None, lead=0, tail=0, nsyms=None):
         """The LoRaMod block (LoRaMod.cpp:109-238) for a batch of packets: syms is a (n_frames, nsyms) 16-bit device
-        tensor; returns a (n_frames, lead + frame_stride + tail) complex64 device tensor, zero outside the frames."""
+        tensor; returns a (n_frames, lead + frame_stride + tail) complex64 device tensor, zero outside the frames.
+
+        nsyms: an optional (n_frames,) int32 device tensor of per-frame symbol counts (the encoder's output), read on the device
+        (lorahip_mod_frames_var): frame f is modulated from its first nsyms[f] symbols and continued with zero chirps to the length
+        of a frame of syms.shape[1] symbols; a negative or larger count gives an all-zero row."""
         import torch
         if syms.dim() != 2 or syms.dtype not in (torch.int16, torch.uint16):
             raise ValueError("syms must be a (n_frames, nsyms) 16-bit integer device tensor")
@@ -261,6 +265,12 @@ class Context:
         iq = torch.zeros((F, row), dtype=torch.complex64, device=syms.device)
         self.use_torch_stream()
         base = iq.data_ptr() + 8 * lead
+        if nsyms is not None:
+            if nsyms.dtype != torch.int32 or nsyms.numel() != F:
+                raise ValueError("nsyms must be a (n_frames,) int32 device tensor")
+            check(self._lib.lorahip_mod_frames_var(self._h, C.c_void_p(base), row, _dptr(syms), S, _dptr(nsyms.contiguous()), F, S,
+                                                   int(sync) & 0xff, float(ampl), int(padding)), "lorahip_mod_frames_var")
+            return iq
         check(self._lib.lorahip_mod_frames(self._h, C.c_void_p(base), row, _dptr(syms), F, S, int(sync) & 0xff, float(ampl),
                                            int(padding)), "lorahip_mod_frames")
         return iq
@@ -1125,3 +1135,114 @@ class LoRaDecoder:
             else:
                 res.append(out[i, :2 * out_len[i]].view(np.uint16).copy())
         return res
+
+
+class LoRaEncoder:
+    """The `/lora/lora_encoder` block (LoRaEncoder.cpp), same setters and defaults, for batches of byte messages of different lengths.
+
+    work(messages): list of bytes-like -> list of uint16 symbol arrays (None where the block has no defined result: an empty message
+    without crc and header); encode_batch(): the same on device tensors. Pad nibbles are 0 (include/lorahip.h)."""
+
+    _CR = LoRaDecoder._CR
+
+    def __init__(self, device=0, ctx=None):
+        self._ctx = ctx if ctx is not None else Context(7, device=device)   # device + stream only; the encoder has its own sf
+        self._cfg = EncoderCfg(C.sizeof(EncoderCfg), 10, 0, 4, 1, 1, 1)    # LoRaEncoder.cpp:78-85
+
+    @staticmethod
+    def make():
+        return LoRaEncoder()
+
+    def setSpreadFactor(self, sf): self._cfg.sf = int(sf)
+    def setSymbolSize(self, ppm): self._cfg.ppm = int(ppm)
+
+    def setCodingRate(self, cr):
+        if cr not in self._CR:
+            raise ValueError("LoRaEncoder::setCodingRate(%s): unknown coding rate" % cr)   # InvalidArgumentException :118
+        self._cfg.rdd = self._CR[cr]
+
+    def enableWhitening(self, on): self._cfg.whitening = int(bool(on))
+    def enableExplicit(self, on): self._cfg.explicit_hdr = int(bool(on))
+    def enableCrc(self, on): self._cfg.crc = int(bool(on))
+
+    def num_symbols(self, n_bytes):
+        """symbols of a message of n_bytes bytes (host arithmetic); -1 where nothing is defined or the configuration is refused"""
+        return int(self._ctx._lib.lorahip_encode_num_symbols(C.byref(self._cfg), int(n_bytes)))
+
+    def encode_batch(self, data, nbytes, sym_stride=None):
+        """data: (P, stride) uint8 device tensor, nbytes: (P,) int32 device tensor -> (syms uint16-as-int16 (P, sym_stride), nsyms int32
+        (P,)) device tensors, queued on the torch stream. sym_stride defaults to what a message of `stride` bytes needs."""
+        import torch
+        if data.dim() != 2 or data.dtype != torch.uint8 or nbytes.dtype != torch.int32 or nbytes.numel() != data.shape[0]:
+            raise ValueError("data must be a (P, stride) uint8, nbytes a (P,) int32 device tensor")
+        data, nbytes = data.contiguous(), nbytes.contiguous()
+        P, stride = int(data.shape[0]), int(data.shape[1])
+        if sym_stride is None:
+            sym_stride = max(8, self.num_symbols(min(stride, self._ctx._lib.lorahip_encode_max_bytes())))
+        syms = torch.empty((P, int(sym_stride)), dtype=torch.int16, device=data.device)
+        nsyms = torch.empty(P, dtype=torch.int32, device=data.device)
+        self._ctx.use_torch_stream()
+        check(self._ctx._lib.lorahip_encode_packets(self._ctx._h, C.byref(self._cfg), C.c_void_p(data.data_ptr()), stride, _dptr(nbytes), P,
+                                                    _dptr(syms), int(sym_stride), _dptr(nsyms)), "lorahip_encode_packets")
+        return syms, nsyms
+
+    def work(self, messages):
+        import torch
+        if self._cfg.ppm > self._cfg.sf:
+            raise ValueError("LoRaEncoder::work(): failed check: PPM <= SF")            # Pothos::Exception :166
+        P = len(messages)
+        if P == 0:
+            return []
+        host, n = _pack_rows(messages)
+        dev = torch.device("cuda", self._ctx.device)
+        syms, nsyms = self.encode_batch(torch.from_numpy(host).to(dev), torch.from_numpy(n).to(dev))
+        syms, nsyms = syms.cpu().numpy().view(np.uint16), nsyms.cpu().numpy()
+        if (nsyms == -2).any():
+            raise ValueError("LoRaEncoder.work(): a message is longer than this build encodes (lorahip_encode_max_bytes())")
+        return [syms[i, :nsyms[i]].copy() if nsyms[i] >= 0 else None for i in range(P)]
+
+
+def _pack_rows(messages):
+    """list of bytes-like -> ((P, stride) uint8 rows, (P,) int32 lengths)"""
+    arrs = [np.frombuffer(bytes(m), np.uint8) if isinstance(m, (bytes, bytearray, memoryview)) else np.asarray(m).astype(np.uint8).reshape(-1)
+            for m in messages]
+    host = np.zeros((len(arrs), max(1, max(a.size for a in arrs))), np.uint8)
+    for i, a in enumerate(arrs):
+        host[i, :a.size] = a
+    return host, np.array([a.size for a in arrs], np.int32)
+
+
+def transmit(payloads, sf=10, cr="4/8", sync=0x12, ampl=1.0, padding=1, sigma=0.0, seed=0, nbytes=None, ppm=0, explicit=True, crc=True,
+             whitening=True, lead=0, tail=0, ctx=None, device=0):
+    """bytes -> symbols -> IQ -> (noise) on the device, for messages of different lengths: LoRaEncoder.encode_batch ->
+    Context.mod_frames(nsyms=) -> Context.add_awgn, all queued on the torch stream with no host synchronisation in between.
+
+    payloads: a list of bytes-like, or a (P, stride) uint8 device tensor with nbytes a (P,) int32 device tensor.
+    ctx: a Context(sf) to reuse (one is made and closed otherwise). Returns (iq (P, lead + frame + tail) complex64, nsyms (P,) int32):
+    every row has the length of the longest message `stride` bytes can make; a refused message (nsyms < 0) gives a silent row."""
+    import torch
+    own = ctx is None
+    if own:
+        ctx = Context(sf, device=device)
+    elif ctx.sf != int(sf):
+        raise ValueError("ctx is a Context of SF%d, not SF%d" % (ctx.sf, sf))
+    try:
+        if not _is_torch(payloads):
+            host, n = _pack_rows(payloads)
+            dev = torch.device("cuda", ctx.device)
+            payloads, nbytes = torch.from_numpy(host).to(dev), torch.from_numpy(n).to(dev)
+        elif nbytes is None:
+            raise ValueError("device payload rows need nbytes, a (P,) int32 device tensor")
+        enc = LoRaEncoder(ctx=ctx)
+        enc.setSpreadFactor(sf); enc.setSymbolSize(ppm); enc.setCodingRate(cr)
+        enc.enableExplicit(explicit); enc.enableCrc(crc); enc.enableWhitening(whitening)
+        syms, nsyms = enc.encode_batch(payloads, nbytes)
+        iq = ctx.mod_frames(syms, sync=sync, ampl=ampl, padding=padding, lead=lead, tail=tail, nsyms=nsyms)
+        if sigma:
+            ctx.add_awgn(iq, sigma, seed)
+        if own:
+            ctx.synchronize()                  # the context's tables must outlive the queued work
+        return iq, nsyms
+    finally:
+        if own:
+            ctx.close()

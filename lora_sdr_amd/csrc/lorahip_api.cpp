@@ -545,6 +545,94 @@ int lorahip_decode_max_symbols(void) { return decodeMaxSymbols(); }
 int lorahip_decode_max_data_length(void) { return decodeMaxDataLength(); }
 
 /***********************************************************************
+ * batched encoder (lorahip_codec.hip: encodeGroup) and the modulator with per-frame symbol counts (lorahip_tx.hip)
+ **********************************************************************/
+//! what LoRaEncoder::work() cannot do either: PPM > SF throws (LoRaEncoder.cpp:166); an explicit header with PPM < 5 makes `PPM - cOfs`
+//! wrap (:200). sf as the decoder configuration accepts it.
+static bool encoderCfgOk(const lorahip_encoder_cfg *cfg)
+{
+    if (cfg == nullptr || cfg->struct_size != sizeof(lorahip_encoder_cfg)) return false;
+    if (cfg->sf < 1 || cfg->sf > LORAHIP_SF_MAX || cfg->ppm < 0 || cfg->ppm > cfg->sf || cfg->rdd < 0 || cfg->rdd > 4) return false;
+    if (cfg->explicit_hdr && (cfg->ppm ? cfg->ppm : cfg->sf) < 5)
+    {
+        setLastError("explicit header needs a symbol size (PPM) of at least 5 bits");
+        return false;
+    }
+    return true;
+}
+
+long lorahip_encode_num_symbols(const lorahip_encoder_cfg *cfg, const size_t n_bytes)
+{
+    if (!encoderCfgOk(cfg) || n_bytes > size_t(decodeMaxDataLength())) return -1;
+    return encodeNumSymbols(cfg->sf, cfg->ppm, cfg->rdd, cfg->explicit_hdr, cfg->crc, n_bytes);
+}
+
+int lorahip_encode_max_bytes(void) { return decodeMaxDataLength(); }
+
+int lorahip_encode_packets(lorahip_ctx *ctx, const lorahip_encoder_cfg *cfg, const uint8_t *bytes_dev, const size_t byte_stride,
+                           const int32_t *nbytes_dev, const size_t n_packets, uint16_t *syms_dev, const size_t sym_stride,
+                           int32_t *nsyms_dev)
+{
+    if (ctx == nullptr || !encoderCfgOk(cfg)) return LORAHIP_E_INVALID;
+    if (byte_stride > size_t(lorahip_encode_max_bytes()) || sym_stride == 0 || sym_stride > size_t(decodeMaxSymbols())) return LORAHIP_E_INVALID;
+    if (n_packets == 0) return LORAHIP_OK;
+    if ((byte_stride && !bytes_dev) || !nbytes_dev || !syms_dev || !nsyms_dev || n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
+    const DeviceGuard guard(ctx->device);
+    EncodeArgs a;
+    a.bytes = bytes_dev; a.nbytes = nbytes_dev; a.syms = syms_dev; a.nsyms = nsyms_dev;
+    a.nPackets = unsigned(n_packets); a.byteStride = int(byte_stride); a.symStride = int(sym_stride);
+    a.sf = cfg->sf; a.ppm = cfg->ppm; a.rdd = cfg->rdd; a.explicitHdr = cfg->explicit_hdr ? 1 : 0; a.crc = cfg->crc ? 1 : 0;
+    a.whitening = cfg->whitening ? 1 : 0;
+    LORAHIP_TRY(launchEncode(a, ctx->stream));
+    return LORAHIP_OK;
+}
+
+/* The same for a caller in HOST memory: staged through the context's pinned buffer like lorahip_decode_packets_host; synchronous. */
+int lorahip_encode_packets_host(lorahip_ctx *ctx, const lorahip_encoder_cfg *cfg, const uint8_t *bytes, const size_t byte_stride,
+                                const int32_t *nbytes, const size_t n_packets, uint16_t *syms, const size_t sym_stride, int32_t *nsyms)
+{
+    if (ctx == nullptr || !encoderCfgOk(cfg)) return LORAHIP_E_INVALID;
+    if (byte_stride > size_t(lorahip_encode_max_bytes()) || sym_stride == 0 || sym_stride > size_t(decodeMaxSymbols())) return LORAHIP_E_INVALID;
+    if (n_packets == 0) return LORAHIP_OK;
+    if ((byte_stride && !bytes) || !nbytes || !syms || !nsyms || n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
+    const DeviceGuard guard(ctx->device);
+    struct Piece { size_t off, bytes; };
+    size_t cur = 0;
+    auto carve = [&cur](const size_t bytes) { Piece p = { cur, bytes }; cur += (bytes + 255) & ~size_t(255); return p; };
+    const Piece pByte = carve(n_packets * byte_stride);
+    const Piece pN = carve(n_packets * sizeof(int32_t));
+    const size_t inBytes = cur;
+    const Piece pSym = carve(n_packets * sym_stride * sizeof(uint16_t));
+    const Piece pLen = carve(n_packets * sizeof(int32_t));
+    { const int rc = growStage(ctx, cur, cur); if (rc != LORAHIP_OK) return rc; }
+    char *d = static_cast<char *>(ctx->dStage), *h = static_cast<char *>(ctx->hStage);
+    if (pByte.bytes) std::memcpy(h + pByte.off, bytes, pByte.bytes);
+    std::memcpy(h + pN.off, nbytes, pN.bytes);
+    LORAHIP_TRY(hipMemcpyAsync(d, h, inBytes, hipMemcpyHostToDevice, ctx->stream));
+    const int rc = lorahip_encode_packets(ctx, cfg, reinterpret_cast<const uint8_t *>(d + pByte.off), byte_stride, reinterpret_cast<const int32_t *>(d + pN.off),
+                                          n_packets, reinterpret_cast<uint16_t *>(d + pSym.off), sym_stride, reinterpret_cast<int32_t *>(d + pLen.off));
+    if (rc != LORAHIP_OK) return rc;
+    LORAHIP_TRY(hipMemcpyAsync(h + inBytes, d + inBytes, cur - inBytes, hipMemcpyDeviceToHost, ctx->stream));
+    LORAHIP_TRY(hipStreamSynchronize(ctx->stream));
+    std::memcpy(syms, h + pSym.off, pSym.bytes);
+    std::memcpy(nsyms, h + pLen.off, pLen.bytes);
+    return LORAHIP_OK;
+}
+
+int lorahip_mod_frames_var(lorahip_ctx *ctx, float *iq_dev, const size_t frame_stride, const uint16_t *syms_dev, const size_t sym_stride,
+                           const int32_t *nsyms_dev, const size_t n_frames, const size_t max_nsyms, const unsigned char sync,
+                           const float ampl, const size_t padding)
+{
+    if (ctx == nullptr || (n_frames && (!iq_dev || !syms_dev || !nsyms_dev)) || max_nsyms == 0 || max_nsyms > 0x7fffffu || padding > 0x7fffffu) return LORAHIP_E_INVALID;
+    // a frame reads up to max_nsyms symbols of its row
+    if (sym_stride < max_nsyms || n_frames > 0xffffffffu || frame_stride < lorahip_mod_frame_len(ctx->sf, max_nsyms, padding)) return LORAHIP_E_INVALID;
+    const DeviceGuard guard(ctx->device);
+    LORAHIP_TRY(launchModFramesVar(reinterpret_cast<float2 *>(iq_dev), (long long)frame_stride, syms_dev, (long long)sym_stride, nsyms_dev, n_frames,
+                                   int(max_nsyms), int(sync), ampl, int(padding), ctx->sf, ctx->stream));
+    return LORAHIP_OK;
+}
+
+/***********************************************************************
  * LoRaDetector<float> shim
  **********************************************************************/
 } // extern "C"

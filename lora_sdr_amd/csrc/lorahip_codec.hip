@@ -645,6 +645,200 @@ hipError_t launchDecode(const DecodeArgs &a, const int variant, hipStream_t stre
     return launchDecodeGroup<64>(a, caps, stream);
 }
 
+/***********************************************************************
+ * group-per-packet encoder (LoRaEncoder.cpp:161-233 on LoRaCodes.hpp): bytes -> symbols
+ **********************************************************************/
+namespace {
+
+//! the sx FEC of one nibble at coding rate rdd (LoRaCodes.hpp: encodeHamming84sx / 74sx, encodeParity64 / 54): the parity bits are
+//! the decoder's cover masks over the data bits; 4/7 and 4/6 are prefixes of 4/8, 4/5 is one parity bit over the nibble
+__device__ __forceinline__ unsigned encodeNibble(const unsigned nib, const int rdd)
+{
+    const unsigned x = nib & 0xf;
+    if (rdd == 0) return x;
+    if (rdd == 1) return x | ((unsigned)parityOf(x) << 4);
+    const unsigned full = x | ((unsigned)parityOf(x & LORAHIP_COVER0 & 0xf) << 4) | ((unsigned)parityOf(x & LORAHIP_COVER1 & 0xf) << 5) |
+                          ((unsigned)parityOf(x & LORAHIP_COVER2 & 0xf) << 6) | ((unsigned)parityOf(x & LORAHIP_COVER3 & 0xf) << 7);
+    return full & (0xffu >> (4 - rdd));
+}
+
+} // namespace
+
+/*! What a launch can need of a group's LDS slice: the payload + crc bytes, then the codewords. Both follow from the ROWS (a packet whose
+ * bytes or symbols do not fit its rows is refused with -2 before it touches the slice), not from the packet. */
+struct EncodeCaps { int byteCap, cwCap; };
+
+/* A group of G lanes owns a packet. Pass 1: a lane per payload byte -- load (contiguous), keep in LDS, its term of the crc (byte * x^(8 k)
+ * mod P, as decodeGroup sums it); the group's xor is the checksum, lane 0 appends it. Pass 2: a lane per codeword -- nibble from LDS, FEC,
+ * whitening from the sequence table (the encoder's Sx1272ComputeWhitening and the decoder's two registers give the same bytes: position
+ * = codeword index behind the header codewords, in both blocks). Pass 3: a lane per output symbol -- bit m = bit k of codeword
+ * (m + k) % PPM of its interleaver block, Gray -> binary, shift; lanes store consecutive symbols of the row, zeros behind the packet.
+ * Pad nibbles (codewords behind the last byte, up to a whole block) are 0: the reference reads them past the end of its vector. */
+template <int G>
+__global__ void __launch_bounds__(256) encodeGroup(const EncodeArgs a, const EncodeCaps caps, const int perBlock)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smemEnc[];
+    const int slice = (caps.byteCap + caps.cwCap + 15) & ~15;
+    const int g = threadIdx.x / G, t = threadIdx.x % G;
+    unsigned char *sByte = smemEnc + (size_t)g * slice;
+    unsigned char *sCw = sByte + caps.byteCap;
+    const unsigned p = blockIdx.x * perBlock + g;
+    const bool have = g < perBlock && p < a.nPackets;
+    const unsigned pc = have ? p : 0;
+    const int len = have ? a.nbytes[pc] : 0;
+    const unsigned char *in = a.bytes + (size_t)pc * a.byteStride;
+    unsigned short *out = a.syms + (size_t)pc * a.symStride;
+
+    const int sf = a.sf;
+    const int PPM = a.ppm == 0 ? sf : a.ppm;                                                 // LoRaEncoder.cpp:165
+    const int bs = 4 + a.rdd;
+    const int hdrCw = a.explicitHdr ? LORAHIP_N_HDR_CODEWORDS : 0;
+    int outcome = -1;                                                                        // nothing defined (see lorahip.h)
+    bool go = have && len >= 0;
+    if (go && len > a.byteStride) { outcome = -2; go = false; }
+    const int nb = go ? len + (a.crc ? 2 : 0) : 0;                                           // :171
+    const int numCodewords = ((2 * nb + hdrCw + PPM - 1) / PPM) * PPM;                       // :175
+    const int numSymbols = LORAHIP_N_HDR_SYMBOLS + (numCodewords / PPM - 1) * bs;            // :176
+    if (go && numCodewords == 0) go = false;                                                 // numCodewords / PPM - 1 wraps in the reference
+    if (go && (numSymbols > a.symStride || numCodewords > caps.cwCap || nb > caps.byteCap)) { outcome = -2; go = false; }
+
+    // ---- pass 1: bytes into LDS, checksum (:181-185; sx1272DataChecksum = the crc of decodeGroup) ---------------------------
+    if (go)
+    {
+        unsigned acc = 0;
+        for (int i = t; i < len; i += G)
+        {
+            const unsigned byte = in[i];
+            sByte[i] = (unsigned char)byte;
+            if (a.crc) acc ^= crcShift(byte, kCodec.xpow[len - 1 - i]);
+        }
+        if (a.crc)
+        {
+            unsigned crc = groupXor<G>(acc);
+            crc ^= kCodec.lfsr8[len];
+            crc ^= (unsigned)kCodec.lfsr8[len + 1] << 8;
+            if (t == 0) { sByte[len] = (unsigned char)(crc & 0xff); sByte[len + 1] = (unsigned char)((crc >> 8) & 0xff); }
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __syncthreads();
+
+    // ---- pass 2: FEC + whitening, one codeword per lane and round (:187-212) -------------------------------------------------
+    if (go)
+    {
+        unsigned char h[3] = { 0, 0, 0 };
+        if (a.explicitHdr)
+        {
+            h[0] = (unsigned char)(len & 0xff);                                              // :189-192
+            h[1] = (unsigned char)((a.crc ? 1 : 0) | (a.rdd << 1));
+            h[2] = headerChecksum(h);
+        }
+        for (int c = t; c < numCodewords; c += G)
+        {
+            unsigned cw;
+            if (c < hdrCw)                                                                   // :194-198, always 4/8, never whitened
+            {
+                const unsigned nib = c == 0 ? h[0] >> 4 : c == 1 ? h[0] & 0xf : c == 2 ? h[1] & 0xf : c == 3 ? h[2] >> 4 : h[2] & 0xf;
+                cw = encodeNibble(nib, LORAHIP_HDR_RDD);
+            }
+            else
+            {
+                const int d = c - hdrCw;                                                     // data nibble, low nibble of a byte first
+                const int R = c < PPM ? LORAHIP_HDR_RDD : a.rdd;                             // the first block is always 4/8
+                const unsigned byte = (d >> 1) < nb ? sByte[d >> 1] : 0u;                    // pad nibbles are 0
+                cw = encodeNibble((d & 1) ? byte >> 4 : byte & 0xf, R);
+                if (a.whitening && (d >> 1) < LORAHIP_WHITEN_LEN)
+                    cw ^= kCodec.white[R == 1 ? 1 : 0][d & 1][d >> 1] & (0xffu >> (4 - R));
+            }
+            sCw[c] = (unsigned char)cw;
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __syncthreads();
+
+    // ---- pass 3: diagonal interleave (LoRaCodes.hpp diagonalInterleaveSx), Gray -> binary, shift (:215-226) ------------------
+    if (have)
+    {
+        const int nOut = go ? numSymbols : 0;
+        for (int s = t; s < a.symStride; s += G)
+        {
+            unsigned sym = 0;
+            if (s < nOut)
+            {
+                int cwOff = 0, k = s;
+                if (s >= LORAHIP_N_HDR_SYMBOLS)
+                {
+                    const int x = (s - LORAHIP_N_HDR_SYMBOLS) / bs;
+                    k = (s - LORAHIP_N_HDR_SYMBOLS) - x * bs;
+                    cwOff = PPM + x * PPM;
+                }
+                int i = k % PPM;
+                for (int m = 0; m < PPM; m++)
+                {
+                    sym |= ((sCw[cwOff + i] >> k) & 1u) << m;
+                    if (++i == PPM) i = 0;
+                }
+                sym ^= sym >> 8; sym ^= sym >> 4; sym ^= sym >> 2; sym ^= sym >> 1;          // grayToBinary16
+                sym = (sym << (sf - PPM)) & 0xffffu;
+            }
+            out[s] = (unsigned short)sym;
+        }
+        if (t == 0) a.nsyms[p] = go ? numSymbols : outcome;
+    }
+}
+
+//! symbols of a packet of n payload bytes (LoRaEncoder.cpp:171-176); -1 where the reference's own expression wraps
+long encodeNumSymbols(const int sf, const int ppm, const int rdd, const int explicitHdr, const int crc, const size_t nBytes)
+{
+    const long PPM = ppm == 0 ? sf : ppm;
+    const long nb = long(nBytes) + (crc ? 2 : 0);
+    const long numCodewords = ((2 * nb + (explicitHdr ? LORAHIP_N_HDR_CODEWORDS : 0) + PPM - 1) / PPM) * PPM;
+    if (numCodewords == 0) return -1;
+    return LORAHIP_N_HDR_SYMBOLS + (numCodewords / PPM - 1) * (4 + rdd);
+}
+
+static EncodeCaps encodeCaps(const EncodeArgs &a)
+{
+    const long PPM = a.ppm == 0 ? a.sf : a.ppm, bs = 4 + a.rdd;
+    const long nbMax = long(a.byteStride) + (a.crc ? 2 : 0);
+    const long cwByBytes = ((2 * nbMax + (a.explicitHdr ? LORAHIP_N_HDR_CODEWORDS : 0) + PPM - 1) / PPM) * PPM;
+    const long cwBySyms = a.symStride < LORAHIP_N_HDR_SYMBOLS ? 0 : ((a.symStride - LORAHIP_N_HDR_SYMBOLS) / bs + 1) * PPM;
+    EncodeCaps c;
+    c.cwCap = int(cwByBytes < cwBySyms ? cwByBytes : cwBySyms);
+    c.byteCap = (c.cwCap / 2 + 2 + 3) & ~3;
+    return c;
+}
+
+template <int G>
+static hipError_t launchEncodeGroup(const EncodeArgs &a, const EncodeCaps &caps, hipStream_t stream)
+{
+    const size_t slice = size_t((caps.byteCap + caps.cwCap + 15) & ~15);
+    const size_t ldsMax = 160 * 1024;
+    unsigned perBlock = 256 / G;
+    if (slice > ldsMax) return hipErrorInvalidValue;                // (lorahip_encode_packets bounds byte_stride: cannot happen)
+    if (slice * perBlock > ldsMax) perBlock = unsigned(ldsMax / slice);
+    static unsigned long long attrDone = 0;
+    {
+        const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(encodeGroup<G>), ldsMax, attrDone);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((encodeGroup<G>), dim3((a.nPackets + perBlock - 1) / perBlock), dim3(256), slice * perBlock, stream, a, caps, int(perBlock));
+    return hipGetLastError();
+}
+
+hipError_t launchEncode(const EncodeArgs &a, hipStream_t stream)
+{
+    if (a.nPackets == 0) return hipSuccess;
+    const EncodeCaps caps = encodeCaps(a);
+    // lanes per packet by the symbols a row of this launch can hold (a lane per symbol in the last pass, about as many codewords)
+    const long bySyms = LORAHIP_N_HDR_SYMBOLS + (caps.cwCap / (a.ppm == 0 ? a.sf : a.ppm) - 1) * (4 + a.rdd);
+    const long rowSyms = caps.cwCap == 0 ? 0 : bySyms;
+    if (rowSyms <= 48) return launchEncodeGroup<8>(a, caps, stream);
+    if (rowSyms <= 96) return launchEncodeGroup<16>(a, caps, stream);
+    if (rowSyms <= 200) return launchEncodeGroup<32>(a, caps, stream);
+    return launchEncodeGroup<64>(a, caps, stream);
+}
+
 // rows: the de-whitening takes its length as a uint16_t in the reference (LoRaCodes.hpp: Sx1272ComputeWhiteningLfsr), i.e. messages of
 // up to 65535 codewords are what the reference itself decodes as written; 16384 symbols stay below that at every setting
 int decodeMaxSymbols() { return 16384; }

@@ -253,6 +253,20 @@ hipError_t launchDecode(const DecodeArgs &a, int variant, hipStream_t stream);  
 int decodeMaxSymbols();
 int decodeMaxDataLength();
 
+//! argument block of the batched encoder (lorahip_codec.hip: encodeGroup); device pointers
+struct EncodeArgs
+{
+    const unsigned char *bytes;     // [nPackets][byteStride]
+    const int *nbytes;              // [nPackets]
+    unsigned short *syms;           // [nPackets][symStride], zero behind a packet's symbols
+    int *nsyms;                     // [nPackets] symbols written, -1 nothing defined, -2 a row is too short
+    unsigned nPackets;
+    int byteStride, symStride;
+    int sf, ppm, rdd, explicitHdr, crc, whitening;
+};
+hipError_t launchEncode(const EncodeArgs &a, hipStream_t stream);
+long encodeNumSymbols(int sf, int ppm, int rdd, int explicitHdr, int crc, size_t nBytes);
+
 //! launchers (lorahip_kernels.hip / lorahip_fast.hip)
 hipError_t launchDetect(int sf, int variant, const DetectArgs &a, const FastTables &ft, hipStream_t stream);
 bool fastAvailable(int sf);
@@ -290,6 +304,9 @@ hipError_t launchSynth(int sf, float2 *iq, const unsigned short *sym, size_t nWi
 
 hipError_t launchModFrames(float2 *iq, long long frameStride, const unsigned short *syms, size_t nFrames, int nsyms, int sync,
                            float ampl, int padding, int sf, hipStream_t stream);
+//! per-frame symbol counts read on the device (lorahip_tx.hip); every frame is walked to the length of maxNsyms symbols
+hipError_t launchModFramesVar(float2 *iq, long long frameStride, const unsigned short *syms, long long symStride, const int *nsyms,
+                              size_t nFrames, int maxNsyms, int sync, float ampl, int padding, int sf, hipStream_t stream);
 hipError_t launchAwgn(float2 *iq, size_t n, float sigma, unsigned long long seed, hipStream_t stream);
 hipError_t launchMembw(const float2 *iq, size_t nBytes, int pattern, int blocks, float *scratch, hipStream_t stream);
 
