@@ -1,6 +1,6 @@
 // C ABI of liblorahip.so: context management, the batch entry points and the
 // LoRaDetector shim (include/lorahip.h). Host-side only; kernels are in lorahip_kernels.hip.
-#include "lorahip_internal.h"
+#include "lorahip_own.h"
 #include <cmath>
 #include <cstdlib>
 #include <cstdio>
@@ -69,19 +69,63 @@ static bool isGfx950(const int device)
 //! device and pinned-host staging of the host-pointer entry point (the IQ itself goes through gatherUpload: device side only)
 static int growStage(lorahip_ctx *ctx, const size_t devBytes, const size_t hostBytes)
 {
-    if (devBytes <= ctx->dStageBytes && hostBytes <= ctx->hStageBytes) return LORAHIP_OK;
-    if (ctx->dStage) { (void)hipFree(ctx->dStage); ctx->dStage = nullptr; }
-    if (ctx->hStage) { (void)hipHostFree(ctx->hStage); ctx->hStage = nullptr; }
-    ctx->dStageBytes = ctx->hStageBytes = 0;                    // both or neither: a half-grown pair must not look usable
-    const size_t dCap = devBytes + devBytes / 4, hCap = hostBytes + hostBytes / 4 + 256;
-    LORAHIP_TRY(hipMalloc(&ctx->dStage, dCap));
-    const hipError_t e = hipHostMalloc(&ctx->hStage, hCap, hipHostMallocDefault);
-    if (e != hipSuccess)
+    if (devBytes <= ctx->dStage.bytes() && hostBytes <= ctx->hStage.bytes()) return LORAHIP_OK;
+    LORAHIP_TRY(regrowPair(ctx->dStage, devBytes + devBytes / 4, ctx->hStage, hostBytes + hostBytes / 4 + 256, hipHostMallocDefault));
+    return LORAHIP_OK;
+}
+
+//! the stream, the events and the tables of a new context; the caller destroys the context when a step fails
+static int fillContext(lorahip_ctx *ctx, const int device, const int sf)
+{
+    ctx->device = device;
+    ctx->sf = sf;
+    ctx->N = size_t(1) << sf;
+    ctx->powerScale = float(20 * std::log10(double(ctx->N)));   // LoRaDetector.hpp:18
+
+    HostTables t;
+    buildHostTables(sf, t, true);
+    const size_t nb = ctx->N * sizeof(cf32);
     {
-        (void)hipFree(ctx->dStage); ctx->dStage = nullptr; ctx->hStage = nullptr;
-        return hipFail(e, "hipHostMalloc(staging)");
+        // LORAHIP_PART_PRIORITY=1 (a measurement: profiles/r06): the stream of a context at SF11 / 12 above, at SF7 / 8 below the
+        // others -- in a mixed object the long windows' launches then get the device first and their tail starts earliest
+        static const bool byPrio = std::getenv("LORAHIP_PART_PRIORITY") != nullptr;
+        int least = 0, greatest = 0;
+        if (byPrio && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
+        {
+            const int prio = sf >= 11 ? greatest : (sf <= 8 ? least : (least + greatest) / 2);
+            LORAHIP_TRY(ctx->ownStream.ensure(hipStreamNonBlocking, &prio));
+        }
+        else LORAHIP_TRY(ctx->ownStream.ensure(hipStreamNonBlocking));
     }
-    ctx->dStageBytes = dCap; ctx->hStageBytes = hCap;
+    ctx->stream = ctx->ownStream.get();
+    LORAHIP_TRY(ctx->ev0.ensure());
+    LORAHIP_TRY(ctx->ev1.ensure());
+    LORAHIP_TRY(ctx->dUp.grow(nb));
+    LORAHIP_TRY(ctx->dDown.grow(nb));
+    LORAHIP_TRY(ctx->dTw.grow(nb));
+    LORAHIP_TRY(ctx->dFine.grow(nb * LORAHIP_FINE_STEPS));
+    LORAHIP_TRY(hipMemcpy(ctx->dUp.get(), t.up.data(), nb, hipMemcpyHostToDevice));
+    LORAHIP_TRY(hipMemcpy(ctx->dDown.get(), t.down.data(), nb, hipMemcpyHostToDevice));
+    LORAHIP_TRY(hipMemcpy(ctx->dTw.get(), t.twiddle.data(), nb, hipMemcpyHostToDevice));
+    LORAHIP_TRY(hipMemcpy(ctx->dFine.get(), t.fine.data(), nb * LORAHIP_FINE_STEPS, hipMemcpyHostToDevice));
+    {
+        // fp64 factor tables that reproduce the fine-tune table without a gather (lorahip_fine.h); only when the host check of
+        // all 128*N entries passes -- otherwise the kernels keep reading the table itself
+        std::vector<double> fa, fb;
+        if (buildFineSplit(sf, t.fine, fa, fb))
+        {
+            LORAHIP_TRY(ctx->dFineA.grow(fa.size() * sizeof(double)));
+            LORAHIP_TRY(ctx->dFineB.grow(fb.size() * sizeof(double)));
+            LORAHIP_TRY(hipMemcpy(ctx->dFineA.get(), fa.data(), fa.size() * sizeof(double), hipMemcpyHostToDevice));
+            LORAHIP_TRY(hipMemcpy(ctx->dFineB.get(), fb.data(), fb.size() * sizeof(double), hipMemcpyHostToDevice));
+        }
+    }
+    const std::vector<cf32> st = buildStageTwiddles(sf, t.twiddle);
+    LORAHIP_TRY(ctx->dTwStage.grow((st.size() + 1) * sizeof(cf32)));
+    LORAHIP_TRY(hipMemcpy(ctx->dTwStage.get(), st.data(), st.size() * sizeof(cf32), hipMemcpyHostToDevice));
+    hipDeviceProp_t prop;
+    LORAHIP_TRY(hipGetDeviceProperties(&prop, device));
+    ctx->cuCount = prop.multiProcessorCount;
     return LORAHIP_OK;
 }
 
@@ -138,62 +182,7 @@ int lorahip_create(lorahip_ctx **out, const int device, const int sf)
 
     lorahip_ctx *ctx = new (std::nothrow) lorahip_ctx();
     if (ctx == nullptr) return LORAHIP_E_NOMEM;
-    std::memset(ctx, 0, sizeof(*ctx));
-    ctx->device = device;
-    ctx->sf = sf;
-    ctx->N = size_t(1) << sf;
-    ctx->powerScale = float(20 * std::log10(double(ctx->N)));   // LoRaDetector.hpp:18
-
-    HostTables t;
-    buildHostTables(sf, t, true);
-    const size_t nb = ctx->N * sizeof(cf32);
-    int rc = LORAHIP_OK;
-    do
-    {
-#define LORAHIP_CK(expr) { hipError_t _e = (expr); if (_e != hipSuccess) { rc = hipFail(_e, #expr); break; } }
-        {
-            // LORAHIP_PART_PRIORITY=1 (a measurement: profiles/r06): the stream of a context at SF11 / 12 above, at SF7 / 8 below the
-            // others -- in a mixed object the long windows' launches then get the device first and their tail starts earliest
-            static const bool byPrio = std::getenv("LORAHIP_PART_PRIORITY") != nullptr;
-            int least = 0, greatest = 0;
-            if (byPrio && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
-            {
-                const int prio = sf >= 11 ? greatest : (sf <= 8 ? least : (least + greatest) / 2);
-                LORAHIP_CK(hipStreamCreateWithPriority(&ctx->ownStream, hipStreamNonBlocking, prio));
-            }
-            else LORAHIP_CK(hipStreamCreateWithFlags(&ctx->ownStream, hipStreamNonBlocking));
-        }
-        ctx->stream = ctx->ownStream;
-        LORAHIP_CK(hipEventCreate(&ctx->ev0));
-        LORAHIP_CK(hipEventCreate(&ctx->ev1));
-        LORAHIP_CK(hipMalloc((void **)&ctx->dUp, nb));
-        LORAHIP_CK(hipMalloc((void **)&ctx->dDown, nb));
-        LORAHIP_CK(hipMalloc((void **)&ctx->dTw, nb));
-        LORAHIP_CK(hipMalloc((void **)&ctx->dFine, nb * LORAHIP_FINE_STEPS));
-        LORAHIP_CK(hipMemcpy(ctx->dUp, t.up.data(), nb, hipMemcpyHostToDevice));
-        LORAHIP_CK(hipMemcpy(ctx->dDown, t.down.data(), nb, hipMemcpyHostToDevice));
-        LORAHIP_CK(hipMemcpy(ctx->dTw, t.twiddle.data(), nb, hipMemcpyHostToDevice));
-        LORAHIP_CK(hipMemcpy(ctx->dFine, t.fine.data(), nb * LORAHIP_FINE_STEPS, hipMemcpyHostToDevice));
-        {
-            // fp64 factor tables that reproduce the fine-tune table without a gather (lorahip_fine.h); only when the host check of
-            // all 128*N entries passes -- otherwise the kernels keep reading the table itself
-            std::vector<double> fa, fb;
-            if (buildFineSplit(sf, t.fine, fa, fb))
-            {
-                LORAHIP_CK(hipMalloc((void **)&ctx->dFineA, fa.size() * sizeof(double)));
-                LORAHIP_CK(hipMalloc((void **)&ctx->dFineB, fb.size() * sizeof(double)));
-                LORAHIP_CK(hipMemcpy(ctx->dFineA, fa.data(), fa.size() * sizeof(double), hipMemcpyHostToDevice));
-                LORAHIP_CK(hipMemcpy(ctx->dFineB, fb.data(), fb.size() * sizeof(double), hipMemcpyHostToDevice));
-            }
-        }
-        const std::vector<cf32> st = buildStageTwiddles(sf, t.twiddle);
-        LORAHIP_CK(hipMalloc((void **)&ctx->dTwStage, (st.size() + 1) * sizeof(cf32)));
-        LORAHIP_CK(hipMemcpy(ctx->dTwStage, st.data(), st.size() * sizeof(cf32), hipMemcpyHostToDevice));
-        hipDeviceProp_t prop;
-        LORAHIP_CK(hipGetDeviceProperties(&prop, device));
-        ctx->cuCount = prop.multiProcessorCount;
-#undef LORAHIP_CK
-    } while (false);
+    const int rc = fillContext(ctx, device, sf);
     if (rc != LORAHIP_OK) { lorahip_destroy(ctx); return rc; }
     *out = ctx;
     return LORAHIP_OK;
@@ -203,21 +192,8 @@ void lorahip_destroy(lorahip_ctx *ctx)
 {
     if (ctx == nullptr) return;
     const DeviceGuard guard(ctx->device);
-    if (ctx->ownStream) (void)hipStreamSynchronize(ctx->ownStream);
-    if (ctx->dUp) (void)hipFree(ctx->dUp);
-    if (ctx->dDown) (void)hipFree(ctx->dDown);
-    if (ctx->dTw) (void)hipFree(ctx->dTw);
-    if (ctx->dFine) (void)hipFree(ctx->dFine);
-    if (ctx->dTwStage) (void)hipFree(ctx->dTwStage);
-    if (ctx->dFineA) (void)hipFree(ctx->dFineA);
-    if (ctx->dFineB) (void)hipFree(ctx->dFineB);
-    if (ctx->dStage) (void)hipFree(ctx->dStage);
-    if (ctx->hStage) (void)hipHostFree(ctx->hStage);
-    destroyUploader(ctx);
-    if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
-    if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-    if (ctx->ownStream) (void)hipStreamDestroy(ctx->ownStream);
-    delete ctx;
+    if (ctx->ownStream.get()) (void)hipStreamSynchronize(ctx->ownStream.get());
+    delete ctx;                                                 // inside the guard: the members release with the context's device current
 }
 
 int lorahip_sf(const lorahip_ctx *ctx) { return ctx ? ctx->sf : LORAHIP_E_INVALID; }
@@ -233,7 +209,7 @@ int lorahip_set_stream(lorahip_ctx *ctx, void *hip_stream)
 int lorahip_reset_stream(lorahip_ctx *ctx)
 {
     if (ctx == nullptr) return LORAHIP_E_INVALID;
-    ctx->stream = ctx->ownStream;
+    ctx->stream = ctx->ownStream.get();
     return LORAHIP_OK;
 }
 
@@ -262,7 +238,7 @@ int lorahip_set_fine_gather(lorahip_ctx *ctx, const int enable)
 int lorahip_fine_split_active(const lorahip_ctx *ctx)
 {
     if (ctx == nullptr) return LORAHIP_E_INVALID;
-    return (ctx->dFineA != nullptr && ctx->dFineB != nullptr && !ctx->fineGather) ? 1 : 0;
+    return (ctx->dFineA.get() != nullptr && ctx->dFineB.get() != nullptr && !ctx->fineGather) ? 1 : 0;
 }
 
 static int checkBatch(const lorahip_ctx *ctx, const lorahip_batch *b)
@@ -292,12 +268,12 @@ static void fillArgs(const lorahip_ctx *ctx, const lorahip_batch *b, DetectArgs 
     a.fineIdxOut = b->fine_idx_out;
     a.fftOut = reinterpret_cast<float2 *>(b->fft_out);
     a.decOut = reinterpret_cast<float2 *>(b->dec_out);
-    a.up = ctx->dUp;
-    a.down = ctx->dDown;
-    a.fine = ctx->dFine;
-    a.tw = ctx->dTw;
-    a.fineA = ctx->fineGather ? nullptr : ctx->dFineA;
-    a.fineB = ctx->fineGather ? nullptr : ctx->dFineB;
+    a.up = ctx->dUp.get();
+    a.down = ctx->dDown.get();
+    a.fine = ctx->dFine.get();
+    a.tw = ctx->dTw.get();
+    a.fineA = ctx->fineGather ? nullptr : ctx->dFineA.get();
+    a.fineB = ctx->fineGather ? nullptr : ctx->dFineB.get();
     a.nWindows = unsigned(b->n_windows);
     a.powerScale = ctx->powerScale;
 }
@@ -310,7 +286,7 @@ int lorahip_detect_batch(lorahip_ctx *ctx, const lorahip_batch *b)
     DetectArgs a;
     fillArgs(ctx, b, a);
     FastTables ft;
-    ft.twStage = ctx->dTwStage;
+    ft.twStage = ctx->dTwStage.get();
     ft.nBlocksHint = ctx->cuCount;
     LORAHIP_TRY(launchDetect(ctx->sf, ctx->variant, a, ft, ctx->stream));
     return LORAHIP_OK;
@@ -366,7 +342,7 @@ int lorahip_detect_batch_host(lorahip_ctx *ctx, const lorahip_batch *b)
     rc = growStage(ctx, cur, cur - hShift);
     if (rc != LORAHIP_OK) return rc;
 
-    char *d = static_cast<char *>(ctx->dStage), *h = static_cast<char *>(ctx->hStage) - hShift;   // h + off is valid for off >= hShift
+    char *d = ctx->dStage.get(), *h = ctx->hStage.get() - hShift;   // h + off is valid for off >= hShift
     {
         const void *src[1] = { b->iq };
         const size_t len[1] = { pIq.bytes };
@@ -411,7 +387,7 @@ int lorahip_timer_start(lorahip_ctx *ctx)
 {
     if (ctx == nullptr) return LORAHIP_E_INVALID;
     const DeviceGuard guard(ctx->device);
-    LORAHIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    LORAHIP_TRY(hipEventRecord(ctx->ev0.get(), ctx->stream));
     return LORAHIP_OK;
 }
 
@@ -419,9 +395,9 @@ int lorahip_timer_stop(lorahip_ctx *ctx, float *elapsed_ms)
 {
     if (ctx == nullptr || elapsed_ms == nullptr) return LORAHIP_E_INVALID;
     const DeviceGuard guard(ctx->device);
-    LORAHIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-    LORAHIP_TRY(hipEventSynchronize(ctx->ev1));
-    LORAHIP_TRY(hipEventElapsedTime(elapsed_ms, ctx->ev0, ctx->ev1));
+    LORAHIP_TRY(hipEventRecord(ctx->ev1.get(), ctx->stream));
+    LORAHIP_TRY(hipEventSynchronize(ctx->ev1.get()));
+    LORAHIP_TRY(hipEventElapsedTime(elapsed_ms, ctx->ev0.get(), ctx->ev1.get()));
     return LORAHIP_OK;
 }
 
@@ -430,7 +406,7 @@ int lorahip_membw_probe(lorahip_ctx *ctx, const float *buf_dev, const size_t n_b
     if (ctx == nullptr || buf_dev == nullptr || blocks_per_cu < 1) return LORAHIP_E_INVALID;
     const DeviceGuard guard(ctx->device);
     LORAHIP_TRY(launchMembw(reinterpret_cast<const float2 *>(buf_dev), n_bytes, pattern, ctx->cuCount * blocks_per_cu,
-                            reinterpret_cast<float *>(ctx->dTwStage), ctx->stream));
+                            reinterpret_cast<float *>(ctx->dTwStage.get()), ctx->stream));
     return LORAHIP_OK;
 }
 
@@ -525,7 +501,7 @@ int lorahip_decode_packets_host(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfg
     const Piece pLen = carve(n_packets * sizeof(int32_t));
     const Piece pDrop = carve(n_packets * sizeof(int32_t));
     { const int rc = growStage(ctx, cur, cur); if (rc != LORAHIP_OK) return rc; }
-    char *d = static_cast<char *>(ctx->dStage), *h = static_cast<char *>(ctx->hStage);
+    char *d = ctx->dStage.get(), *h = ctx->hStage.get();
     std::memcpy(h + pSym.off, syms, pSym.bytes);
     std::memcpy(h + pN.off, nsyms, pN.bytes);
     LORAHIP_TRY(hipMemcpyAsync(d, h, inBytes, hipMemcpyHostToDevice, ctx->stream));
@@ -605,7 +581,7 @@ int lorahip_encode_packets_host(lorahip_ctx *ctx, const lorahip_encoder_cfg *cfg
     const Piece pSym = carve(n_packets * sym_stride * sizeof(uint16_t));
     const Piece pLen = carve(n_packets * sizeof(int32_t));
     { const int rc = growStage(ctx, cur, cur); if (rc != LORAHIP_OK) return rc; }
-    char *d = static_cast<char *>(ctx->dStage), *h = static_cast<char *>(ctx->hStage);
+    char *d = ctx->dStage.get(), *h = ctx->hStage.get();
     if (pByte.bytes) std::memcpy(h + pByte.off, bytes, pByte.bytes);
     std::memcpy(h + pN.off, nbytes, pN.bytes);
     LORAHIP_TRY(hipMemcpyAsync(d, h, inBytes, hipMemcpyHostToDevice, ctx->stream));
@@ -645,7 +621,7 @@ struct lorahip_detector
     // (_fftInput, LoRaDetector.hpp:68), its bins (_fftOutput, :69) and detect()'s four results. A detect() is then ONE kernel launch
     // and one wait -- the kernel reads its 8 N bytes over PCIe and writes 8 N + 14 back -- instead of a staged upload, the kernel and
     // five downloads (28 -> the figure in DESIGN.md section 5 per call; the verbatim CPU detector takes 1-30 us for N = 2^7 ... 2^12).
-    char *block;
+    HostBuf<char> block;
     cf32 *input, *output;
     uint16_t *sym;
     float *res;                   // power, powerAvg, fIndex
@@ -662,21 +638,17 @@ int lorahip_detector_create(lorahip_detector **out, const int device, const size
     if (sf < 0) return LORAHIP_E_INVALID;
     lorahip_detector *det = new (std::nothrow) lorahip_detector();
     if (det == nullptr) return LORAHIP_E_NOMEM;
-    det->ctx = nullptr;
     det->N = N;
-    det->block = nullptr;
     const int rc = lorahip_create(&det->ctx, device, sf);
     if (rc != LORAHIP_OK) { delete det; return rc; }
     {
         const DeviceGuard guard(det->ctx->device);
         const size_t bytes = 2 * N * sizeof(cf32) + 256;
-        void *p = nullptr;
-        const hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocMapped | hipHostMallocPortable);
+        const hipError_t e = det->block.grow(bytes, hipHostMallocMapped | hipHostMallocPortable);
         if (e != hipSuccess) { (void)hipGetLastError(); lorahip_destroy(det->ctx); delete det; return hipFail(e, "hipHostMalloc (detector staging)"); }
-        std::memset(p, 0, bytes);
-        det->block = static_cast<char *>(p);
+        std::memset(det->block.get(), 0, bytes);
     }
-    det->input = reinterpret_cast<cf32 *>(det->block);
+    det->input = reinterpret_cast<cf32 *>(det->block.get());
     det->output = det->input + N;
     det->res = reinterpret_cast<float *>(det->output + N);
     det->sym = reinterpret_cast<uint16_t *>(det->res + 4);
@@ -687,14 +659,13 @@ int lorahip_detector_create(lorahip_detector **out, const int device, const size
 void lorahip_detector_destroy(lorahip_detector *det)
 {
     if (det == nullptr) return;
-    if (det->block)
+    lorahip_ctx *ctx = det->ctx;
     {
-        const DeviceGuard guard(det->ctx->device);
-        (void)hipStreamSynchronize(det->ctx->stream);
-        (void)hipHostFree(det->block);
+        const DeviceGuard guard(ctx->device);
+        if (det->block.get()) (void)hipStreamSynchronize(ctx->stream);
+        delete det;                                             // the mapped block goes before the context whose stream wrote into it
     }
-    lorahip_destroy(det->ctx);
-    delete det;
+    lorahip_destroy(ctx);
 }
 
 int lorahip_detector_feed(lorahip_detector *det, const size_t i, const float re, const float im)

@@ -15,7 +15,7 @@
 //     16*RM v_pk_fma_f32;
 //   * the NCO is a 64-bit phase counter (w_k * n mod 2^64): exact wrap-around, no drift, and a stream cut into
 //     chunks gives the same bits as one call.
-#include "lorahip_internal.h"
+#include "lorahip_own.h"
 #include <cmath>
 #include <cstdlib>
 #include <new>
@@ -25,11 +25,11 @@ struct lorahip_channelizer
     lorahip_ctx *ctx;
     int K, L, D, HC, QP, RM, nGroups;
     size_t ldsBytes;
-    float2 *dTaps;                  // [nGroups][L+1][8], tap order reversed (oldest sample first), last entry a dummy
-    unsigned *dTapOff;              // [L+2]
-    unsigned long long *dW;         // [nGroups*8]
-    float2 *dRot;                   // [nGroups*8] phase step over 256 outputs, then [nGroups*8][256] phase over t outputs
-    float2 *dHist[2];               // the HC samples before n0 (zeros before the start of the stream)
+    lorahip::DevBuf<float2> dTaps;  // [nGroups][L+1][8], tap order reversed (oldest sample first), last entry a dummy
+    lorahip::DevBuf<unsigned> dTapOff;          // [L+2]
+    lorahip::DevBuf<unsigned long long> dW;     // [nGroups*8]
+    lorahip::DevBuf<float2> dRot;   // [nGroups*8] phase step over 256 outputs, then [nGroups*8][256] phase over t outputs
+    lorahip::DevBuf<float2> dHist[2];           // the HC samples before n0 (zeros before the start of the stream)
     int cur;
     unsigned long long n0;          // samples consumed since the last reset
 };
@@ -309,14 +309,14 @@ static int chanRun(lorahip_channelizer *c, const float2 *wide, const size_t nIn,
     if (nOut > (size_t(1) << 30)) { setLastError("channeliser: more than 2^30 outputs per channel in one call"); return LORAHIP_E_INVALID; }
     ChanArgs a;
     a.chunk = wide; a.nChunk = (long long)nIn;
-    a.hist = c->dHist[c->cur]; a.histLen = captures ? 0 : c->HC;        // no history: samples before the capture read as 0
+    a.hist = c->dHist[c->cur].get(); a.histLen = captures ? 0 : c->HC;        // no history: samples before the capture read as 0
     a.n0 = (long long)n0;
     a.captureIn = (long long)captureStride; a.captureOut = (long long)(size_t(c->K) * outStride);
-    a.taps = reinterpret_cast<const v2f *>(c->dTaps);
-    a.w = c->dW;
-    a.step = reinterpret_cast<const v2f *>(c->dRot);
+    a.taps = reinterpret_cast<const v2f *>(c->dTaps.get());
+    a.w = c->dW.get();
+    a.step = reinterpret_cast<const v2f *>(c->dRot.get());
     a.laneRot = a.step + size_t(c->nGroups) * CHAN_KG;
-    a.tapOff = c->dTapOff;
+    a.tapOff = c->dTapOff.get();
     a.out = out; a.outStride = (long long)outStride;
     a.mLo = (long long)mLo; a.nOut = (long long)nOut;
     a.K = c->K; a.L = c->L; a.D = c->D; a.QP = c->QP; a.nGroups = c->nGroups;
@@ -339,7 +339,7 @@ static int chanRun(lorahip_channelizer *c, const float2 *wide, const size_t nIn,
         LORAHIP_TRY(hipGetLastError());
     }
     if (captures) return LORAHIP_OK;
-    hipLaunchKernelGGL(chanHistory, dim3((c->HC + 255) / 256), dim3(256), 0, ctx->stream, a, c->dHist[c->cur ^ 1]);
+    hipLaunchKernelGGL(chanHistory, dim3((c->HC + 255) / 256), dim3(256), 0, ctx->stream, a, c->dHist[c->cur ^ 1].get());
     LORAHIP_TRY(hipGetLastError());
     c->cur ^= 1;
     c->n0 += nIn;
@@ -386,7 +386,7 @@ int lorahip_channelizer_create(lorahip_channelizer **out, lorahip_ctx *ctx, cons
     if (c == nullptr) return LORAHIP_E_NOMEM;
     c->ctx = ctx; c->K = int(n_channels); c->L = L; c->D = D; c->HC = L - 1 + D; c->QP = QP; c->RM = RM;
     c->nGroups = int((n_channels + CHAN_KG - 1) / CHAN_KG);
-    c->ldsBytes = lds; c->dTaps = nullptr; c->dTapOff = nullptr; c->dW = nullptr; c->dRot = nullptr; c->dHist[0] = c->dHist[1] = nullptr; c->cur = 0; c->n0 = 0;
+    c->ldsBytes = lds; c->cur = 0; c->n0 = 0;
 
     const size_t KP = size_t(c->nGroups) * CHAN_KG;
     std::vector<unsigned long long> w(KP, 0);
@@ -416,22 +416,20 @@ int lorahip_channelizer_create(lorahip_channelizer **out, lorahip_ctx *ctx, cons
         }
     const DeviceGuard guard(ctx->device);
     const size_t histBytes = size_t(c->HC) * sizeof(float2);
-    if (hipMalloc((void **)&c->dTaps, g.size() * sizeof(float2)) != hipSuccess ||
-        hipMalloc((void **)&c->dTapOff, off.size() * sizeof(unsigned)) != hipSuccess ||
-        hipMalloc((void **)&c->dW, w.size() * sizeof(unsigned long long)) != hipSuccess ||
-        hipMalloc((void **)&c->dRot, rot.size() * sizeof(float2)) != hipSuccess ||
-        hipMalloc((void **)&c->dHist[0], histBytes) != hipSuccess || hipMalloc((void **)&c->dHist[1], histBytes) != hipSuccess)
-    {
-        lorahip_channelizer_destroy(c);
-        return LORAHIP_E_NOMEM;
-    }
-    hipError_t e = hipMemcpy(c->dTaps, g.data(), g.size() * sizeof(float2), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(c->dTapOff, off.data(), off.size() * sizeof(unsigned), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(c->dW, w.data(), w.size() * sizeof(unsigned long long), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(c->dRot, rot.data(), rot.size() * sizeof(float2), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(c->dHist[0], 0, histBytes);
+    hipError_t e = c->dTaps.grow(g.size() * sizeof(float2));
+    if (e == hipSuccess) e = c->dTapOff.grow(off.size() * sizeof(unsigned));
+    if (e == hipSuccess) e = c->dW.grow(w.size() * sizeof(unsigned long long));
+    if (e == hipSuccess) e = c->dRot.grow(rot.size() * sizeof(float2));
+    if (e == hipSuccess) e = c->dHist[0].grow(histBytes);
+    if (e == hipSuccess) e = c->dHist[1].grow(histBytes);
+    if (e != hipSuccess) { delete c; return LORAHIP_E_NOMEM; }
+    e = hipMemcpy(c->dTaps.get(), g.data(), g.size() * sizeof(float2), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(c->dTapOff.get(), off.data(), off.size() * sizeof(unsigned), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(c->dW.get(), w.data(), w.size() * sizeof(unsigned long long), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(c->dRot.get(), rot.data(), rot.size() * sizeof(float2), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(c->dHist[0].get(), 0, histBytes);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { lorahip_channelizer_destroy(c); return hipFail(e, "channeliser table upload"); }
+    if (e != hipSuccess) { delete c; return hipFail(e, "channeliser table upload"); }
     *out = c;
     return LORAHIP_OK;
 }
@@ -440,12 +438,6 @@ void lorahip_channelizer_destroy(lorahip_channelizer *c)
 {
     if (c == nullptr) return;
     const DeviceGuard guard(c->ctx->device);
-    if (c->dTaps) (void)hipFree(c->dTaps);
-    if (c->dW) (void)hipFree(c->dW);
-    if (c->dTapOff) (void)hipFree(c->dTapOff);
-    if (c->dRot) (void)hipFree(c->dRot);
-    if (c->dHist[0]) (void)hipFree(c->dHist[0]);
-    if (c->dHist[1]) (void)hipFree(c->dHist[1]);
     delete c;
 }
 
@@ -453,7 +445,7 @@ int lorahip_channelizer_reset(lorahip_channelizer *c)
 {
     if (c == nullptr) return LORAHIP_E_INVALID;
     const DeviceGuard guard(c->ctx->device);
-    LORAHIP_TRY(hipMemsetAsync(c->dHist[c->cur], 0, size_t(c->HC) * sizeof(float2), c->ctx->stream));
+    LORAHIP_TRY(hipMemsetAsync(c->dHist[c->cur].get(), 0, size_t(c->HC) * sizeof(float2), c->ctx->stream));
     c->n0 = 0;
     return LORAHIP_OK;
 }

@@ -10,7 +10,7 @@
 //
 // The three members the reference leaves uninitialised (_finefreqError, _freqError,
 // _prevValue) start at zero here.
-#include "lorahip_internal.h"
+#include "lorahip_own.h"
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -110,17 +110,18 @@ struct Pipe
 {
     bool active;                    // steps are in flight: only receive / flush may touch the object
     unsigned k;                     // steps launched since the pipeline was entered
-    char *dev[2]; size_t bytes[2];  // record sets (a StreamLayout each; the state and the carry rows are the object's own)
+    Stream side;                    // step k's packets are packed HERE while step k + 1's kernel runs on the launch stream (declared before
+                                    // the events and buffers used on it: they are released first)
+    DevBuf<char> dev[2];            // record sets (a StreamLayout each; the state and the carry rows are the object's own)
     StreamLayout lay[2];
-    StreamSummary *hSum;            // [2] pinned and mapped: the summary kernel writes here directly (no copy to enqueue)
-    hipEvent_t ev[2];
+    HostBuf<StreamSummary> hSum;    // [2] pinned and mapped: the summary kernel writes here directly (no copy to enqueue)
+    Event ev[2];
     bool pending[2];                // the set's kernel has been launched, its summary not read yet
     bool held[2];                   // the set's summary has been read, its packets are still in the set (rows too small: nothing is lost)
     size_t nPk[2]; int64_t nCalls[2];   // ... what that summary said
     size_t nSig[2]; bool sigs[2];       // ... and the signals kept in the set (the step ran with lorahip_demod_set_signals on)
-    hipStream_t side;               // step k's packets are packed HERE while step k + 1's kernel runs on the launch stream
-    hipEvent_t packDone;            // ... which waits for this before anything later (the next kernel reuses the record set, the caller reads the rows)
-    hipEvent_t entry;               // ... and the side stream for this: where the launch stream stood when the call began (the caller's
+    Event packDone;                 // the launch stream waits for this before anything later (the next kernel reuses the record set, the caller reads the rows)
+    Event entry;                    // ... and the side stream for this: where the launch stream stood when the call began (the caller's
                                     // consumer of the rows handed out by the call before, earlier packing on the launch stream)
 };
 
@@ -131,12 +132,12 @@ struct Resident
     bool unavailable;               // tried and refused for this object (no instance, the grid not resident at once, a step timed out)
     unsigned seq;                   // steps rung
     unsigned reported;              // steps whose report the caller has had
-    ResidentCtl *ctl;               // device: the mirror of the ring, the steps' counters
-    ResidentHost *host;             // pinned and mapped: the ring the host writes, the steps' reports, the abort flag
-    char *rec; size_t recBytes;     // the channels' records of a step (a StreamLayout; the state and the carry rows are the object's own)
+    Stream run;                     // the kernel's stream (declared before what the kernel uses: released last)
+    DevBuf<ResidentCtl> ctl;        // device: the mirror of the ring, the steps' counters
+    HostBuf<ResidentHost> host;     // pinned and mapped: the ring the host writes, the steps' reports, the abort flag
+    DevBuf<char> rec;               // the channels' records of a step (a StreamLayout; the state and the carry rows are the object's own)
     StreamLayout lay;
-    hipStream_t run;                // the kernel's stream
-    hipEvent_t ev;
+    Event ev;
     unsigned grid;
     size_t lastValid;
     bool lastMore;                  // the last reported step left a channel with samples it could not record
@@ -176,23 +177,22 @@ struct lorahip_demod
     bool sigRowsOn;
     size_t lastSignals;              // ... how many the last receive / receive_flush delivered there
     // per-round staging (host pinned + device), sized for B windows
-    char *h, *d;
-    size_t stageBytes;
-    float *dIq; size_t dIqSamples;   // owned upload buffer for lorahip_demod_run
+    HostBuf<char> h; DevBuf<char> d;
+    DevBuf<float> dIq;               // owned upload buffer for lorahip_demod_run
     int mode;                        // 0 auto, 1 device streaming kernel, 2 host-driven rounds
     // streaming path: device + pinned-host mirrors, grown on demand
-    char *sDev, *sHost; size_t sBytes;
-    char *dDense, *hDense; size_t denseBytes;   // the used part of the record arrays, packed for the copy back
-    hipEvent_t evK0, evK1;           // around the streaming kernel launches of a run (lorahip_demod_kernel_ms)
-    hipEvent_t evJoin;               // lorahip_demod_stream_wait
-    void *dSumScratch;               // streamSummary's partial records (more than 32768 channels)
+    DevBuf<char> sDev; HostBuf<char> sHost;     // (the pinned one holds the head only)
+    DevBuf<char> dDense; HostBuf<char> hDense;  // the used part of the record arrays, packed for the copy back
+    Event evK0, evK1;                // around the streaming kernel launches of a run (lorahip_demod_kernel_ms)
+    Event evJoin;                    // lorahip_demod_stream_wait
+    DevBuf<char> dSumScratch;        // streamSummary's partial records (more than 32768 channels)
     double kernelMs;
     int lastLaunches;                // streaming kernel launches of the last run
     lorahip_demod_ports ports;       // level-3 debug ports (all pointers null: off); DEVICE pointers (the library's own when the caller's are host buffers)
     lorahip_demod_ports hostPorts;   // the caller's host buffers (host_buffers == 1)
-    float *ownFft, *ownDec, *ownRaw; // device mirrors owned by the library for host_buffers
+    DevBuf<float> ownFft, ownDec, ownRaw;   // device mirrors owned by the library for host_buffers
     bool portsOn, userTracing;
-    char *dPort; size_t dPortBytes;  // scratch of the port replay: window descriptors, replayed fft / dec windows
+    DevBuf<char> dPort;              // scratch of the port replay: window descriptors, replayed fft / dec windows
     int64_t nNearSquelch, nNearStep; // decisions float rounding could flip, since activate() (lorahip_demod_near_threshold)
     // Streaming mode keeps the per-channel frame-machine state ON THE DEVICE between runs (its pinned copy in sHost is what the host
     // reads); the Channel mirrors above are brought up to date only when somebody needs them (host-driven rounds, ports, accessors)
@@ -214,7 +214,7 @@ struct lorahip_demod
     // The symbols of the packet a channel is INSIDE when a streaming run ends stay on the device too: the kernel leaves them in dCarry
     // and copies them to the head of the channel's symbol row at the start of the next run, then appends behind them -- a packet
     // that spans runs is assembled without the host (the running receiver: lorahip_demod_run_device_segments + packets_to_device).
-    short *dCarry; size_t carryCap;  // [B][carryCap]
+    DevBuf<short> dCarry; size_t carryCap;      // [B][carryCap]
     bool devCarryValid;              // dCarry holds the open packets of the state on the device
     bool hostCarryStale;             // ch[].outSymbols lack what the runs since the last drain received (implies devCarryValid)
     size_t callsPerWindowQ8 = 288;   // streaming runs: work() calls per N samples the record buffers are sized for, in 1/256 (adapts, see runStream;
@@ -267,8 +267,8 @@ static Round carve(char *p, const size_t B)
 static int launchRound(lorahip_demod *dm, const float *iqDev, const size_t n)
 {
     lorahip_ctx *ctx = dm->ctx;
-    const Round hr = carve(dm->h, dm->B), dr = carve(dm->d, dm->B);
-    LORAHIP_TRY(hipMemcpyAsync(dm->d, dm->h, hr.inBytes, hipMemcpyHostToDevice, ctx->stream));
+    const Round hr = carve(dm->h.get(), dm->B), dr = carve(dm->d.get(), dm->B);
+    LORAHIP_TRY(hipMemcpyAsync(dm->d.get(), dm->h.get(), hr.inBytes, hipMemcpyHostToDevice, ctx->stream));
     lorahip_batch b;
     std::memset(&b, 0, sizeof(b));
     b.struct_size = sizeof(b);
@@ -282,7 +282,7 @@ static int launchRound(lorahip_demod *dm, const float *iqDev, const size_t n)
     b.fine_idx_out = dr.idxOut;
     const int rc = lorahip_detect_batch(ctx, &b);
     if (rc != LORAHIP_OK) return rc;
-    LORAHIP_TRY(hipMemcpyAsync(dm->h + hr.inBytes, dm->d + hr.inBytes, hr.total - hr.inBytes,
+    LORAHIP_TRY(hipMemcpyAsync(dm->h.get() + hr.inBytes, dm->d.get() + hr.inBytes, hr.total - hr.inBytes,
                                hipMemcpyDeviceToHost, ctx->stream));
     LORAHIP_TRY(hipStreamSynchronize(ctx->stream));
     return LORAHIP_OK;
@@ -323,15 +323,6 @@ template <class BaseOf> static void placeSegments(lorahip_demod *dm, const size_
     }
 }
 
-//! the owned upload buffer of lorahip_demod_run / lorahip_demod_run_host_rows, regrown to hold `samples` (callers grow it only)
-static int regrowIq(lorahip_demod *dm, const size_t samples)
-{
-    if (dm->dIq) { (void)hipFree(dm->dIq); dm->dIq = nullptr; dm->dIqSamples = 0; }
-    LORAHIP_TRY(hipMalloc((void **)&dm->dIq, samples * sizeof(cf32)));
-    dm->dIqSamples = samples;
-    return LORAHIP_OK;
-}
-
 static int syncMirrors(lorahip_demod *dm);
 
 static int runRounds(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
@@ -343,7 +334,7 @@ static int runRounds(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
     dm->devStateFresh = false;                                  // the mirrors are about to change: the device copy goes stale
     dm->devCarryValid = false;                                  // ... and so do the open packets' symbols it holds (syncMirrors fetched them)
     const DeviceGuard guard(dm->ctx->device);
-    const Round hr = carve(dm->h, B);
+    const Round hr = carve(dm->h.get(), B);
     std::vector<uint32_t> live, second;
     std::vector<lorahip_work_result> res(B);
     int64_t rounds = 0;
@@ -528,15 +519,8 @@ static int runRounds(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
 //! device + pinned scratch pair for packed records (grown on demand, both or neither)
 static int growDense(lorahip_demod *dm, const size_t bytes)
 {
-    if (bytes <= dm->denseBytes) return LORAHIP_OK;
-    if (dm->dDense) { (void)hipFree(dm->dDense); dm->dDense = nullptr; }
-    if (dm->hDense) { (void)hipHostFree(dm->hDense); dm->hDense = nullptr; }
-    dm->denseBytes = 0;
-    const size_t want = bytes + bytes / 4;
-    LORAHIP_TRY(hipMalloc((void **)&dm->dDense, want));
-    const hipError_t e = hipHostMalloc((void **)&dm->hDense, want, hipHostMallocDefault);
-    if (e != hipSuccess) { (void)hipFree(dm->dDense); dm->dDense = nullptr; dm->hDense = nullptr; return hipFail(e, "hipHostMalloc(dense records)"); }
-    dm->denseBytes = want;
+    if (bytes <= dm->dDense.bytes()) return LORAHIP_OK;
+    LORAHIP_TRY(regrowPair(dm->dDense, bytes + bytes / 4, dm->hDense, bytes + bytes / 4, hipHostMallocDefault));
     return LORAHIP_OK;
 }
 
@@ -591,10 +575,10 @@ static StreamLayout headLayout(const lorahip_demod *dm)
 //! only its summary; whoever needs the arrays -- the Channel mirrors, consumed(), a drain of the records -- asks here first.
 static int ensureHead(lorahip_demod *dm)
 {
-    if (!dm->headStale || dm->sHost == nullptr || dm->sDev == nullptr) return LORAHIP_OK;
+    if (!dm->headStale || dm->sHost.get() == nullptr || dm->sDev.get() == nullptr) return LORAHIP_OK;
     const StreamLayout L = headLayout(dm);
     const DeviceGuard guard(dm->ctx->device);
-    LORAHIP_TRY(hipMemcpyAsync(dm->sHost + L.oState, dm->sDev + L.oState, L.oPkt - L.oState, hipMemcpyDeviceToHost, dm->ctx->stream));
+    LORAHIP_TRY(hipMemcpyAsync(dm->sHost.get() + L.oState, dm->sDev.get() + L.oState, L.oPkt - L.oState, hipMemcpyDeviceToHost, dm->ctx->stream));
     LORAHIP_TRY(hipStreamSynchronize(dm->ctx->stream));
     dm->headStale = false;
     return LORAHIP_OK;
@@ -606,7 +590,7 @@ static int drainLaunch(lorahip_demod *dm, const StreamLayout &L)
     lorahip_ctx *ctx = dm->ctx;
     const size_t B = L.B;
     { const int rc = ensureHead(dm); if (rc != LORAHIP_OK) return rc; }
-    char *h = dm->sHost, *d = dm->sDev;
+    char *h = dm->sHost.get(), *d = dm->sDev.get();
     const int *hN = reinterpret_cast<int *>(h + L.oN), *hNSym = reinterpret_cast<int *>(h + L.oNSym), *hNPkt = reinterpret_cast<int *>(h + L.oNPkt);
     std::vector<size_t> &carry = dm->carry;
     // only as many columns of the [channel][capacity] record arrays as the fullest channel used cross PCIe: the capacities are
@@ -625,19 +609,19 @@ static int drainLaunch(lorahip_demod *dm, const StreamLayout &L)
     const size_t nbSig = align256(B * maxSig * sizeof(StreamSignal));
     const size_t nbDense = nbPkt + nbSym + nbCalls + nbSig;
     { const int grc = growDense(dm, nbDense); if (grc != LORAHIP_OK) return grc; }
-    LORAHIP_TRY(launchCompactRows(dm->dDense, d + L.oPkt, B, L.capPkt * sizeof(StreamPacket), maxPkt * sizeof(StreamPacket), ctx->stream));
-    LORAHIP_TRY(launchCompactRows(dm->dDense + nbPkt, d + L.oSym, B, L.symStride * sizeof(short), maxSym * sizeof(short), ctx->stream));
+    LORAHIP_TRY(launchCompactRows(dm->dDense.get(), d + L.oPkt, B, L.capPkt * sizeof(StreamPacket), maxPkt * sizeof(StreamPacket), ctx->stream));
+    LORAHIP_TRY(launchCompactRows(dm->dDense.get() + nbPkt, d + L.oSym, B, L.symStride * sizeof(short), maxSym * sizeof(short), ctx->stream));
     if (L.tracing)
-        LORAHIP_TRY(launchCompactRows(dm->dDense + nbPkt + nbSym, d + L.oCalls, B, L.cap * sizeof(lorahip_work_result),
+        LORAHIP_TRY(launchCompactRows(dm->dDense.get() + nbPkt + nbSym, d + L.oCalls, B, L.cap * sizeof(lorahip_work_result),
                                       maxCalls * sizeof(lorahip_work_result), ctx->stream));
     if (maxSig)
-        LORAHIP_TRY(launchCompactRows(dm->dDense + nbPkt + nbSym + nbCalls, d + L.oSig, B, L.capPkt * sizeof(StreamSignal), maxSig * sizeof(StreamSignal), ctx->stream));
-    if (nbDense) LORAHIP_TRY(hipMemcpyAsync(dm->hDense, dm->dDense, nbDense, hipMemcpyDeviceToHost, ctx->stream));
+        LORAHIP_TRY(launchCompactRows(dm->dDense.get() + nbPkt + nbSym + nbCalls, d + L.oSig, B, L.capPkt * sizeof(StreamSignal), maxSig * sizeof(StreamSignal), ctx->stream));
+    if (nbDense) LORAHIP_TRY(hipMemcpyAsync(dm->hDense.get(), dm->dDense.get(), nbDense, hipMemcpyDeviceToHost, ctx->stream));
     LORAHIP_TRY(hipStreamSynchronize(ctx->stream));
-    const StreamPacket *hPkt = reinterpret_cast<const StreamPacket *>(dm->hDense);
-    const short *hSym = reinterpret_cast<const short *>(dm->hDense + nbPkt);
-    const lorahip_work_result *hCalls = reinterpret_cast<const lorahip_work_result *>(dm->hDense + nbPkt + nbSym);
-    const StreamSignal *hSig = reinterpret_cast<const StreamSignal *>(dm->hDense + nbPkt + nbSym + nbCalls);
+    const StreamPacket *hPkt = reinterpret_cast<const StreamPacket *>(dm->hDense.get());
+    const short *hSym = reinterpret_cast<const short *>(dm->hDense.get() + nbPkt);
+    const lorahip_work_result *hCalls = reinterpret_cast<const lorahip_work_result *>(dm->hDense.get() + nbPkt + nbSym);
+    const StreamSignal *hSig = reinterpret_cast<const StreamSignal *>(dm->hDense.get() + nbPkt + nbSym + nbCalls);
     for (size_t c = 0; c < B; c++)
     {
         Channel &k = dm->ch[c];
@@ -703,7 +687,7 @@ static int drainPending(lorahip_demod *dm)
 
 static StreamState *hostStates(lorahip_demod *dm)
 {
-    return reinterpret_cast<StreamState *>(dm->sHost + headLayout(dm).oState);
+    return reinterpret_cast<StreamState *>(dm->sHost.get() + headLayout(dm).oState);
 }
 
 //! the open packets' symbols the device holds (dCarry) into the mirrors' outSymbols; the mirrors' state must be current
@@ -713,12 +697,12 @@ static int fetchCarry(lorahip_demod *dm)
     const size_t B = dm->B, cap = dm->carryCap;
     bool any = false;
     for (size_t c = 0; c < B && !any; c++) any = dm->ch[c].state == ST_DATASYMBOLS && dm->ch[c].symCount != 0;
-    if (any && dm->dCarry && dm->devCarryValid)
+    if (any && dm->dCarry.get() && dm->devCarryValid)
     {
         const DeviceGuard guard(dm->ctx->device);
         std::vector<short> rows;
         try { rows.resize(B * cap); } catch (...) { setLastError("no memory for the open packets' symbols"); return LORAHIP_E_NOMEM; }   // nothing may cross the C ABI
-        LORAHIP_TRY(hipMemcpyAsync(rows.data(), dm->dCarry, B * cap * sizeof(short), hipMemcpyDeviceToHost, dm->ctx->stream));
+        LORAHIP_TRY(hipMemcpyAsync(rows.data(), dm->dCarry.get(), B * cap * sizeof(short), hipMemcpyDeviceToHost, dm->ctx->stream));
         LORAHIP_TRY(hipStreamSynchronize(dm->ctx->stream));
         for (size_t c = 0; c < B; c++)
         {
@@ -737,7 +721,7 @@ static int fetchCarry(lorahip_demod *dm)
 static int syncMirrors(lorahip_demod *dm)
 {
     { const int rc = refuseWhilePiped(dm); if (rc != LORAHIP_OK) return rc; }
-    if (dm->mirrorsStale && dm->sHost)
+    if (dm->mirrorsStale && dm->sHost.get())
     {
         { const int rc = ensureHead(dm); if (rc != LORAHIP_OK) return rc; }
         const StreamState *hs = hostStates(dm);
@@ -814,16 +798,16 @@ static StreamArgs makeStreamArgs(const lorahip_demod *dm, const float *iqDev, co
     StreamArgs a{};
     a.iq = reinterpret_cast<const float2 *>(iqDev);
     a.uniformStride = (long long)dm->uniStride;
-    a.state = reinterpret_cast<StreamState *>(dm->sDev + H.oState);
-    a.near = reinterpret_cast<unsigned *>(dm->sDev + H.oNear);
-    a.carry = dm->dCarry; a.carryCap = int(dm->carryCap);
+    a.state = reinterpret_cast<StreamState *>(dm->sDev.get() + H.oState);
+    a.near = reinterpret_cast<unsigned *>(dm->sDev.get() + H.oNear);
+    a.carry = dm->dCarry.get(); a.carryCap = int(dm->carryCap);
     a.nCalls = reinterpret_cast<int *>(rec + L.oN); a.nSym = reinterpret_cast<int *>(rec + L.oNSym); a.nPkt = reinterpret_cast<int *>(rec + L.oNPkt);
     a.nSig = reinterpret_cast<int *>(rec + L.oNSig); a.end = reinterpret_cast<int2 *>(rec + L.oEnd);
     a.pktOut = reinterpret_cast<StreamPacket *>(rec + L.oPkt); a.symOut = reinterpret_cast<short *>(rec + L.oSym);
     a.sigOut = L.signals ? reinterpret_cast<StreamSignal *>(rec + L.oSig) : nullptr;
     a.calls = L.tracing ? reinterpret_cast<lorahip_work_result *>(rec + L.oCalls) : nullptr;
-    a.down = ctx->dDown; a.fine = ctx->dFine; a.twStage = ctx->dTwStage;
-    a.fineA = ctx->fineGather ? nullptr : ctx->dFineA; a.fineB = ctx->fineGather ? nullptr : ctx->dFineB;
+    a.down = ctx->dDown.get(); a.fine = ctx->dFine.get(); a.twStage = ctx->dTwStage.get();
+    a.fineA = ctx->fineGather ? nullptr : ctx->dFineA.get(); a.fineB = ctx->fineGather ? nullptr : ctx->dFineB.get();
     a.nChannels = unsigned(L.B); a.cap = int(L.cap); a.symStride = int(L.symStride); a.capPkt = int(L.capPkt);
     a.powerScale = ctx->powerScale; a.thresh = dm->thresh; a.sync = dm->sync;
     a.mtu = dm->mtu > 0xffffffffu ? 0xffffffffu : unsigned(dm->mtu);
@@ -862,10 +846,9 @@ static int runStream(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
     if (useDevCarry && dm->mtu + 1 > dm->carryCap)
     {
         { const int rc = syncMirrors(dm); if (rc != LORAHIP_OK) return rc; }      // what the device holds of open packets goes to the mirrors first
-        if (dm->dCarry) { (void)hipFree(dm->dCarry); dm->dCarry = nullptr; }
         dm->carryCap = 0; dm->devCarryValid = false;
         const size_t rows = dm->mtu + 1 < 64 ? 64 : dm->mtu + 1;
-        LORAHIP_TRY(hipMalloc((void **)&dm->dCarry, B * rows * sizeof(short)));
+        LORAHIP_TRY(dm->dCarry.grow(B * rows * sizeof(short)));      // (more rows than it has: the old block goes, then the new one is made)
         dm->carryCap = rows;
     }
 
@@ -876,25 +859,19 @@ static int runStream(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
     if (const char *e = std::getenv("LORAHIP_SYM_PAD")) { const long v = std::atol(e); if (v >= 0 && v < (1 << 20)) rowPad = v; }
 #endif
     L.make(B, cap, capPkt, dm->tracing, size_t(long(useDevCarry ? dm->carryCap : 0) + rowPad), dm->wantSignals);
-    if (L.total > dm->sBytes)
+    if (L.total > dm->sDev.bytes())
     {
         { const int rc = syncMirrors(dm); if (rc != LORAHIP_OK) return rc; }      // the pinned copy of the state goes away with the buffers
-        if (dm->sDev) { (void)hipFree(dm->sDev); dm->sDev = nullptr; }
-        if (dm->sHost) { (void)hipHostFree(dm->sHost); dm->sHost = nullptr; }
-        dm->sBytes = 0;
         dm->devStateFresh = false;
         dm->headStale = false;                       // (syncMirrors has read what there was)
         // a quarter more than this run needs: the chunks of a running receiver differ by the remainders they start with, and every
         // growth costs two allocations and an upload of the state
-        const size_t want = L.total + L.total / 4;
-        LORAHIP_TRY(hipMalloc((void **)&dm->sDev, want));
-        LORAHIP_TRY(hipHostMalloc((void **)&dm->sHost, L.oPkt, hipHostMallocDefault));       // the host mirrors only the head: placement, state, counts
-        dm->sBytes = want;
+        LORAHIP_TRY(regrowPair(dm->sDev, L.total + L.total / 4, dm->sHost, L.oPkt, hipHostMallocDefault));   // the host mirrors only the head: placement, state, counts
         // the kernels' near-threshold counters only ever add: they start at zero with the buffers
-        LORAHIP_TRY(hipMemsetAsync(dm->sDev + L.oNear, 0, 2 * sizeof(unsigned), ctx->stream));
+        LORAHIP_TRY(hipMemsetAsync(dm->sDev.get() + L.oNear, 0, 2 * sizeof(unsigned), ctx->stream));
         dm->nearSeen[0] = dm->nearSeen[1] = 0;
     }
-    char *h = dm->sHost, *d = dm->sDev;
+    char *h = dm->sHost.get(), *d = dm->sDev.get();
     long long *hBase = reinterpret_cast<long long *>(h + L.oBase), *hLen = reinterpret_cast<long long *>(h + L.oLen);
     StreamState *hState = reinterpret_cast<StreamState *>(h + L.oState);
     const StreamSummary *hSum = reinterpret_cast<const StreamSummary *>(h + L.oSum);
@@ -952,10 +929,10 @@ static int runStream(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
             // the mirrors hold them (a host-driven run, or a resumed one, came before): up they go
             const size_t cc = dm->carryCap;
             { const int grc = growDense(dm, B * cc * sizeof(short)); if (grc != LORAHIP_OK) return grc; }
-            short *stage = reinterpret_cast<short *>(dm->hDense);
+            short *stage = reinterpret_cast<short *>(dm->hDense.get());
             for (size_t c = 0; c < B; c++)
                 if (carry[c]) std::memcpy(stage + c * cc, dm->ch[c].outSymbols.data(), (carry[c] < dm->ch[c].outSymbols.size() ? carry[c] : dm->ch[c].outSymbols.size()) * sizeof(short));
-            LORAHIP_TRY(hipMemcpyAsync(dm->dCarry, stage, B * cc * sizeof(short), hipMemcpyHostToDevice, ctx->stream));
+            LORAHIP_TRY(hipMemcpyAsync(dm->dCarry.get(), stage, B * cc * sizeof(short), hipMemcpyHostToDevice, ctx->stream));
             LORAHIP_TRY(hipStreamSynchronize(ctx->stream));       // the pinned scratch is reused
         }
         carry.assign(B, 0);
@@ -991,7 +968,8 @@ static int runStream(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
     const size_t firstNewPacket = dm->packets.size();
     const Clock::time_point t1 = Clock::now();
     dm->kernelMs = 0.0;
-    if (dm->evK0 == nullptr) { LORAHIP_TRY(hipEventCreate(&dm->evK0)); LORAHIP_TRY(hipEventCreate(&dm->evK1)); }
+    LORAHIP_TRY(dm->evK0.ensure());
+    LORAHIP_TRY(dm->evK1.ensure());
     bool lastPending = false;
     int launches = 0;
     size_t runCalls = 0;                              // calls of the fullest channel, launch by launch
@@ -999,21 +977,21 @@ static int runStream(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
     while (true)
     {
         const Clock::time_point ta = Clock::now();
-        LORAHIP_TRY(hipEventRecord(dm->evK0, ctx->stream));
+        LORAHIP_TRY(hipEventRecord(dm->evK0.get(), ctx->stream));
         LORAHIP_TRY(launchStream(ctx->sf, a, ctx->stream));
-        LORAHIP_TRY(hipEventRecord(dm->evK1, ctx->stream));
+        LORAHIP_TRY(hipEventRecord(dm->evK1.get(), ctx->stream));
         a.flags = 0;                                  // a resumed launch continues where the state says
         // what the host needs of the launch, reduced on the device: 72 bytes come back, not 52 per channel
         // (written by the kernel straight into the pinned staging block when the device can address it: no copy to enqueue)
         void *sumDev = nullptr;
         const bool direct = hipHostGetDevicePointer(&sumDev, const_cast<StreamSummary *>(hSum), 0) == hipSuccess && sumDev != nullptr;
         if (!direct) (void)hipGetLastError();
-        LORAHIP_TRY(launchStreamSummary(a.end, a.nCalls, a.nSym, a.nPkt, dm->wantSignals ? a.nSig : nullptr, B, int(cap), int(capPkt), a.near, dm->dSumScratch,
+        LORAHIP_TRY(launchStreamSummary(a.end, a.nCalls, a.nSym, a.nPkt, dm->wantSignals ? a.nSig : nullptr, B, int(cap), int(capPkt), a.near, dm->dSumScratch.get(),
                                         direct ? static_cast<StreamSummary *>(sumDev) : reinterpret_cast<StreamSummary *>(d + L.oSum), ctx->stream));
         if (!direct) LORAHIP_TRY(hipMemcpyAsync(h + L.oSum, d + L.oSum, sizeof(StreamSummary), hipMemcpyDeviceToHost, ctx->stream));
         LORAHIP_TRY(hipStreamSynchronize(ctx->stream));
         dm->headStale = true;                         // the pinned copy of the per-channel state and counts lags the device now
-        { float ms = 0.0f; if (hipEventElapsedTime(&ms, dm->evK0, dm->evK1) == hipSuccess) dm->kernelMs += ms; }
+        { float ms = 0.0f; if (hipEventElapsedTime(&ms, dm->evK0.get(), dm->evK1.get()) == hipSuccess) dm->kernelMs += ms; }
         const Clock::time_point tb = Clock::now();
         tDev += std::chrono::duration<double>(tb - ta).count();
         sum = *hSum;
@@ -1096,8 +1074,8 @@ static int runStream(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
  * for a packet. Anything else takes the ordinary step (which establishes exactly that). */
 static bool steadyAppend(const lorahip_demod *dm, const size_t rowStride, const size_t nValid)
 {
-    return usesStreamKernel(dm) && !dm->tracing && !dm->portsOn && !dm->activatePending && dm->sDev != nullptr && dm->append && !dm->appendFresh &&
-           dm->uniStride == rowStride && nValid >= dm->appendPrev && dm->dCarry != nullptr && dm->mtu + 1 <= dm->carryCap;
+    return usesStreamKernel(dm) && !dm->tracing && !dm->portsOn && !dm->activatePending && dm->sDev.get() != nullptr && dm->append && !dm->appendFresh &&
+           dm->uniStride == rowStride && nValid >= dm->appendPrev && dm->dCarry.get() != nullptr && dm->mtu + 1 <= dm->carryCap;
 }
 
 //! ... and to enter either mode: the state and the open packets' symbols on the device, no records of a launch left there
@@ -1130,8 +1108,8 @@ static hipError_t packPackets(const lorahip_demod *dm, const StreamLayout &L, co
 {
     const size_t nbRow = align256(L.B * sizeof(int));
     return launchPackPackets(reinterpret_cast<const StreamPacket *>(rec + L.oPkt), reinterpret_cast<const int *>(rec + L.oNPkt),
-                             reinterpret_cast<const short *>(rec + L.oSym), reinterpret_cast<int *>(dm->dDense), L.B, int(L.symStride), int(L.capPkt), n,
-                             reinterpret_cast<long long *>(dm->dDense + nbRow), syms, int(symStride), nsyms, chan, st);
+                             reinterpret_cast<const short *>(rec + L.oSym), reinterpret_cast<int *>(dm->dDense.get()), L.B, int(L.symStride), int(L.capPkt), n,
+                             reinterpret_cast<long long *>(dm->dDense.get() + nbRow), syms, int(symStride), nsyms, chan, st);
 }
 
 //! the signals of a record set of layout L at `rec` into the registered signal rows from row `first` on (stream-ordered on `st`, no wait)
@@ -1146,9 +1124,9 @@ static hipError_t packSignals(const lorahip_demod *dm, const StreamLayout &L, co
 static int pipeRead(lorahip_demod *dm, const int set)
 {
     Pipe &P = dm->pipe;
-    LORAHIP_TRY(hipEventSynchronize(P.ev[set]));
+    LORAHIP_TRY(hipEventSynchronize(P.ev[set].get()));
     P.pending[set] = false;
-    const StreamSummary sum = P.hSum[set];
+    const StreamSummary sum = P.hSum.get()[set];
     foldNear(dm, sum.nearSquelch, sum.nearStep);
     dm->workCalls += sum.calls;
     dm->lastSum = sum;
@@ -1183,16 +1161,16 @@ static int pipePack(lorahip_demod *dm, const int set, const lorahip_packet_rows 
     // stream then waits for the packing before anything later: the next kernel reuses this record set, the caller reads the rows.
     // Worth it for short steps only (profiles/r04/s37_*: 8-window chunks at SF7 +14 %; at 128-window chunks the packing kernels
     // displace workgroups of a streaming grid that exactly fills the device, -5 %).
-    hipStream_t packStream = beside ? P.side : ctx->stream;
-    if (beside) LORAHIP_TRY(hipStreamWaitEvent(P.side, P.entry, 0));
+    hipStream_t packStream = beside ? P.side.get() : ctx->stream;
+    if (beside) LORAHIP_TRY(hipStreamWaitEvent(P.side.get(), P.entry.get(), 0));
     if (n)
-        LORAHIP_TRY(packPackets(dm, L, P.dev[set], n, rows->syms_dev + firstRow * rows->sym_stride, rows->sym_stride, rows->nsyms_dev + firstRow,
+        LORAHIP_TRY(packPackets(dm, L, P.dev[set].get(), n, rows->syms_dev + firstRow * rows->sym_stride, rows->sym_stride, rows->nsyms_dev + firstRow,
                                 rows->channel_dev ? rows->channel_dev + firstRow : nullptr, packStream));
-    if (ns) LORAHIP_TRY(packSignals(dm, L, P.dev[set], firstSig, packStream));
+    if (ns) LORAHIP_TRY(packSignals(dm, L, P.dev[set].get(), firstSig, packStream));
     if (beside)
     {
-        LORAHIP_TRY(hipEventRecord(P.packDone, P.side));
-        LORAHIP_TRY(hipStreamWaitEvent(ctx->stream, P.packDone, 0));
+        LORAHIP_TRY(hipEventRecord(P.packDone.get(), P.side.get()));
+        LORAHIP_TRY(hipStreamWaitEvent(ctx->stream, P.packDone.get(), 0));
     }
     P.held[set] = false;                              // only now: a launch that failed above leaves the packets where they are
     return LORAHIP_OK;
@@ -1255,7 +1233,7 @@ static int pipeFlush(lorahip_demod *dm, const lorahip_packet_rows *rows, size_t 
     if (rows == nullptr) P.held[0] = P.held[1] = false;                       // dropped on request
     else
     {
-        LORAHIP_TRY(hipEventRecord(P.entry, dm->ctx->stream));
+        LORAHIP_TRY(hipEventRecord(P.entry.get(), dm->ctx->stream));
         const int rc = pipeDeliverHeld(dm, last ^ 1, 2, rows, &n1, &c1, false);
         if (nPackets) *nPackets = n1;
         if (rc != LORAHIP_OK) return rc;              // (the pipeline stays entered: flush again with rows that hold *n_packets)
@@ -1282,14 +1260,12 @@ static int pipeStep(lorahip_demod *dm, const float *iqDev, const size_t rowStrid
     const DeviceGuard guard(ctx->device);
     if (!P.active)
     {
-        if (P.hSum == nullptr)
-        {
-            LORAHIP_TRY(hipHostMalloc((void **)&P.hSum, 2 * sizeof(StreamSummary), hipHostMallocMapped));
-            for (int i = 0; i < 2; i++) LORAHIP_TRY(hipEventCreateWithFlags(&P.ev[i], hipEventDisableTiming));
-            LORAHIP_TRY(hipEventCreateWithFlags(&P.packDone, hipEventDisableTiming));
-            LORAHIP_TRY(hipEventCreateWithFlags(&P.entry, hipEventDisableTiming));
-            LORAHIP_TRY(hipStreamCreateWithFlags(&P.side, hipStreamNonBlocking));
-        }
+        // (made on first use; each is asked for every time a pipeline is entered, so that a call that failed half way is completed by the next)
+        LORAHIP_TRY(P.hSum.grow(2 * sizeof(StreamSummary), hipHostMallocMapped));
+        for (int i = 0; i < 2; i++) LORAHIP_TRY(P.ev[i].ensure(hipEventDisableTiming));
+        LORAHIP_TRY(P.packDone.ensure(hipEventDisableTiming));
+        LORAHIP_TRY(P.entry.ensure(hipEventDisableTiming));
+        LORAHIP_TRY(P.side.ensure(hipStreamNonBlocking));
         P.active = true; P.k = 0; P.pending[0] = P.pending[1] = false; P.held[0] = P.held[1] = false;
         dm->devStateFresh = false;                    // until the pipeline is flushed, only it knows where the state stands
     }
@@ -1297,7 +1273,7 @@ static int pipeStep(lorahip_demod *dm, const float *iqDev, const size_t rowStrid
     if (nPackets) *nPackets = 0;
     if (calls) *calls = 0;
     // where the launch stream stands now: behind whatever the caller queued to read the rows of the call before (pipePack)
-    LORAHIP_TRY(hipEventRecord(P.entry, ctx->stream));
+    LORAHIP_TRY(hipEventRecord(P.entry.get(), ctx->stream));
     bool delivered = false;
     dm->lastSignals = 0;
     if (P.held[set] || P.held[set ^ 1])
@@ -1318,16 +1294,10 @@ static int pipeStep(lorahip_demod *dm, const float *iqDev, const size_t rowStrid
     streamCapacity(dm, nValid - dm->appendPrev + 2 * N, cap, capPkt);
     StreamLayout L;
     L.make(B, cap, capPkt, false, dm->carryCap, dm->wantSignals);
-    if (L.total > P.bytes[set])
-    {
-        // (this set's last use, step k - 2, was packed during step k - 1's call, stream-ordered before kernel k - 1: freeing waits for it)
-        if (P.dev[set]) { (void)hipFree(P.dev[set]); P.dev[set] = nullptr; P.bytes[set] = 0; }
-        const size_t want = L.total + L.total / 4;
-        LORAHIP_TRY(hipMalloc((void **)&P.dev[set], want));
-        P.bytes[set] = want;
-    }
+    // (this set's last use, step k - 2, was packed during step k - 1's call, stream-ordered before kernel k - 1: freeing waits for it)
+    LORAHIP_TRY(P.dev[set].grow(L.total, L.total / 4));
     P.lay[set] = L;
-    StreamArgs a = makeStreamArgs(dm, iqDev, L, P.dev[set]);
+    StreamArgs a = makeStreamArgs(dm, iqDev, L, P.dev[set].get());
     a.uniformLen = (long long)nValid;
     a.flags = 4 | 8;                                  // continue the streams; open packets in from / out to the carry rows
     // the block's signals (:267-269), kept per step like the packets and delivered with them one step late
@@ -1337,8 +1307,8 @@ static int pipeStep(lorahip_demod *dm, const float *iqDev, const size_t rowStrid
     // -- it reads only this record set's counts and end words -- was measured: two more API calls and the hand-over between the streams
     // cost more than the 11 us the next kernel would no longer queue behind, 93 -> 108 us per 8-window step at SF7; profiles/r05/s36_*.)
     LORAHIP_TRY(launchStream(ctx->sf, a, ctx->stream));
-    LORAHIP_TRY(launchStreamSummary(a.end, a.nCalls, a.nSym, a.nPkt, dm->wantSignals ? a.nSig : nullptr, B, int(cap), int(capPkt), a.near, dm->dSumScratch, &P.hSum[set], ctx->stream));
-    LORAHIP_TRY(hipEventRecord(P.ev[set], ctx->stream));
+    LORAHIP_TRY(launchStreamSummary(a.end, a.nCalls, a.nSym, a.nPkt, dm->wantSignals ? a.nSig : nullptr, B, int(cap), int(capPkt), a.near, dm->dSumScratch.get(), P.hSum.get() + set, ctx->stream));
+    LORAHIP_TRY(hipEventRecord(P.ev[set].get(), ctx->stream));
     P.pending[set] = true;
     P.k++;
     dm->stepIq = iqDev; dm->stepStride = rowStride;
@@ -1422,7 +1392,7 @@ static void residentAbort(lorahip_demod *dm)
     Resident &R = dm->res;
     if (!R.active) return;
     __atomic_store_n(&R.host->abort, 1u, __ATOMIC_RELEASE);
-    (void)hipStreamSynchronize(R.run);
+    (void)hipStreamSynchronize(R.run.get());
     R.active = false; R.unavailable = true;
     dm->devStateFresh = false;                        // the steps' bookkeeping is incomplete: nothing on the device is trusted
 }
@@ -1454,7 +1424,7 @@ static int residentFlush(lorahip_demod *dm, size_t *nPackets, int64_t *calls)
     }
     // the quit message, then the kernel's end: the state, the read positions and the open packets are on the device as a streaming run leaves them
     { const int rc = residentRing(dm, R.lastValid, nullptr, 1u); if (rc != LORAHIP_OK) { residentAbort(dm); return rc; } }
-    LORAHIP_TRY(hipStreamSynchronize(R.run));
+    LORAHIP_TRY(hipStreamSynchronize(R.run.get()));
     R.active = false;
     if (nPackets) *nPackets = pk;
     if (calls) *calls = cl;
@@ -1467,7 +1437,7 @@ static int residentFlush(lorahip_demod *dm, size_t *nPackets, int64_t *calls)
     {
         std::vector<char> cbuf(sizeof(ResidentCtl));
         ResidentCtl &c = *reinterpret_cast<ResidentCtl *>(cbuf.data());
-        if (hipMemcpy(&c, R.ctl, sizeof(c), hipMemcpyDeviceToHost) == hipSuccess)
+        if (hipMemcpy(&c, R.ctl.get(), sizeof(c), hipMemcpyDeviceToHost) == hipSuccess)
             for (int k = 0; k < 8; k++)                     // (slot k holds the last step with (step - 1) & 7 == k; the wait stamp of slot k is of the step after)
                 std::fprintf(stderr, "resident slot %d (workgroup 0, wave 0; us): waited %.1f, setup %.1f, windows + records %.1f, look-ahead + step end %.1f; since the end of the slot before %.1f\n", k + 1,
                              (c.dbg[k][1] - c.dbg[k][0]) / 100.0, (c.dbg[k][2] - c.dbg[k][1]) / 100.0, (c.dbg[k][4] - c.dbg[k][2]) / 100.0,
@@ -1516,7 +1486,7 @@ static int residentFlush(lorahip_demod *dm, size_t *nPackets, int64_t *calls)
         // the kernels' running near-threshold counters
         const StreamLayout H = headLayout(dm);
         unsigned near[2] = {0, 0};
-        LORAHIP_TRY(hipMemcpy(near, dm->sDev + H.oNear, sizeof(near), hipMemcpyDeviceToHost));
+        LORAHIP_TRY(hipMemcpy(near, dm->sDev.get() + H.oNear, sizeof(near), hipMemcpyDeviceToHost));
         foldNear(dm, near[0], near[1]);
     }
     if (lost)
@@ -1550,42 +1520,35 @@ static int residentStep(lorahip_demod *dm, const float *iqDev, const size_t rowS
         const bool ready = compatible && !R.unavailable && stateOnDevice(dm);
         if (!ready) return LORAHIP_OK;
         const DeviceGuard guard(ctx->device);
-        if (R.ctl == nullptr)
-        {
-            LORAHIP_TRY(hipMalloc((void **)&R.ctl, sizeof(ResidentCtl)));
-            LORAHIP_TRY(hipHostMalloc((void **)&R.host, sizeof(ResidentHost), hipHostMallocMapped));
-            LORAHIP_TRY(hipStreamCreateWithFlags(&R.run, hipStreamNonBlocking));
-            LORAHIP_TRY(hipEventCreateWithFlags(&R.ev, hipEventDisableTiming));
-        }
+        // (made on first use; each is asked for at every launch, so that a call that failed half way is completed by the next)
+        LORAHIP_TRY(R.ctl.grow(sizeof(ResidentCtl)));
+        LORAHIP_TRY(R.host.grow(sizeof(ResidentHost), hipHostMallocMapped));
+        LORAHIP_TRY(R.run.ensure(hipStreamNonBlocking));
+        LORAHIP_TRY(R.ev.ensure(hipEventDisableTiming));
         // a step's records: sized for a step as long as this one (a longer one fills them, stops the channel and the next step resumes it)
         size_t cap, capPkt;
         streamCapacity(dm, nValid - dm->appendPrev + 2 * N, cap, capPkt);
         StreamLayout L;
         L.make(B, cap, capPkt, false, dm->carryCap, dm->wantSignals);
         // (RES_RING sets of record arrays: a step writes set step & 3 -- StreamArgs::resRecStride)
-        if (RES_RING * L.total > R.recBytes)
-        {
-            if (R.rec) { (void)hipFree(R.rec); R.rec = nullptr; R.recBytes = 0; }
-            LORAHIP_TRY(hipMalloc((void **)&R.rec, RES_RING * L.total + L.total / 4));
-            R.recBytes = RES_RING * L.total + L.total / 4;
-        }
+        LORAHIP_TRY(R.rec.grow(RES_RING * L.total, L.total / 4));
         R.lay = L;
         R.sigs = dm->wantSignals;
         void *hostDev = nullptr;
-        LORAHIP_TRY(hipHostGetDevicePointer(&hostDev, R.host, 0));
-        std::memset(R.host, 0, sizeof(ResidentHost));
-        LORAHIP_TRY(hipMemsetAsync(R.ctl, 0, std::getenv("LORAHIP_RESIDENT_DEBUG") ? sizeof(ResidentCtl) : offsetof(ResidentCtl, dbgWave), ctx->stream));
-        StreamArgs a = makeStreamArgs(dm, iqDev, L, R.rec);
+        LORAHIP_TRY(hipHostGetDevicePointer(&hostDev, R.host.get(), 0));
+        std::memset(R.host.get(), 0, sizeof(ResidentHost));
+        LORAHIP_TRY(hipMemsetAsync(R.ctl.get(), 0, std::getenv("LORAHIP_RESIDENT_DEBUG") ? sizeof(ResidentCtl) : offsetof(ResidentCtl, dbgWave), ctx->stream));
+        StreamArgs a = makeStreamArgs(dm, iqDev, L, R.rec.get());
         a.uniformLen = 0;                             // (the length of a step comes with its message)
         a.flags = 4 | 8;
         a.maxBlocks = 0; a.lanes = -1;
-        a.res = R.ctl; a.resHost = static_cast<ResidentHost *>(hostDev); a.resWatchdog = kResidentWatchdog; a.resRecStride = L.total;
+        a.res = R.ctl.get(); a.resHost = static_cast<ResidentHost *>(hostDev); a.resWatchdog = kResidentWatchdog; a.resRecStride = L.total;
         if (const char *e = std::getenv("LORAHIP_RESIDENT_DEBUG")) a.resDebug = unsigned(std::atoi(e));     // (the step whose stamps every wavefront leaves)
         if (const char *e = std::getenv("LORAHIP_RESIDENT_SLEEP")) a.resSleep = std::atoi(e);             // (measurements: profiles/r06)
         // behind everything queued on the launch stream (the state of the run before, the cleared control block)
-        LORAHIP_TRY(hipEventRecord(R.ev, ctx->stream));
-        LORAHIP_TRY(hipStreamWaitEvent(R.run, R.ev, 0));
-        const hipError_t le = launchStreamResident(ctx->sf, a, R.run, &R.grid);
+        LORAHIP_TRY(hipEventRecord(R.ev.get(), ctx->stream));
+        LORAHIP_TRY(hipStreamWaitEvent(R.run.get(), R.ev.get(), 0));
+        const hipError_t le = launchStreamResident(ctx->sf, a, R.run.get(), &R.grid);
         if (le == hipErrorNotSupported) { (void)hipGetLastError(); R.unavailable = true; return LORAHIP_OK; }     // not for this geometry: ordinary steps
         LORAHIP_TRY(le);
         R.active = true; R.seq = 0; R.reported = 0; R.lastMore = false;
@@ -1651,15 +1614,6 @@ static int residentStep(lorahip_demod *dm, const float *iqDev, const size_t rowS
  * kernels -- the same arithmetic on the same inputs, hence the same bits -- and scattered into the caller's per-channel
  * port streams. Off unless asked for: they triple the HBM traffic.
  **********************************************************************/
-static int growPort(lorahip_demod *dm, const size_t bytes)
-{
-    if (bytes <= dm->dPortBytes) return LORAHIP_OK;
-    if (dm->dPort) { (void)hipFree(dm->dPort); dm->dPort = nullptr; dm->dPortBytes = 0; }
-    LORAHIP_TRY(hipMalloc((void **)&dm->dPort, bytes));
-    dm->dPortBytes = bytes;
-    return LORAHIP_OK;
-}
-
 static int fillPorts(lorahip_demod *dm, const float *iqDev)
 {
     lorahip_ctx *ctx = dm->ctx;
@@ -1734,8 +1688,8 @@ static int fillPorts(lorahip_demod *dm, const float *iqDev)
     const size_t winBytes = align256(chunk * N * sizeof(cf32));
     const size_t inBytes = align256(chunk * sizeof(int64_t)) + 3 * align256(chunk * sizeof(int32_t));
     const size_t outBytes = align256(chunk * sizeof(uint16_t)) + 3 * align256(chunk * sizeof(float));
-    { const int rc = growPort(dm, descBytes + 2 * winBytes + inBytes + outBytes); if (rc != LORAHIP_OK) return rc; }
-    char *cur = dm->dPort;
+    LORAHIP_TRY(dm->dPort.grow(descBytes + 2 * winBytes + inBytes + outBytes));
+    char *cur = dm->dPort.get();
     char *dDesc = cur; cur += descBytes;
     float *tFft = reinterpret_cast<float *>(cur); cur += winBytes;
     float *tDec = reinterpret_cast<float *>(cur); cur += winBytes;
@@ -1845,22 +1799,16 @@ int lorahip_demod_create(lorahip_demod **out, const int device, const int sf, co
     dm->B = n_channels;
     try { dm->ch.resize(n_channels); }                              // (value-initialised too: every count and position zero)
     catch (const std::bad_alloc &) { lorahip_demod_destroy(dm); return LORAHIP_E_NOMEM; }
-    dm->stageBytes = carve(nullptr, n_channels).total;
-    bool staged;
+    const size_t stageBytes = carve(nullptr, n_channels).total, sumBytes = streamSummaryScratchBytes(n_channels);
+    hipError_t e;
     {
         const DeviceGuard guard(device);                    // lorahip_create() restored the caller's device: allocate on OURS
-        staged = hipMalloc((void **)&dm->d, dm->stageBytes) == hipSuccess &&
-                 hipHostMalloc((void **)&dm->h, dm->stageBytes, hipHostMallocDefault) == hipSuccess;
+        e = regrowPair(dm->d, stageBytes, dm->h, stageBytes, hipHostMallocDefault);
         // (more than 32768 channels: the summary of a streaming launch is reduced by one workgroup per 4096 of them and a second launch)
-        if (staged && n_channels > 32768)
-            staged = hipMalloc(&dm->dSumScratch, streamSummaryScratchBytes(n_channels)) == hipSuccess &&
-                     hipMemset(dm->dSumScratch, 0, streamSummaryScratchBytes(n_channels)) == hipSuccess;
+        if (e == hipSuccess && n_channels > 32768) e = dm->dSumScratch.grow(sumBytes);
+        if (e == hipSuccess && n_channels > 32768) e = hipMemset(dm->dSumScratch.get(), 0, sumBytes);
     }
-    if (!staged)
-    {
-        lorahip_demod_destroy(dm);
-        return LORAHIP_E_NOMEM;
-    }
+    if (e != hipSuccess) { lorahip_demod_destroy(dm); return LORAHIP_E_NOMEM; }
     lorahip_demod_activate(dm);
     *out = dm;
     return LORAHIP_OK;
@@ -1915,45 +1863,15 @@ void lorahip_demod_destroy(lorahip_demod *dm)
 {
     if (dm == nullptr) return;
     if (dm->comp) { delete dm->comp; delete dm; return; }
+    lorahip_ctx *ctx = dm->ctx;
     {
-    const DeviceGuard guard(dm->ctx ? dm->ctx->device : 0);   // the caller's current device is restored on return
-    if (dm->ctx) (void)hipStreamSynchronize(dm->ctx->stream);  // a pipelined step may still be writing into what is freed below
-    if (dm->d) (void)hipFree(dm->d);
-    if (dm->h) (void)hipHostFree(dm->h);
-    if (dm->dIq) (void)hipFree(dm->dIq);
-    if (dm->sDev) (void)hipFree(dm->sDev);
-    if (dm->sHost) (void)hipHostFree(dm->sHost);
-    if (dm->dCarry) (void)hipFree(dm->dCarry);
-    if (dm->dDense) (void)hipFree(dm->dDense);
-    if (dm->hDense) (void)hipHostFree(dm->hDense);
-    if (dm->dPort) (void)hipFree(dm->dPort);
-    if (dm->ownFft) (void)hipFree(dm->ownFft);
-    if (dm->ownDec) (void)hipFree(dm->ownDec);
-    if (dm->ownRaw) (void)hipFree(dm->ownRaw);
-    if (dm->evK0) (void)hipEventDestroy(dm->evK0);
-    if (dm->evK1) (void)hipEventDestroy(dm->evK1);
-    if (dm->evJoin) (void)hipEventDestroy(dm->evJoin);
-    if (dm->dSumScratch) (void)hipFree(dm->dSumScratch);
-    residentAbort(dm);                                        // (a resident kernel must leave before its memory goes)
-    const Resident &R = dm->res;
-    if (R.ctl) (void)hipFree(R.ctl);
-    if (R.host) (void)hipHostFree(R.host);
-    if (R.rec) (void)hipFree(R.rec);
-    if (R.run) (void)hipStreamDestroy(R.run);
-    if (R.ev) (void)hipEventDestroy(R.ev);
-    const Pipe &P = dm->pipe;
-    for (int i = 0; i < 2; i++)
-    {
-        if (P.dev[i]) (void)hipFree(P.dev[i]);
-        if (P.hSum) (void)hipEventDestroy(P.ev[i]);
+        const DeviceGuard guard(ctx ? ctx->device : 0);           // the caller's current device is restored on return
+        if (ctx) (void)hipStreamSynchronize(ctx->stream);         // a pipelined step may still be writing into what is released below
+        residentAbort(dm);                                        // a resident kernel must leave before its memory goes
+        if (dm->pipe.side.get()) (void)hipStreamSynchronize(dm->pipe.side.get());
+        delete dm;                                                // inside the guard: the members release with the object's device current
     }
-    if (P.side) { (void)hipStreamSynchronize(P.side); (void)hipStreamDestroy(P.side); }
-    if (P.packDone) (void)hipEventDestroy(P.packDone);
-    if (P.entry) (void)hipEventDestroy(P.entry);
-    if (P.hSum) (void)hipHostFree(P.hSum);
-    }
-    lorahip_destroy(dm->ctx);
-    delete dm;
+    lorahip_destroy(ctx);                                         // last: its stream outlives everything that was ordered on it
 }
 
 int lorahip_demod_set_sync(lorahip_demod *dm, const unsigned char sync)
@@ -2006,9 +1924,9 @@ int lorahip_demod_stream_wait(lorahip_demod *dm, void *hip_stream)
     if (dm == nullptr) return LORAHIP_E_INVALID;
     if (dm->comp) return dm->comp->streamWait(hip_stream);
     const DeviceGuard guard(dm->ctx->device);
-    if (dm->evJoin == nullptr) LORAHIP_TRY(hipEventCreateWithFlags(&dm->evJoin, hipEventDisableTiming));
-    LORAHIP_TRY(hipEventRecord(dm->evJoin, dm->ctx->stream));
-    LORAHIP_TRY(hipStreamWaitEvent(reinterpret_cast<hipStream_t>(hip_stream), dm->evJoin, 0));
+    LORAHIP_TRY(dm->evJoin.ensure(hipEventDisableTiming));
+    LORAHIP_TRY(hipEventRecord(dm->evJoin.get(), dm->ctx->stream));
+    LORAHIP_TRY(hipStreamWaitEvent(reinterpret_cast<hipStream_t>(hip_stream), dm->evJoin.get(), 0));
     return LORAHIP_OK;
 }
 
@@ -2019,9 +1937,9 @@ int lorahip_demod_stream_follow(lorahip_demod *dm, void *hip_stream)
     if (dm == nullptr) return LORAHIP_E_INVALID;
     if (dm->comp) return dm->comp->streamFollow(hip_stream);
     const DeviceGuard guard(dm->ctx->device);
-    if (dm->evJoin == nullptr) LORAHIP_TRY(hipEventCreateWithFlags(&dm->evJoin, hipEventDisableTiming));
-    LORAHIP_TRY(hipEventRecord(dm->evJoin, reinterpret_cast<hipStream_t>(hip_stream)));
-    LORAHIP_TRY(hipStreamWaitEvent(dm->ctx->stream, dm->evJoin, 0));
+    LORAHIP_TRY(dm->evJoin.ensure(hipEventDisableTiming));
+    LORAHIP_TRY(hipEventRecord(dm->evJoin.get(), reinterpret_cast<hipStream_t>(hip_stream)));
+    LORAHIP_TRY(hipStreamWaitEvent(dm->ctx->stream, dm->evJoin.get(), 0));
     return LORAHIP_OK;
 }
 
@@ -2181,7 +2099,7 @@ int lorahip_demod_run(lorahip_demod *dm, const float *const *streams, const size
         if ((n_samples[c] && streams[c] == nullptr) || n_samples[c] > (size_t(1) << 48)) return LORAHIP_E_INVALID;
     size_t total = 0;
     for (size_t c = 0; c < dm->B; c++) total += n_samples[c];
-    if (total > dm->dIqSamples) { const int rc = regrowIq(dm, total); if (rc != LORAHIP_OK) return rc; }
+    LORAHIP_TRY(dm->dIq.grow(total * sizeof(cf32)));
     total = 0;
     placeSegments(dm, n_samples, [&](const size_t c) { const size_t at = total; total += n_samples[c]; return at; });     // back to back
     {
@@ -2189,11 +2107,11 @@ int lorahip_demod_run(lorahip_demod *dm, const float *const *streams, const size
         std::vector<const void *> src(dm->B);
         std::vector<size_t> len(dm->B);
         for (size_t c = 0; c < dm->B; c++) { src[c] = streams[c]; len[c] = n_samples[c] * sizeof(cf32); }
-        const int rc = gatherUpload(dm->ctx, dm->dIq, src.data(), len.data(), dm->B);
+        const int rc = gatherUpload(dm->ctx, dm->dIq.get(), src.data(), len.data(), dm->B);
         if (rc != LORAHIP_OK) return rc;
     }
     LORAHIP_TRY(hipStreamSynchronize(dm->ctx->stream));
-    return runAny(dm, dm->dIq, rounds);
+    return runAny(dm, dm->dIq.get(), rounds);
 }
 
 /* Host buffers that are the ROWS of one block of host memory -- channel c's n_samples[c] samples begin at sample first_sample[c] of
@@ -2233,12 +2151,12 @@ int lorahip_demod_run_host_rows(lorahip_demod *dm, const float *rows, const size
     if (width && rows == nullptr) return LORAHIP_E_INVALID;
     if (width > (size_t(1) << 40) / (dm->B ? dm->B : 1)) return LORAHIP_E_INVALID;
     const DeviceGuard guard(dm->ctx->device);
-    if (dm->B * width > dm->dIqSamples) { const int rc = regrowIq(dm, dm->B * width); if (rc != LORAHIP_OK) return rc; }
+    LORAHIP_TRY(dm->dIq.grow(dm->B * width * sizeof(cf32)));
     if (width)
-        LORAHIP_TRY(hipMemcpy2DAsync(dm->dIq, width * sizeof(cf32), rows + 2 * lo, row_stride * sizeof(cf32), width * sizeof(cf32), dm->B, hipMemcpyHostToDevice,
+        LORAHIP_TRY(hipMemcpy2DAsync(dm->dIq.get(), width * sizeof(cf32), rows + 2 * lo, row_stride * sizeof(cf32), width * sizeof(cf32), dm->B, hipMemcpyHostToDevice,
                                      dm->ctx->stream));
     placeSegments(dm, n_samples, [&](const size_t c) { return n_samples[c] ? c * width + (size_t(first_sample[c]) - lo) : 0; });
-    return runAny(dm, dm->dIq, rounds);               // (in stream order behind the copy; returns with the stream drained: the rows are the caller's again)
+    return runAny(dm, dm->dIq.get(), rounds);               // (in stream order behind the copy; returns with the stream drained: the rows are the caller's again)
 }
 
 //! accessors of the host queue first bring over what the last streaming launch left on the device; a failure there is the
@@ -2335,7 +2253,7 @@ static int packetsToDevice(lorahip_demod *dm, uint16_t *syms_dev, const size_t s
             hipStream_t st = dm->ctx->stream;
             // the rows are numbered on the device (scanDescribe: exclusive prefix sum of the per-channel packet counts): nothing is
             // uploaded, and nothing on the host is reused, so the caller decides whether to wait
-            LORAHIP_TRY(packPackets(dm, Q.lay, dm->sDev, n, syms_dev, sym_stride, nsyms_dev, channel_dev, st));
+            LORAHIP_TRY(packPackets(dm, Q.lay, dm->sDev.get(), n, syms_dev, sym_stride, nsyms_dev, channel_dev, st));
             if (sync) LORAHIP_TRY(hipStreamSynchronize(st));
             return LORAHIP_OK;
         }
@@ -2348,8 +2266,8 @@ static int packetsToDevice(lorahip_demod *dm, uint16_t *syms_dev, const size_t s
     const DeviceGuard guard(dm->ctx->device);
     const size_t nbSym = align256(P * sym_stride * sizeof(uint16_t)), nbInt = align256(P * sizeof(int32_t));
     { const int grc = growDense(dm, nbSym + 2 * nbInt); if (grc != LORAHIP_OK) return grc; }
-    uint16_t *hs = reinterpret_cast<uint16_t *>(dm->hDense);
-    int32_t *hn = reinterpret_cast<int32_t *>(dm->hDense + nbSym), *hc = reinterpret_cast<int32_t *>(dm->hDense + nbSym + nbInt);
+    uint16_t *hs = reinterpret_cast<uint16_t *>(dm->hDense.get());
+    int32_t *hn = reinterpret_cast<int32_t *>(dm->hDense.get() + nbSym), *hc = reinterpret_cast<int32_t *>(dm->hDense.get() + nbSym + nbInt);
     std::memset(hs, 0, P * sym_stride * sizeof(uint16_t));
     for (size_t i = 0; i < P; i++)
     {
@@ -2389,7 +2307,7 @@ static int signalsToRows(lorahip_demod *dm, const size_t first, size_t *n, const
         if (*n == 0) return LORAHIP_OK;
         if (first + *n > R.cap) { setLastError("lorahip_demod_receive: the signal rows cannot hold the signals that are due"); return LORAHIP_E_INVALID; }
         if (!Q.lay.signals) { *n = 0; return LORAHIP_OK; }
-        LORAHIP_TRY(packSignals(dm, Q.lay, dm->sDev, first, st));
+        LORAHIP_TRY(packSignals(dm, Q.lay, dm->sDev.get(), first, st));
         if (sync) LORAHIP_TRY(hipStreamSynchronize(st));
         return LORAHIP_OK;
     }
@@ -2400,8 +2318,8 @@ static int signalsToRows(lorahip_demod *dm, const size_t first, size_t *n, const
     if (first + S > R.cap) { setLastError("lorahip_demod_receive: the signal rows cannot hold the signals that are due"); return LORAHIP_E_INVALID; }
     const size_t nb = align256(S * sizeof(int32_t));
     { const int grc = growDense(dm, 4 * nb); if (grc != LORAHIP_OK) return grc; }
-    int32_t *hc = reinterpret_cast<int32_t *>(dm->hDense), *he = reinterpret_cast<int32_t *>(dm->hDense + nb);
-    float *hp = reinterpret_cast<float *>(dm->hDense + 2 * nb), *hs = reinterpret_cast<float *>(dm->hDense + 3 * nb);
+    int32_t *hc = reinterpret_cast<int32_t *>(dm->hDense.get()), *he = reinterpret_cast<int32_t *>(dm->hDense.get() + nb);
+    float *hp = reinterpret_cast<float *>(dm->hDense.get() + 2 * nb), *hs = reinterpret_cast<float *>(dm->hDense.get() + 3 * nb);
     for (size_t i = 0; i < S; i++) { const Signal &g = dm->signals[i]; hc[i] = g.channel; he[i] = g.error; hp[i] = g.power; hs[i] = g.snr; }
     if (R.channel) LORAHIP_TRY(hipMemcpyAsync(R.channel + first, hc, S * sizeof(int32_t), hipMemcpyDefault, st));
     if (R.error) LORAHIP_TRY(hipMemcpyAsync(R.error + first, he, S * sizeof(int32_t), hipMemcpyDefault, st));
@@ -2608,7 +2526,7 @@ int64_t lorahip_demod_consumed(const lorahip_demod *dm, const size_t channel)
 {
     if (dm == nullptr || channel >= dm->B) return LORAHIP_E_INVALID;
     if (dm->comp) return dm->comp->consumed(channel);
-    if (dm->mirrorsStale && dm->posOnDevice && dm->sHost)
+    if (dm->mirrorsStale && dm->posOnDevice && dm->sHost.get())
     {
         lorahip_demod *m = const_cast<lorahip_demod *>(dm);
         if (ensureHead(m) != LORAHIP_OK) return LORAHIP_E_HIP;
@@ -2630,7 +2548,7 @@ int lorahip_demod_consumed_all(const lorahip_demod *dm, int64_t *out)
     }
     // the one read that can fail -- the per-channel state back from the device -- up front: an error is the call's, not a negative
     // entry a caller would take for "nothing consumed"
-    if (dm->mirrorsStale && dm->posOnDevice && dm->sHost)
+    if (dm->mirrorsStale && dm->posOnDevice && dm->sHost.get())
     {
         const int rc = ensureHead(const_cast<lorahip_demod *>(dm));
         if (rc != LORAHIP_OK) return rc;
@@ -2669,9 +2587,7 @@ int lorahip_demod_set_ports(lorahip_demod *dm, const lorahip_demod_ports *p)
     if (dm == nullptr) return LORAHIP_E_INVALID;
     if (dm->comp) return dm->comp->setPorts(p);
     const DeviceGuard guard(dm->ctx->device);
-    if (dm->ownFft) { (void)hipFree(dm->ownFft); dm->ownFft = nullptr; }
-    if (dm->ownDec) { (void)hipFree(dm->ownDec); dm->ownDec = nullptr; }
-    if (dm->ownRaw) { (void)hipFree(dm->ownRaw); dm->ownRaw = nullptr; }
+    dm->ownFft.reset(); dm->ownDec.reset(); dm->ownRaw.reset();
     std::memset(&dm->ports, 0, sizeof(dm->ports));
     std::memset(&dm->hostPorts, 0, sizeof(dm->hostPorts));
     dm->portsOn = false;
@@ -2685,9 +2601,9 @@ int lorahip_demod_set_ports(lorahip_demod *dm, const lorahip_demod_ports *p)
             dm->hostPorts = *p;
             dm->ports.host_buffers = 0;
             dm->ports.fft_dev = dm->ports.dec_dev = dm->ports.raw_dev = nullptr;
-            if (p->fft_dev) { LORAHIP_TRY(hipMalloc((void **)&dm->ownFft, dm->B * p->fft_cap_frames * dm->N * sizeof(cf32))); dm->ports.fft_dev = dm->ownFft; }
-            if (p->dec_dev) { LORAHIP_TRY(hipMalloc((void **)&dm->ownDec, dm->B * p->dec_cap_samples * sizeof(cf32))); dm->ports.dec_dev = dm->ownDec; }
-            if (p->raw_dev) { LORAHIP_TRY(hipMalloc((void **)&dm->ownRaw, dm->B * p->raw_cap_samples * sizeof(cf32))); dm->ports.raw_dev = dm->ownRaw; }
+            if (p->fft_dev) { LORAHIP_TRY(dm->ownFft.grow(dm->B * p->fft_cap_frames * dm->N * sizeof(cf32))); dm->ports.fft_dev = dm->ownFft.get(); }
+            if (p->dec_dev) { LORAHIP_TRY(dm->ownDec.grow(dm->B * p->dec_cap_samples * sizeof(cf32))); dm->ports.dec_dev = dm->ownDec.get(); }
+            if (p->raw_dev) { LORAHIP_TRY(dm->ownRaw.grow(dm->B * p->raw_cap_samples * sizeof(cf32))); dm->ports.raw_dev = dm->ownRaw.get(); }
         }
         dm->portsOn = dm->ports.fft_dev || dm->ports.dec_dev || dm->ports.raw_dev;
     }

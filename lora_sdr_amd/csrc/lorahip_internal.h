@@ -1,4 +1,5 @@
-// Internal declarations shared by the host-side translation units of liblorahip.so.
+// Internal declarations shared by the translation units of liblorahip.so, the kernels' included. lorahip_ctx is an incomplete type
+// here: the host code that looks inside it includes lorahip_own.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
@@ -359,31 +360,6 @@ int hipFail(hipError_t e, const char *what);
 } // namespace lorahip
 
 namespace lorahip {
-//! two pinned staging buffers of the host -> device gather (lorahip_upload.cpp)
-struct Uploader { void *buf[2] = {nullptr, nullptr}; hipEvent_t ev[2] = {nullptr, nullptr}; bool busy[2] = {false, false}; bool ready = false; void *pool = nullptr; /* CopyPool: lorahip_upload.cpp */ };
-}
-
-struct lorahip_ctx
-{
-    int device;
-    int sf;
-    size_t N;
-    int variant;
-    hipStream_t ownStream;
-    hipStream_t stream;
-    float2 *dUp, *dDown, *dFine, *dTw, *dTwStage;
-    double2 *dFineA, *dFineB;   // nullptr when the split did not verify on this host (kernels gather then)
-    int fineGather;             // A/B switch (lorahip_set_fine_gather): read the fine-tune table itself even though the split verified
-    int cuCount;
-    hipEvent_t ev0, ev1;
-    float powerScale;
-    // staging for the host-pointer entry point (grown on demand)
-    void *dStage; size_t dStageBytes;
-    void *hStage; size_t hStageBytes;
-    lorahip::Uploader up;
-};
-
-namespace lorahip {
 //! A level-3 object over several (device, SF) parts behind one lorahip_demod handle (lorahip_rx.cpp; lorahip_demod_create_mixed).
 //! The entry points of lorahip_demod.cpp hand over to it when the handle carries one; it speaks global channel numbers.
 class Composite
@@ -421,5 +397,4 @@ private:
 //! n host pieces -> device memory back to back from dDst, asynchronous on ctx->stream (pinned pieces by DMA straight away, the
 //! others through the context's double-buffered pinned staging); the caller synchronises the stream
 int gatherUpload(lorahip_ctx *ctx, void *dDst, const void *const *src, const size_t *bytes, size_t n);
-void destroyUploader(lorahip_ctx *ctx);
 }

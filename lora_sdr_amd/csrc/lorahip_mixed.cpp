@@ -8,7 +8,7 @@
 // splits the channels over the devices with the byte-weighted rule of lora_sdr_amd/shard.py (lorahip_shard_plan, host-only), gives
 // every device its own single-device scheduler and a host thread that issues that device's launches; a step ends when every
 // device's events have passed (lorahip_mixed_synchronize). No data-path collective: channels are independent units.
-#include "lorahip_internal.h"
+#include "lorahip_own.h"
 #include <algorithm>
 #include <condition_variable>
 #include <cstring>
@@ -44,8 +44,8 @@ struct lorahip_mixed
         lorahip_ctx *ctx;
         std::vector<uint32_t> channels;      // ascending
         size_t firstRow;
-        int64_t *dOffsets;                   // [channels * S] start sample of every window
-        hipEvent_t done;
+        lorahip::DevBuf<int64_t> dOffsets;   // [channels * S] start sample of every window
+        lorahip::Event done;
     };
     std::vector<Bucket> buckets;
     bool planned;
@@ -133,15 +133,12 @@ void lorahip_mixed_destroy(lorahip_mixed *m)
     stopWorkers(m);
     for (lorahip_mixed *sh : m->shards) lorahip_mixed_destroy(sh);
     m->shards.clear();
+    while (!m->buckets.empty())
     {
-        const DeviceGuard guard(m->device);
-        for (auto &b : m->buckets)
-        {
-            if (b.dOffsets) (void)hipFree(b.dOffsets);
-            if (b.done) (void)hipEventDestroy(b.done);
-        }
+        lorahip_ctx *ctx = m->buckets.back().ctx;
+        { const DeviceGuard guard(m->device); m->buckets.pop_back(); }      // the offsets and the event go with the device current, before the context they were used on
+        lorahip_destroy(ctx);
     }
-    for (auto &b : m->buckets) lorahip_destroy(b.ctx);
     delete m;
 }
 
@@ -160,14 +157,14 @@ int lorahip_mixed_create(lorahip_mixed **out, const int device, const int32_t *c
     for (int sf = LORAHIP_SF_MIN; sf <= LORAHIP_SF_MAX; sf++)
     {
         lorahip_mixed::Bucket b;
-        b.sf = sf; b.ctx = nullptr; b.firstRow = rows; b.dOffsets = nullptr; b.done = nullptr;
+        b.sf = sf; b.ctx = nullptr; b.firstRow = rows;
         for (size_t c = 0; c < n_channels; c++) if (channel_sf[c] == sf) { m->row[c] = int64_t(rows++); b.channels.push_back(uint32_t(c)); }
         if (b.channels.empty()) continue;
         const int rc = lorahip_create(&b.ctx, device, sf);          // private non-blocking stream: the buckets overlap
         if (rc != LORAHIP_OK) { lorahip_mixed_destroy(m); return rc; }
-        m->buckets.push_back(b);
+        m->buckets.push_back(std::move(b));
         const DeviceGuard guard(device);
-        if (hipEventCreateWithFlags(&m->buckets.back().done, hipEventDisableTiming) != hipSuccess) { lorahip_mixed_destroy(m); return LORAHIP_E_HIP; }
+        if (m->buckets.back().done.ensure(hipEventDisableTiming) != hipSuccess) { lorahip_mixed_destroy(m); return LORAHIP_E_HIP; }
     }
     *out = m;
     return LORAHIP_OK;
@@ -330,9 +327,9 @@ int lorahip_mixed_plan(lorahip_mixed *m, const int64_t *channel_offset, const si
             if (base < 0) return LORAHIP_E_INVALID;
             for (size_t k = 0; k < windows_per_channel; k++) off[i * windows_per_channel + k] = base + int64_t(k * N);
         }
-        if (b.dOffsets) { (void)hipFree(b.dOffsets); b.dOffsets = nullptr; }
-        LORAHIP_TRY(hipMalloc((void **)&b.dOffsets, W * sizeof(int64_t)));
-        LORAHIP_TRY(hipMemcpy(b.dOffsets, off.data(), W * sizeof(int64_t), hipMemcpyHostToDevice));
+        b.dOffsets.reset();                  // (every plan allocates anew, as large as it needs)
+        LORAHIP_TRY(b.dOffsets.grow(W * sizeof(int64_t)));
+        LORAHIP_TRY(hipMemcpy(b.dOffsets.get(), off.data(), W * sizeof(int64_t), hipMemcpyHostToDevice));
     }
     m->S = windows_per_channel;
     m->planned = true;
@@ -353,12 +350,12 @@ int lorahip_mixed_detect(lorahip_mixed *m, const float *iq_dev, uint16_t *sym_de
         q.struct_size = sizeof(q);
         q.iq = iq_dev;
         q.n_windows = b.channels.size() * m->S;
-        q.offsets = b.dOffsets;
+        q.offsets = b.dOffsets.get();
         q.chirp_sel_all = LORAHIP_CHIRP_UP;
         q.sym = sym_dev + r0; q.power = power_dev + r0; q.power_avg = power_avg_dev + r0; q.f_index = f_index_dev + r0;
         const int rc = lorahip_detect_batch(b.ctx, &q);
         if (rc != LORAHIP_OK) return rc;
-        LORAHIP_TRY(hipEventRecord(b.done, b.ctx->stream));
+        LORAHIP_TRY(hipEventRecord(b.done.get(), b.ctx->stream));
     }
     return LORAHIP_OK;
 }
@@ -372,7 +369,7 @@ int lorahip_mixed_synchronize(lorahip_mixed *m)
         return LORAHIP_OK;
     }
     const DeviceGuard guard(m->device);
-    for (auto &b : m->buckets) LORAHIP_TRY(hipEventSynchronize(b.done));
+    for (auto &b : m->buckets) LORAHIP_TRY(hipEventSynchronize(b.done.get()));
     return LORAHIP_OK;
 }
 

@@ -4,7 +4,7 @@
 // back to back through two pinned staging buffers -- several threads copy into one while the DMA engine drains the other -- and
 // pieces that already live in pinned memory (lorahip_host_alloc, or anything hipHostMalloc'ed / hipHostRegister'ed) skip the
 // staging copy and go straight to the DMA engine.
-#include "lorahip_internal.h"
+#include "lorahip_own.h"
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
@@ -155,15 +155,13 @@ int gatherUpload(lorahip_ctx *ctx, void *dDstV, const void *const *src, const si
     {
         // both buffers and both events, or nothing: a transient failure (pinned memory exhausted) must leave the uploader in the
         // state "not initialised", not half of it -- the next call tries again from scratch
-        destroyUploader(ctx);
         for (int k = 0; k < 2; k++)
         {
-            hipError_t e = hipHostMalloc(&u.buf[k], kStageBytes, hipHostMallocDefault);
-            if (e != hipSuccess) u.buf[k] = nullptr;
-            else e = hipEventCreateWithFlags(&u.ev[k], hipEventDisableTiming);
+            hipError_t e = u.buf[k].grow(kStageBytes, hipHostMallocDefault);
+            if (e == hipSuccess) e = u.ev[k].ensure(hipEventDisableTiming);
             if (e != hipSuccess)
             {
-                destroyUploader(ctx);
+                u.release();
                 return hipFail(e, "upload staging (hipHostMalloc / hipEventCreate)");
             }
             u.busy[k] = false;
@@ -178,15 +176,15 @@ int gatherUpload(lorahip_ctx *ctx, void *dDstV, const void *const *src, const si
     {
         if (fill == 0) return LORAHIP_OK;
         copySegments(u, segs, fill);
-        LORAHIP_TRY(hipMemcpyAsync(dDst + done, u.buf[k], fill, hipMemcpyHostToDevice, ctx->stream));
-        LORAHIP_TRY(hipEventRecord(u.ev[k], ctx->stream));
+        LORAHIP_TRY(hipMemcpyAsync(dDst + done, u.buf[k].get(), fill, hipMemcpyHostToDevice, ctx->stream));
+        LORAHIP_TRY(hipEventRecord(u.ev[k].get(), ctx->stream));
         u.busy[k] = true;
         done += fill; fill = 0; segs.clear();
         k ^= 1;
-        if (u.busy[k]) { LORAHIP_TRY(hipEventSynchronize(u.ev[k])); u.busy[k] = false; }     // the other buffer's DMA of two fills ago
+        if (u.busy[k]) { LORAHIP_TRY(hipEventSynchronize(u.ev[k].get())); u.busy[k] = false; }     // the other buffer's DMA of two fills ago
         return LORAHIP_OK;
     };
-    if (u.busy[k]) { LORAHIP_TRY(hipEventSynchronize(u.ev[k])); u.busy[k] = false; }
+    if (u.busy[k]) { LORAHIP_TRY(hipEventSynchronize(u.ev[k].get())); u.busy[k] = false; }
     size_t askedUntil = 0;
     for (size_t i = 0; i < n; i++)
     {
@@ -226,7 +224,7 @@ int gatherUpload(lorahip_ctx *ctx, void *dDstV, const void *const *src, const si
         while (left)
         {
             const size_t take = left < kStageBytes - fill ? left : kStageBytes - fill;
-            segs.push_back(Seg{static_cast<char *>(u.buf[k]) + fill, p, take});
+            segs.push_back(Seg{u.buf[k].get() + fill, p, take});
             fill += take; p += take; left -= take;
             if (fill == kStageBytes) { const int rc = flush(); if (rc != LORAHIP_OK) return rc; }
         }
@@ -234,17 +232,12 @@ int gatherUpload(lorahip_ctx *ctx, void *dDstV, const void *const *src, const si
     return flush();
 }
 
-void destroyUploader(lorahip_ctx *ctx)
+void Uploader::release()
 {
-    for (int k = 0; k < 2; k++)
-    {
-        if (ctx->up.buf[k]) (void)hipHostFree(ctx->up.buf[k]);
-        if (ctx->up.ev[k]) (void)hipEventDestroy(ctx->up.ev[k]);
-        ctx->up.buf[k] = nullptr; ctx->up.ev[k] = nullptr; ctx->up.busy[k] = false;
-    }
-    ctx->up.ready = false;
-    delete static_cast<CopyPool *>(ctx->up.pool);         // (parks no thread beyond the context's life)
-    ctx->up.pool = nullptr;
+    for (int k = 0; k < 2; k++) { buf[k].reset(); ev[k].reset(); busy[k] = false; }
+    ready = false;
+    delete static_cast<CopyPool *>(pool);                 // (parks no thread beyond the context's life)
+    pool = nullptr;
 }
 
 } // namespace lorahip
