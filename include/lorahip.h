@@ -700,6 +700,41 @@ int lorahip_channelizer_run(lorahip_channelizer *c, const float *wide_dev, size_
 int lorahip_channelizer_run_captures(lorahip_channelizer *c, const float *wide_dev, size_t n_captures, size_t capture_stride,
                                      size_t n_in, float *out_dev, size_t out_stride, size_t *n_out);
 
+/* -------------------------------------------------------------------------------------
+ * Front-end synthesiser: the channeliser's mirror image on the transmit side. K channel-rate streams (the rows
+ * lorahip_mod_frames / lorahip_mod_frames_var write and the demodulator reads) go onto their carriers in ONE wideband stream:
+ * what a gateway's single DAC sends and what a channeliser on the other side takes apart. NOT a reference component.
+ * Definition (x_k[m] = channel k's stream since the last reset, x_k[m<0] = 0, U = interp, L = n_taps, h = taps,
+ * w_k = lorahip_channelizer_phase_inc(freq[k]) with freq[k] in cycles per OUTPUT sample -- the same array serves a
+ * channeliser of decim = interp on the other side --, gain[k] real, gain == NULL: all 1):
+ *
+ *     y[n] = sum_k gain[k] exp(+2 pi i frac(w_k n / 2^64)) sum_{j<L, (n-j) mod U == 0, n-j >= 0} h[j] x_k[(n-j)/U]
+ *
+ * i.e. zero-stuff by U, low-pass with h, mix up to the channel's centre, scale, sum the channels. Pass
+ * U * design_lowpass(U, L, ...) for unit passband gain. Output phases without a tap (L < U) are exact zeros.
+ * n_in samples per channel always give exactly n_in * interp outputs. Evaluated in fp32 (fused multiply-add) on taps that
+ * are scaled and pre-rotated in double; every input sample is rotated once by exp(+i theta_k U m), the phase taken from a
+ * 64-bit counter, and the channels are summed in ascending order: no drift, and a stream cut into arbitrary chunks gives
+ * bit-identical outputs to one call.
+ * run(): row k of the input is the n_in complex64 samples at in_dev + 2*k*in_stride floats (in_stride in samples >= n_in);
+ * writes *n_out = lorahip_synthesizer_out_count(s, n_in) = n_in * interp samples at wide_dev. Asynchronous on the context's
+ * stream. Between calls the object keeps the stream position and the ceil(L/U) - 1 trailing input samples of every channel.
+ * Limits: interp 1..256, n_taps 1..65536, n_channels 1..65535*8, finite gains (a non-finite freq counts as 0, as in
+ * lorahip_channelizer_phase_inc), and 8 * (256 + ceil(n_taps/interp)) samples must fit the LDS (ceil(n_taps/interp) <= 2295).
+ * Limits of one call (a longer stream is fed in several calls): at most 2^30 outputs (8 GiB), and tiles x phase blocks =
+ * (n_in / 256 + 2) * ceil(interp / 8) at most 2^31 - 1 (the launch grid). Anything beyond a limit is refused with
+ * LORAHIP_E_INVALID and a lorahip_last_error() text, consumes nothing and leaves the stream state untouched. Rows, strides
+ * and the stream position are addressed with 64 bits.
+ * ------------------------------------------------------------------------------------- */
+typedef struct lorahip_synthesizer lorahip_synthesizer;
+int lorahip_synthesizer_create(lorahip_synthesizer **out, lorahip_ctx *ctx, size_t n_channels, const double *freq,
+                               const float *gain /* nullable */, size_t interp, const float *taps, size_t n_taps);
+void lorahip_synthesizer_destroy(lorahip_synthesizer *s);
+int lorahip_synthesizer_reset(lorahip_synthesizer *s);
+size_t lorahip_synthesizer_out_count(const lorahip_synthesizer *s, size_t n_in);      /* n_in * interp; 0 for NULL */
+int lorahip_synthesizer_run(lorahip_synthesizer *s, const float *in_dev, size_t in_stride, size_t n_in,
+                            float *wide_dev, size_t *n_out);
+
 /* Measurement aid: one read-only streaming pass over n_bytes of device memory (pattern 0: linear
  * 16 B per lane; 1: the access shape of the tuned SF7 kernel). Time it with lorahip_timer_*; the
  * result is the practical HBM ceiling the roofline fraction can be compared with. */

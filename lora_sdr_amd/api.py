@@ -511,6 +511,62 @@ class Channelizer:
         return out
 
 
+class Synthesizer:
+    """K channel-rate complex64 streams onto their carriers in one wideband stream: zero-stuff by interp, low-pass with taps, mix each
+    row up to its centre frequency (cycles per OUTPUT sample: the array a Channelizer of decim = interp takes), scale by gains (None:
+    all 1), sum. The mirror image of Channelizer; pass interp * design_lowpass(interp, n_taps, ...) for unit passband gain. Stateful:
+    consecutive run() calls continue one stream (filter history and mixer phase carried, bit-identical to one call), reset() starts a
+    new one. See include/lorahip.h."""
+
+    def __init__(self, ctx, freqs, interp, taps, gains=None):
+        self._lib = load()
+        self._ctx = ctx                                                  # borrowed: device and stream
+        self._h = C.c_void_p()
+        f = np.ascontiguousarray(freqs, np.float64).reshape(-1)
+        t = np.ascontiguousarray(taps, np.float32).reshape(-1)
+        g = None if gains is None else np.ascontiguousarray(gains, np.float32).reshape(-1)
+        if g is not None and g.size != f.size:
+            raise ValueError("one gain per channel")
+        check(self._lib.lorahip_synthesizer_create(C.byref(self._h), ctx._h, f.size, f.ctypes.data, None if g is None else g.ctypes.data,
+                                                   int(interp), t.ctypes.data, t.size), "lorahip_synthesizer_create")
+        self.n_channels, self.interp, self.n_taps = int(f.size), int(interp), int(t.size)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.lorahip_synthesizer_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def reset(self):
+        check(self._lib.lorahip_synthesizer_reset(self._h), "lorahip_synthesizer_reset")
+
+    def out_count(self, n_in):
+        return int(self._lib.lorahip_synthesizer_out_count(self._h, int(n_in)))
+
+    def run(self, rows, out=None):
+        """rows: (K, n) complex64 device tensor with unit column stride (the next n samples of every channel; may be the columns
+        [a, a + n) of a wider buffer); returns the 1-D complex64 tensor of n * interp wideband samples (written into out if given)"""
+        import torch
+        if (rows.dim() != 2 or rows.dtype != torch.complex64 or rows.shape[0] != self.n_channels
+                or (rows.numel() and (rows.stride(1) != 1 or (rows.shape[0] > 1 and rows.stride(0) < rows.shape[1])))):
+            raise ValueError("rows must be a (K, n) complex64 device tensor with unit column stride (rows may be a slice of a wider buffer)")
+        n_in = int(rows.shape[1])
+        n_out = self.out_count(n_in)
+        if out is None:
+            out = torch.empty(n_out, dtype=torch.complex64, device=rows.device)
+        elif out.dim() != 1 or out.dtype != torch.complex64 or out.numel() < n_out or (out.numel() and out.stride(0) != 1):
+            raise ValueError("out must be a 1-D complex64 tensor of >= n * interp samples with unit stride")
+        self._ctx.use_torch_stream()
+        got = C.c_size_t()
+        # the row stride is the tensor's own: `rows` may be a column slice of a (K, capacity) buffer
+        check(self._lib.lorahip_synthesizer_run(self._h, C.c_void_p(rows.data_ptr()) if rows.numel() else None,
+                                                int(rows.stride(0)) if rows.numel() and rows.shape[0] > 1 else n_in, n_in,
+                                                C.c_void_p(out.data_ptr()) if out.numel() else None, C.byref(got)),
+              "lorahip_synthesizer_run")
+        return out[:got.value]
+
+
 class LoRaDetector:
     """`LoRaDetector<float>` (LoRaDetector.hpp:8-72): feed N samples, detect() -> arg-max bin."""
 

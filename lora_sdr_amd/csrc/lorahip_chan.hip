@@ -16,6 +16,7 @@
 //   * the NCO is a 64-bit phase counter (w_k * n mod 2^64): exact wrap-around, no drift, and a stream cut into
 //     chunks gives the same bits as one call.
 #include "lorahip_own.h"
+#include "lorahip_mixer.h"
 #include <cmath>
 #include <cstdlib>
 #include <new>
@@ -35,8 +36,6 @@ struct lorahip_channelizer
 };
 
 namespace lorahip {
-
-typedef float v2f __attribute__((ext_vector_type(2)));
 
 constexpr int CHAN_THREADS = 256;
 constexpr int CHAN_KG = 8;          // channels per workgroup
@@ -70,19 +69,6 @@ __device__ __forceinline__ float2 streamSample(const ChanArgs &a, const float2 *
     float2 v = make_float2(0.0f, 0.0f);
     if (ok) v = *src;
     return v;
-}
-
-//! acc += g * x, complex, two packed FMAs; g is wave-uniform (SGPR pair)
-__device__ __forceinline__ void cmacS(v2f &acc, const v2f g, const v2f x)
-{
-    asm volatile("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[0,1,1]" : "+v"(acc) : "s"(g), "v"(x));                   // (g.x*x.x, g.x*x.y)
-    asm volatile("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]" : "+v"(acc) : "s"(g), "v"(x));    // (-g.y*x.y, g.y*x.x)
-}
-
-//! complex product with fused multiply-adds
-__device__ __forceinline__ v2f cmulF(const v2f a, const v2f b)
-{
-    return (v2f){fmaf(a.x, b.x, -(a.y * b.y)), fmaf(a.x, b.y, a.y * b.x)};
 }
 
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -130,21 +116,6 @@ __device__ __forceinline__ void tapFma(v2f (&acc)[RM][CHAN_KG], const TapCoef &G
 #pragma unroll
         for (int r = 0; r < RM; r++)
             asm volatile("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]" : "+v"(acc[r][k]) : "s"(gk[k]), "v"(x[r]));   // (-g.y*x.y, g.y*x.x)
-}
-
-//! e^{-2 pi i ph / 2^32}: nearest quarter turn taken out exactly, then the fp32 sine / cosine kernels on [-pi/4, pi/4]
-//! (minimax polynomials, error ~1e-7); the phase bits below 2^-32 turn (1.5e-9 rad) are dropped
-__device__ __forceinline__ v2f mixerPhase(const unsigned ph)
-{
-    const unsigned q = (ph + 0x20000000u) >> 30;                                    // quadrant 0..3 (4 wraps to 0 below)
-    const float x = float(int(ph - (q << 30))) * 1.4629180792671596e-09f;           // 2 pi / 2^32
-    const float z = x * x;
-    const float sn = fmaf(x * z, fmaf(z, fmaf(z, -1.9515295891e-4f, 8.3321608736e-3f), -1.6666654611e-1f), x);
-    const float cs = fmaf(z, fmaf(z, fmaf(z, fmaf(z, 2.443315711809948e-5f, -1.388731625493765e-3f), 4.166664568298827e-2f), -0.5f), 1.0f);
-    // angle = q * pi/2 + x; the result is (cos, -sin) of it
-    const float c1 = (q & 1) ? -sn : cs, s1 = (q & 1) ? cs : sn;                    // cos/sin of (x + pi/2) = (-sin x, cos x)
-    const bool neg = (q & 2) != 0;
-    return (v2f){neg ? -c1 : c1, neg ? s1 : -s1};
 }
 
 //! the common tile: wholly inside this call's chunk. Uniform base + 32-bit byte offsets (no 64-bit vector arithmetic),
