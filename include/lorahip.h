@@ -735,6 +735,47 @@ size_t lorahip_synthesizer_out_count(const lorahip_synthesizer *s, size_t n_in);
 int lorahip_synthesizer_run(lorahip_synthesizer *s, const float *in_dev, size_t in_stride, size_t n_in,
                             float *wide_dev, size_t *n_out);
 
+/* -------------------------------------------------------------------------------------
+ * Polyphase filter-bank channeliser: the front end for a UNIFORM channel plan, K channels on the grid fs / M (lorahip_pfb.hip).
+ * NOT a reference component. For M = n_bins a power of two, b / M is exact in the 64-bit phase counter --
+ * lorahip_channelizer_phase_inc(b / M) == (b mod M) * 2^64 / M --, and row i of this object is BY DEFINITION what the channeliser
+ * above defines for freq = bins[i] / M (x[n] = the wideband stream since the last reset, x[n<0] = 0, D = decim, L = n_taps, h = taps,
+ * b = bins[i]):
+ *
+ *     n_m    = (m + 1) D - 1
+ *     y_b[m] = sum_{j<L} h[j] x[n_m - j] exp(-2 pi i b (n_m - j) / M)
+ *
+ * evaluated as M folded sums and one forward M-point DFT per output time, whatever the number of rows:
+ *
+ *     v_s[m] = sum_{j<L, (n_m - j) mod M == s} h[j] x[n_m - j]
+ *     y_b[m] = sum_{s<M} v_s[m] exp(-2 pi i b s / M)
+ *
+ * in fp32 (fused multiply-add; the fold runs over j = r, r + M, ... in ascending order, the transform is an ordinary radix-2
+ * decimation-in-frequency FFT with twiddles computed in double). The phase is the stream position modulo M: integer arithmetic, no
+ * drift, and a stream cut into arbitrary chunks gives bit-identical outputs to one call. The values agree with the direct form's
+ * within the tolerance both are held to (4e-6 sum|h| max|x|), not bit for bit.
+ * bins: n_sel entries, any int32, taken modulo M (negative bins are the lower half of the band, duplicates are allowed); NULL: the
+ * bins 0 .. n_bins - 1 in order (n_sel must be n_bins then). The centre frequencies bins[i] / M are what a lorahip_synthesizer or a
+ * lorahip_channelizer takes for the same plan.
+ * run(): consumes n_in samples, writes *n_out = lorahip_pfb_out_count(p, n_in) samples of row i at out_dev + 2*i*out_stride floats
+ * (complex64, out_stride in samples >= *n_out). Asynchronous on the context's stream. Between calls the object keeps the stream
+ * position and the trailing samples the next outputs reach back to (n_taps rounded up to a multiple of n_bins, less one).
+ * Limits: n_bins a power of two in 8..1024 (other radices, e.g. 5 * 2^a, are refused), decim 1..4096, n_taps 1..65536, n_sel
+ * 1..65535*8; lorahip_pfb_check answers for these four without a device (LORAHIP_OK or LORAHIP_E_INVALID). Limits of one call (a
+ * longer stream is fed in several calls): at most 2^30 outputs per row, and tiles = outputs / T + 1 (T = 4096 / n_bins, 16 at least,
+ * 256 at most) at most 2^31 - 1 (the launch grid). Anything beyond a limit is refused with LORAHIP_E_INVALID and a
+ * lorahip_last_error() text, consumes nothing and leaves the stream state untouched. Rows, strides and the stream position are
+ * addressed with 64 bits.
+ * ------------------------------------------------------------------------------------- */
+typedef struct lorahip_pfb lorahip_pfb;
+int lorahip_pfb_check(size_t n_bins, size_t decim, size_t n_taps, size_t n_sel);       /* host only */
+int lorahip_pfb_create(lorahip_pfb **out, lorahip_ctx *ctx, size_t n_bins, const int32_t *bins /* nullable */, size_t n_sel,
+                       size_t decim, const float *taps, size_t n_taps);
+void lorahip_pfb_destroy(lorahip_pfb *p);
+int lorahip_pfb_reset(lorahip_pfb *p);
+size_t lorahip_pfb_out_count(const lorahip_pfb *p, size_t n_in);
+int lorahip_pfb_run(lorahip_pfb *p, const float *wide_dev, size_t n_in, float *out_dev, size_t out_stride, size_t *n_out);
+
 /* Measurement aid: one read-only streaming pass over n_bytes of device memory (pattern 0: linear
  * 16 B per lane; 1: the access shape of the tuned SF7 kernel). Time it with lorahip_timer_*; the
  * result is the practical HBM ceiling the roofline fraction can be compared with. */

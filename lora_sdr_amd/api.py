@@ -511,6 +511,67 @@ class Channelizer:
         return out
 
 
+class PolyphaseChannelizer:
+    """The channeliser for a uniform channel plan: rows on the grid fs / n_bins (n_bins a power of two, 8..1024), row i at centre
+    bins[i] / n_bins cycles per input sample (any integers, taken modulo n_bins; negative = the lower half of the band; None: all
+    n_bins bins in order). One polyphase fold and one n_bins-point FFT per output time serve every row, so the cost does not grow with
+    the number of channels as Channelizer's does. Row i is by definition Channelizer(ctx, [bins[i] / n_bins], decim, taps)'s; .freqs is
+    the array a Channelizer or a Synthesizer takes for the same plan. Stateful like Channelizer: consecutive run() calls continue one
+    stream, bit-identical to one call; reset() starts a new one. See include/lorahip.h."""
+
+    def __init__(self, ctx, n_bins, decim, taps, bins=None):
+        self._lib = load()
+        self._ctx = ctx                                                  # borrowed: device and stream
+        self._h = C.c_void_p()
+        t = np.ascontiguousarray(taps, np.float32).reshape(-1)
+        if bins is None:
+            b = np.arange(int(n_bins) if 0 < int(n_bins) <= 1024 else 0, dtype=np.int32)
+        else:
+            b64 = np.ascontiguousarray(bins, np.int64).reshape(-1)
+            if b64.size and (b64.min() < -2 ** 31 or b64.max() >= 2 ** 31):
+                raise ValueError("bins must fit 32 bits")
+            b = b64.astype(np.int32)
+        check(self._lib.lorahip_pfb_create(C.byref(self._h), ctx._h, int(n_bins), None if bins is None else b.ctypes.data,
+                                           int(n_bins) if bins is None else b.size, int(decim), t.ctypes.data, t.size), "lorahip_pfb_create")
+        self.n_bins, self.decim, self.n_taps, self.n_channels = int(n_bins), int(decim), int(t.size), int(b.size)
+        self.bins = b
+        self.freqs = b.astype(np.float64) / float(self.n_bins)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.lorahip_pfb_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def reset(self):
+        check(self._lib.lorahip_pfb_reset(self._h), "lorahip_pfb_reset")
+
+    def out_count(self, n_in):
+        return int(self._lib.lorahip_pfb_out_count(self._h, int(n_in)))
+
+    def run(self, wide, out=None):
+        """wide: 1-D complex64 device tensor (the next samples of the stream); returns the (K, n_out) complex64 tensor (written into
+        out if given: it may be the columns [w, w + n) of a (K, capacity) buffer)"""
+        import torch
+        if wide.dim() != 1 or wide.dtype != torch.complex64:
+            raise ValueError("wide must be a 1-D complex64 device tensor")
+        wide = wide.contiguous()
+        n_out = self.out_count(wide.numel())
+        if out is None:
+            out = torch.empty((self.n_channels, n_out), dtype=torch.complex64, device=wide.device)
+        elif (out.dim() != 2 or out.shape[0] != self.n_channels or out.shape[1] < n_out or out.dtype != torch.complex64
+              or (out.numel() and (out.stride(1) != 1 or out.stride(0) < out.shape[1]))):
+            raise ValueError("out must be a (K, >= n_out) complex64 tensor with unit column stride (rows may be a slice of a wider buffer)")
+        self._ctx.use_torch_stream()
+        got = C.c_size_t()
+        check(self._lib.lorahip_pfb_run(self._h, C.c_void_p(wide.data_ptr()) if wide.numel() else None, wide.numel(),
+                                        C.c_void_p(out.data_ptr()) if out.numel() else None,
+                                        int(out.stride(0)) if out.numel() and out.shape[0] > 1 else int(out.shape[1]), C.byref(got)),
+              "lorahip_pfb_run")
+        return out[:, :got.value]
+
+
 class Synthesizer:
     """K channel-rate complex64 streams onto their carriers in one wideband stream: zero-stuff by interp, low-pass with taps, mix each
     row up to its centre frequency (cycles per OUTPUT sample: the array a Channelizer of decim = interp takes), scale by gains (None:

@@ -1,0 +1,398 @@
+// Polyphase filter-bank channeliser: the front end for a UNIFORM channel plan -- K channels on the grid fs/M, M a power of two
+// (include/lorahip.h has the definition; DESIGN.md section 8c the shape and the measurements). Row i is, by definition, what the
+// direct-form channeliser (lorahip_chan.hip) defines for freq = bins[i] / M: that frequency is exact in the 64-bit phase counter, so
+// the mixer phase of sample n is exp(-2 pi i b (n mod M) / M) and the L products of an output fold, by absolute sample time modulo M,
+// into M sums that one forward M-point DFT turns into every bin at once:
+//
+//     v_s[m] = sum_{j<L, (n_m - j) mod M == s} h[j] x[n_m - j]            n_m = (m + 1) D - 1
+//     y_b[m] = sum_{s<M} v_s[m] exp(-2 pi i b s / M)
+//
+// L real-by-complex multiply-adds and one FFT per output time, whatever K is (the direct form: K L complex multiply-adds).
+//
+// One workgroup = one tile of T consecutive output times (T = 4096 / M, 16 at least and 256 at most), three stages in one launch:
+//   * polyphase: lane = s (consecutive lanes read consecutive samples and consecutive taps), the fold runs over j = r + M q in
+//     ascending q with r = (n_m - s) mod M, one fused multiply-add per component and tap; the tap table is padded with zeros to a whole
+//     number Q of rounds, so every sum has Q terms. The samples come from an LDS copy of the tile's input span where that fits beside
+//     the sums, and straight from global memory / L2 where it does not (large D). Tiles sit on absolute multiples of T and every sum
+//     has one fixed order, so a result does not depend on where a call or a tile starts;
+//   * FFT: T transforms of M points in place in the LDS, decimation in frequency, 2 to 4 radix-2 stages per pass in registers
+//     (passes of 16 / 8 points a lane), twiddles from a host table computed in double. The result is left in bit-reversed order:
+//     the host reverses the selected bins instead;
+//   * store: only the selected bins leave the LDS; lane = output time, so a row's run of a tile is T * 8 >= 128 bytes. Rows of the
+//     sums are M + 1 samples apart: the T lanes that read one bin of T rows hit T different banks.
+// The phase is the stream position modulo M -- integer arithmetic, no drift.
+#include "lorahip_own.h"
+#include <cmath>
+#include <new>
+
+struct lorahip_pfb
+{
+    lorahip_ctx *ctx;
+    int M, logM, D, L, Lp, Q, K, T, logT, staged, span, HC;
+    size_t ldsBytes;
+    lorahip::DevBuf<float> dTaps;               // [Lp] h[j], zeros from L on
+    lorahip::DevBuf<float2> dTw;                // [M/2] exp(-2 pi i k / M)
+    lorahip::DevBuf<int> dSel;                  // [K] where row i's bin stands after the transform: bitrev(bins[i] mod M)
+    lorahip::DevBuf<float2> dHist[2];           // the HC samples before n0 (zeros before the start of the stream)
+    int cur;
+    unsigned long long n0;                      // samples consumed since the last reset
+};
+
+namespace lorahip {
+
+constexpr int PFB_THREADS = 256;
+constexpr int PFB_LOGM_MIN = 3, PFB_LOGM_MAX = 10;
+constexpr size_t PFB_STAGE_LDS = 80u << 10;     // sums + twiddles + input span up to this: two workgroups a compute unit
+
+struct PfbArgs
+{
+    const float2 *chunk;
+    long long nChunk;
+    const float2 *hist;
+    int histLen;
+    long long n0;                   // absolute index of chunk[0]
+    const float *taps;
+    const float2 *tw;
+    const int *sel;
+    float2 *out;
+    long long outStride;
+    long long mLo;                  // absolute index of the first output of this call
+    long long nOut;
+    int D, Lp, Q, K, T, logT, span;
+};
+
+//! sample n of the stream (absolute index): from this call's chunk, from the history kept from earlier calls, or 0
+__device__ __forceinline__ float2 pfbSample(const PfbArgs &a, const long long n)
+{
+    const long long c = n - a.n0, h = c + a.histLen;
+    const float2 *src = c >= 0 ? a.chunk + c : a.hist + h;
+    const bool ok = c >= 0 ? c < a.nChunk : h >= 0;
+    float2 v = make_float2(0.0f, 0.0f);
+    if (ok) v = *src;
+    return v;
+}
+
+//! one folded sum from samples that lie in a row: xp = the newest sample of residue s, the older ones M apart below it
+template <int M>
+__device__ __forceinline__ float2 pfbFold(const float2 *xp, const float *hp, const int Q)
+{
+    float re = 0.0f, im = 0.0f;
+#pragma unroll 4
+    for (int q = 0; q < Q; q++)
+    {
+        const float2 x = xp[-q * M];
+        const float h = hp[q * M];
+        re = __builtin_fmaf(h, x.x, re);
+        im = __builtin_fmaf(h, x.y, im);
+    }
+    return make_float2(re, im);
+}
+
+//! (a - b) * w with the rounding fixed: one product, one fused multiply-add per component
+__device__ __forceinline__ float2 pfbTwiddle(const float2 d, const float2 w)
+{
+    return make_float2(__builtin_fmaf(-d.y, w.y, d.x * w.x), __builtin_fmaf(d.y, w.x, d.x * w.y));
+}
+
+constexpr int pfbPassBits(const int left) { return (left + (left + 3) / 4 - 1) / ((left + 3) / 4); }   // ceil(left / passes left), passes of <= 4 stages
+
+//! the stages DONE .. LOGM - 1 of the decimation-in-frequency transform of every row, R stages per pass: a lane takes the 2^R points
+//! hs apart that those stages combine with each other
+template <int LOGM, int DONE>
+__device__ __forceinline__ void pfbFft(float2 *v, const float2 *tw, const int T, const int tid)
+{
+    if constexpr (DONE < LOGM)
+    {
+        constexpr int M = 1 << LOGM, R = pfbPassBits(LOGM - DONE), P = 1 << R;
+        constexpr int LOGHS = LOGM - DONE - R, HS = 1 << LOGHS;     // distance of the lane's points = half span of the pass's last stage
+        constexpr int PER = M >> R;                                 // lanes a row
+        for (int item = tid; item < T * PER; item += PFB_THREADS)
+        {
+            const int t = item >> (LOGM - R), w = item & (PER - 1);
+            const int j = w & (HS - 1), grp = w >> LOGHS;
+            float2 *row = v + t * (M + 1) + (grp << (LOGHS + R)) + j;
+            float2 e[P];
+#pragma unroll
+            for (int u = 0; u < P; u++) e[u] = row[u * HS];
+#pragma unroll
+            for (int rho = 0; rho < R; rho++)
+            {
+                const int hu = 1 << (R - 1 - rho);                  // half span of this stage in the lane's points
+                const int twStep = M >> (R - rho + LOGHS);          // M / (2 * hu * HS)
+#pragma unroll
+                for (int u = 0; u < P; u++)
+                {
+                    if (u & hu) continue;
+                    const float2 x = e[u], y = e[u + hu];
+                    e[u] = make_float2(x.x + y.x, x.y + y.y);
+                    e[u + hu] = pfbTwiddle(make_float2(x.x - y.x, x.y - y.y), tw[(j + (u & (hu - 1)) * HS) * twStep]);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < P; u++) row[u * HS] = e[u];
+        }
+        __syncthreads();
+        pfbFft<LOGM, DONE + R>(v, tw, T, tid);
+    }
+}
+
+template <int LOGM, bool STAGED>
+__global__ __launch_bounds__(PFB_THREADS) void pfbChannelize(const PfbArgs a)
+{
+    extern __shared__ float2 pfbLds[];
+    constexpr int M = 1 << LOGM;
+    const int tid = threadIdx.x;
+    const int T = a.T, D = a.D, Lp = a.Lp, Q = a.Q;
+    float2 *v = pfbLds;                             // [T][M + 1]
+    float2 *tw = v + T * (M + 1);                   // [M / 2]
+    float2 *xs = tw + M / 2;                        // [span] (STAGED)
+    const long long mTile = ((a.mLo >> a.logT) + (long long)blockIdx.x) << a.logT;
+    const long long nFirst = (mTile + 1) * D - 1;   // n_m of the tile's first output
+    const long long tileStart = nFirst - (Lp - 1);  // oldest sample of the tile's first output
+    const long long rel = tileStart - a.n0;
+    const bool inside = rel >= 0 && rel + a.span <= a.nChunk;       // the tile's whole input lies in this call's chunk
+
+    for (int k = tid; k < M / 2; k += PFB_THREADS) tw[k] = a.tw[k];
+    if constexpr (STAGED)
+    {
+        if (inside)
+        {
+            const float2 *__restrict__ src = a.chunk + rel;
+#pragma unroll 8
+            for (int i = tid; i < a.span; i += PFB_THREADS) xs[i] = src[i];
+        }
+        else
+        {
+#pragma unroll 4
+            for (int i = tid; i < a.span; i += PFB_THREADS) xs[i] = pfbSample(a, tileStart + i);
+        }
+        __syncthreads();
+    }
+
+    // polyphase stage: lane = residue s
+    for (int idx = tid; idx < T * M; idx += PFB_THREADS)
+    {
+        const int s = idx & (M - 1), t = idx >> LOGM;
+        const long long n = nFirst + (long long)t * D;
+        const int r = int((n - s) & (M - 1));       // the newest sample of residue s is r samples old: taps r, r + M, ...
+        const int at = t * D + Lp - 1 - r;          // ... and stands here in the tile's span
+        const float *hp = a.taps + r;
+        float2 acc;
+        if constexpr (STAGED) acc = pfbFold<M>(xs + at, hp, Q);
+        else if (inside) acc = pfbFold<M>(a.chunk + rel + at, hp, Q);
+        else
+        {
+            float re = 0.0f, im = 0.0f;
+            for (int q = 0; q < Q; q++)
+            {
+                const float2 x = pfbSample(a, n - r - (long long)q * M);
+                const float h = hp[q * M];
+                re = __builtin_fmaf(h, x.x, re);
+                im = __builtin_fmaf(h, x.y, im);
+            }
+            acc = make_float2(re, im);
+        }
+        v[t * (M + 1) + s] = acc;
+    }
+    __syncthreads();
+
+    pfbFft<LOGM, 0>(v, tw, T, tid);
+
+    // store stage: lane = output time
+    const long long mTileLoc = mTile - a.mLo;       // the tile's first output in this call (< 0: the call starts inside the tile)
+    const int nItems = a.K << a.logT;
+    for (int item = tid; item < nItems; item += PFB_THREADS)
+    {
+        const int t = item & (T - 1), i = item >> a.logT;
+        const long long ml = mTileLoc + t;
+        if (ml >= 0 && ml < a.nOut) a.out[(long long)i * a.outStride + ml] = v[t * (M + 1) + a.sel[i]];
+    }
+}
+
+//! the HC samples that precede the next call
+__global__ void pfbHistory(const PfbArgs a, float2 *newHist)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < a.histLen) newHist[i] = pfbSample(a, a.n0 + a.nChunk - a.histLen + i);
+}
+
+static unsigned long long gPfbLdsMask[PFB_LOGM_MAX + 1][2];
+
+template <int LOGM>
+static hipError_t pfbLaunch(const lorahip_pfb *p, const PfbArgs &a, const unsigned grid)
+{
+    if (p->staged)
+    {
+        const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(&pfbChannelize<LOGM, true>), 160 * 1024, gPfbLdsMask[LOGM][1]);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((pfbChannelize<LOGM, true>), dim3(grid), dim3(PFB_THREADS), p->ldsBytes, p->ctx->stream, a);
+    }
+    else
+    {
+        const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(&pfbChannelize<LOGM, false>), 160 * 1024, gPfbLdsMask[LOGM][0]);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((pfbChannelize<LOGM, false>), dim3(grid), dim3(PFB_THREADS), p->ldsBytes, p->ctx->stream, a);
+    }
+    return hipGetLastError();
+}
+
+//! nullptr when the shape is one this file handles, the reason otherwise
+static const char *pfbProblem(const size_t nBins, const size_t decim, const size_t nTaps, const size_t nSel)
+{
+    if (nBins < (size_t(1) << PFB_LOGM_MIN) || nBins > (size_t(1) << PFB_LOGM_MAX) || (nBins & (nBins - 1)))
+        return "polyphase channeliser: n_bins must be a power of two in 8..1024";
+    if (decim == 0 || decim > 4096) return "polyphase channeliser: decim must be 1..4096";
+    if (nTaps == 0 || nTaps > (size_t(1) << 16)) return "polyphase channeliser: n_taps must be 1..65536";
+    if (nSel == 0 || nSel > size_t(65535) * 8) return "polyphase channeliser: n_sel must be 1..524280";
+    return nullptr;
+}
+
+static int pfbRun(lorahip_pfb *p, const float2 *wide, const size_t nIn, float2 *out, const size_t outStride, size_t *nOutP)
+{
+    lorahip_ctx *ctx = p->ctx;
+    const unsigned long long D = (unsigned long long)p->D;
+    const unsigned long long mLo = p->n0 / D, mHi = (p->n0 + nIn) / D;
+    const size_t nOut = size_t(mHi - mLo);
+    if (nOutP) *nOutP = nOut;
+    if (nIn == 0) return LORAHIP_OK;
+    if (nOut && (out == nullptr || outStride < nOut)) { setLastError("polyphase channeliser: no output rows, or out_stride below the outputs of this call"); return LORAHIP_E_INVALID; }
+    if (nOut > (size_t(1) << 30)) { setLastError("polyphase channeliser: more than 2^30 outputs per channel in one call"); return LORAHIP_E_INVALID; }
+    const size_t nTiles = nOut ? size_t((mLo & (unsigned long long)(p->T - 1)) + nOut + size_t(p->T) - 1) >> p->logT : 0;
+    if (nTiles > 0x7fffffffu) { setLastError("polyphase channeliser: the outputs of one call exceed the launch grid"); return LORAHIP_E_INVALID; }
+    const DeviceGuard guard(ctx->device);
+    PfbArgs a;
+    a.chunk = wide; a.nChunk = (long long)nIn;
+    a.hist = p->dHist[p->cur].get(); a.histLen = p->HC;
+    a.n0 = (long long)p->n0;
+    a.taps = p->dTaps.get(); a.tw = p->dTw.get(); a.sel = p->dSel.get();
+    a.out = out; a.outStride = (long long)outStride;
+    a.mLo = (long long)mLo; a.nOut = (long long)nOut;
+    a.D = p->D; a.Lp = p->Lp; a.Q = p->Q; a.K = p->K; a.T = p->T; a.logT = p->logT; a.span = p->span;
+    if (nOut)
+    {
+        hipError_t e = hipErrorInvalidValue;
+        switch (p->logM)
+        {
+            case 3: e = pfbLaunch<3>(p, a, unsigned(nTiles)); break;
+            case 4: e = pfbLaunch<4>(p, a, unsigned(nTiles)); break;
+            case 5: e = pfbLaunch<5>(p, a, unsigned(nTiles)); break;
+            case 6: e = pfbLaunch<6>(p, a, unsigned(nTiles)); break;
+            case 7: e = pfbLaunch<7>(p, a, unsigned(nTiles)); break;
+            case 8: e = pfbLaunch<8>(p, a, unsigned(nTiles)); break;
+            case 9: e = pfbLaunch<9>(p, a, unsigned(nTiles)); break;
+            case 10: e = pfbLaunch<10>(p, a, unsigned(nTiles)); break;
+        }
+        LORAHIP_TRY(e);
+    }
+    hipLaunchKernelGGL(pfbHistory, dim3((p->HC + 255) / 256), dim3(256), 0, ctx->stream, a, p->dHist[p->cur ^ 1].get());
+    LORAHIP_TRY(hipGetLastError());
+    p->cur ^= 1;
+    p->n0 += nIn;
+    return LORAHIP_OK;
+}
+
+} // namespace lorahip
+
+using namespace lorahip;
+
+extern "C" {
+
+int lorahip_pfb_check(const size_t n_bins, const size_t decim, const size_t n_taps, const size_t n_sel)
+{
+    const char *why = pfbProblem(n_bins, decim, n_taps, n_sel);
+    if (why == nullptr) return LORAHIP_OK;
+    setLastError(why);
+    return LORAHIP_E_INVALID;
+}
+
+int lorahip_pfb_create(lorahip_pfb **out, lorahip_ctx *ctx, const size_t n_bins, const int32_t *bins, const size_t n_sel,
+                       const size_t decim, const float *taps, const size_t n_taps)
+{
+    if (out == nullptr) return LORAHIP_E_INVALID;
+    *out = nullptr;
+    if (ctx == nullptr || taps == nullptr) { setLastError("polyphase channeliser: no context or no taps"); return LORAHIP_E_INVALID; }
+    if (lorahip_pfb_check(n_bins, decim, n_taps, n_sel) != LORAHIP_OK) return LORAHIP_E_INVALID;
+    if (bins == nullptr && n_sel != n_bins) { setLastError("polyphase channeliser: without a bin list n_sel must be n_bins"); return LORAHIP_E_INVALID; }
+
+    lorahip_pfb *p = new (std::nothrow) lorahip_pfb();
+    if (p == nullptr) return LORAHIP_E_NOMEM;
+    const int M = int(n_bins);
+    int logM = 0;
+    while ((1 << logM) < M) logM++;
+    p->ctx = ctx; p->M = M; p->logM = logM; p->D = int(decim); p->L = int(n_taps); p->K = int(n_sel);
+    p->Q = (p->L + M - 1) / M; p->Lp = p->Q * M;
+    p->HC = p->Lp - 1;
+    p->logT = 12 - logM < 4 ? 4 : (12 - logM > 8 ? 8 : 12 - logM);
+    p->T = 1 << p->logT;
+    const size_t fixedLds = (size_t(p->T) * size_t(M + 1) + size_t(M / 2)) * sizeof(float2);
+    const size_t span = size_t(p->T - 1) * size_t(p->D) + size_t(p->Lp);
+    p->span = int(span);                        // < 2^21
+    p->staged = fixedLds + span * sizeof(float2) <= PFB_STAGE_LDS;
+    p->ldsBytes = fixedLds + (p->staged ? span * sizeof(float2) : 0);
+    p->cur = 0; p->n0 = 0;
+
+    std::vector<float> h(size_t(p->Lp), 0.0f);
+    for (size_t j = 0; j < n_taps; j++) h[j] = taps[j];
+    std::vector<float2> tw(size_t(M / 2));
+    for (int k = 0; k < M / 2; k++)
+    {
+        const double ang = 2.0 * M_PI * double(k) / double(M);
+        tw[size_t(k)] = make_float2(float(std::cos(ang)), float(-std::sin(ang)));
+    }
+    std::vector<int> sel(n_sel);
+    for (size_t i = 0; i < n_sel; i++)
+    {
+        const unsigned b = bins ? unsigned(((long long)bins[i] % M + M) % M) : unsigned(i);
+        unsigned rev = 0;
+        for (int bit = 0; bit < logM; bit++) rev |= ((b >> bit) & 1u) << (logM - 1 - bit);
+        sel[i] = int(rev);
+    }
+    const DeviceGuard guard(ctx->device);
+    const size_t histBytes = size_t(p->HC) * sizeof(float2);
+    hipError_t e = p->dTaps.grow(h.size() * sizeof(float));
+    if (e == hipSuccess) e = p->dTw.grow(tw.size() * sizeof(float2));
+    if (e == hipSuccess) e = p->dSel.grow(sel.size() * sizeof(int));
+    if (e == hipSuccess) e = p->dHist[0].grow(histBytes);
+    if (e == hipSuccess) e = p->dHist[1].grow(histBytes);
+    if (e != hipSuccess) { delete p; return LORAHIP_E_NOMEM; }
+    e = hipMemcpy(p->dTaps.get(), h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(p->dTw.get(), tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(p->dSel.get(), sel.data(), sel.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(p->dHist[0].get(), 0, histBytes);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { delete p; return hipFail(e, "polyphase channeliser table upload"); }
+    *out = p;
+    return LORAHIP_OK;
+}
+
+void lorahip_pfb_destroy(lorahip_pfb *p)
+{
+    if (p == nullptr) return;
+    const DeviceGuard guard(p->ctx->device);
+    delete p;
+}
+
+int lorahip_pfb_reset(lorahip_pfb *p)
+{
+    if (p == nullptr) return LORAHIP_E_INVALID;
+    const DeviceGuard guard(p->ctx->device);
+    LORAHIP_TRY(hipMemsetAsync(p->dHist[p->cur].get(), 0, size_t(p->HC) * sizeof(float2), p->ctx->stream));
+    p->n0 = 0;
+    return LORAHIP_OK;
+}
+
+size_t lorahip_pfb_out_count(const lorahip_pfb *p, const size_t n_in)
+{
+    if (p == nullptr) return 0;
+    const unsigned long long D = (unsigned long long)p->D;
+    return size_t((p->n0 + n_in) / D - p->n0 / D);
+}
+
+int lorahip_pfb_run(lorahip_pfb *p, const float *wide_dev, const size_t n_in, float *out_dev, const size_t out_stride, size_t *n_out)
+{
+    if (p == nullptr) return LORAHIP_E_INVALID;
+    if (n_in && wide_dev == nullptr) { setLastError("polyphase channeliser: no input"); return LORAHIP_E_INVALID; }
+    return pfbRun(p, reinterpret_cast<const float2 *>(wide_dev), n_in, reinterpret_cast<float2 *>(out_dev), out_stride, n_out);
+}
+
+} // extern "C"
