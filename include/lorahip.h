@@ -712,6 +712,10 @@ int lorahip_channelizer_run_captures(lorahip_channelizer *c, const float *wide_d
  *
  * i.e. zero-stuff by U, low-pass with h, mix up to the channel's centre, scale, sum the channels. Pass
  * U * design_lowpass(U, L, ...) for unit passband gain. Output phases without a tap (L < U) are exact zeros.
+ * Non-finite samples: the taps are padded with zeros to ceil(L/U) whole rounds of U and the products with the padding ARE formed
+ * (0 * NaN = NaN), so a NaN or Inf in x_k[m] makes the U * ceil(L/U) outputs m U .. (m + ceil(L/U)) U - 1 non-finite (phases
+ * without a tap stay zero): the L outputs of the definition when L is a multiple of U, up to U - 1 more behind them otherwise.
+ * Every other output is untouched.
  * n_in samples per channel always give exactly n_in * interp outputs. Evaluated in fp32 (fused multiply-add) on taps that
  * are scaled and pre-rotated in double; every input sample is rotated once by exp(+i theta_k U m), the phase taken from a
  * 64-bit counter, and the channels are summed in ascending order: no drift, and a stream cut into arbitrary chunks gives
@@ -753,7 +757,9 @@ int lorahip_synthesizer_run(lorahip_synthesizer *s, const float *in_dev, size_t 
  * in fp32 (fused multiply-add; the fold runs over j = r, r + M, ... in ascending order, the transform is an ordinary radix-2
  * decimation-in-frequency FFT with twiddles computed in double). The phase is the stream position modulo M: integer arithmetic, no
  * drift, and a stream cut into arbitrary chunks gives bit-identical outputs to one call. The values agree with the direct form's
- * within the tolerance both are held to (4e-6 sum|h| max|x|), not bit for bit.
+ * within the tolerance both are held to (4e-6 sum|h| max|x|), not bit for bit. Each fold runs over the taps below L only (the
+ * padding of the tap table to whole rounds of M is never multiplied), so a NaN or Inf at sample n reaches exactly the outputs
+ * with n_m - L < n <= n_m, as in the direct form.
  * bins: n_sel entries, any int32, taken modulo M (negative bins are the lower half of the band, duplicates are allowed); NULL: the
  * bins 0 .. n_bins - 1 in order (n_sel must be n_bins then). The centre frequencies bins[i] / M are what a lorahip_synthesizer or a
  * lorahip_channelizer takes for the same plan.
@@ -762,8 +768,8 @@ int lorahip_synthesizer_run(lorahip_synthesizer *s, const float *in_dev, size_t 
  * position and the trailing samples the next outputs reach back to (n_taps rounded up to a multiple of n_bins, less one).
  * Limits: n_bins a power of two in 8..1024 (other radices, e.g. 5 * 2^a, are refused), decim 1..4096, n_taps 1..65536, n_sel
  * 1..65535*8; lorahip_pfb_check answers for these four without a device (LORAHIP_OK or LORAHIP_E_INVALID). Limits of one call (a
- * longer stream is fed in several calls): at most 2^30 outputs per row, and tiles = outputs / T + 1 (T = 4096 / n_bins, 16 at least,
- * 256 at most) at most 2^31 - 1 (the launch grid). Anything beyond a limit is refused with LORAHIP_E_INVALID and a
+ * longer stream is fed in several calls): at most 2^30 outputs per row, and tiles <= outputs / T + 2 (T = 4096 / n_bins, 16 at least,
+ * 256 at most; a call may start and end inside a tile) at most 2^31 - 1 (the launch grid). Anything beyond a limit is refused with LORAHIP_E_INVALID and a
  * lorahip_last_error() text, consumes nothing and leaves the stream state untouched. Rows, strides and the stream position are
  * addressed with 64 bits.
  * ------------------------------------------------------------------------------------- */

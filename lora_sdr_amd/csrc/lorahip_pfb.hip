@@ -11,10 +11,11 @@
 //
 // One workgroup = one tile of T consecutive output times (T = 4096 / M, 16 at least and 256 at most), three stages in one launch:
 //   * polyphase: lane = s (consecutive lanes read consecutive samples and consecutive taps), the fold runs over j = r + M q in
-//     ascending q with r = (n_m - s) mod M, one fused multiply-add per component and tap; the tap table is padded with zeros to a whole
-//     number Q of rounds, so every sum has Q terms. The samples come from an LDS copy of the tile's input span where that fits beside
-//     the sums, and straight from global memory / L2 where it does not (large D). Tiles sit on absolute multiples of T and every sum
-//     has one fixed order, so a result does not depend on where a call or a tile starts;
+//     ascending q with r = (n_m - s) mod M, one fused multiply-add per component and tap, ceil((L - r) / M) rounds: the taps the
+//     filter has and no others (the table is padded with zeros to Q = ceil(L / M) whole rounds, but no product is formed with the
+//     padding: a NaN or Inf reaches the L outputs of the definition). The samples come from an LDS copy of the tile's input span
+//     where that fits beside the sums, and straight from global memory / L2 where it does not (large D). Tiles sit on absolute
+//     multiples of T and every sum has one fixed order, so a result does not depend on where a call or a tile starts;
 //   * FFT: T transforms of M points in place in the LDS, decimation in frequency, 2 to 4 radix-2 stages per pass in registers
 //     (passes of 16 / 8 points a lane), twiddles from a host table computed in double. The result is left in bit-reversed order:
 //     the host reverses the selected bins instead;
@@ -58,7 +59,7 @@ struct PfbArgs
     long long outStride;
     long long mLo;                  // absolute index of the first output of this call
     long long nOut;
-    int D, Lp, Q, K, T, logT, span;
+    int D, L, Lp, K, T, logT, span;
 };
 
 //! sample n of the stream (absolute index): from this call's chunk, from the history kept from earlier calls, or 0
@@ -72,13 +73,14 @@ __device__ __forceinline__ float2 pfbSample(const PfbArgs &a, const long long n)
     return v;
 }
 
-//! one folded sum from samples that lie in a row: xp = the newest sample of residue s, the older ones M apart below it
+//! one folded sum from samples that lie in a row: xp = the newest sample of residue s, the older ones M apart below it; rounds = the
+//! number of taps r, r + M, ... below L
 template <int M>
-__device__ __forceinline__ float2 pfbFold(const float2 *xp, const float *hp, const int Q)
+__device__ __forceinline__ float2 pfbFold(const float2 *xp, const float *hp, const int rounds)
 {
     float re = 0.0f, im = 0.0f;
 #pragma unroll 4
-    for (int q = 0; q < Q; q++)
+    for (int q = 0; q < rounds; q++)
     {
         const float2 x = xp[-q * M];
         const float h = hp[q * M];
@@ -142,7 +144,7 @@ __global__ __launch_bounds__(PFB_THREADS) void pfbChannelize(const PfbArgs a)
     extern __shared__ float2 pfbLds[];
     constexpr int M = 1 << LOGM;
     const int tid = threadIdx.x;
-    const int T = a.T, D = a.D, Lp = a.Lp, Q = a.Q;
+    const int T = a.T, D = a.D, Lp = a.Lp;
     float2 *v = pfbLds;                             // [T][M + 1]
     float2 *tw = v + T * (M + 1);                   // [M / 2]
     float2 *xs = tw + M / 2;                        // [span] (STAGED)
@@ -177,13 +179,14 @@ __global__ __launch_bounds__(PFB_THREADS) void pfbChannelize(const PfbArgs a)
         const int r = int((n - s) & (M - 1));       // the newest sample of residue s is r samples old: taps r, r + M, ...
         const int at = t * D + Lp - 1 - r;          // ... and stands here in the tile's span
         const float *hp = a.taps + r;
+        const int rounds = (a.L - r + M - 1) >> LOGM;   // taps r, r + M, ... < L: the padding of the table is never multiplied (0 where r >= L)
         float2 acc;
-        if constexpr (STAGED) acc = pfbFold<M>(xs + at, hp, Q);
-        else if (inside) acc = pfbFold<M>(a.chunk + rel + at, hp, Q);
+        if constexpr (STAGED) acc = pfbFold<M>(xs + at, hp, rounds);
+        else if (inside) acc = pfbFold<M>(a.chunk + rel + at, hp, rounds);
         else
         {
             float re = 0.0f, im = 0.0f;
-            for (int q = 0; q < Q; q++)
+            for (int q = 0; q < rounds; q++)
             {
                 const float2 x = pfbSample(a, n - r - (long long)q * M);
                 const float h = hp[q * M];
@@ -267,7 +270,7 @@ static int pfbRun(lorahip_pfb *p, const float2 *wide, const size_t nIn, float2 *
     a.taps = p->dTaps.get(); a.tw = p->dTw.get(); a.sel = p->dSel.get();
     a.out = out; a.outStride = (long long)outStride;
     a.mLo = (long long)mLo; a.nOut = (long long)nOut;
-    a.D = p->D; a.Lp = p->Lp; a.Q = p->Q; a.K = p->K; a.T = p->T; a.logT = p->logT; a.span = p->span;
+    a.D = p->D; a.L = p->L; a.Lp = p->Lp; a.K = p->K; a.T = p->T; a.logT = p->logT; a.span = p->span;
     if (nOut)
     {
         hipError_t e = hipErrorInvalidValue;

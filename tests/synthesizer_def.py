@@ -36,6 +36,34 @@ def synthesize(rows, freqs, interp, taps, gains=None, n0=0):
     return y
 
 
+def synthesize_at(rows, freqs, interp, taps, gains=None, n=(), n0=0):
+    """the definition for SELECTED outputs: n holds absolute output indices (int array), rows (K, cnt) the samples n0 .. n0 + cnt - 1
+    of every channel; every sample outside them (and before the start of the stream) reads as 0. Returns len(n) complex128. Only the
+    products the definition names are formed (j < L, (n - j) mod U == 0), so a non-finite sample reaches exactly those outputs."""
+    x = np.asarray(rows, np.complex128)
+    h = np.asarray(taps, np.float64)
+    U, L = int(interp), h.size
+    K, cnt = x.shape
+    g = np.ones(K) if gains is None else np.asarray(gains, np.float64)
+    n = np.asarray(n, np.int64)
+    i = np.arange(-(-L // U), dtype=np.int64)
+    j = (n % U)[:, None] + i[None, :] * U                                     # the taps of output n: j = n mod U + i U
+    c = (n // U)[:, None] - i[None, :] - int(n0)                              # and where their samples stand in rows
+    ok = (j < L) & (c >= -int(n0)) & (c >= 0) & (c < cnt)
+    hj = np.where(ok, h[np.minimum(j, L - 1)], 0.0)
+    cc = np.clip(c, 0, max(cnt - 1, 0))
+    w = np.array([phase_inc(f) for f in freqs], np.uint64)
+    nu = n.astype(np.uint64)
+    y = np.zeros(n.size, np.complex128)
+    step = max(1, (1 << 21) // max(1, n.size * i.size))
+    for a in range(0, K, step):
+        with np.errstate(invalid="ignore", over="ignore"):
+            f = np.sum(np.where(ok[None], hj[None] * x[a:a + step][:, cc], 0.0), axis=2) if cnt else np.zeros((min(step, K - a), n.size))
+            ph = (w[a:a + step, None] * nu[None, :]).astype(np.int64)         # wraps mod 2^64, read as signed
+            y += np.sum(g[a:a + step, None] * f * np.exp(2j * np.pi * (ph.astype(np.float64) * 2.0 ** -64)), axis=0)
+    return y
+
+
 def error_scale(rows, taps, interp, gains=None):
     """max|x| * sum_k |gain_k| * max_p sum_i |h[p + i U]|: what no output can exceed"""
     h = np.abs(np.asarray(taps, np.float64))
