@@ -782,6 +782,50 @@ int lorahip_pfb_reset(lorahip_pfb *p);
 size_t lorahip_pfb_out_count(const lorahip_pfb *p, size_t n_in);
 int lorahip_pfb_run(lorahip_pfb *p, const float *wide_dev, size_t n_in, float *out_dev, size_t out_stride, size_t *n_out);
 
+/* -------------------------------------------------------------------------------------
+ * Polyphase synthesis filter bank: the transmit front end for a UNIFORM channel plan, K channel streams onto the grid fs / M
+ * (lorahip_psb.hip). The mirror image of lorahip_pfb_*. NOT a reference component. For M = n_bins a power of two, b / M is exact in
+ * the 64-bit phase counter, and the output of this object is BY DEFINITION what the synthesiser above defines for
+ * freq[k] = bins[k] / M (x_k[m] = channel k's stream since the last reset, x_k[m<0] = 0, U = interp, L = n_taps, h = taps,
+ * g = gain, NULL: all 1, b_k = bins[k]):
+ *
+ *     y[n] = sum_k g_k exp(+2 pi i b_k n / M) sum_{j<L, (n-j) mod U == 0, n-j >= 0} h[j] x_k[(n-j)/U]
+ *
+ * evaluated as one gather and one inverse M-point DFT per INPUT time and a fold per output, whatever the number of rows (p = n mod U):
+ *
+ *     X_b[m] = sum_{k : b_k mod M == b} g_k x_k[m]
+ *     u_s[m] = sum_{b<M} X_b[m] exp(+2 pi i b s / M)
+ *     y[n]   = sum_{i : p + iU < L} h[p + iU] u_{n mod M}[n/U - i]
+ *
+ * in fp32 (fused multiply-add; the rows of a bin are summed in ascending k with the gain applied there, the transform is an ordinary
+ * radix-2 decimation-in-frequency FFT with twiddles computed in double, the fold runs over i in ascending order). The phase is the
+ * stream position modulo M: integer arithmetic, no drift, and a stream cut into arbitrary chunks gives bit-identical outputs to one
+ * call. The values agree with the direct form's within the tolerance both are held to (4e-6 of max|x| sum|g| max_p sum_i |h[p + iU]|),
+ * not bit for bit. Each fold runs over the taps below L only (no product with padding is formed), so a NaN or Inf in x_k[m] makes
+ * exactly the outputs m U .. m U + L - 1 non-finite, as in the definition -- not the direct synthesiser's whole rounds of U. Output
+ * phases without a tap (L < U) are exact zeros. n_in samples per row always give exactly n_in * interp outputs.
+ * bins: n_sel entries, any int32, taken modulo M (negative bins are the lower half of the band; rows that share a bin are summed);
+ * NULL: the bins 0 .. n_bins - 1 in order (n_sel must be n_bins then). bins[k] / M is what a lorahip_synthesizer, a
+ * lorahip_channelizer or a lorahip_pfb takes for the same plan.
+ * run(): row k of the input is the n_in complex64 samples at in_dev + 2*k*in_stride floats (in_stride in samples >= n_in);
+ * writes *n_out = lorahip_psb_out_count(p, n_in) = n_in * interp samples at wide_dev. Asynchronous on the context's stream. Between
+ * calls the object keeps the stream position and the transforms u_s[m] of the last ceil(L/U) - 1 input times; a call works through
+ * a device workspace of at most 32 MiB that grows on first use.
+ * Limits: n_bins a power of two in 8..1024, interp 1..4096, n_taps 1..65536, n_sel 1..65535*8; lorahip_psb_check answers for these
+ * four without a device (LORAHIP_OK or LORAHIP_E_INVALID); finite gains. Limit of one call (a longer stream is fed in several
+ * calls): at most 2^30 outputs (8 GiB); a call is worked off in segments whose launch grids stay far below 2^31 - 1. Anything
+ * beyond a limit is refused with LORAHIP_E_INVALID and a lorahip_last_error() text that begins "polyphase synthesiser", consumes
+ * nothing and leaves the stream state untouched. Rows, strides and the stream position are addressed with 64 bits.
+ * ------------------------------------------------------------------------------------- */
+typedef struct lorahip_psb lorahip_psb;
+int lorahip_psb_check(size_t n_bins, size_t interp, size_t n_taps, size_t n_sel);      /* host only */
+int lorahip_psb_create(lorahip_psb **out, lorahip_ctx *ctx, size_t n_bins, const int32_t *bins /* nullable */, size_t n_sel,
+                       const float *gain /* nullable */, size_t interp, const float *taps, size_t n_taps);
+void lorahip_psb_destroy(lorahip_psb *p);
+int lorahip_psb_reset(lorahip_psb *p);
+size_t lorahip_psb_out_count(const lorahip_psb *p, size_t n_in);                       /* n_in * interp; 0 for NULL */
+int lorahip_psb_run(lorahip_psb *p, const float *in_dev, size_t in_stride, size_t n_in, float *wide_dev, size_t *n_out);
+
 /* Measurement aid: one read-only streaming pass over n_bytes of device memory (pattern 0: linear
  * 16 B per lane; 1: the access shape of the tuned SF7 kernel). Time it with lorahip_timer_*; the
  * result is the practical HBM ceiling the roofline fraction can be compared with. */

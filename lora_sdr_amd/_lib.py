@@ -182,6 +182,12 @@ SIGNATURES = {
     "lorahip_pfb_reset": (C.c_int, [C.c_void_p]),
     "lorahip_pfb_out_count": (C.c_size_t, [C.c_void_p, C.c_size_t]),
     "lorahip_pfb_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "lorahip_psb_check": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
+    "lorahip_psb_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "lorahip_psb_destroy": (None, [C.c_void_p]),
+    "lorahip_psb_reset": (C.c_int, [C.c_void_p]),
+    "lorahip_psb_out_count": (C.c_size_t, [C.c_void_p, C.c_size_t]),
+    "lorahip_psb_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]),
     "lorahip_demod_activate": (C.c_int, [C.c_void_p]),
     "lorahip_demod_set_mode": (C.c_int, [C.c_void_p, C.c_int]),
     "lorahip_demod_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -628,6 +628,73 @@ class Synthesizer:
         return out[:got.value]
 
 
+class PolyphaseSynthesizer:
+    """The synthesiser for a uniform channel plan: row k goes to centre bins[k] / n_bins cycles per OUTPUT sample (n_bins a power of
+    two, 8..1024; any integers, taken modulo n_bins; negative = the lower half of the band; rows that share a bin are summed; None: all
+    n_bins bins in order), scaled by gains (None: all 1). One inverse n_bins-point FFT per input time and one fold per output serve
+    every row, so the cost does not grow with the number of channels as Synthesizer's does, and interp may be 1..4096. The output is
+    by definition Synthesizer(ctx, bins / n_bins, interp, taps, gains)'s; .freqs is the array a Synthesizer, a Channelizer or a
+    PolyphaseChannelizer's plan takes. Stateful like Synthesizer: consecutive run() calls continue one stream, bit-identical to one
+    call; reset() starts a new one. See include/lorahip.h."""
+
+    def __init__(self, ctx, n_bins, interp, taps, bins=None, gains=None):
+        self._lib = load()
+        self._ctx = ctx                                                  # borrowed: device and stream
+        self._h = C.c_void_p()
+        t = np.ascontiguousarray(taps, np.float32).reshape(-1)
+        if bins is None:
+            b = np.arange(int(n_bins) if 0 < int(n_bins) <= 1024 else 0, dtype=np.int32)
+        else:
+            b64 = np.ascontiguousarray(bins, np.int64).reshape(-1)
+            if b64.size and (b64.min() < -2 ** 31 or b64.max() >= 2 ** 31):
+                raise ValueError("bins must fit 32 bits")
+            b = b64.astype(np.int32)
+        g = None if gains is None else np.ascontiguousarray(gains, np.float32).reshape(-1)
+        if g is not None and g.size != b.size:
+            raise ValueError("one gain per channel")
+        check(self._lib.lorahip_psb_create(C.byref(self._h), ctx._h, int(n_bins), None if bins is None else b.ctypes.data,
+                                           int(n_bins) if bins is None else b.size, None if g is None else g.ctypes.data,
+                                           int(interp), t.ctypes.data, t.size), "lorahip_psb_create")
+        self.n_bins, self.interp, self.n_taps, self.n_channels = int(n_bins), int(interp), int(t.size), int(b.size)
+        self.bins = b
+        self.freqs = b.astype(np.float64) / float(self.n_bins)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.lorahip_psb_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def reset(self):
+        check(self._lib.lorahip_psb_reset(self._h), "lorahip_psb_reset")
+
+    def out_count(self, n_in):
+        return int(self._lib.lorahip_psb_out_count(self._h, int(n_in)))
+
+    def run(self, rows, out=None):
+        """rows: (K, n) complex64 device tensor with unit column stride (the next n samples of every channel; may be the columns
+        [a, a + n) of a wider buffer); returns the 1-D complex64 tensor of n * interp wideband samples (written into out if given)"""
+        import torch
+        if (rows.dim() != 2 or rows.dtype != torch.complex64 or rows.shape[0] != self.n_channels
+                or (rows.numel() and (rows.stride(1) != 1 or (rows.shape[0] > 1 and rows.stride(0) < rows.shape[1])))):
+            raise ValueError("rows must be a (K, n) complex64 device tensor with unit column stride (rows may be a slice of a wider buffer)")
+        n_in = int(rows.shape[1])
+        n_out = self.out_count(n_in)
+        if out is None:
+            out = torch.empty(n_out, dtype=torch.complex64, device=rows.device)
+        elif out.dim() != 1 or out.dtype != torch.complex64 or out.numel() < n_out or (out.numel() and out.stride(0) != 1):
+            raise ValueError("out must be a 1-D complex64 tensor of >= n * interp samples with unit stride")
+        self._ctx.use_torch_stream()
+        got = C.c_size_t()
+        # the row stride is the tensor's own: `rows` may be a column slice of a (K, capacity) buffer
+        check(self._lib.lorahip_psb_run(self._h, C.c_void_p(rows.data_ptr()) if rows.numel() else None,
+                                        int(rows.stride(0)) if rows.numel() and rows.shape[0] > 1 else n_in, n_in,
+                                        C.c_void_p(out.data_ptr()) if out.numel() else None, C.byref(got)),
+              "lorahip_psb_run")
+        return out[:got.value]
+
+
 class LoRaDetector:
     """`LoRaDetector<float>` (LoRaDetector.hpp:8-72): feed N samples, detect() -> arg-max bin."""
 
