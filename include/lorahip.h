@@ -555,6 +555,10 @@ int lorahip_demod_get_trace(const lorahip_demod *d, size_t channel, lorahip_work
  * Synthetic IQ directly in HBM (bench / tests input; ChirpGenerator.hpp:22-47 semantics in
  * closed form): window w of channel c = ampl * upchirp(sym[c*S+w]) (+ AWGN of per-component
  * sigma `noise_sigma`, counter-based RNG keyed by seed). iq_dev: B*S*N cf32.
+ * The symbol is MASKED to its low sf bits (sym & (N-1)); lorahip_mod_frames below does not mask. Without noise a
+ * sample is (ampl * (float)cos(phi), ampl * (float)sin(phi)) with phi the chirp's phase from 0 in double, cos and
+ * sin taken in double and rounded once (tests/modulator_def.py: synth_symbols_def restates it, expression for
+ * expression; the kernel gives those values).
  * ------------------------------------------------------------------------------------- */
 int lorahip_synth_symbols(lorahip_ctx *ctx, float *iq_dev, const uint16_t *sym_dev,
                           size_t n_windows, float ampl, float noise_sigma, uint64_t seed);
@@ -565,6 +569,16 @@ int lorahip_synth_symbols(lorahip_ctx *ctx, float *iq_dev, const uint16_t *sym_d
  * ChirpGenerator.hpp:22-47, ovs = 1): 10 up-chirps, the two sync-word chirps, 2 1/4 down-chirps, one chirp
  * per symbol, max(padding,1) zero symbols; one running float phase accumulator per frame. Frame f is written
  * at iq_dev + f*frame_stride samples; frame_stride >= lorahip_mod_frame_len(sf, nsyms, padding).
+ * A symbol is used AS GIVEN, as the block uses it: f0 = 2 pi sym / N also for sym >= N (lorahip_synth_symbols above
+ * masks instead); mask on the caller's side if that is wanted.
+ * Definition (tests/modulator_def.py): the block's float recurrence -- f += 2 pi / N with one wrap at +pi,
+ * phase +-= f, phase reduced mod 2 pi in double at the end of every chirp -- with the sample
+ * (ampl * (float)cos((double)phase), ampl * (float)sin((double)phase)), cos and sin rounded ONCE. The kernels give
+ * these values. The block itself calls the platform's cosf / sinf, which miss the correctly rounded value by one ulp
+ * in a percent or two of the samples: against the block's own output a sample is within 1 float ulp when |ampl| is
+ * a power of two and within 2 when it is not (a last-place step of cos is up to two of ampl * cos).
+ * Refused with LORAHIP_E_INVALID, nothing written: nsyms 0 or > 0x7fffff, padding > 0x7fffff, a frame_stride shorter
+ * than the frame, a null pointer with n_frames > 0. n_frames 0 is no work. lorahip_mod_frame_len is 0 outside SF 6..12.
  * ------------------------------------------------------------------------------------- */
 size_t lorahip_mod_frame_len(int sf, size_t nsyms, size_t padding);
 int lorahip_mod_frames(lorahip_ctx *ctx, float *iq_dev, size_t frame_stride, const uint16_t *syms_dev,

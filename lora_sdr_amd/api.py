@@ -229,7 +229,8 @@ class Context:
         return out
 
     def synth_symbols(self, sym, ampl=1.0, noise_sigma=0.0, seed=0):
-        """IQ of len(sym) back-to-back up-chirp symbols generated in HBM -> complex64 device tensor."""
+        """IQ of len(sym) back-to-back up-chirp symbols generated in HBM -> complex64 device tensor. Symbols are masked to their
+        low sf bits (mod_frames does not mask)."""
         import torch
         sym = sym.reshape(-1)
         if sym.dtype not in (torch.int16, torch.uint16):
@@ -247,7 +248,8 @@ class Context:
 
     def mod_frames(self, syms, sync=0x12, ampl=1.0, padding=1, frame_stride=None, lead=0, tail=0, nsyms=None):
         """The LoRaMod block (LoRaMod.cpp:109-238) for a batch of packets: syms is a (n_frames, nsyms) 16-bit device
-        tensor; returns a (n_frames, lead + frame_stride + tail) complex64 device tensor, zero outside the frames.
+        tensor; returns a (n_frames, lead + frame_stride + tail) complex64 device tensor, zero outside the frames. Symbols are
+        used as given (f0 = 2 pi sym / N also for sym >= N, as the block does; synth_symbols masks to sf bits instead).
 
         nsyms: an optional (n_frames,) int32 device tensor of per-frame symbol counts (the encoder's output), read on the device
         (lorahip_mod_frames_var): frame f is modulated from its first nsyms[f] symbols and continued with zero chirps to the length
