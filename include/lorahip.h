@@ -780,17 +780,36 @@ int lorahip_synthesizer_run(lorahip_synthesizer *s, const float *in_dev, size_t 
  * run(): consumes n_in samples, writes *n_out = lorahip_pfb_out_count(p, n_in) samples of row i at out_dev + 2*i*out_stride floats
  * (complex64, out_stride in samples >= *n_out). Asynchronous on the context's stream. Between calls the object keeps the stream
  * position and the trailing samples the next outputs reach back to (n_taps rounded up to a multiple of n_bins, less one).
- * Limits: n_bins a power of two in 8..1024 (other radices, e.g. 5 * 2^a, are refused), decim 1..4096, n_taps 1..65536, n_sel
- * 1..65535*8; lorahip_pfb_check answers for these four without a device (LORAHIP_OK or LORAHIP_E_INVALID). Limits of one call (a
- * longer stream is fed in several calls): at most 2^30 outputs per row, and tiles <= outputs / T + 2 (T = 4096 / n_bins, 16 at least,
- * 256 at most; a call may start and end inside a tile) at most 2^31 - 1 (the launch grid). Anything beyond a limit is refused with LORAHIP_E_INVALID and a
+ * Limits: n_bins a power of two in 8..1024 (lorahip_pfb_check / lorahip_pfb_create) or 5 * 2^a, a = 0..6 (the _radix5 pair below);
+ * decim 1..4096, n_taps 1..65536, n_sel 1..65535*8; lorahip_pfb_check answers for these four without a device (LORAHIP_OK or
+ * LORAHIP_E_INVALID). Limits of one call (a longer stream is fed in several calls): at most 2^30 outputs per row, and tiles <=
+ * outputs / T + 2 (T = the largest power of two with T * n_bins <= 4096, 16 at least, 256 at most; a call may start and end inside
+ * a tile) at most 2^31 - 1 (the launch grid). Anything beyond a limit is refused with LORAHIP_E_INVALID and a
  * lorahip_last_error() text, consumes nothing and leaves the stream state untouched. Rows, strides and the stream position are
  * addressed with 64 bits.
+ *
+ * Bin counts 5 * 2^a: M = 5, 10, 20, 40, 80, 160, 320 -- the grids of the LoRaWAN plans with 125 kHz channels 200 kHz apart, where
+ * decim / n_bins = 8 / 5 (fs = 1 MHz: M = 5, D = 8 ... fs = 16 MHz: M = 80, D = 128). lorahip_pfb_check_radix5 and
+ * lorahip_pfb_create_radix5 take the arguments of lorahip_pfb_check and lorahip_pfb_create with the same limits, meanings, refusal
+ * texts ("polyphase channeliser ...") and untouched state on refusal; they accept these seven bin counts and nothing else (powers of
+ * two are refused here as 5 * 2^a is refused there: the two pairs are disjoint). The handle is a lorahip_pfb: run, reset, out_count
+ * and destroy serve it unchanged. One difference in the definition: for these M, b / M is NOT exact in the direct form's 64-bit
+ * phase counter (lorahip_channelizer_phase_inc(b / M) is off by less than 2^-64 cycle per sample), so the rows are defined by the
+ * folded formula above, i.e. by the exact phase b (n mod M) / M:
+ *
+ *     y_b[m] = sum_{j<L} h[j] x[n_m - j] exp(-2 pi i b ((n_m - j) mod M) / M)
+ *
+ * They agree with a lorahip_channelizer for freq = bins[i] / M far inside the tolerance both are held to. The transform is one
+ * radix-5 decimation-in-frequency stage (a 5-point DFT over the points M / 5 apart, constants and twiddles exp(-2 pi i r n / M) from
+ * a table computed in double) followed by five radix-2 transforms of M / 5 points; everything else is as above.
  * ------------------------------------------------------------------------------------- */
 typedef struct lorahip_pfb lorahip_pfb;
 int lorahip_pfb_check(size_t n_bins, size_t decim, size_t n_taps, size_t n_sel);       /* host only */
 int lorahip_pfb_create(lorahip_pfb **out, lorahip_ctx *ctx, size_t n_bins, const int32_t *bins /* nullable */, size_t n_sel,
                        size_t decim, const float *taps, size_t n_taps);
+int lorahip_pfb_check_radix5(size_t n_bins, size_t decim, size_t n_taps, size_t n_sel);   /* host only */
+int lorahip_pfb_create_radix5(lorahip_pfb **out, lorahip_ctx *ctx, size_t n_bins, const int32_t *bins /* nullable */, size_t n_sel,
+                              size_t decim, const float *taps, size_t n_taps);
 void lorahip_pfb_destroy(lorahip_pfb *p);
 int lorahip_pfb_reset(lorahip_pfb *p);
 size_t lorahip_pfb_out_count(const lorahip_pfb *p, size_t n_in);

@@ -178,6 +178,8 @@ SIGNATURES = {
     "lorahip_synthesizer_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]),
     "lorahip_pfb_check": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
     "lorahip_pfb_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "lorahip_pfb_check_radix5": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
+    "lorahip_pfb_create_radix5": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t]),
     "lorahip_pfb_destroy": (None, [C.c_void_p]),
     "lorahip_pfb_reset": (C.c_int, [C.c_void_p]),
     "lorahip_pfb_out_count": (C.c_size_t, [C.c_void_p, C.c_size_t]),

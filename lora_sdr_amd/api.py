@@ -513,8 +513,42 @@ class Channelizer:
         return out
 
 
+RADIX5_BINS = (5, 10, 20, 40, 80, 160, 320)
+
+
+def uniform_plan(sample_rate_hz, centre_hz, channel_hz, spacing_hz=200e3, bandwidth_hz=125e3):
+    """(n_bins, decim, bins) of a uniform channel plan for PolyphaseChannelizer.for_plan: channels bandwidth_hz wide on a grid of
+    spacing_hz round centre_hz, received at sample_rate_hz. n_bins = fs / spacing, decim = fs / bandwidth (the demodulator takes its
+    input at exactly the bandwidth), bins[i] = (channel_hz[i] - centre_hz) / spacing. Host only. ValueError, with the reason, when
+    one of the three is no integer (to 1e-9 relative), n_bins is neither a power of two 8..1024 nor 5 * 2^a (a = 0..6), decim is
+    outside 1..4096, or a channel lies outside the band (|bin| > n_bins / 2)."""
+    fs, spacing, bw = float(sample_rate_hz), float(spacing_hz), float(bandwidth_hz)
+    if not (fs > 0 and spacing > 0 and bw > 0):
+        raise ValueError("uniform_plan: sample rate, spacing and bandwidth must be positive")
+
+    def whole(value, what):
+        value = np.asarray(value, np.float64)
+        near = np.rint(value)
+        if not np.all(np.isfinite(value)) or np.any(np.abs(value - near) > 1e-9 * np.maximum(1.0, np.abs(value))):
+            raise ValueError("uniform_plan: %s is not an integer (%s)" % (what, np.array2string(value, threshold=8)))
+        return near.astype(np.int64)
+
+    n_bins = int(whole(fs / spacing, "n_bins = sample rate / spacing"))
+    decim = int(whole(fs / bw, "decim = sample rate / bandwidth"))
+    ch = np.ascontiguousarray(channel_hz, np.float64).reshape(-1)
+    bins = whole((ch - float(centre_hz)) / spacing, "a bin = (channel - centre) / spacing: the centre is off the channel grid, and it")
+    if not ((8 <= n_bins <= 1024 and n_bins & (n_bins - 1) == 0) or n_bins in RADIX5_BINS):
+        raise ValueError("uniform_plan: n_bins = %d is neither a power of two 8..1024 nor one of %s" % (n_bins, list(RADIX5_BINS)))
+    if not 1 <= decim <= 4096:
+        raise ValueError("uniform_plan: decim = %d is outside 1..4096" % decim)
+    if bins.size and np.abs(bins).max() > n_bins / 2:
+        raise ValueError("uniform_plan: a channel is out of band (|bin| = %d > n_bins / 2 = %g)" % (np.abs(bins).max(), n_bins / 2))
+    return n_bins, decim, bins.astype(np.int32)
+
+
 class PolyphaseChannelizer:
-    """The channeliser for a uniform channel plan: rows on the grid fs / n_bins (n_bins a power of two, 8..1024), row i at centre
+    """The channeliser for a uniform channel plan: rows on the grid fs / n_bins (n_bins a power of two, 8..1024; 5 * 2^a, a = 0..6,
+    the 200 kHz LoRaWAN grids, through PolyphaseChannelizer.radix5 or .for_plan), row i at centre
     bins[i] / n_bins cycles per input sample (any integers, taken modulo n_bins; negative = the lower half of the band; None: all
     n_bins bins in order). One polyphase fold and one n_bins-point FFT per output time serve every row, so the cost does not grow with
     the number of channels as Channelizer's does. Row i is by definition Channelizer(ctx, [bins[i] / n_bins], decim, taps)'s; .freqs is
@@ -522,6 +556,10 @@ class PolyphaseChannelizer:
     stream, bit-identical to one call; reset() starts a new one. See include/lorahip.h."""
 
     def __init__(self, ctx, n_bins, decim, taps, bins=None):
+        self._build("lorahip_pfb_create", ctx, n_bins, decim, taps, bins)
+
+    def _build(self, create, ctx, n_bins, decim, taps, bins):
+        """create the handle through the C entry point `create` and set the attributes"""
         self._lib = load()
         self._ctx = ctx                                                  # borrowed: device and stream
         self._h = C.c_void_p()
@@ -533,11 +571,26 @@ class PolyphaseChannelizer:
             if b64.size and (b64.min() < -2 ** 31 or b64.max() >= 2 ** 31):
                 raise ValueError("bins must fit 32 bits")
             b = b64.astype(np.int32)
-        check(self._lib.lorahip_pfb_create(C.byref(self._h), ctx._h, int(n_bins), None if bins is None else b.ctypes.data,
-                                           int(n_bins) if bins is None else b.size, int(decim), t.ctypes.data, t.size), "lorahip_pfb_create")
+        check(getattr(self._lib, create)(C.byref(self._h), ctx._h, int(n_bins), None if bins is None else b.ctypes.data,
+                                         int(n_bins) if bins is None else b.size, int(decim), t.ctypes.data, t.size), create)
         self.n_bins, self.decim, self.n_taps, self.n_channels = int(n_bins), int(decim), int(t.size), int(b.size)
         self.bins = b
         self.freqs = b.astype(np.float64) / float(self.n_bins)
+
+    @classmethod
+    def radix5(cls, ctx, n_bins, decim, taps, bins=None):
+        """the same object on n_bins = 5 * 2^a bins (5, 10, 20, 40, 80, 160, 320; lorahip_pfb_create_radix5): channels 200 kHz apart
+        and 125 kHz wide have decim / n_bins = 8 / 5. The constructor takes the powers of two only, this the seven counts only."""
+        self = cls.__new__(cls)
+        self._build("lorahip_pfb_create_radix5", ctx, n_bins, decim, taps, bins)
+        return self
+
+    @classmethod
+    def for_plan(cls, ctx, plan, taps):
+        """the object for plan = (n_bins, decim, bins) as uniform_plan returns it: the constructor or radix5, by n_bins"""
+        n_bins, decim, bins = plan
+        make = cls.radix5 if int(n_bins) in RADIX5_BINS else cls
+        return make(ctx, n_bins, decim, taps, bins)
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:

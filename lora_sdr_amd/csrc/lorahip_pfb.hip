@@ -1,6 +1,7 @@
 // Polyphase filter-bank channeliser: the front end for a UNIFORM channel plan -- K channels on the grid fs/M, M a power of two
-// (include/lorahip.h has the definition; DESIGN.md section 8c the shape and the measurements). Row i is, by definition, what the
-// direct-form channeliser (lorahip_chan.hip) defines for freq = bins[i] / M: that frequency is exact in the 64-bit phase counter, so
+// 8..1024 or 5 * 2^a, a = 0..6 (include/lorahip.h has the definition; DESIGN.md section 8c the shape and the measurements). Row i is,
+// by definition, what the direct-form channeliser (lorahip_chan.hip) defines for freq = bins[i] / M with the exact phase (for a
+// power of two that frequency is exact in the 64-bit phase counter; for 5 * 2^a it is not, and the formula below is the definition):
 // the mixer phase of sample n is exp(-2 pi i b (n mod M) / M) and the L products of an output fold, by absolute sample time modulo M,
 // into M sums that one forward M-point DFT turns into every bin at once:
 //
@@ -9,7 +10,8 @@
 //
 // L real-by-complex multiply-adds and one FFT per output time, whatever K is (the direct form: K L complex multiply-adds).
 //
-// One workgroup = one tile of T consecutive output times (T = 4096 / M, 16 at least and 256 at most), three stages in one launch:
+// One workgroup = one tile of T consecutive output times (T = the largest power of two with T M <= 4096, 16 at least and 256 at most),
+// three stages in one launch:
 //   * polyphase: lane = s (consecutive lanes read consecutive samples and consecutive taps), the fold runs over j = r + M q in
 //     ascending q with r = (n_m - s) mod M, one fused multiply-add per component and tap, ceil((L - r) / M) rounds: the taps the
 //     filter has and no others (the table is padded with zeros to Q = ceil(L / M) whole rounds, but no product is formed with the
@@ -18,23 +20,26 @@
 //     multiples of T and every sum has one fixed order, so a result does not depend on where a call or a tile starts;
 //   * FFT: T transforms of M points in place in the LDS, decimation in frequency, 2 to 4 radix-2 stages per pass in registers
 //     (passes of 16 / 8 points a lane), twiddles from a host table computed in double. The result is left in bit-reversed order:
-//     the host reverses the selected bins instead;
+//     the host reverses the selected bins instead. M = 5 * 2^a: one radix-5 stage first, then five such transforms of M / 5 points
+//     (lorahip_pfbfft5.h; bin 5 k + r is left at r M / 5 + bitrev(k));
 //   * store: only the selected bins leave the LDS; lane = output time, so a row's run of a tile is T * 8 >= 128 bytes. Rows of the
-//     sums are M + 1 samples apart: the T lanes that read one bin of T rows hit T different banks.
-// The phase is the stream position modulo M -- integer arithmetic, no drift.
+//     sums are M + 1 samples apart: the T lanes that read one bin of T rows hit T different banks (M + 1 odd; M = 5: 6 samples =
+//     12 banks apart, lanes 16 apart share a bank: two-way).
+// The phase is the stream position modulo M -- integer arithmetic, no drift. M is a template constant: for the power-of-two banks
+// the divisions and remainders by it are shifts and masks, for the others multiplications.
 #include "lorahip_own.h"
-#include "lorahip_pfbfft.h"
+#include "lorahip_pfbfft5.h"
 #include <cmath>
 #include <new>
 
 struct lorahip_pfb
 {
     lorahip_ctx *ctx;
-    int M, logM, D, L, Lp, Q, K, T, logT, staged, span, HC;
+    int M, D, L, Lp, Q, K, T, logT, staged, span, HC;
     size_t ldsBytes;
     lorahip::DevBuf<float> dTaps;               // [Lp] h[j], zeros from L on
-    lorahip::DevBuf<float2> dTw;                // [M/2] exp(-2 pi i k / M)
-    lorahip::DevBuf<int> dSel;                  // [K] where row i's bin stands after the transform: bitrev(bins[i] mod M)
+    lorahip::DevBuf<float2> dTw;                // [pfbTwiddles(M)] exp(-2 pi i k / M), k < M / 2; 5 * 2^a: the same for M / 5, then exp(-2 pi i n / M), n < M
+    lorahip::DevBuf<int> dSel;                  // [K] where row i's bin stands after the transform: pfbPlace(M, bins[i] mod M)
     lorahip::DevBuf<float2> dHist[2];           // the HC samples before n0 (zeros before the start of the stream)
     int cur;
     unsigned long long n0;                      // samples consumed since the last reset
@@ -43,6 +48,7 @@ struct lorahip_pfb
 namespace lorahip {
 
 constexpr int PFB_LOGM_MIN = 3, PFB_LOGM_MAX = 10;
+constexpr int PFB5_A_MAX = 6;                   // M = 5 * 2^a, a = 0 .. 6
 constexpr size_t PFB_STAGE_LDS = 80u << 10;     // sums + twiddles + input span up to this: two workgroups a compute unit
 
 struct PfbArgs
@@ -61,6 +67,23 @@ struct PfbArgs
     long long nOut;
     int D, L, Lp, K, T, logT, span;
 };
+
+constexpr bool pfbIsPow2(const int M) { return (M & (M - 1)) == 0; }
+constexpr int pfbLog2(const int n) { return n <= 1 ? 0 : 1 + pfbLog2(n >> 1); }
+//! the radix-2 part of M: M itself, or M / 5
+constexpr int pfbPow2Part(const int M) { return pfbIsPow2(M) ? M : M / 5; }
+//! entries of the twiddle table
+constexpr int pfbTwiddles(const int M) { return pfbIsPow2(M) ? M / 2 : M / 10 + M; }
+
+//! where bin b (0 <= b < M) stands in a row after the transform
+static int pfbPlace(const int M, const int b)
+{
+    const int N = pfbPow2Part(M), logN = pfbLog2(N), fifth = pfbIsPow2(M) ? 1 : 5;
+    const unsigned k = unsigned(b / fifth);
+    unsigned rev = 0;
+    for (int bit = 0; bit < logN; bit++) rev |= ((k >> bit) & 1u) << (logN - 1 - bit);
+    return (b % fifth) * N + int(rev);
+}
 
 //! sample n of the stream (absolute index): from this call's chunk, from the history kept from earlier calls, or 0
 __device__ __forceinline__ float2 pfbSample(const PfbArgs &a, const long long n)
@@ -90,23 +113,24 @@ __device__ __forceinline__ float2 pfbFold(const float2 *xp, const float *hp, con
     return make_float2(re, im);
 }
 
-template <int LOGM, bool STAGED>
+template <int M, bool STAGED>
 __global__ __launch_bounds__(PFB_THREADS) void pfbChannelize(const PfbArgs a)
 {
     extern __shared__ float2 pfbLds[];
-    constexpr int M = 1 << LOGM;
+    constexpr bool POW2 = pfbIsPow2(M);
+    constexpr int LOGN = pfbLog2(pfbPow2Part(M)), TW = pfbTwiddles(M);
     const int tid = threadIdx.x;
     const int T = a.T, D = a.D, Lp = a.Lp;
     float2 *v = pfbLds;                             // [T][M + 1]
-    float2 *tw = v + T * (M + 1);                   // [M / 2]
-    float2 *xs = tw + M / 2;                        // [span] (STAGED)
+    float2 *tw = v + T * (M + 1);                   // [TW]
+    float2 *xs = tw + TW;                           // [span] (STAGED)
     const long long mTile = ((a.mLo >> a.logT) + (long long)blockIdx.x) << a.logT;
     const long long nFirst = (mTile + 1) * D - 1;   // n_m of the tile's first output
     const long long tileStart = nFirst - (Lp - 1);  // oldest sample of the tile's first output
     const long long rel = tileStart - a.n0;
     const bool inside = rel >= 0 && rel + a.span <= a.nChunk;       // the tile's whole input lies in this call's chunk
 
-    for (int k = tid; k < M / 2; k += PFB_THREADS) tw[k] = a.tw[k];
+    for (int k = tid; k < TW; k += PFB_THREADS) tw[k] = a.tw[k];
     if constexpr (STAGED)
     {
         if (inside)
@@ -124,14 +148,22 @@ __global__ __launch_bounds__(PFB_THREADS) void pfbChannelize(const PfbArgs a)
     }
 
     // polyphase stage: lane = residue s
+    [[maybe_unused]] const int nFirstModM = int((unsigned long long)nFirst % unsigned(M)), dModM = D % M;    // nFirst >= 0
     for (int idx = tid; idx < T * M; idx += PFB_THREADS)
     {
-        const int s = idx & (M - 1), t = idx >> LOGM;
+        int s, t, r;                                // r = (n - s) mod M, the floor remainder (n - s < 0 at the start of a stream when D < M)
+        if constexpr (POW2) { s = idx & (M - 1); t = idx >> LOGN; }
+        else { t = int(unsigned(idx) / unsigned(M)); s = idx - t * M; }
         const long long n = nFirst + (long long)t * D;
-        const int r = int((n - s) & (M - 1));       // the newest sample of residue s is r samples old: taps r, r + M, ...
+        if constexpr (POW2) r = int((n - s) & (M - 1));
+        else
+        {
+            r = int(unsigned(nFirstModM + t * dModM) % unsigned(M)) - s;
+            if (r < 0) r += M;
+        }                                           // the newest sample of residue s is r samples old: taps r, r + M, ...
         const int at = t * D + Lp - 1 - r;          // ... and stands here in the tile's span
         const float *hp = a.taps + r;
-        const int rounds = (a.L - r + M - 1) >> LOGM;   // taps r, r + M, ... < L: the padding of the table is never multiplied (0 where r >= L)
+        const int rounds = POW2 ? (a.L - r + M - 1) >> LOGN : int(unsigned(a.L - r + M - 1) / unsigned(M));   // taps r, r + M, ... < L: the padding of the table is never multiplied (0 where r >= L)
         float2 acc;
         if constexpr (STAGED) acc = pfbFold<M>(xs + at, hp, rounds);
         else if (inside) acc = pfbFold<M>(a.chunk + rel + at, hp, rounds);
@@ -151,7 +183,8 @@ __global__ __launch_bounds__(PFB_THREADS) void pfbChannelize(const PfbArgs a)
     }
     __syncthreads();
 
-    pfbFft<LOGM, 0>(v, tw, T, tid);
+    if constexpr (POW2) pfbFft<LOGN, 0>(v, tw, T, tid);
+    else pfbFft5<LOGN>(v, tw, tw + (M / 10), T, tid);
 
     // store stage: lane = output time
     const long long mTileLoc = mTile - a.mLo;       // the tile's first output in this call (< 0: the call starts inside the tile)
@@ -171,30 +204,35 @@ __global__ void pfbHistory(const PfbArgs a, float2 *newHist)
     if (i < a.histLen) newHist[i] = pfbSample(a, a.n0 + a.nChunk - a.histLen + i);
 }
 
-static unsigned long long gPfbLdsMask[PFB_LOGM_MAX + 1][2];
-
-template <int LOGM>
+template <int M>
 static hipError_t pfbLaunch(const lorahip_pfb *p, const PfbArgs &a, const unsigned grid)
 {
+    static unsigned long long ldsMask[2];
     if (p->staged)
     {
-        const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(&pfbChannelize<LOGM, true>), 160 * 1024, gPfbLdsMask[LOGM][1]);
+        const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(&pfbChannelize<M, true>), 160 * 1024, ldsMask[1]);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((pfbChannelize<LOGM, true>), dim3(grid), dim3(PFB_THREADS), p->ldsBytes, p->ctx->stream, a);
+        hipLaunchKernelGGL((pfbChannelize<M, true>), dim3(grid), dim3(PFB_THREADS), p->ldsBytes, p->ctx->stream, a);
     }
     else
     {
-        const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(&pfbChannelize<LOGM, false>), 160 * 1024, gPfbLdsMask[LOGM][0]);
+        const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(&pfbChannelize<M, false>), 160 * 1024, ldsMask[0]);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((pfbChannelize<LOGM, false>), dim3(grid), dim3(PFB_THREADS), p->ldsBytes, p->ctx->stream, a);
+        hipLaunchKernelGGL((pfbChannelize<M, false>), dim3(grid), dim3(PFB_THREADS), p->ldsBytes, p->ctx->stream, a);
     }
     return hipGetLastError();
 }
 
 //! nullptr when the shape is one this file handles, the reason otherwise
-static const char *pfbProblem(const size_t nBins, const size_t decim, const size_t nTaps, const size_t nSel)
+static const char *pfbProblem(const bool radix5, const size_t nBins, const size_t decim, const size_t nTaps, const size_t nSel)
 {
-    if (nBins < (size_t(1) << PFB_LOGM_MIN) || nBins > (size_t(1) << PFB_LOGM_MAX) || (nBins & (nBins - 1)))
+    if (radix5)
+    {
+        const size_t n = nBins / 5;
+        if (nBins % 5 || n == 0 || n > (size_t(1) << PFB5_A_MAX) || (n & (n - 1)))
+            return "polyphase channeliser: n_bins of the radix-5 bank must be 5 * 2^a, a = 0..6 (5, 10, 20, 40, 80, 160 or 320)";
+    }
+    else if (nBins < (size_t(1) << PFB_LOGM_MIN) || nBins > (size_t(1) << PFB_LOGM_MAX) || (nBins & (nBins - 1)))
         return "polyphase channeliser: n_bins must be a power of two in 8..1024";
     if (decim == 0 || decim > 4096) return "polyphase channeliser: decim must be 1..4096";
     if (nTaps == 0 || nTaps > (size_t(1) << 16)) return "polyphase channeliser: n_taps must be 1..65536";
@@ -226,16 +264,23 @@ static int pfbRun(lorahip_pfb *p, const float2 *wide, const size_t nIn, float2 *
     if (nOut)
     {
         hipError_t e = hipErrorInvalidValue;
-        switch (p->logM)
+        switch (p->M)
         {
-            case 3: e = pfbLaunch<3>(p, a, unsigned(nTiles)); break;
-            case 4: e = pfbLaunch<4>(p, a, unsigned(nTiles)); break;
-            case 5: e = pfbLaunch<5>(p, a, unsigned(nTiles)); break;
-            case 6: e = pfbLaunch<6>(p, a, unsigned(nTiles)); break;
-            case 7: e = pfbLaunch<7>(p, a, unsigned(nTiles)); break;
             case 8: e = pfbLaunch<8>(p, a, unsigned(nTiles)); break;
-            case 9: e = pfbLaunch<9>(p, a, unsigned(nTiles)); break;
+            case 16: e = pfbLaunch<16>(p, a, unsigned(nTiles)); break;
+            case 32: e = pfbLaunch<32>(p, a, unsigned(nTiles)); break;
+            case 64: e = pfbLaunch<64>(p, a, unsigned(nTiles)); break;
+            case 128: e = pfbLaunch<128>(p, a, unsigned(nTiles)); break;
+            case 256: e = pfbLaunch<256>(p, a, unsigned(nTiles)); break;
+            case 512: e = pfbLaunch<512>(p, a, unsigned(nTiles)); break;
+            case 1024: e = pfbLaunch<1024>(p, a, unsigned(nTiles)); break;
+            case 5: e = pfbLaunch<5>(p, a, unsigned(nTiles)); break;
             case 10: e = pfbLaunch<10>(p, a, unsigned(nTiles)); break;
+            case 20: e = pfbLaunch<20>(p, a, unsigned(nTiles)); break;
+            case 40: e = pfbLaunch<40>(p, a, unsigned(nTiles)); break;
+            case 80: e = pfbLaunch<80>(p, a, unsigned(nTiles)); break;
+            case 160: e = pfbLaunch<160>(p, a, unsigned(nTiles)); break;
+            case 320: e = pfbLaunch<320>(p, a, unsigned(nTiles)); break;
         }
         LORAHIP_TRY(e);
     }
@@ -246,40 +291,34 @@ static int pfbRun(lorahip_pfb *p, const float2 *wide, const size_t nIn, float2 *
     return LORAHIP_OK;
 }
 
-} // namespace lorahip
-
-using namespace lorahip;
-
-extern "C" {
-
-int lorahip_pfb_check(const size_t n_bins, const size_t decim, const size_t n_taps, const size_t n_sel)
+static int pfbCheck(const bool radix5, const size_t n_bins, const size_t decim, const size_t n_taps, const size_t n_sel)
 {
-    const char *why = pfbProblem(n_bins, decim, n_taps, n_sel);
+    const char *why = pfbProblem(radix5, n_bins, decim, n_taps, n_sel);
     if (why == nullptr) return LORAHIP_OK;
     setLastError(why);
     return LORAHIP_E_INVALID;
 }
 
-int lorahip_pfb_create(lorahip_pfb **out, lorahip_ctx *ctx, const size_t n_bins, const int32_t *bins, const size_t n_sel,
-                       const size_t decim, const float *taps, const size_t n_taps)
+//! lorahip_pfb_create (power-of-two bin counts) and lorahip_pfb_create_radix5 (5 * 2^a): the same object
+static int pfbCreate(const bool radix5, lorahip_pfb **out, lorahip_ctx *ctx, const size_t n_bins, const int32_t *bins, const size_t n_sel,
+                     const size_t decim, const float *taps, const size_t n_taps)
 {
     if (out == nullptr) return LORAHIP_E_INVALID;
     *out = nullptr;
     if (ctx == nullptr || taps == nullptr) { setLastError("polyphase channeliser: no context or no taps"); return LORAHIP_E_INVALID; }
-    if (lorahip_pfb_check(n_bins, decim, n_taps, n_sel) != LORAHIP_OK) return LORAHIP_E_INVALID;
+    if (pfbCheck(radix5, n_bins, decim, n_taps, n_sel) != LORAHIP_OK) return LORAHIP_E_INVALID;
     if (bins == nullptr && n_sel != n_bins) { setLastError("polyphase channeliser: without a bin list n_sel must be n_bins"); return LORAHIP_E_INVALID; }
 
     lorahip_pfb *p = new (std::nothrow) lorahip_pfb();
     if (p == nullptr) return LORAHIP_E_NOMEM;
     const int M = int(n_bins);
-    int logM = 0;
-    while ((1 << logM) < M) logM++;
-    p->ctx = ctx; p->M = M; p->logM = logM; p->D = int(decim); p->L = int(n_taps); p->K = int(n_sel);
+    p->ctx = ctx; p->M = M; p->D = int(decim); p->L = int(n_taps); p->K = int(n_sel);
     p->Q = (p->L + M - 1) / M; p->Lp = p->Q * M;
     p->HC = p->Lp - 1;
-    p->logT = 12 - logM < 4 ? 4 : (12 - logM > 8 ? 8 : 12 - logM);
+    const int logT = pfbLog2(4096 / M);         // the largest power of two with T M <= 4096 ...
+    p->logT = logT < 4 ? 4 : (logT > 8 ? 8 : logT);     // ... 16 at least, 256 at most
     p->T = 1 << p->logT;
-    const size_t fixedLds = (size_t(p->T) * size_t(M + 1) + size_t(M / 2)) * sizeof(float2);
+    const size_t fixedLds = (size_t(p->T) * size_t(M + 1) + size_t(pfbTwiddles(M))) * sizeof(float2);
     const size_t span = size_t(p->T - 1) * size_t(p->D) + size_t(p->Lp);
     p->span = int(span);                        // < 2^21
     p->staged = fixedLds + span * sizeof(float2) <= PFB_STAGE_LDS;
@@ -288,20 +327,19 @@ int lorahip_pfb_create(lorahip_pfb **out, lorahip_ctx *ctx, const size_t n_bins,
 
     std::vector<float> h(size_t(p->Lp), 0.0f);
     for (size_t j = 0; j < n_taps; j++) h[j] = taps[j];
-    std::vector<float2> tw(size_t(M / 2));
-    for (int k = 0; k < M / 2; k++)
+    std::vector<float2> tw;
+    tw.reserve(size_t(pfbTwiddles(M)));
+    const auto root = [&tw](const int k, const int P)      // exp(-2 pi i k / P)
     {
-        const double ang = 2.0 * M_PI * double(k) / double(M);
-        tw[size_t(k)] = make_float2(float(std::cos(ang)), float(-std::sin(ang)));
-    }
+        const double ang = 2.0 * M_PI * double(k) / double(P);
+        tw.push_back(make_float2(float(std::cos(ang)), float(-std::sin(ang))));
+    };
+    const int N = pfbPow2Part(M);
+    for (int k = 0; k < N / 2; k++) root(k, N);
+    if (radix5)
+        for (int n = 0; n < M; n++) root(n, M);
     std::vector<int> sel(n_sel);
-    for (size_t i = 0; i < n_sel; i++)
-    {
-        const unsigned b = bins ? unsigned(((long long)bins[i] % M + M) % M) : unsigned(i);
-        unsigned rev = 0;
-        for (int bit = 0; bit < logM; bit++) rev |= ((b >> bit) & 1u) << (logM - 1 - bit);
-        sel[i] = int(rev);
-    }
+    for (size_t i = 0; i < n_sel; i++) sel[i] = pfbPlace(M, bins ? int(((long long)bins[i] % M + M) % M) : int(i));
     const DeviceGuard guard(ctx->device);
     const size_t histBytes = size_t(p->HC) * sizeof(float2);
     hipError_t e = p->dTaps.grow(h.size() * sizeof(float));
@@ -318,6 +356,34 @@ int lorahip_pfb_create(lorahip_pfb **out, lorahip_ctx *ctx, const size_t n_bins,
     if (e != hipSuccess) { delete p; return hipFail(e, "polyphase channeliser table upload"); }
     *out = p;
     return LORAHIP_OK;
+}
+
+} // namespace lorahip
+
+using namespace lorahip;
+
+extern "C" {
+
+int lorahip_pfb_check(const size_t n_bins, const size_t decim, const size_t n_taps, const size_t n_sel)
+{
+    return pfbCheck(false, n_bins, decim, n_taps, n_sel);
+}
+
+int lorahip_pfb_check_radix5(const size_t n_bins, const size_t decim, const size_t n_taps, const size_t n_sel)
+{
+    return pfbCheck(true, n_bins, decim, n_taps, n_sel);
+}
+
+int lorahip_pfb_create(lorahip_pfb **out, lorahip_ctx *ctx, const size_t n_bins, const int32_t *bins, const size_t n_sel,
+                       const size_t decim, const float *taps, const size_t n_taps)
+{
+    return pfbCreate(false, out, ctx, n_bins, bins, n_sel, decim, taps, n_taps);
+}
+
+int lorahip_pfb_create_radix5(lorahip_pfb **out, lorahip_ctx *ctx, const size_t n_bins, const int32_t *bins, const size_t n_sel,
+                              const size_t decim, const float *taps, const size_t n_taps)
+{
+    return pfbCreate(true, out, ctx, n_bins, bins, n_sel, decim, taps, n_taps);
 }
 
 void lorahip_pfb_destroy(lorahip_pfb *p)

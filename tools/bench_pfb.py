@@ -1,7 +1,11 @@
 """Polyphase filter-bank channeliser beside the direct-form channeliser: the same shape, the same input, one process. HIP events on the
 context (lorahip_timer_*), 0.4 s of warm-up per shape, then alternating windows of both; the median window is reported with its
 spread. A shape the direct form refuses is printed as refused, never skipped. One JSON line per shape, then a table for DESIGN.md.
-    python tools/bench_pfb.py [--windows 7] [--reps 10] [--shapes "M,K,D,L,W;..."]"""
+M may be a power of two or 5 * 2^a (the radix-5 bank: PolyphaseChannelizer.for_plan picks the constructor).
+    python tools/bench_pfb.py [--windows 7] [--reps 10] [--shapes "M,K,D,L,W;..."]
+the 200 kHz LoRaWAN grid at 16 MHz beside its power-of-two neighbours:
+    python tools/bench_pfb.py --shapes "80,80,128,640,16777216;80,64,128,640,16777216;64,64,128,640,16777216;128,128,128,640,16777216"
+"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -36,7 +40,7 @@ for M, K, D, Lt, W in SHAPES:
     wide = torch.view_as_complex(torch.randn((W, 2), generator=g, device="cuda"))
     h = L.design_lowpass(D, Lt)
     bins = np.arange(K) - K // 2
-    pf = L.PolyphaseChannelizer(ctx, M, D, h, bins)
+    pf = L.PolyphaseChannelizer.for_plan(ctx, (M, D, bins), h)
     narrow = torch.empty((K, W // D + 1), dtype=torch.complex64, device="cuda")
     run_p = lambda: pf.run(wide, out=narrow)
     try:
