@@ -844,16 +844,38 @@ int lorahip_pfb_run(lorahip_pfb *p, const float *wide_dev, size_t n_in, float *o
  * writes *n_out = lorahip_psb_out_count(p, n_in) = n_in * interp samples at wide_dev. Asynchronous on the context's stream. Between
  * calls the object keeps the stream position and the transforms u_s[m] of the last ceil(L/U) - 1 input times; a call works through
  * a device workspace of at most 32 MiB that grows on first use.
- * Limits: n_bins a power of two in 8..1024, interp 1..4096, n_taps 1..65536, n_sel 1..65535*8; lorahip_psb_check answers for these
+ * Limits: n_bins a power of two in 8..1024 (lorahip_psb_check / lorahip_psb_create) or 5 * 2^a, a = 0..6 (the _radix5 pair below);
+ * interp 1..4096, n_taps 1..65536, n_sel 1..65535*8; lorahip_psb_check answers for these
  * four without a device (LORAHIP_OK or LORAHIP_E_INVALID); finite gains. Limit of one call (a longer stream is fed in several
  * calls): at most 2^30 outputs (8 GiB); a call is worked off in segments whose launch grids stay far below 2^31 - 1. Anything
  * beyond a limit is refused with LORAHIP_E_INVALID and a lorahip_last_error() text that begins "polyphase synthesiser", consumes
  * nothing and leaves the stream state untouched. Rows, strides and the stream position are addressed with 64 bits.
+ *
+ * Bin counts 5 * 2^a: M = 5, 10, 20, 40, 80, 160, 320 -- the transmit side of the LoRaWAN plans with 125 kHz channels 200 kHz apart,
+ * where interp / n_bins = 8 / 5 (fs = 1 MHz: M = 5, U = 8 ... fs = 64 MHz: M = 320, U = 512). lorahip_psb_check_radix5 and
+ * lorahip_psb_create_radix5 take the arguments of lorahip_psb_check and lorahip_psb_create with the same limits, meanings, refusal
+ * texts ("polyphase synthesiser ...") and untouched state on refusal; they accept these seven bin counts and nothing else (powers of
+ * two are refused here as 5 * 2^a is refused there: the two pairs are disjoint). The handle is a lorahip_psb: run, reset, out_count
+ * and destroy serve it unchanged, with the same 2^30 outputs a call, the same workspace and carried history. One difference in the
+ * definition: for these M, b / M is NOT exact in the direct form's 64-bit phase counter (lorahip_channelizer_phase_inc(b / M) is off
+ * by less than 2^-64 cycle per sample), so the output is defined by the exact phase b (n mod M) / M:
+ *
+ *     y[n] = sum_k g_k exp(+2 pi i b_k (n mod M) / M) sum_{j<L, (n-j) mod U == 0, n-j >= 0} h[j] x_k[(n-j)/U]
+ *
+ * evaluated as the three formulas above (gather X_b[m], inverse M-point DFT u_s[m], fold over i ascending with the taps below L
+ * only). It agrees with a lorahip_synthesizer for freq[k] = bins[k] / M far inside the tolerance both are held to. Chunked calls are
+ * bit-identical to one call, phases without a tap are exact zeros, and a NaN or Inf in x_k[m] makes exactly the outputs
+ * m U .. m U + L - 1 non-finite, as above. The transform is one radix-5 decimation-in-frequency stage (a 5-point DFT over the points
+ * M / 5 apart, constants and twiddles exp(+2 pi i r n / M) from a table computed in double) followed by five radix-2 transforms of
+ * M / 5 points: the receive bank's, with the conjugate tables.
  * ------------------------------------------------------------------------------------- */
 typedef struct lorahip_psb lorahip_psb;
 int lorahip_psb_check(size_t n_bins, size_t interp, size_t n_taps, size_t n_sel);      /* host only */
 int lorahip_psb_create(lorahip_psb **out, lorahip_ctx *ctx, size_t n_bins, const int32_t *bins /* nullable */, size_t n_sel,
                        const float *gain /* nullable */, size_t interp, const float *taps, size_t n_taps);
+int lorahip_psb_check_radix5(size_t n_bins, size_t interp, size_t n_taps, size_t n_sel);   /* host only */
+int lorahip_psb_create_radix5(lorahip_psb **out, lorahip_ctx *ctx, size_t n_bins, const int32_t *bins /* nullable */, size_t n_sel,
+                              const float *gain /* nullable */, size_t interp, const float *taps, size_t n_taps);
 void lorahip_psb_destroy(lorahip_psb *p);
 int lorahip_psb_reset(lorahip_psb *p);
 size_t lorahip_psb_out_count(const lorahip_psb *p, size_t n_in);                       /* n_in * interp; 0 for NULL */

@@ -186,6 +186,8 @@ SIGNATURES = {
     "lorahip_pfb_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "lorahip_psb_check": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
     "lorahip_psb_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "lorahip_psb_check_radix5": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
+    "lorahip_psb_create_radix5": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "lorahip_psb_destroy": (None, [C.c_void_p]),
     "lorahip_psb_reset": (C.c_int, [C.c_void_p]),
     "lorahip_psb_out_count": (C.c_size_t, [C.c_void_p, C.c_size_t]),

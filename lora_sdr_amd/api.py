@@ -517,9 +517,10 @@ RADIX5_BINS = (5, 10, 20, 40, 80, 160, 320)
 
 
 def uniform_plan(sample_rate_hz, centre_hz, channel_hz, spacing_hz=200e3, bandwidth_hz=125e3):
-    """(n_bins, decim, bins) of a uniform channel plan for PolyphaseChannelizer.for_plan: channels bandwidth_hz wide on a grid of
-    spacing_hz round centre_hz, received at sample_rate_hz. n_bins = fs / spacing, decim = fs / bandwidth (the demodulator takes its
-    input at exactly the bandwidth), bins[i] = (channel_hz[i] - centre_hz) / spacing. Host only. ValueError, with the reason, when
+    """(n_bins, decim, bins) of a uniform channel plan for PolyphaseChannelizer.for_plan and PolyphaseSynthesizer.for_plan (interp =
+    decim): channels bandwidth_hz wide on a grid of spacing_hz round centre_hz, received or generated at sample_rate_hz. n_bins =
+    fs / spacing, decim = fs / bandwidth (the demodulator takes its input, and the modulator gives its output, at exactly the
+    bandwidth), bins[i] = (channel_hz[i] - centre_hz) / spacing. Host only. ValueError, with the reason, when
     one of the three is no integer (to 1e-9 relative), n_bins is neither a power of two 8..1024 nor 5 * 2^a (a = 0..6), decim is
     outside 1..4096, or a channel lies outside the band (|bin| > n_bins / 2)."""
     fs, spacing, bw = float(sample_rate_hz), float(spacing_hz), float(bandwidth_hz)
@@ -685,14 +686,19 @@ class Synthesizer:
 
 class PolyphaseSynthesizer:
     """The synthesiser for a uniform channel plan: row k goes to centre bins[k] / n_bins cycles per OUTPUT sample (n_bins a power of
-    two, 8..1024; any integers, taken modulo n_bins; negative = the lower half of the band; rows that share a bin are summed; None: all
-    n_bins bins in order), scaled by gains (None: all 1). One inverse n_bins-point FFT per input time and one fold per output serve
-    every row, so the cost does not grow with the number of channels as Synthesizer's does, and interp may be 1..4096. The output is
-    by definition Synthesizer(ctx, bins / n_bins, interp, taps, gains)'s; .freqs is the array a Synthesizer, a Channelizer or a
-    PolyphaseChannelizer's plan takes. Stateful like Synthesizer: consecutive run() calls continue one stream, bit-identical to one
-    call; reset() starts a new one. See include/lorahip.h."""
+    two, 8..1024; 5 * 2^a, a = 0..6, the 200 kHz LoRaWAN grids, through PolyphaseSynthesizer.radix5 or .for_plan; bins any integers,
+    taken modulo n_bins; negative = the lower half of the band; rows that share a bin are summed; None: all n_bins bins in order),
+    scaled by gains (None: all 1). One inverse n_bins-point FFT per input time and one fold per output serve every row, so the cost
+    does not grow with the number of channels as Synthesizer's does, and interp may be 1..4096. The output is by definition
+    Synthesizer(ctx, bins / n_bins, interp, taps, gains)'s (with the exact phase bins (n mod n_bins) / n_bins where n_bins is no power
+    of two); .freqs is the array a Synthesizer, a Channelizer or a PolyphaseChannelizer's plan takes. Stateful like Synthesizer:
+    consecutive run() calls continue one stream, bit-identical to one call; reset() starts a new one. See include/lorahip.h."""
 
     def __init__(self, ctx, n_bins, interp, taps, bins=None, gains=None):
+        self._build("lorahip_psb_create", ctx, n_bins, interp, taps, bins, gains)
+
+    def _build(self, create, ctx, n_bins, interp, taps, bins, gains):
+        """create the handle through the C entry point `create` and set the attributes"""
         self._lib = load()
         self._ctx = ctx                                                  # borrowed: device and stream
         self._h = C.c_void_p()
@@ -707,12 +713,27 @@ class PolyphaseSynthesizer:
         g = None if gains is None else np.ascontiguousarray(gains, np.float32).reshape(-1)
         if g is not None and g.size != b.size:
             raise ValueError("one gain per channel")
-        check(self._lib.lorahip_psb_create(C.byref(self._h), ctx._h, int(n_bins), None if bins is None else b.ctypes.data,
-                                           int(n_bins) if bins is None else b.size, None if g is None else g.ctypes.data,
-                                           int(interp), t.ctypes.data, t.size), "lorahip_psb_create")
+        check(getattr(self._lib, create)(C.byref(self._h), ctx._h, int(n_bins), None if bins is None else b.ctypes.data,
+                                         int(n_bins) if bins is None else b.size, None if g is None else g.ctypes.data,
+                                         int(interp), t.ctypes.data, t.size), create)
         self.n_bins, self.interp, self.n_taps, self.n_channels = int(n_bins), int(interp), int(t.size), int(b.size)
         self.bins = b
         self.freqs = b.astype(np.float64) / float(self.n_bins)
+
+    @classmethod
+    def radix5(cls, ctx, n_bins, interp, taps, bins=None, gains=None):
+        """the same object on n_bins = 5 * 2^a bins (5, 10, 20, 40, 80, 160, 320; lorahip_psb_create_radix5): channels 200 kHz apart
+        and 125 kHz wide have interp / n_bins = 8 / 5. The constructor takes the powers of two only, this the seven counts only."""
+        self = cls.__new__(cls)
+        self._build("lorahip_psb_create_radix5", ctx, n_bins, interp, taps, bins, gains)
+        return self
+
+    @classmethod
+    def for_plan(cls, ctx, plan, taps, gains=None):
+        """the object for plan = (n_bins, decim, bins) as uniform_plan returns it, interp = decim: the constructor or radix5, by n_bins"""
+        n_bins, decim, bins = plan
+        make = cls.radix5 if int(n_bins) in RADIX5_BINS else cls
+        return make(ctx, n_bins, decim, taps, bins, gains)
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:

@@ -1,7 +1,8 @@
 // Polyphase synthesis filter bank: the transmit front end for a UNIFORM channel plan -- K channel streams onto the grid fs/M, M a power
-// of two (include/lorahip.h has the definition; DESIGN.md section 8d the shape and the measurements). The mirror image of
-// lorahip_pfb.hip. The output is, by definition, what the direct-form synthesiser (lorahip_synth.hip) defines for freq[k] = bins[k] / M:
-// that frequency is exact in the 64-bit phase counter, so the mixer phase of output n is exp(+2 pi i b (n mod M) / M) and the K mixers
+// of two 8..1024 or 5 * 2^a, a = 0..6 (include/lorahip.h has the definition; DESIGN.md section 8d the shape and the measurements). The
+// mirror image of lorahip_pfb.hip. The output is, by definition, what the direct-form synthesiser (lorahip_synth.hip) defines for
+// freq[k] = bins[k] / M with the exact phase (for a power of two that frequency is exact in the 64-bit phase counter; for 5 * 2^a it is
+// not, and the formulas below are the definition): the mixer phase of output n is exp(+2 pi i b (n mod M) / M) and the K mixers
 // collapse into one inverse M-point DFT per INPUT time:
 //
 //     X_b[m] = sum_{k : b_k mod M == b} g_k x_k[m]
@@ -13,7 +14,8 @@
 //
 // A call is cut into segments of input times whose transforms fit a workspace of PSB_WS_POINTS samples (small enough to stay in the
 // last-level cache between the two launches of a segment):
-//   * psbTransform: one workgroup = T consecutive input times (T = 4096 / M, 8 at least and 256 at most). Gather: lane = time (a row's
+//   * psbTransform: one workgroup = T consecutive input times (T = the largest power of two with T M <= 4096, 8 at least and 256 at
+//     most). Gather: lane = time (a row's
 //     run of a tile is contiguous), the rows of a bin are summed in ascending k with one fused multiply-add per component, the gain
 //     applied there; a bin without a row is 0. Then T transforms of M points in place in the LDS -- the pass structure of the receive
 //     bank (lorahip_pfbfft.h) with conjugated twiddles from a host table computed in double. The result stands in bit-reversed order
@@ -26,8 +28,11 @@
 //     recomputed) in one of two small buffers. Before the start of the stream they are zeros.
 // Every u_s[m] depends on the inputs of time m alone and every sum has one fixed order, so an output does not depend on how the
 // stream was cut into calls or segments. The phase is the stream position modulo M -- integer arithmetic, no drift.
+// M = 5 * 2^a (psb5Transform, psb5Fold, psb5History, beside the power-of-two kernels, which are as they were): the transform is
+// lorahip_pfbfft5.h with the conjugate tables -- one radix-5 stage, then five radix-2 transforms of N = M / 5 points, residue 5 k + r
+// left at r N + bitrev(k) --, and the divisions and remainders by M are by a compile-time constant instead of shifts and masks.
 #include "lorahip_own.h"
-#include "lorahip_pfbfft.h"
+#include "lorahip_pfbfft5.h"
 #include <cmath>
 #include <new>
 #include <vector>
@@ -36,10 +41,11 @@ struct lorahip_psb
 {
     lorahip_ctx *ctx;
     int M, logM, U, L, I, HC, K, T, logT;
+    bool radix5;                                // M = 5 * 2^a: the psb5 kernels
     size_t seg;                                 // input times per segment at most
     size_t ldsBytes;
     lorahip::DevBuf<float> dTaps;               // [L] h[j]
-    lorahip::DevBuf<float2> dTw;                // [M/2] exp(+2 pi i k / M)
+    lorahip::DevBuf<float2> dTw;                // [psbTwiddles] exp(+2 pi i k / M), k < M / 2; 5 * 2^a: the same for M / 5, then exp(+2 pi i n / M), n < M
     lorahip::DevBuf<int> dBinStart;             // [M + 1] the rows of bin b are dBinRow[dBinStart[b] .. dBinStart[b + 1]), ascending
     lorahip::DevBuf<int> dBinRow;               // [K]
     lorahip::DevBuf<float> dBinGain;            // [K] the gain of that row
@@ -52,6 +58,7 @@ struct lorahip_psb
 namespace lorahip {
 
 constexpr int PSB_LOGM_MIN = 3, PSB_LOGM_MAX = 10;
+constexpr int PSB5_A_MAX = 6;                           // M = 5 * 2^a, a = 0 .. 6
 constexpr int PSB_FOLD_THREADS = 256;
 constexpr size_t PSB_WS_POINTS = size_t(1) << 22;       // 32 MiB of transforms per segment
 constexpr size_t PSB_SEG_OUTPUTS = size_t(1) << 30;     // the outputs of a segment are indexed with 32 bits
@@ -184,10 +191,121 @@ static hipError_t psbLaunch(const lorahip_psb *p, const PsbArgs &a, float2 *newH
     return e;
 }
 
-//! nullptr when the shape is one this file handles, the reason otherwise
-static const char *psbProblem(const size_t nBins, const size_t interp, const size_t nTaps, const size_t nSel)
+// ---- M = 5 * 2^A ----
+
+template <int A>
+__global__ __launch_bounds__(PFB_THREADS) void psb5Transform(const PsbArgs a)
 {
-    if (nBins < (size_t(1) << PSB_LOGM_MIN) || nBins > (size_t(1) << PSB_LOGM_MAX) || (nBins & (nBins - 1)))
+    extern __shared__ float2 psbLds[];
+    constexpr int N = 1 << A, M = 5 * N;
+    const int tid = threadIdx.x;
+    const int T = a.T;
+    float2 *v = psbLds;                             // [T][M + 1]
+    float2 *tw = v + T * (M + 1);                   // [N / 2] exp(+2 pi i k / N)
+    float2 *w5 = tw + N / 2;                        // [M] exp(+2 pi i n / M)
+    const int c0 = int(blockIdx.x) << a.logT;       // the tile's first input time in the segment
+
+    for (int k = tid; k < N / 2 + M; k += PFB_THREADS) tw[k] = a.tw[k];
+
+    // gather: lane = input time
+    for (int item = tid; item < T * M; item += PFB_THREADS)
+    {
+        const int t = item & (T - 1), b = item >> a.logT;
+        float re = 0.0f, im = 0.0f;
+        if (c0 + t < a.cnt)
+        {
+            const float2 *col = a.in + (c0 + t);
+            const int e1 = a.binStart[b + 1];
+            for (int e = a.binStart[b]; e < e1; e++)
+            {
+                const float2 x = col[(long long)a.binRow[e] * a.inStride];
+                const float g = a.binGain[e];
+                re = __builtin_fmaf(g, x.x, re);
+                im = __builtin_fmaf(g, x.y, im);
+            }
+        }
+        v[t * (M + 1) + b] = make_float2(re, im);
+    }
+    __syncthreads();
+
+    pfbFft5<A>(v, tw, w5, T, tid);
+
+    // store: lane = residue s = 5 k + r, which stands at r N + bitrev(k) of its row (M = 5: no radix-2 stage, k = 0)
+    for (int item = tid; item < T * M; item += PFB_THREADS)
+    {
+        const int t = int(unsigned(item) / unsigned(M)), s = item - t * M;
+        const int k = int(unsigned(s) / 5u), r = s - 5 * k;
+        int at = r * N;
+        if constexpr (A > 0) at += int(__brev(unsigned(k)) >> (32 - A));
+        if (c0 + t < a.cnt) a.ws[(long long)(c0 + t) * M + s] = v[t * (M + 1) + at];
+    }
+}
+
+template <int M>
+__global__ __launch_bounds__(PSB_FOLD_THREADS) void psb5Fold(const PsbArgs a)
+{
+    const unsigned U = unsigned(a.U);
+    const unsigned long long o64 = (unsigned long long)blockIdx.x * PSB_FOLD_THREADS + threadIdx.x;
+    if (o64 >= (unsigned long long)a.cnt * U) return;
+    const unsigned o = unsigned(o64);               // < 2^31
+    const unsigned c = o / U, p = o - c * U;        // input time in the segment, output phase
+    const unsigned m0 = unsigned((unsigned long long)a.m0 % unsigned(M));      // the same in every lane
+    const int s = int((((m0 + c) % unsigned(M)) * U + p) % unsigned(M));       // (m U + p) mod M; 319 * 4096 + 4095 fits
+    const int rounds = int(p) < a.L ? (a.L - int(p) + int(U) - 1) / int(U) : 0;    // taps p, p + U, ... < L
+    const float *hp = a.taps + p;
+    float re = 0.0f, im = 0.0f;
+#pragma unroll 4
+    for (int i = 0; i < rounds; i++)
+    {
+        const float2 u = psbU<M>(a, int(c) - i, s);
+        const float h = hp[(long long)i * U];
+        re = __builtin_fmaf(h, u.x, re);
+        im = __builtin_fmaf(h, u.y, im);
+    }
+    a.out[o] = make_float2(re, im);
+}
+
+//! the transforms of the HC input times that precede the next segment
+template <int M>
+__global__ void psb5History(const PsbArgs a, float2 *newHist)
+{
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long long)a.HC * M) return;
+    const int h = int(unsigned(idx) / unsigned(M)), s = int(unsigned(idx)) - h * M;    // HC M < 2^25
+    newHist[idx] = psbU<M>(a, a.cnt - a.HC + h, s);         // >= -HC
+}
+
+template <int A>
+static hipError_t psb5Launch(const lorahip_psb *p, const PsbArgs &a, float2 *newHist)
+{
+    constexpr int M = 5 << A;
+    hipStream_t st = p->ctx->stream;
+    const unsigned tiles = unsigned((a.cnt + a.T - 1) >> a.logT);
+    hipLaunchKernelGGL((psb5Transform<A>), dim3(tiles), dim3(PFB_THREADS), p->ldsBytes, st, a);     // at most 22 616 bytes of LDS
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const unsigned long long nOut = (unsigned long long)a.cnt * (unsigned long long)a.U;        // <= 2^30
+    hipLaunchKernelGGL((psb5Fold<M>), dim3(unsigned((nOut + PSB_FOLD_THREADS - 1) / PSB_FOLD_THREADS)), dim3(PSB_FOLD_THREADS), 0, st, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (a.HC)
+    {
+        const unsigned long long n = (unsigned long long)a.HC * M;                              // < 2^25
+        hipLaunchKernelGGL((psb5History<M>), dim3(unsigned((n + 255) / 256)), dim3(256), 0, st, a, newHist);
+        e = hipGetLastError();
+    }
+    return e;
+}
+
+//! nullptr when the shape is one this file handles, the reason otherwise
+static const char *psbProblem(const bool radix5, const size_t nBins, const size_t interp, const size_t nTaps, const size_t nSel)
+{
+    if (radix5)
+    {
+        const size_t n = nBins / 5;
+        if (nBins % 5 || n == 0 || n > (size_t(1) << PSB5_A_MAX) || (n & (n - 1)))
+            return "polyphase synthesiser: n_bins of the radix-5 bank must be 5 * 2^a, a = 0..6 (5, 10, 20, 40, 80, 160 or 320)";
+    }
+    else if (nBins < (size_t(1) << PSB_LOGM_MIN) || nBins > (size_t(1) << PSB_LOGM_MAX) || (nBins & (nBins - 1)))
         return "polyphase synthesiser: n_bins must be a power of two in 8..1024";
     if (interp == 0 || interp > 4096) return "polyphase synthesiser: interp must be 1..4096";
     if (nTaps == 0 || nTaps > (size_t(1) << 16)) return "polyphase synthesiser: n_taps must be 1..65536";
@@ -226,7 +344,18 @@ static int psbRun(lorahip_psb *p, const float2 *in, const size_t inStride, const
         a.out = out + done * U;
         hipError_t e = hipErrorInvalidValue;
         float2 *newHist = p->dHist[p->cur ^ 1].get();
-        switch (p->logM)
+        if (p->radix5)
+            switch (p->M)
+            {
+                case 5: e = psb5Launch<0>(p, a, newHist); break;
+                case 10: e = psb5Launch<1>(p, a, newHist); break;
+                case 20: e = psb5Launch<2>(p, a, newHist); break;
+                case 40: e = psb5Launch<3>(p, a, newHist); break;
+                case 80: e = psb5Launch<4>(p, a, newHist); break;
+                case 160: e = psb5Launch<5>(p, a, newHist); break;
+                case 320: e = psb5Launch<6>(p, a, newHist); break;
+            }
+        else switch (p->logM)
         {
             case 3: e = psbLaunch<3>(p, a, newHist); break;
             case 4: e = psbLaunch<4>(p, a, newHist); break;
@@ -246,27 +375,22 @@ static int psbRun(lorahip_psb *p, const float2 *in, const size_t inStride, const
     return LORAHIP_OK;
 }
 
-} // namespace lorahip
-
-using namespace lorahip;
-
-extern "C" {
-
-int lorahip_psb_check(const size_t n_bins, const size_t interp, const size_t n_taps, const size_t n_sel)
+static int psbCheck(const bool radix5, const size_t n_bins, const size_t interp, const size_t n_taps, const size_t n_sel)
 {
-    const char *why = psbProblem(n_bins, interp, n_taps, n_sel);
+    const char *why = psbProblem(radix5, n_bins, interp, n_taps, n_sel);
     if (why == nullptr) return LORAHIP_OK;
     setLastError(why);
     return LORAHIP_E_INVALID;
 }
 
-int lorahip_psb_create(lorahip_psb **out, lorahip_ctx *ctx, const size_t n_bins, const int32_t *bins, const size_t n_sel, const float *gain,
-                       const size_t interp, const float *taps, const size_t n_taps)
+//! lorahip_psb_create (power-of-two bin counts) and lorahip_psb_create_radix5 (5 * 2^a): the same object
+static int psbCreate(const bool radix5, lorahip_psb **out, lorahip_ctx *ctx, const size_t n_bins, const int32_t *bins, const size_t n_sel,
+                     const float *gain, const size_t interp, const float *taps, const size_t n_taps)
 {
     if (out == nullptr) return LORAHIP_E_INVALID;
     *out = nullptr;
     if (ctx == nullptr || taps == nullptr) { setLastError("polyphase synthesiser: no context or no taps"); return LORAHIP_E_INVALID; }
-    if (lorahip_psb_check(n_bins, interp, n_taps, n_sel) != LORAHIP_OK) return LORAHIP_E_INVALID;
+    if (psbCheck(radix5, n_bins, interp, n_taps, n_sel) != LORAHIP_OK) return LORAHIP_E_INVALID;
     if (bins == nullptr && n_sel != n_bins) { setLastError("polyphase synthesiser: without a bin list n_sel must be n_bins"); return LORAHIP_E_INVALID; }
     if (gain)
         for (size_t k = 0; k < n_sel; k++)
@@ -275,14 +399,18 @@ int lorahip_psb_create(lorahip_psb **out, lorahip_ctx *ctx, const size_t n_bins,
     lorahip_psb *p = new (std::nothrow) lorahip_psb();
     if (p == nullptr) return LORAHIP_E_NOMEM;
     const int M = int(n_bins);
+    const int N = radix5 ? M / 5 : M;           // the radix-2 part of M
     int logM = 0;
     while ((1 << logM) < M) logM++;
-    p->ctx = ctx; p->M = M; p->logM = logM; p->U = int(interp); p->L = int(n_taps); p->K = int(n_sel);
+    p->ctx = ctx; p->M = M; p->logM = logM; p->radix5 = radix5; p->U = int(interp); p->L = int(n_taps); p->K = int(n_sel);
     p->I = (p->L + p->U - 1) / p->U;
     p->HC = p->I - 1;
-    p->logT = 12 - logM < 3 ? 3 : (12 - logM > 8 ? 8 : 12 - logM);
+    int logT = 0;
+    while ((2 << logT) * M <= 4096) logT++;     // the largest power of two with T M <= 4096 ...
+    p->logT = logT < 3 ? 3 : (logT > 8 ? 8 : logT);     // ... 8 at least, 256 at most
     p->T = 1 << p->logT;
-    p->ldsBytes = (size_t(p->T) * size_t(M + 1) + size_t(M / 2)) * sizeof(float2);
+    const size_t nTw = size_t(N / 2) + (radix5 ? size_t(M) : 0);
+    p->ldsBytes = (size_t(p->T) * size_t(M + 1) + nTw) * sizeof(float2);
     const size_t byWs = PSB_WS_POINTS / size_t(M), byOut = PSB_SEG_OUTPUTS / interp;
     p->seg = byWs < byOut ? byWs : byOut;
     p->cur = 0; p->n0 = 0;
@@ -292,17 +420,20 @@ int lorahip_psb_create(lorahip_psb **out, lorahip_ctx *ctx, const size_t n_bins,
     std::vector<float> g;
     try
     {
-        tw.resize(size_t(M / 2));
+        tw.reserve(nTw);
         start.assign(size_t(M) + 1, 0);
         row.resize(n_sel);
         g.resize(n_sel);
     }
     catch (const std::bad_alloc &) { delete p; return LORAHIP_E_NOMEM; }
-    for (int k = 0; k < M / 2; k++)
+    const auto root = [&tw](const int k, const int P)       // exp(+2 pi i k / P)
     {
-        const double ang = 2.0 * M_PI * double(k) / double(M);
-        tw[size_t(k)] = make_float2(float(std::cos(ang)), float(std::sin(ang)));
-    }
+        const double ang = 2.0 * M_PI * double(k) / double(P);
+        tw.push_back(make_float2(float(std::cos(ang)), float(std::sin(ang))));
+    };
+    for (int k = 0; k < N / 2; k++) root(k, N);
+    if (radix5)
+        for (int n = 0; n < M; n++) root(n, M);
     // the rows of every bin, in ascending k (a counting sort is stable)
     const auto binOf = [&](const size_t k) { return bins ? size_t(((long long)bins[k] % M + M) % M) : k; };
     for (size_t k = 0; k < n_sel; k++) start[binOf(k) + 1]++;
@@ -336,6 +467,34 @@ int lorahip_psb_create(lorahip_psb **out, lorahip_ctx *ctx, const size_t n_bins,
     if (e != hipSuccess) { delete p; return hipFail(e, "polyphase synthesiser table upload"); }
     *out = p;
     return LORAHIP_OK;
+}
+
+} // namespace lorahip
+
+using namespace lorahip;
+
+extern "C" {
+
+int lorahip_psb_check(const size_t n_bins, const size_t interp, const size_t n_taps, const size_t n_sel)
+{
+    return psbCheck(false, n_bins, interp, n_taps, n_sel);
+}
+
+int lorahip_psb_check_radix5(const size_t n_bins, const size_t interp, const size_t n_taps, const size_t n_sel)
+{
+    return psbCheck(true, n_bins, interp, n_taps, n_sel);
+}
+
+int lorahip_psb_create(lorahip_psb **out, lorahip_ctx *ctx, const size_t n_bins, const int32_t *bins, const size_t n_sel, const float *gain,
+                       const size_t interp, const float *taps, const size_t n_taps)
+{
+    return psbCreate(false, out, ctx, n_bins, bins, n_sel, gain, interp, taps, n_taps);
+}
+
+int lorahip_psb_create_radix5(lorahip_psb **out, lorahip_ctx *ctx, const size_t n_bins, const int32_t *bins, const size_t n_sel,
+                              const float *gain, const size_t interp, const float *taps, const size_t n_taps)
+{
+    return psbCreate(true, out, ctx, n_bins, bins, n_sel, gain, interp, taps, n_taps);
 }
 
 void lorahip_psb_destroy(lorahip_psb *p)

@@ -1,6 +1,7 @@
 """Polyphase synthesis filter bank beside the direct-form synthesiser: the same plan, the same rows, one process. HIP events on the
 context (lorahip_timer_*), 0.4 s of warm-up per shape, then alternating windows of both; the median window is reported with its
-spread. A shape the direct form refuses is printed as refused, never skipped. One JSON line per shape, then a table for DESIGN.md.
+spread. M is a power of two 8..1024 or 5 * 2^a (5 .. 320). A shape the direct form refuses is printed as refused, never skipped. One
+JSON line per shape, then a table for DESIGN.md.
     python tools/bench_psb.py [--windows 7] [--reps 10] [--shapes "M,K,U,L,W;..."]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -11,7 +12,10 @@ import lora_sdr_amd as L
 COPY_TBPS = 6.29            # the achievable copy rate the project measures against
 # M, K (rows: the first K bins around 0), U, L, wideband samples per call; the last two: 16 rows against all 64 (independence of K)
 SHAPES = [(16, 16, 16, 128, 1 << 24), (64, 64, 64, 512, 1 << 24), (256, 256, 256, 2048, 1 << 24), (1024, 1024, 1024, 8192, 1 << 24),
-          (64, 64, 80, 512, 1 << 24), (512, 512, 256, 2048, 1 << 24), (64, 16, 64, 512, 1 << 24)]
+          (64, 64, 80, 512, 1 << 24), (512, 512, 256, 2048, 1 << 24), (64, 16, 64, 512, 1 << 24),
+          # the 200 kHz LoRaWAN grids (M = 5 * 2^a, U = 8 M / 5, L = 16 U): 1, 8, 16, 32 and 64 MHz
+          (5, 3, 8, 128, 1 << 24), (40, 8, 64, 1024, 1 << 24), (40, 40, 64, 1024, 1 << 24), (80, 64, 128, 2048, 1 << 24),
+          (160, 128, 256, 4096, 1 << 24), (320, 256, 512, 8192, 1 << 24)]
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--windows", type=int, default=7); ap.add_argument("--reps", type=int, default=10)
@@ -38,7 +42,7 @@ for M, K, U, Lt, W in SHAPES:
     rows = torch.view_as_complex(torch.randn((K, n_in, 2), generator=g, device="cuda"))
     h = (L.design_lowpass(U, Lt) * U).astype(np.float32)
     bins = np.arange(K) - K // 2
-    ps = L.PolyphaseSynthesizer(ctx, M, U, h, bins)
+    ps = L.PolyphaseSynthesizer.for_plan(ctx, (M, U, bins), h)     # the constructor or radix5, by M
     wide = torch.empty(W, dtype=torch.complex64, device="cuda")
     run_p = lambda: ps.run(rows, out=wide)
     try:
