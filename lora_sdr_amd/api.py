@@ -547,6 +547,37 @@ def uniform_plan(sample_rate_hz, centre_hz, channel_hz, spacing_hz=200e3, bandwi
     return n_bins, decim, bins.astype(np.int32)
 
 
+def _plan_bins(n_bins, bins):
+    """the int32 bin list of a polyphase bank: `bins`, which must fit 32 bits, or all n_bins bins in order for None"""
+    if bins is None:
+        return np.arange(int(n_bins) if 0 < int(n_bins) <= 1024 else 0, dtype=np.int32)
+    b64 = np.ascontiguousarray(bins, np.int64).reshape(-1)
+    if b64.size and (b64.min() < -2 ** 31 or b64.max() >= 2 ** 31):
+        raise ValueError("bins must fit 32 bits")
+    return b64.astype(np.int32)
+
+
+def _synth_run(obj, run, rows, out):
+    """Synthesizer.run and PolyphaseSynthesizer.run: check rows and out, call the C entry point `run`, return the outputs it wrote"""
+    import torch
+    if (rows.dim() != 2 or rows.dtype != torch.complex64 or rows.shape[0] != obj.n_channels
+            or (rows.numel() and (rows.stride(1) != 1 or (rows.shape[0] > 1 and rows.stride(0) < rows.shape[1])))):
+        raise ValueError("rows must be a (K, n) complex64 device tensor with unit column stride (rows may be a slice of a wider buffer)")
+    n_in = int(rows.shape[1])
+    n_out = obj.out_count(n_in)
+    if out is None:
+        out = torch.empty(n_out, dtype=torch.complex64, device=rows.device)
+    elif out.dim() != 1 or out.dtype != torch.complex64 or out.numel() < n_out or (out.numel() and out.stride(0) != 1):
+        raise ValueError("out must be a 1-D complex64 tensor of >= n * interp samples with unit stride")
+    obj._ctx.use_torch_stream()
+    got = C.c_size_t()
+    # the row stride is the tensor's own: `rows` may be a column slice of a (K, capacity) buffer
+    check(getattr(obj._lib, run)(obj._h, C.c_void_p(rows.data_ptr()) if rows.numel() else None,
+                                 int(rows.stride(0)) if rows.numel() and rows.shape[0] > 1 else n_in, n_in,
+                                 C.c_void_p(out.data_ptr()) if out.numel() else None, C.byref(got)), run)
+    return out[:got.value]
+
+
 class PolyphaseChannelizer:
     """The channeliser for a uniform channel plan: rows on the grid fs / n_bins (n_bins a power of two, 8..1024; 5 * 2^a, a = 0..6,
     the 200 kHz LoRaWAN grids, through PolyphaseChannelizer.radix5 or .for_plan), row i at centre
@@ -565,13 +596,7 @@ class PolyphaseChannelizer:
         self._ctx = ctx                                                  # borrowed: device and stream
         self._h = C.c_void_p()
         t = np.ascontiguousarray(taps, np.float32).reshape(-1)
-        if bins is None:
-            b = np.arange(int(n_bins) if 0 < int(n_bins) <= 1024 else 0, dtype=np.int32)
-        else:
-            b64 = np.ascontiguousarray(bins, np.int64).reshape(-1)
-            if b64.size and (b64.min() < -2 ** 31 or b64.max() >= 2 ** 31):
-                raise ValueError("bins must fit 32 bits")
-            b = b64.astype(np.int32)
+        b = _plan_bins(n_bins, bins)
         check(getattr(self._lib, create)(C.byref(self._h), ctx._h, int(n_bins), None if bins is None else b.ctypes.data,
                                          int(n_bins) if bins is None else b.size, int(decim), t.ctypes.data, t.size), create)
         self.n_bins, self.decim, self.n_taps, self.n_channels = int(n_bins), int(decim), int(t.size), int(b.size)
@@ -664,24 +689,7 @@ class Synthesizer:
     def run(self, rows, out=None):
         """rows: (K, n) complex64 device tensor with unit column stride (the next n samples of every channel; may be the columns
         [a, a + n) of a wider buffer); returns the 1-D complex64 tensor of n * interp wideband samples (written into out if given)"""
-        import torch
-        if (rows.dim() != 2 or rows.dtype != torch.complex64 or rows.shape[0] != self.n_channels
-                or (rows.numel() and (rows.stride(1) != 1 or (rows.shape[0] > 1 and rows.stride(0) < rows.shape[1])))):
-            raise ValueError("rows must be a (K, n) complex64 device tensor with unit column stride (rows may be a slice of a wider buffer)")
-        n_in = int(rows.shape[1])
-        n_out = self.out_count(n_in)
-        if out is None:
-            out = torch.empty(n_out, dtype=torch.complex64, device=rows.device)
-        elif out.dim() != 1 or out.dtype != torch.complex64 or out.numel() < n_out or (out.numel() and out.stride(0) != 1):
-            raise ValueError("out must be a 1-D complex64 tensor of >= n * interp samples with unit stride")
-        self._ctx.use_torch_stream()
-        got = C.c_size_t()
-        # the row stride is the tensor's own: `rows` may be a column slice of a (K, capacity) buffer
-        check(self._lib.lorahip_synthesizer_run(self._h, C.c_void_p(rows.data_ptr()) if rows.numel() else None,
-                                                int(rows.stride(0)) if rows.numel() and rows.shape[0] > 1 else n_in, n_in,
-                                                C.c_void_p(out.data_ptr()) if out.numel() else None, C.byref(got)),
-              "lorahip_synthesizer_run")
-        return out[:got.value]
+        return _synth_run(self, "lorahip_synthesizer_run", rows, out)
 
 
 class PolyphaseSynthesizer:
@@ -703,13 +711,7 @@ class PolyphaseSynthesizer:
         self._ctx = ctx                                                  # borrowed: device and stream
         self._h = C.c_void_p()
         t = np.ascontiguousarray(taps, np.float32).reshape(-1)
-        if bins is None:
-            b = np.arange(int(n_bins) if 0 < int(n_bins) <= 1024 else 0, dtype=np.int32)
-        else:
-            b64 = np.ascontiguousarray(bins, np.int64).reshape(-1)
-            if b64.size and (b64.min() < -2 ** 31 or b64.max() >= 2 ** 31):
-                raise ValueError("bins must fit 32 bits")
-            b = b64.astype(np.int32)
+        b = _plan_bins(n_bins, bins)
         g = None if gains is None else np.ascontiguousarray(gains, np.float32).reshape(-1)
         if g is not None and g.size != b.size:
             raise ValueError("one gain per channel")
@@ -751,24 +753,7 @@ class PolyphaseSynthesizer:
     def run(self, rows, out=None):
         """rows: (K, n) complex64 device tensor with unit column stride (the next n samples of every channel; may be the columns
         [a, a + n) of a wider buffer); returns the 1-D complex64 tensor of n * interp wideband samples (written into out if given)"""
-        import torch
-        if (rows.dim() != 2 or rows.dtype != torch.complex64 or rows.shape[0] != self.n_channels
-                or (rows.numel() and (rows.stride(1) != 1 or (rows.shape[0] > 1 and rows.stride(0) < rows.shape[1])))):
-            raise ValueError("rows must be a (K, n) complex64 device tensor with unit column stride (rows may be a slice of a wider buffer)")
-        n_in = int(rows.shape[1])
-        n_out = self.out_count(n_in)
-        if out is None:
-            out = torch.empty(n_out, dtype=torch.complex64, device=rows.device)
-        elif out.dim() != 1 or out.dtype != torch.complex64 or out.numel() < n_out or (out.numel() and out.stride(0) != 1):
-            raise ValueError("out must be a 1-D complex64 tensor of >= n * interp samples with unit stride")
-        self._ctx.use_torch_stream()
-        got = C.c_size_t()
-        # the row stride is the tensor's own: `rows` may be a column slice of a (K, capacity) buffer
-        check(self._lib.lorahip_psb_run(self._h, C.c_void_p(rows.data_ptr()) if rows.numel() else None,
-                                        int(rows.stride(0)) if rows.numel() and rows.shape[0] > 1 else n_in, n_in,
-                                        C.c_void_p(out.data_ptr()) if out.numel() else None, C.byref(got)),
-              "lorahip_psb_run")
-        return out[:got.value]
+        return _synth_run(self, "lorahip_psb_run", rows, out)
 
 
 class LoRaDetector:

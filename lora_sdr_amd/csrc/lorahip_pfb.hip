@@ -27,9 +27,7 @@
 //     12 banks apart, lanes 16 apart share a bank: two-way).
 // The phase is the stream position modulo M -- integer arithmetic, no drift. M is a template constant: for the power-of-two banks
 // the divisions and remainders by it are shifts and masks, for the others multiplications.
-#include "lorahip_own.h"
-#include "lorahip_pfbfft5.h"
-#include <cmath>
+#include "lorahip_bank.h"
 #include <new>
 
 struct lorahip_pfb
@@ -38,8 +36,8 @@ struct lorahip_pfb
     int M, D, L, Lp, Q, K, T, logT, staged, span, HC;
     size_t ldsBytes;
     lorahip::DevBuf<float> dTaps;               // [Lp] h[j], zeros from L on
-    lorahip::DevBuf<float2> dTw;                // [pfbTwiddles(M)] exp(-2 pi i k / M), k < M / 2; 5 * 2^a: the same for M / 5, then exp(-2 pi i n / M), n < M
-    lorahip::DevBuf<int> dSel;                  // [K] where row i's bin stands after the transform: pfbPlace(M, bins[i] mod M)
+    lorahip::DevBuf<float2> dTw;                // [bankTwiddles(M)] exp(-2 pi i k / M), k < M / 2; 5 * 2^a: the same for M / 5, then exp(-2 pi i n / M), n < M
+    lorahip::DevBuf<int> dSel;                  // [K] where row i's bin stands after the transform: bankPlace(M, bins[i] mod M)
     lorahip::DevBuf<float2> dHist[2];           // the HC samples before n0 (zeros before the start of the stream)
     int cur;
     unsigned long long n0;                      // samples consumed since the last reset
@@ -47,8 +45,6 @@ struct lorahip_pfb
 
 namespace lorahip {
 
-constexpr int PFB_LOGM_MIN = 3, PFB_LOGM_MAX = 10;
-constexpr int PFB5_A_MAX = 6;                   // M = 5 * 2^a, a = 0 .. 6
 constexpr size_t PFB_STAGE_LDS = 80u << 10;     // sums + twiddles + input span up to this: two workgroups a compute unit
 
 struct PfbArgs
@@ -67,23 +63,6 @@ struct PfbArgs
     long long nOut;
     int D, L, Lp, K, T, logT, span;
 };
-
-constexpr bool pfbIsPow2(const int M) { return (M & (M - 1)) == 0; }
-constexpr int pfbLog2(const int n) { return n <= 1 ? 0 : 1 + pfbLog2(n >> 1); }
-//! the radix-2 part of M: M itself, or M / 5
-constexpr int pfbPow2Part(const int M) { return pfbIsPow2(M) ? M : M / 5; }
-//! entries of the twiddle table
-constexpr int pfbTwiddles(const int M) { return pfbIsPow2(M) ? M / 2 : M / 10 + M; }
-
-//! where bin b (0 <= b < M) stands in a row after the transform
-static int pfbPlace(const int M, const int b)
-{
-    const int N = pfbPow2Part(M), logN = pfbLog2(N), fifth = pfbIsPow2(M) ? 1 : 5;
-    const unsigned k = unsigned(b / fifth);
-    unsigned rev = 0;
-    for (int bit = 0; bit < logN; bit++) rev |= ((k >> bit) & 1u) << (logN - 1 - bit);
-    return (b % fifth) * N + int(rev);
-}
 
 //! sample n of the stream (absolute index): from this call's chunk, from the history kept from earlier calls, or 0
 __device__ __forceinline__ float2 pfbSample(const PfbArgs &a, const long long n)
@@ -117,8 +96,8 @@ template <int M, bool STAGED>
 __global__ __launch_bounds__(PFB_THREADS) void pfbChannelize(const PfbArgs a)
 {
     extern __shared__ float2 pfbLds[];
-    constexpr bool POW2 = pfbIsPow2(M);
-    constexpr int LOGN = pfbLog2(pfbPow2Part(M)), TW = pfbTwiddles(M);
+    constexpr bool POW2 = bankIsPow2(M);
+    constexpr int LOGN = bankLog2(bankPow2Part(M)), TW = bankTwiddles(M);
     const int tid = threadIdx.x;
     const int T = a.T, D = a.D, Lp = a.Lp;
     float2 *v = pfbLds;                             // [T][M + 1]
@@ -223,23 +202,6 @@ static hipError_t pfbLaunch(const lorahip_pfb *p, const PfbArgs &a, const unsign
     return hipGetLastError();
 }
 
-//! nullptr when the shape is one this file handles, the reason otherwise
-static const char *pfbProblem(const bool radix5, const size_t nBins, const size_t decim, const size_t nTaps, const size_t nSel)
-{
-    if (radix5)
-    {
-        const size_t n = nBins / 5;
-        if (nBins % 5 || n == 0 || n > (size_t(1) << PFB5_A_MAX) || (n & (n - 1)))
-            return "polyphase channeliser: n_bins of the radix-5 bank must be 5 * 2^a, a = 0..6 (5, 10, 20, 40, 80, 160 or 320)";
-    }
-    else if (nBins < (size_t(1) << PFB_LOGM_MIN) || nBins > (size_t(1) << PFB_LOGM_MAX) || (nBins & (nBins - 1)))
-        return "polyphase channeliser: n_bins must be a power of two in 8..1024";
-    if (decim == 0 || decim > 4096) return "polyphase channeliser: decim must be 1..4096";
-    if (nTaps == 0 || nTaps > (size_t(1) << 16)) return "polyphase channeliser: n_taps must be 1..65536";
-    if (nSel == 0 || nSel > size_t(65535) * 8) return "polyphase channeliser: n_sel must be 1..524280";
-    return nullptr;
-}
-
 static int pfbRun(lorahip_pfb *p, const float2 *wide, const size_t nIn, float2 *out, const size_t outStride, size_t *nOutP)
 {
     lorahip_ctx *ctx = p->ctx;
@@ -263,25 +225,7 @@ static int pfbRun(lorahip_pfb *p, const float2 *wide, const size_t nIn, float2 *
     a.D = p->D; a.L = p->L; a.Lp = p->Lp; a.K = p->K; a.T = p->T; a.logT = p->logT; a.span = p->span;
     if (nOut)
     {
-        hipError_t e = hipErrorInvalidValue;
-        switch (p->M)
-        {
-            case 8: e = pfbLaunch<8>(p, a, unsigned(nTiles)); break;
-            case 16: e = pfbLaunch<16>(p, a, unsigned(nTiles)); break;
-            case 32: e = pfbLaunch<32>(p, a, unsigned(nTiles)); break;
-            case 64: e = pfbLaunch<64>(p, a, unsigned(nTiles)); break;
-            case 128: e = pfbLaunch<128>(p, a, unsigned(nTiles)); break;
-            case 256: e = pfbLaunch<256>(p, a, unsigned(nTiles)); break;
-            case 512: e = pfbLaunch<512>(p, a, unsigned(nTiles)); break;
-            case 1024: e = pfbLaunch<1024>(p, a, unsigned(nTiles)); break;
-            case 5: e = pfbLaunch<5>(p, a, unsigned(nTiles)); break;
-            case 10: e = pfbLaunch<10>(p, a, unsigned(nTiles)); break;
-            case 20: e = pfbLaunch<20>(p, a, unsigned(nTiles)); break;
-            case 40: e = pfbLaunch<40>(p, a, unsigned(nTiles)); break;
-            case 80: e = pfbLaunch<80>(p, a, unsigned(nTiles)); break;
-            case 160: e = pfbLaunch<160>(p, a, unsigned(nTiles)); break;
-            case 320: e = pfbLaunch<320>(p, a, unsigned(nTiles)); break;
-        }
+        const hipError_t e = bankDispatch(p->M, BankCounts(), [&](const auto m) { return pfbLaunch<decltype(m)::value>(p, a, unsigned(nTiles)); });
         LORAHIP_TRY(e);
     }
     hipLaunchKernelGGL(pfbHistory, dim3((p->HC + 255) / 256), dim3(256), 0, ctx->stream, a, p->dHist[p->cur ^ 1].get());
@@ -293,10 +237,7 @@ static int pfbRun(lorahip_pfb *p, const float2 *wide, const size_t nIn, float2 *
 
 static int pfbCheck(const bool radix5, const size_t n_bins, const size_t decim, const size_t n_taps, const size_t n_sel)
 {
-    const char *why = pfbProblem(radix5, n_bins, decim, n_taps, n_sel);
-    if (why == nullptr) return LORAHIP_OK;
-    setLastError(why);
-    return LORAHIP_E_INVALID;
+    return bankCheck("polyphase channeliser", "decim", radix5, n_bins, decim, n_taps, n_sel);
 }
 
 //! lorahip_pfb_create (power-of-two bin counts) and lorahip_pfb_create_radix5 (5 * 2^a): the same object
@@ -315,10 +256,9 @@ static int pfbCreate(const bool radix5, lorahip_pfb **out, lorahip_ctx *ctx, con
     p->ctx = ctx; p->M = M; p->D = int(decim); p->L = int(n_taps); p->K = int(n_sel);
     p->Q = (p->L + M - 1) / M; p->Lp = p->Q * M;
     p->HC = p->Lp - 1;
-    const int logT = pfbLog2(4096 / M);         // the largest power of two with T M <= 4096 ...
-    p->logT = logT < 4 ? 4 : (logT > 8 ? 8 : logT);     // ... 16 at least, 256 at most
+    p->logT = bankLogT(M, 4);                   // T = 16 at least
     p->T = 1 << p->logT;
-    const size_t fixedLds = (size_t(p->T) * size_t(M + 1) + size_t(pfbTwiddles(M))) * sizeof(float2);
+    const size_t fixedLds = (size_t(p->T) * size_t(M + 1) + size_t(bankTwiddles(M))) * sizeof(float2);
     const size_t span = size_t(p->T - 1) * size_t(p->D) + size_t(p->Lp);
     p->span = int(span);                        // < 2^21
     p->staged = fixedLds + span * sizeof(float2) <= PFB_STAGE_LDS;
@@ -327,19 +267,9 @@ static int pfbCreate(const bool radix5, lorahip_pfb **out, lorahip_ctx *ctx, con
 
     std::vector<float> h(size_t(p->Lp), 0.0f);
     for (size_t j = 0; j < n_taps; j++) h[j] = taps[j];
-    std::vector<float2> tw;
-    tw.reserve(size_t(pfbTwiddles(M)));
-    const auto root = [&tw](const int k, const int P)      // exp(-2 pi i k / P)
-    {
-        const double ang = 2.0 * M_PI * double(k) / double(P);
-        tw.push_back(make_float2(float(std::cos(ang)), float(-std::sin(ang))));
-    };
-    const int N = pfbPow2Part(M);
-    for (int k = 0; k < N / 2; k++) root(k, N);
-    if (radix5)
-        for (int n = 0; n < M; n++) root(n, M);
+    const std::vector<float2> tw = bankTwiddleTable(M, false);
     std::vector<int> sel(n_sel);
-    for (size_t i = 0; i < n_sel; i++) sel[i] = pfbPlace(M, bins ? int(((long long)bins[i] % M + M) % M) : int(i));
+    for (size_t i = 0; i < n_sel; i++) sel[i] = bankPlace(M, bins ? bankBin(M, bins[i]) : int(i));
     const DeviceGuard guard(ctx->device);
     const size_t histBytes = size_t(p->HC) * sizeof(float2);
     hipError_t e = p->dTaps.grow(h.size() * sizeof(float));

@@ -1,7 +1,7 @@
 // The radix-2 transform the two polyphase banks share: lorahip_pfb.hip runs it forward (twiddles exp(-2 pi i k / M)) and
-// lorahip_psb.hip inverse (the conjugate table). T rows of M points, M + 1 samples apart, in place in the LDS; the result is left in
-// bit-reversed order. With SUBS > 1 a row of STRIDE samples holds SUBS independent sub-rows of M points side by side, each
-// transformed on its own (the 5 * 2^a banks of lorahip_pfbfft5.h); the defaults are the power-of-two banks' layout.
+// lorahip_psb.hip inverse (the conjugate table; lorahip_bank.h builds both). T rows of M points, M + 1 samples apart, in place in the
+// LDS; the result is left in bit-reversed order. With SUBS > 1 a row of STRIDE samples holds SUBS independent sub-rows of M points
+// side by side, each transformed on its own (the 5 * 2^a banks of lorahip_pfbfft5.h); the defaults are the power-of-two banks' layout.
 #pragma once
 #include <hip/hip_runtime.h>
 

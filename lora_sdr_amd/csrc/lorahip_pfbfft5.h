@@ -1,6 +1,7 @@
-// The transform of the polyphase channeliser's 5 * 2^a banks (lorahip_pfb.hip): M = 5 N points, N = 2^a, a = 0..6, T rows M + 1
-// samples apart, in place in the LDS. One radix-5 decimation-in-frequency stage, then five independent radix-2 transforms of N points
-// (lorahip_pfbfft.h with five sub-rows a row):
+// The transform of the two polyphase banks on 5 * 2^a bins (lorahip_pfb.hip forward, lorahip_psb.hip inverse: the same code with the
+// conjugate tables; lorahip_bank.h builds both): M = 5 N points, N = 2^a, a = 0..6, T rows M + 1 samples apart, in place in the LDS.
+// One radix-5 decimation-in-frequency stage, then five independent radix-2 transforms of N points (lorahip_pfbfft.h with five
+// sub-rows a row):
 //
 //     X[5 k + r] = sum_{n<N} ( W_M^(r n) sum_{q<5} x[n + N q] W_5^(r q) ) W_N^(k n)            W_P = exp(-2 pi i / P)
 //

@@ -28,24 +28,20 @@
 //     recomputed) in one of two small buffers. Before the start of the stream they are zeros.
 // Every u_s[m] depends on the inputs of time m alone and every sum has one fixed order, so an output does not depend on how the
 // stream was cut into calls or segments. The phase is the stream position modulo M -- integer arithmetic, no drift.
-// M = 5 * 2^a (psb5Transform, psb5Fold, psb5History, beside the power-of-two kernels, which are as they were): the transform is
-// lorahip_pfbfft5.h with the conjugate tables -- one radix-5 stage, then five radix-2 transforms of N = M / 5 points, residue 5 k + r
-// left at r N + bitrev(k) --, and the divisions and remainders by M are by a compile-time constant instead of shifts and masks.
-#include "lorahip_own.h"
-#include "lorahip_pfbfft5.h"
-#include <cmath>
+// The three kernels are templates on M, like the receive bank's. M = 5 * 2^a: the transform is lorahip_pfbfft5.h with the conjugate
+// tables -- one radix-5 stage, then five radix-2 transforms of N = M / 5 points, residue 5 k + r left at r N + bitrev(k) --, and the
+// divisions and remainders by M are by a compile-time constant where the powers of two have shifts and masks.
+#include "lorahip_bank.h"
 #include <new>
-#include <vector>
 
 struct lorahip_psb
 {
     lorahip_ctx *ctx;
-    int M, logM, U, L, I, HC, K, T, logT;
-    bool radix5;                                // M = 5 * 2^a: the psb5 kernels
+    int M, U, L, I, HC, K, T, logT;
     size_t seg;                                 // input times per segment at most
     size_t ldsBytes;
     lorahip::DevBuf<float> dTaps;               // [L] h[j]
-    lorahip::DevBuf<float2> dTw;                // [psbTwiddles] exp(+2 pi i k / M), k < M / 2; 5 * 2^a: the same for M / 5, then exp(+2 pi i n / M), n < M
+    lorahip::DevBuf<float2> dTw;                // [bankTwiddles(M)] exp(+2 pi i k / M), k < M / 2; 5 * 2^a: the same for M / 5, then exp(+2 pi i n / M), n < M
     lorahip::DevBuf<int> dBinStart;             // [M + 1] the rows of bin b are dBinRow[dBinStart[b] .. dBinStart[b + 1]), ascending
     lorahip::DevBuf<int> dBinRow;               // [K]
     lorahip::DevBuf<float> dBinGain;            // [K] the gain of that row
@@ -57,8 +53,6 @@ struct lorahip_psb
 
 namespace lorahip {
 
-constexpr int PSB_LOGM_MIN = 3, PSB_LOGM_MAX = 10;
-constexpr int PSB5_A_MAX = 6;                           // M = 5 * 2^a, a = 0 .. 6
 constexpr int PSB_FOLD_THREADS = 256;
 constexpr size_t PSB_WS_POINTS = size_t(1) << 22;       // 32 MiB of transforms per segment
 constexpr size_t PSB_SEG_OUTPUTS = size_t(1) << 30;     // the outputs of a segment are indexed with 32 bits
@@ -87,18 +81,19 @@ __device__ __forceinline__ float2 psbU(const PsbArgs &a, const int c, const int 
     return *src;
 }
 
-template <int LOGM>
+template <int M>
 __global__ __launch_bounds__(PFB_THREADS) void psbTransform(const PsbArgs a)
 {
     extern __shared__ float2 psbLds[];
-    constexpr int M = 1 << LOGM;
+    constexpr bool POW2 = bankIsPow2(M);
+    constexpr int LOGN = bankLog2(bankPow2Part(M)), TW = bankTwiddles(M);
     const int tid = threadIdx.x;
     const int T = a.T;
     float2 *v = psbLds;                             // [T][M + 1]
-    float2 *tw = v + T * (M + 1);                   // [M / 2]
+    float2 *tw = v + T * (M + 1);                   // [TW]
     const int c0 = int(blockIdx.x) << a.logT;       // the tile's first input time in the segment
 
-    for (int k = tid; k < M / 2; k += PFB_THREADS) tw[k] = a.tw[k];
+    for (int k = tid; k < TW; k += PFB_THREADS) tw[k] = a.tw[k];
 
     // gather: lane = input time
     for (int item = tid; item < T * M; item += PFB_THREADS)
@@ -121,128 +116,20 @@ __global__ __launch_bounds__(PFB_THREADS) void psbTransform(const PsbArgs a)
     }
     __syncthreads();
 
-    pfbFft<LOGM, 0>(v, tw, T, tid);
+    if constexpr (POW2) pfbFft<LOGN, 0>(v, tw, T, tid);
+    else pfbFft5<LOGN>(v, tw, tw + M / 10, T, tid);
 
-    // store: lane = residue s, which stands at the bit-reversed place of its row
-    for (int item = tid; item < T * M; item += PFB_THREADS)
-    {
-        const int s = item & (M - 1), t = item >> LOGM;
-        const int at = int(__brev(unsigned(s)) >> (32 - LOGM));
-        if (c0 + t < a.cnt) a.ws[(long long)(c0 + t) * M + s] = v[t * (M + 1) + at];
-    }
-}
-
-template <int LOGM>
-__global__ __launch_bounds__(PSB_FOLD_THREADS) void psbFold(const PsbArgs a)
-{
-    constexpr int M = 1 << LOGM;
-    const unsigned U = unsigned(a.U);
-    const unsigned long long o64 = (unsigned long long)blockIdx.x * PSB_FOLD_THREADS + threadIdx.x;
-    if (o64 >= (unsigned long long)a.cnt * U) return;
-    const unsigned o = unsigned(o64);               // < 2^31
-    const unsigned c = o / U, p = o - c * U;        // input time in the segment, output phase
-    const int s = int((unsigned((a.m0 + c) & (M - 1)) * U + p) & (M - 1));     // (m U + p) mod M
-    const int rounds = int(p) < a.L ? (a.L - int(p) + int(U) - 1) / int(U) : 0;    // taps p, p + U, ... < L
-    const float *hp = a.taps + p;
-    float re = 0.0f, im = 0.0f;
-#pragma unroll 4
-    for (int i = 0; i < rounds; i++)
-    {
-        const float2 u = psbU<M>(a, int(c) - i, s);
-        const float h = hp[(long long)i * U];
-        re = __builtin_fmaf(h, u.x, re);
-        im = __builtin_fmaf(h, u.y, im);
-    }
-    a.out[o] = make_float2(re, im);
-}
-
-//! the transforms of the HC input times that precede the next segment
-template <int LOGM>
-__global__ void psbHistory(const PsbArgs a, float2 *newHist)
-{
-    constexpr int M = 1 << LOGM;
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long long)a.HC * M) return;
-    const int h = int(idx >> LOGM), s = int(idx & (M - 1));
-    newHist[idx] = psbU<M>(a, a.cnt - a.HC + h, s);         // >= -HC
-}
-
-static unsigned long long gPsbLdsMask[PSB_LOGM_MAX + 1];
-
-template <int LOGM>
-static hipError_t psbLaunch(const lorahip_psb *p, const PsbArgs &a, float2 *newHist)
-{
-    constexpr int M = 1 << LOGM;
-    hipStream_t st = p->ctx->stream;
-    hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(&psbTransform<LOGM>), 160 * 1024, gPsbLdsMask[LOGM]);
-    if (e != hipSuccess) return e;
-    const unsigned tiles = unsigned((a.cnt + a.T - 1) >> a.logT);
-    hipLaunchKernelGGL((psbTransform<LOGM>), dim3(tiles), dim3(PFB_THREADS), p->ldsBytes, st, a);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    const unsigned long long nOut = (unsigned long long)a.cnt * (unsigned long long)a.U;        // <= 2^30
-    hipLaunchKernelGGL((psbFold<LOGM>), dim3(unsigned((nOut + PSB_FOLD_THREADS - 1) / PSB_FOLD_THREADS)), dim3(PSB_FOLD_THREADS), 0, st, a);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (a.HC)
-    {
-        const unsigned long long n = (unsigned long long)a.HC * M;                              // < 2^26
-        hipLaunchKernelGGL((psbHistory<LOGM>), dim3(unsigned((n + 255) / 256)), dim3(256), 0, st, a, newHist);
-        e = hipGetLastError();
-    }
-    return e;
-}
-
-// ---- M = 5 * 2^A ----
-
-template <int A>
-__global__ __launch_bounds__(PFB_THREADS) void psb5Transform(const PsbArgs a)
-{
-    extern __shared__ float2 psbLds[];
-    constexpr int N = 1 << A, M = 5 * N;
-    const int tid = threadIdx.x;
-    const int T = a.T;
-    float2 *v = psbLds;                             // [T][M + 1]
-    float2 *tw = v + T * (M + 1);                   // [N / 2] exp(+2 pi i k / N)
-    float2 *w5 = tw + N / 2;                        // [M] exp(+2 pi i n / M)
-    const int c0 = int(blockIdx.x) << a.logT;       // the tile's first input time in the segment
-
-    for (int k = tid; k < N / 2 + M; k += PFB_THREADS) tw[k] = a.tw[k];
-
-    // gather: lane = input time
-    for (int item = tid; item < T * M; item += PFB_THREADS)
-    {
-        const int t = item & (T - 1), b = item >> a.logT;
-        float re = 0.0f, im = 0.0f;
-        if (c0 + t < a.cnt)
-        {
-            const float2 *col = a.in + (c0 + t);
-            const int e1 = a.binStart[b + 1];
-            for (int e = a.binStart[b]; e < e1; e++)
-            {
-                const float2 x = col[(long long)a.binRow[e] * a.inStride];
-                const float g = a.binGain[e];
-                re = __builtin_fmaf(g, x.x, re);
-                im = __builtin_fmaf(g, x.y, im);
-            }
-        }
-        v[t * (M + 1) + b] = make_float2(re, im);
-    }
-    __syncthreads();
-
-    pfbFft5<A>(v, tw, w5, T, tid);
-
-    // store: lane = residue s = 5 k + r, which stands at r N + bitrev(k) of its row (M = 5: no radix-2 stage, k = 0)
+    // store: lane = residue s, which is put straight from its place in the row
     for (int item = tid; item < T * M; item += PFB_THREADS)
     {
         const int t = int(unsigned(item) / unsigned(M)), s = item - t * M;
-        const int k = int(unsigned(s) / 5u), r = s - 5 * k;
-        int at = r * N;
-        if constexpr (A > 0) at += int(__brev(unsigned(k)) >> (32 - A));
+        const int at = bankPlaceDev<M>(s);
         if (c0 + t < a.cnt) a.ws[(long long)(c0 + t) * M + s] = v[t * (M + 1) + at];
     }
 }
 
 template <int M>
-__global__ __launch_bounds__(PSB_FOLD_THREADS) void psb5Fold(const PsbArgs a)
+__global__ __launch_bounds__(PSB_FOLD_THREADS) void psbFold(const PsbArgs a)
 {
     const unsigned U = unsigned(a.U);
     const unsigned long long o64 = (unsigned long long)blockIdx.x * PSB_FOLD_THREADS + threadIdx.x;
@@ -267,50 +154,36 @@ __global__ __launch_bounds__(PSB_FOLD_THREADS) void psb5Fold(const PsbArgs a)
 
 //! the transforms of the HC input times that precede the next segment
 template <int M>
-__global__ void psb5History(const PsbArgs a, float2 *newHist)
+__global__ void psbHistory(const PsbArgs a, float2 *newHist)
 {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (long long)a.HC * M) return;
-    const int h = int(unsigned(idx) / unsigned(M)), s = int(unsigned(idx)) - h * M;    // HC M < 2^25
+    int h, s;                                       // HC M < 2^26; the powers of two shift all 64 bits, as they always have
+    if constexpr (bankIsPow2(M)) { h = int(idx >> bankLog2(M)); s = int(idx & (M - 1)); }
+    else { h = int(unsigned(idx) / unsigned(M)); s = int(unsigned(idx)) - h * M; }
     newHist[idx] = psbU<M>(a, a.cnt - a.HC + h, s);         // >= -HC
 }
 
-template <int A>
-static hipError_t psb5Launch(const lorahip_psb *p, const PsbArgs &a, float2 *newHist)
+template <int M>
+static hipError_t psbLaunch(const lorahip_psb *p, const PsbArgs &a, float2 *newHist)
 {
-    constexpr int M = 5 << A;
+    static unsigned long long ldsMask;
     hipStream_t st = p->ctx->stream;
-    const unsigned tiles = unsigned((a.cnt + a.T - 1) >> a.logT);
-    hipLaunchKernelGGL((psb5Transform<A>), dim3(tiles), dim3(PFB_THREADS), p->ldsBytes, st, a);     // at most 22 616 bytes of LDS
-    hipError_t e = hipGetLastError();
+    hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(&psbTransform<M>), 160 * 1024, ldsMask);
     if (e != hipSuccess) return e;
+    const unsigned tiles = unsigned((a.cnt + a.T - 1) >> a.logT);
+    hipLaunchKernelGGL((psbTransform<M>), dim3(tiles), dim3(PFB_THREADS), p->ldsBytes, st, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
     const unsigned long long nOut = (unsigned long long)a.cnt * (unsigned long long)a.U;        // <= 2^30
-    hipLaunchKernelGGL((psb5Fold<M>), dim3(unsigned((nOut + PSB_FOLD_THREADS - 1) / PSB_FOLD_THREADS)), dim3(PSB_FOLD_THREADS), 0, st, a);
+    hipLaunchKernelGGL((psbFold<M>), dim3(unsigned((nOut + PSB_FOLD_THREADS - 1) / PSB_FOLD_THREADS)), dim3(PSB_FOLD_THREADS), 0, st, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (a.HC)
     {
-        const unsigned long long n = (unsigned long long)a.HC * M;                              // < 2^25
-        hipLaunchKernelGGL((psb5History<M>), dim3(unsigned((n + 255) / 256)), dim3(256), 0, st, a, newHist);
+        const unsigned long long n = (unsigned long long)a.HC * M;                              // < 2^26
+        hipLaunchKernelGGL((psbHistory<M>), dim3(unsigned((n + 255) / 256)), dim3(256), 0, st, a, newHist);
         e = hipGetLastError();
     }
     return e;
-}
-
-//! nullptr when the shape is one this file handles, the reason otherwise
-static const char *psbProblem(const bool radix5, const size_t nBins, const size_t interp, const size_t nTaps, const size_t nSel)
-{
-    if (radix5)
-    {
-        const size_t n = nBins / 5;
-        if (nBins % 5 || n == 0 || n > (size_t(1) << PSB5_A_MAX) || (n & (n - 1)))
-            return "polyphase synthesiser: n_bins of the radix-5 bank must be 5 * 2^a, a = 0..6 (5, 10, 20, 40, 80, 160 or 320)";
-    }
-    else if (nBins < (size_t(1) << PSB_LOGM_MIN) || nBins > (size_t(1) << PSB_LOGM_MAX) || (nBins & (nBins - 1)))
-        return "polyphase synthesiser: n_bins must be a power of two in 8..1024";
-    if (interp == 0 || interp > 4096) return "polyphase synthesiser: interp must be 1..4096";
-    if (nTaps == 0 || nTaps > (size_t(1) << 16)) return "polyphase synthesiser: n_taps must be 1..65536";
-    if (nSel == 0 || nSel > size_t(65535) * 8) return "polyphase synthesiser: n_sel must be 1..524280";
-    return nullptr;
 }
 
 static int psbRun(lorahip_psb *p, const float2 *in, const size_t inStride, const size_t nIn, float2 *out, size_t *nOutP)
@@ -342,30 +215,8 @@ static int psbRun(lorahip_psb *p, const float2 *in, const size_t inStride, const
         a.in = in + done; a.cnt = int(cnt); a.m0 = (long long)p->n0;
         a.hist = p->dHist[p->cur].get();
         a.out = out + done * U;
-        hipError_t e = hipErrorInvalidValue;
         float2 *newHist = p->dHist[p->cur ^ 1].get();
-        if (p->radix5)
-            switch (p->M)
-            {
-                case 5: e = psb5Launch<0>(p, a, newHist); break;
-                case 10: e = psb5Launch<1>(p, a, newHist); break;
-                case 20: e = psb5Launch<2>(p, a, newHist); break;
-                case 40: e = psb5Launch<3>(p, a, newHist); break;
-                case 80: e = psb5Launch<4>(p, a, newHist); break;
-                case 160: e = psb5Launch<5>(p, a, newHist); break;
-                case 320: e = psb5Launch<6>(p, a, newHist); break;
-            }
-        else switch (p->logM)
-        {
-            case 3: e = psbLaunch<3>(p, a, newHist); break;
-            case 4: e = psbLaunch<4>(p, a, newHist); break;
-            case 5: e = psbLaunch<5>(p, a, newHist); break;
-            case 6: e = psbLaunch<6>(p, a, newHist); break;
-            case 7: e = psbLaunch<7>(p, a, newHist); break;
-            case 8: e = psbLaunch<8>(p, a, newHist); break;
-            case 9: e = psbLaunch<9>(p, a, newHist); break;
-            case 10: e = psbLaunch<10>(p, a, newHist); break;
-        }
+        const hipError_t e = bankDispatch(p->M, BankCounts(), [&](const auto m) { return psbLaunch<decltype(m)::value>(p, a, newHist); });
         LORAHIP_TRY(e);
         if (p->HC) p->cur ^= 1;
         p->n0 += cnt;
@@ -377,10 +228,7 @@ static int psbRun(lorahip_psb *p, const float2 *in, const size_t inStride, const
 
 static int psbCheck(const bool radix5, const size_t n_bins, const size_t interp, const size_t n_taps, const size_t n_sel)
 {
-    const char *why = psbProblem(radix5, n_bins, interp, n_taps, n_sel);
-    if (why == nullptr) return LORAHIP_OK;
-    setLastError(why);
-    return LORAHIP_E_INVALID;
+    return bankCheck("polyphase synthesiser", "interp", radix5, n_bins, interp, n_taps, n_sel);
 }
 
 //! lorahip_psb_create (power-of-two bin counts) and lorahip_psb_create_radix5 (5 * 2^a): the same object
@@ -399,18 +247,12 @@ static int psbCreate(const bool radix5, lorahip_psb **out, lorahip_ctx *ctx, con
     lorahip_psb *p = new (std::nothrow) lorahip_psb();
     if (p == nullptr) return LORAHIP_E_NOMEM;
     const int M = int(n_bins);
-    const int N = radix5 ? M / 5 : M;           // the radix-2 part of M
-    int logM = 0;
-    while ((1 << logM) < M) logM++;
-    p->ctx = ctx; p->M = M; p->logM = logM; p->radix5 = radix5; p->U = int(interp); p->L = int(n_taps); p->K = int(n_sel);
+    p->ctx = ctx; p->M = M; p->U = int(interp); p->L = int(n_taps); p->K = int(n_sel);
     p->I = (p->L + p->U - 1) / p->U;
     p->HC = p->I - 1;
-    int logT = 0;
-    while ((2 << logT) * M <= 4096) logT++;     // the largest power of two with T M <= 4096 ...
-    p->logT = logT < 3 ? 3 : (logT > 8 ? 8 : logT);     // ... 8 at least, 256 at most
+    p->logT = bankLogT(M, 3);                   // T = 8 at least
     p->T = 1 << p->logT;
-    const size_t nTw = size_t(N / 2) + (radix5 ? size_t(M) : 0);
-    p->ldsBytes = (size_t(p->T) * size_t(M + 1) + nTw) * sizeof(float2);
+    p->ldsBytes = (size_t(p->T) * size_t(M + 1) + size_t(bankTwiddles(M))) * sizeof(float2);
     const size_t byWs = PSB_WS_POINTS / size_t(M), byOut = PSB_SEG_OUTPUTS / interp;
     p->seg = byWs < byOut ? byWs : byOut;
     p->cur = 0; p->n0 = 0;
@@ -420,22 +262,14 @@ static int psbCreate(const bool radix5, lorahip_psb **out, lorahip_ctx *ctx, con
     std::vector<float> g;
     try
     {
-        tw.reserve(nTw);
+        tw = bankTwiddleTable(M, true);
         start.assign(size_t(M) + 1, 0);
         row.resize(n_sel);
         g.resize(n_sel);
     }
     catch (const std::bad_alloc &) { delete p; return LORAHIP_E_NOMEM; }
-    const auto root = [&tw](const int k, const int P)       // exp(+2 pi i k / P)
-    {
-        const double ang = 2.0 * M_PI * double(k) / double(P);
-        tw.push_back(make_float2(float(std::cos(ang)), float(std::sin(ang))));
-    };
-    for (int k = 0; k < N / 2; k++) root(k, N);
-    if (radix5)
-        for (int n = 0; n < M; n++) root(n, M);
     // the rows of every bin, in ascending k (a counting sort is stable)
-    const auto binOf = [&](const size_t k) { return bins ? size_t(((long long)bins[k] % M + M) % M) : k; };
+    const auto binOf = [&](const size_t k) { return bins ? size_t(bankBin(M, bins[k])) : k; };
     for (size_t k = 0; k < n_sel; k++) start[binOf(k) + 1]++;
     for (int b = 0; b < M; b++) start[size_t(b) + 1] += start[size_t(b)];
     {
