@@ -58,23 +58,35 @@ def _dptr(t, dtype=None):
     return t.data_ptr()
 
 
-class Context:
-    """One (device, SF) batch context: chirp / fine-tune / twiddle tables resident in HBM."""
+class _Handle:
+    """One object of the C library: the library `_lib`, the handle `_h`, and close() -- at garbage collection too, and harmless when
+    repeated -- through the destroy entry point the class names in `_destroy`."""
 
-    def __init__(self, sf, device=0):
+    _destroy = None
+
+    def __init__(self):
         self._lib = load()
         self._h = C.c_void_p()
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+
+class Context(_Handle):
+    """One (device, SF) batch context: chirp / fine-tune / twiddle tables resident in HBM."""
+
+    _destroy = "lorahip_destroy"
+
+    def __init__(self, sf, device=0):
+        super().__init__()
         check(self._lib.lorahip_create(C.byref(self._h), int(device), int(sf)), "lorahip_create")
         self.sf = int(sf)
         self.N = 1 << self.sf
         self.device = int(device)
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.lorahip_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
 
     def __enter__(self):
         return self
@@ -298,15 +310,16 @@ def pinned_empty(shape, dtype=np.complex64):
     return np.frombuffer(buf, dtype=dtype, count=int(np.prod(shape))).reshape(shape)
 
 
-class MixedDetector:
+class MixedDetector(_Handle):
     """Channels of different spreading factors demodulated in one call (lorahip_mixed_*: buckets by SF, one stream per bucket,
     concurrent launches, event join -- all below Python). channel_sf: SF of every channel; plan(offsets, S): channel c's S
     back-to-back windows start at sample offsets[c] of the IQ buffer. detect(iq) -> dict of (rows, S) device tensors in
     bucket-major order; rows[c] is channel c's row."""
 
+    _destroy = "lorahip_mixed_destroy"
+
     def __init__(self, channel_sf, device=0):
-        self._lib = load()
-        self._h = C.c_void_p()
+        super().__init__()
         sf = np.ascontiguousarray(channel_sf, np.int32).reshape(-1)
         check(self._lib.lorahip_mixed_create(C.byref(self._h), int(device), sf.ctypes.data, sf.size), "lorahip_mixed_create")
         self.n_channels, self.device, self.S = int(sf.size), int(device), 0
@@ -317,13 +330,6 @@ class MixedDetector:
             s_, r_, n_ = C.c_int32(), C.c_size_t(), C.c_size_t()
             check(self._lib.lorahip_mixed_bucket(self._h, i, C.byref(s_), C.byref(r_), C.byref(n_)), "lorahip_mixed_bucket")
             self.buckets.append((s_.value, r_.value, n_.value))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.lorahip_mixed_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
 
     def set_variant(self, variant):
         for i in range(len(self.buckets)):
@@ -370,14 +376,15 @@ def shard_plan(channel_sf, n_shards):
     return out
 
 
-class MixedDetectorMulti:
+class MixedDetectorMulti(_Handle):
     """lorahip_mixed_create_multi: mixed-SF channels over several devices of ONE process (one scheduler, host thread and set of
     streams per device, no data-path collective). devices: list of device indices (may repeat). shard_of[c] = index into devices of
     channel c, rows[c] = its row in that device's result arrays, channels_of(s) = shard s's channels in row order per bucket."""
 
+    _destroy = "lorahip_mixed_destroy"
+
     def __init__(self, channel_sf, devices):
-        self._lib = load()
-        self._h = C.c_void_p()
+        super().__init__()
         sf = np.ascontiguousarray(channel_sf, np.int32).reshape(-1)
         dv = np.ascontiguousarray(devices, np.int32).reshape(-1)
         check(self._lib.lorahip_mixed_create_multi(C.byref(self._h), dv.ctypes.data, dv.size, sf.ctypes.data, sf.size), "lorahip_mixed_create_multi")
@@ -391,13 +398,6 @@ class MixedDetectorMulti:
             d_, n_ = C.c_int32(), C.c_size_t()
             check(self._lib.lorahip_mixed_device(self._h, s, C.byref(d_), C.byref(n_)), "lorahip_mixed_device")
             self.counts.append(int(n_.value))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.lorahip_mixed_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
 
     def plan(self, channel_offset, windows_per_channel):
         """channel_offset[c]: first sample of channel c inside the IQ buffer of ITS device"""
@@ -445,27 +445,21 @@ def design_lowpass(decim, n_taps, cutoff=None):
     return (h / h.sum()).astype(np.float32)
 
 
-class Channelizer:
+class Channelizer(_Handle):
     """K channels out of one wideband complex64 stream: mix each centre frequency (cycles per input sample) to 0, low-pass,
     keep every decim-th sample; output (K, n_out) in the layout LoRaDemod.work() takes. Stateful: consecutive run() calls
     continue one stream (filter history and mixer phase carried), reset() starts a new one. See include/lorahip.h."""
 
+    _destroy = "lorahip_channelizer_destroy"
+
     def __init__(self, ctx, freqs, decim, taps):
-        self._lib = load()
+        super().__init__()
         self._ctx = ctx                                                  # borrowed: device and stream
-        self._h = C.c_void_p()
         f = np.ascontiguousarray(freqs, np.float64).reshape(-1)
         t = np.ascontiguousarray(taps, np.float32).reshape(-1)
         check(self._lib.lorahip_channelizer_create(C.byref(self._h), ctx._h, f.size, f.ctypes.data, int(decim), t.ctypes.data, t.size),
               "lorahip_channelizer_create")
         self.n_channels, self.decim, self.n_taps = int(f.size), int(decim), int(t.size)
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.lorahip_channelizer_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
 
     def reset(self):
         check(self._lib.lorahip_channelizer_reset(self._h), "lorahip_channelizer_reset")
@@ -475,25 +469,7 @@ class Channelizer:
 
     def run(self, wide, out=None):
         """wide: 1-D complex64 device tensor (the next samples of the stream); returns the (K, n_out) complex64 tensor"""
-        import torch
-        if wide.dim() != 1 or wide.dtype != torch.complex64:
-            raise ValueError("wide must be a 1-D complex64 device tensor")
-        wide = wide.contiguous()
-        n_out = self.out_count(wide.numel())
-        if out is None:
-            out = torch.empty((self.n_channels, n_out), dtype=torch.complex64, device=wide.device)
-        elif (out.dim() != 2 or out.shape[0] != self.n_channels or out.shape[1] < n_out or out.dtype != torch.complex64
-              or (out.numel() and (out.stride(1) != 1 or out.stride(0) < out.shape[1]))):
-            raise ValueError("out must be a (K, >= n_out) complex64 tensor with unit column stride (rows may be a slice of a wider buffer)")
-        self._ctx.use_torch_stream()
-        got = C.c_size_t()
-        # the row stride is the tensor's own: `out` may be the columns [w, w + n) of a (K, capacity) buffer that fills chunk by chunk
-        check(self._lib.lorahip_channelizer_run(self._h, C.c_void_p(wide.data_ptr()) if wide.numel() else None, wide.numel(),
-                                                C.c_void_p(out.data_ptr()) if out.numel() else None,
-                                                int(out.stride(0)) if out.numel() and out.shape[0] > 1 else int(out.shape[1]), C.byref(got)),
-              "lorahip_channelizer_run")
-        return out[:, :got.value]
-
+        return _chan_run(self, "lorahip_channelizer_run", wide, out)
 
     def run_captures(self, wide):
         """wide: (S, n_in) complex64 device tensor of S independent captures -> (S, K, n_in // decim) tensor, one launch; every
@@ -557,6 +533,27 @@ def _plan_bins(n_bins, bins):
     return b64.astype(np.int32)
 
 
+def _chan_run(obj, run, wide, out):
+    """Channelizer.run and PolyphaseChannelizer.run: check wide and out, call the C entry point `run`, return the outputs it wrote"""
+    import torch
+    if wide.dim() != 1 or wide.dtype != torch.complex64:
+        raise ValueError("wide must be a 1-D complex64 device tensor")
+    wide = wide.contiguous()
+    n_out = obj.out_count(wide.numel())
+    if out is None:
+        out = torch.empty((obj.n_channels, n_out), dtype=torch.complex64, device=wide.device)
+    elif (out.dim() != 2 or out.shape[0] != obj.n_channels or out.shape[1] < n_out or out.dtype != torch.complex64
+          or (out.numel() and (out.stride(1) != 1 or out.stride(0) < out.shape[1]))):
+        raise ValueError("out must be a (K, >= n_out) complex64 tensor with unit column stride (rows may be a slice of a wider buffer)")
+    obj._ctx.use_torch_stream()
+    got = C.c_size_t()
+    # the row stride is the tensor's own: `out` may be the columns [w, w + n) of a (K, capacity) buffer that fills chunk by chunk
+    check(getattr(obj._lib, run)(obj._h, C.c_void_p(wide.data_ptr()) if wide.numel() else None, wide.numel(),
+                                 C.c_void_p(out.data_ptr()) if out.numel() else None,
+                                 int(out.stride(0)) if out.numel() and out.shape[0] > 1 else int(out.shape[1]), C.byref(got)), run)
+    return out[:, :got.value]
+
+
 def _synth_run(obj, run, rows, out):
     """Synthesizer.run and PolyphaseSynthesizer.run: check rows and out, call the C entry point `run`, return the outputs it wrote"""
     import torch
@@ -578,7 +575,51 @@ def _synth_run(obj, run, rows, out):
     return out[:got.value]
 
 
-class PolyphaseChannelizer:
+class _PolyphaseBank(_Handle):
+    """What PolyphaseChannelizer and PolyphaseSynthesizer share. The C entry points are lorahip_<_bank>_*: ..._create takes the powers
+    of two, ..._create_radix5 the counts 5 * 2^a; the rate change is the attribute `_rate` names; the synthesiser also passes gains."""
+
+    _bank = None        # "pfb" / "psb"
+    _rate = None        # "decim" / "interp"
+
+    def _build(self, radix5, ctx, n_bins, rate, taps, bins, *gains):
+        """create the handle and set the attributes"""
+        super().__init__()
+        self._ctx = ctx                                                  # borrowed: device and stream
+        t = np.ascontiguousarray(taps, np.float32).reshape(-1)
+        b = _plan_bins(n_bins, bins)
+        g = [None if x is None else np.ascontiguousarray(x, np.float32).reshape(-1) for x in gains]
+        if any(x is not None and x.size != b.size for x in g):
+            raise ValueError("one gain per channel")
+        create = "lorahip_%s_create%s" % (self._bank, "_radix5" if radix5 else "")
+        check(getattr(self._lib, create)(C.byref(self._h), ctx._h, int(n_bins), None if bins is None else b.ctypes.data,
+                                         int(n_bins) if bins is None else b.size, *[None if x is None else x.ctypes.data for x in g],
+                                         int(rate), t.ctypes.data, t.size), create)
+        self.n_bins, self.n_taps, self.n_channels = int(n_bins), int(t.size), int(b.size)
+        setattr(self, self._rate, int(rate))
+        self.bins = b
+        self.freqs = b.astype(np.float64) / float(self.n_bins)
+
+    @classmethod
+    def _radix5(cls, *args):
+        self = cls.__new__(cls)
+        self._build(True, *args)
+        return self
+
+    @classmethod
+    def _for_plan(cls, ctx, plan, taps, *gains):
+        n_bins, rate, bins = plan
+        make = cls.radix5 if int(n_bins) in RADIX5_BINS else cls
+        return make(ctx, n_bins, rate, taps, bins, *gains)
+
+    def reset(self):
+        check(getattr(self._lib, "lorahip_%s_reset" % self._bank)(self._h), "lorahip_%s_reset" % self._bank)
+
+    def out_count(self, n_in):
+        return int(getattr(self._lib, "lorahip_%s_out_count" % self._bank)(self._h, int(n_in)))
+
+
+class PolyphaseChannelizer(_PolyphaseBank):
     """The channeliser for a uniform channel plan: rows on the grid fs / n_bins (n_bins a power of two, 8..1024; 5 * 2^a, a = 0..6,
     the 200 kHz LoRaWAN grids, through PolyphaseChannelizer.radix5 or .for_plan), row i at centre
     bins[i] / n_bins cycles per input sample (any integers, taken modulo n_bins; negative = the lower half of the band; None: all
@@ -587,83 +628,40 @@ class PolyphaseChannelizer:
     the array a Channelizer or a Synthesizer takes for the same plan. Stateful like Channelizer: consecutive run() calls continue one
     stream, bit-identical to one call; reset() starts a new one. See include/lorahip.h."""
 
-    def __init__(self, ctx, n_bins, decim, taps, bins=None):
-        self._build("lorahip_pfb_create", ctx, n_bins, decim, taps, bins)
+    _bank, _rate, _destroy = "pfb", "decim", "lorahip_pfb_destroy"
 
-    def _build(self, create, ctx, n_bins, decim, taps, bins):
-        """create the handle through the C entry point `create` and set the attributes"""
-        self._lib = load()
-        self._ctx = ctx                                                  # borrowed: device and stream
-        self._h = C.c_void_p()
-        t = np.ascontiguousarray(taps, np.float32).reshape(-1)
-        b = _plan_bins(n_bins, bins)
-        check(getattr(self._lib, create)(C.byref(self._h), ctx._h, int(n_bins), None if bins is None else b.ctypes.data,
-                                         int(n_bins) if bins is None else b.size, int(decim), t.ctypes.data, t.size), create)
-        self.n_bins, self.decim, self.n_taps, self.n_channels = int(n_bins), int(decim), int(t.size), int(b.size)
-        self.bins = b
-        self.freqs = b.astype(np.float64) / float(self.n_bins)
+    def __init__(self, ctx, n_bins, decim, taps, bins=None):
+        self._build(False, ctx, n_bins, decim, taps, bins)
 
     @classmethod
     def radix5(cls, ctx, n_bins, decim, taps, bins=None):
         """the same object on n_bins = 5 * 2^a bins (5, 10, 20, 40, 80, 160, 320; lorahip_pfb_create_radix5): channels 200 kHz apart
         and 125 kHz wide have decim / n_bins = 8 / 5. The constructor takes the powers of two only, this the seven counts only."""
-        self = cls.__new__(cls)
-        self._build("lorahip_pfb_create_radix5", ctx, n_bins, decim, taps, bins)
-        return self
+        return cls._radix5(ctx, n_bins, decim, taps, bins)
 
     @classmethod
     def for_plan(cls, ctx, plan, taps):
         """the object for plan = (n_bins, decim, bins) as uniform_plan returns it: the constructor or radix5, by n_bins"""
-        n_bins, decim, bins = plan
-        make = cls.radix5 if int(n_bins) in RADIX5_BINS else cls
-        return make(ctx, n_bins, decim, taps, bins)
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.lorahip_pfb_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
-
-    def reset(self):
-        check(self._lib.lorahip_pfb_reset(self._h), "lorahip_pfb_reset")
-
-    def out_count(self, n_in):
-        return int(self._lib.lorahip_pfb_out_count(self._h, int(n_in)))
+        return cls._for_plan(ctx, plan, taps)
 
     def run(self, wide, out=None):
         """wide: 1-D complex64 device tensor (the next samples of the stream); returns the (K, n_out) complex64 tensor (written into
         out if given: it may be the columns [w, w + n) of a (K, capacity) buffer)"""
-        import torch
-        if wide.dim() != 1 or wide.dtype != torch.complex64:
-            raise ValueError("wide must be a 1-D complex64 device tensor")
-        wide = wide.contiguous()
-        n_out = self.out_count(wide.numel())
-        if out is None:
-            out = torch.empty((self.n_channels, n_out), dtype=torch.complex64, device=wide.device)
-        elif (out.dim() != 2 or out.shape[0] != self.n_channels or out.shape[1] < n_out or out.dtype != torch.complex64
-              or (out.numel() and (out.stride(1) != 1 or out.stride(0) < out.shape[1]))):
-            raise ValueError("out must be a (K, >= n_out) complex64 tensor with unit column stride (rows may be a slice of a wider buffer)")
-        self._ctx.use_torch_stream()
-        got = C.c_size_t()
-        check(self._lib.lorahip_pfb_run(self._h, C.c_void_p(wide.data_ptr()) if wide.numel() else None, wide.numel(),
-                                        C.c_void_p(out.data_ptr()) if out.numel() else None,
-                                        int(out.stride(0)) if out.numel() and out.shape[0] > 1 else int(out.shape[1]), C.byref(got)),
-              "lorahip_pfb_run")
-        return out[:, :got.value]
+        return _chan_run(self, "lorahip_pfb_run", wide, out)
 
 
-class Synthesizer:
+class Synthesizer(_Handle):
     """K channel-rate complex64 streams onto their carriers in one wideband stream: zero-stuff by interp, low-pass with taps, mix each
     row up to its centre frequency (cycles per OUTPUT sample: the array a Channelizer of decim = interp takes), scale by gains (None:
     all 1), sum. The mirror image of Channelizer; pass interp * design_lowpass(interp, n_taps, ...) for unit passband gain. Stateful:
     consecutive run() calls continue one stream (filter history and mixer phase carried, bit-identical to one call), reset() starts a
     new one. See include/lorahip.h."""
 
+    _destroy = "lorahip_synthesizer_destroy"
+
     def __init__(self, ctx, freqs, interp, taps, gains=None):
-        self._lib = load()
+        super().__init__()
         self._ctx = ctx                                                  # borrowed: device and stream
-        self._h = C.c_void_p()
         f = np.ascontiguousarray(freqs, np.float64).reshape(-1)
         t = np.ascontiguousarray(taps, np.float32).reshape(-1)
         g = None if gains is None else np.ascontiguousarray(gains, np.float32).reshape(-1)
@@ -672,13 +670,6 @@ class Synthesizer:
         check(self._lib.lorahip_synthesizer_create(C.byref(self._h), ctx._h, f.size, f.ctypes.data, None if g is None else g.ctypes.data,
                                                    int(interp), t.ctypes.data, t.size), "lorahip_synthesizer_create")
         self.n_channels, self.interp, self.n_taps = int(f.size), int(interp), int(t.size)
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.lorahip_synthesizer_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
 
     def reset(self):
         check(self._lib.lorahip_synthesizer_reset(self._h), "lorahip_synthesizer_reset")
@@ -692,7 +683,7 @@ class Synthesizer:
         return _synth_run(self, "lorahip_synthesizer_run", rows, out)
 
 
-class PolyphaseSynthesizer:
+class PolyphaseSynthesizer(_PolyphaseBank):
     """The synthesiser for a uniform channel plan: row k goes to centre bins[k] / n_bins cycles per OUTPUT sample (n_bins a power of
     two, 8..1024; 5 * 2^a, a = 0..6, the 200 kHz LoRaWAN grids, through PolyphaseSynthesizer.radix5 or .for_plan; bins any integers,
     taken modulo n_bins; negative = the lower half of the band; rows that share a bin are summed; None: all n_bins bins in order),
@@ -702,53 +693,21 @@ class PolyphaseSynthesizer:
     of two); .freqs is the array a Synthesizer, a Channelizer or a PolyphaseChannelizer's plan takes. Stateful like Synthesizer:
     consecutive run() calls continue one stream, bit-identical to one call; reset() starts a new one. See include/lorahip.h."""
 
-    def __init__(self, ctx, n_bins, interp, taps, bins=None, gains=None):
-        self._build("lorahip_psb_create", ctx, n_bins, interp, taps, bins, gains)
+    _bank, _rate, _destroy = "psb", "interp", "lorahip_psb_destroy"
 
-    def _build(self, create, ctx, n_bins, interp, taps, bins, gains):
-        """create the handle through the C entry point `create` and set the attributes"""
-        self._lib = load()
-        self._ctx = ctx                                                  # borrowed: device and stream
-        self._h = C.c_void_p()
-        t = np.ascontiguousarray(taps, np.float32).reshape(-1)
-        b = _plan_bins(n_bins, bins)
-        g = None if gains is None else np.ascontiguousarray(gains, np.float32).reshape(-1)
-        if g is not None and g.size != b.size:
-            raise ValueError("one gain per channel")
-        check(getattr(self._lib, create)(C.byref(self._h), ctx._h, int(n_bins), None if bins is None else b.ctypes.data,
-                                         int(n_bins) if bins is None else b.size, None if g is None else g.ctypes.data,
-                                         int(interp), t.ctypes.data, t.size), create)
-        self.n_bins, self.interp, self.n_taps, self.n_channels = int(n_bins), int(interp), int(t.size), int(b.size)
-        self.bins = b
-        self.freqs = b.astype(np.float64) / float(self.n_bins)
+    def __init__(self, ctx, n_bins, interp, taps, bins=None, gains=None):
+        self._build(False, ctx, n_bins, interp, taps, bins, gains)
 
     @classmethod
     def radix5(cls, ctx, n_bins, interp, taps, bins=None, gains=None):
         """the same object on n_bins = 5 * 2^a bins (5, 10, 20, 40, 80, 160, 320; lorahip_psb_create_radix5): channels 200 kHz apart
         and 125 kHz wide have interp / n_bins = 8 / 5. The constructor takes the powers of two only, this the seven counts only."""
-        self = cls.__new__(cls)
-        self._build("lorahip_psb_create_radix5", ctx, n_bins, interp, taps, bins, gains)
-        return self
+        return cls._radix5(ctx, n_bins, interp, taps, bins, gains)
 
     @classmethod
     def for_plan(cls, ctx, plan, taps, gains=None):
         """the object for plan = (n_bins, decim, bins) as uniform_plan returns it, interp = decim: the constructor or radix5, by n_bins"""
-        n_bins, decim, bins = plan
-        make = cls.radix5 if int(n_bins) in RADIX5_BINS else cls
-        return make(ctx, n_bins, decim, taps, bins, gains)
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.lorahip_psb_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
-
-    def reset(self):
-        check(self._lib.lorahip_psb_reset(self._h), "lorahip_psb_reset")
-
-    def out_count(self, n_in):
-        return int(self._lib.lorahip_psb_out_count(self._h, int(n_in)))
+        return cls._for_plan(ctx, plan, taps, gains)
 
     def run(self, rows, out=None):
         """rows: (K, n) complex64 device tensor with unit column stride (the next n samples of every channel; may be the columns
@@ -756,21 +715,15 @@ class PolyphaseSynthesizer:
         return _synth_run(self, "lorahip_psb_run", rows, out)
 
 
-class LoRaDetector:
+class LoRaDetector(_Handle):
     """`LoRaDetector<float>` (LoRaDetector.hpp:8-72): feed N samples, detect() -> arg-max bin."""
 
+    _destroy = "lorahip_detector_destroy"
+
     def __init__(self, N, device=0):
-        self._lib = load()
-        self._h = C.c_void_p()
+        super().__init__()
         check(self._lib.lorahip_detector_create(C.byref(self._h), int(device), int(N)), "lorahip_detector_create")
         self.N = int(N)
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.lorahip_detector_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
 
     def feed(self, i, samp):
         samp = complex(samp)
@@ -790,16 +743,17 @@ class LoRaDetector:
         return idx.value, p.value, pa.value, fi.value
 
 
-class LoRaDemod:
+class LoRaDemod(_Handle):
     """B channels of the `/lora/lora_demod` block (LoRaDemod.cpp), same parameters and defaults."""
+
+    _destroy = "lorahip_demod_destroy"
 
     STATES = ("FRAMESYNC", "DOWNCHIRP0", "DOWNCHIRP1", "QUARTERCHIRP", "DATASYMBOLS")
 
     def __init__(self, sf=10, n_channels=1, device=0, channel_sf=None, devices=None):
         """channel_sf (one SF per channel) and devices (a list of device indices) make the mixed-SF / multi-device form
         (lorahip_demod_create_mixed): one handle, global channel numbers; sf / n_channels / device are ignored then"""
-        self._lib = load()
-        self._h = C.c_void_p()
+        super().__init__()
         self._port_bufs = dict(fft=None, dec=None, raw=None)
         self._mtu = 256                                                 # LoRaDemod.cpp:73
         if channel_sf is None:
@@ -832,13 +786,6 @@ class LoRaDemod:
     def device_slot_of(self):
         """mixed form: for every channel the index into `devices` of the GPU that holds it"""
         return np.array([self.parts[p][3] for p in self.part_of], np.int32)
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.lorahip_demod_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
 
     def setSync(self, sync):
         check(self._lib.lorahip_demod_set_sync(self._h, int(sync) & 0xff), "lorahip_demod_set_sync")

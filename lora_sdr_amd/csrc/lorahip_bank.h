@@ -3,7 +3,7 @@
 // of the transform (lorahip_pfbfft.h, lorahip_pfbfft5.h) and where it leaves a bin, the tile rule, and the step from the M of an
 // object to the M a kernel is compiled for.
 #pragma once
-#include "lorahip_own.h"
+#include "lorahip_frontend.h"
 #include "lorahip_pfbfft5.h"
 #include <cmath>
 #include <type_traits>

@@ -15,7 +15,7 @@
 //     16*RM v_pk_fma_f32;
 //   * the NCO is a 64-bit phase counter (w_k * n mod 2^64): exact wrap-around, no drift, and a stream cut into
 //     chunks gives the same bits as one call.
-#include "lorahip_own.h"
+#include "lorahip_frontend.h"
 #include "lorahip_mixer.h"
 #include <cmath>
 #include <cstdlib>
@@ -30,9 +30,7 @@ struct lorahip_channelizer
     lorahip::DevBuf<unsigned> dTapOff;          // [L+2]
     lorahip::DevBuf<unsigned long long> dW;     // [nGroups*8]
     lorahip::DevBuf<float2> dRot;   // [nGroups*8] phase step over 256 outputs, then [nGroups*8][256] phase over t outputs
-    lorahip::DevBuf<float2> dHist[2];           // the HC samples before n0 (zeros before the start of the stream)
-    int cur;
-    unsigned long long n0;          // samples consumed since the last reset
+    lorahip::StreamCarry carry;     // the HC samples before n0
 };
 
 namespace lorahip {
@@ -59,17 +57,6 @@ struct ChanArgs
     int K, L, D, QP, nGroups;
     long long captureIn, captureOut;    // batch of independent captures (blockIdx.y): sample / output-row strides, 0 for a stream
 };
-
-//! sample n of the stream (absolute index): from this call's chunk, from the history kept from earlier calls, or 0
-__device__ __forceinline__ float2 streamSample(const ChanArgs &a, const float2 *chunk, const long long n)
-{
-    const long long c = n - a.n0, h = c + a.histLen;
-    const float2 *src = c >= 0 ? chunk + c : a.hist + h;
-    const bool ok = c >= 0 ? c < a.nChunk : h >= 0;
-    float2 v = make_float2(0.0f, 0.0f);
-    if (ok) v = *src;
-    return v;
-}
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 template <int RM> struct TapRegs { typedef v2f X; };
@@ -150,7 +137,7 @@ __device__ __forceinline__ void tileStage(float2 *xs, const ChanArgs &a, const f
         float2 v[8];
         int q = tt / D, p = tt - q * D;
 #pragma unroll
-        for (int u = 0; u < 8; u++) v[u] = tt + u * CHAN_THREADS < TI ? streamSample(a, chunk, tileStart + tt + u * CHAN_THREADS) : make_float2(0.0f, 0.0f);
+        for (int u = 0; u < 8; u++) v[u] = tt + u * CHAN_THREADS < TI ? carriedSample(chunk, a.nChunk, a.hist, a.histLen, a.n0, tileStart + tt + u * CHAN_THREADS) : make_float2(0.0f, 0.0f);
 #pragma unroll
         for (int u = 0; u < 8; u++)
         {
@@ -254,13 +241,6 @@ __global__ __launch_bounds__(CHAN_THREADS) void channelize(const ChanArgs a)
     }
 }
 
-//! the HC samples that precede the next call
-__global__ void chanHistory(const ChanArgs a, float2 *newHist)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < a.histLen) newHist[i] = streamSample(a, a.chunk, a.n0 + a.nChunk - a.histLen + i);
-}
-
 static unsigned long long gLdsMask[2] = {0, 0};
 
 //! captures == 0: the next nIn samples of THE stream (history and phase carried). captures > 0: that many independent captures of nIn
@@ -270,17 +250,16 @@ static int chanRun(lorahip_channelizer *c, const float2 *wide, const size_t nIn,
 {
     lorahip_ctx *ctx = c->ctx;
     const DeviceGuard guard(ctx->device);
-    const unsigned long long D = (unsigned long long)c->D;
-    const unsigned long long n0 = captures ? 0 : c->n0;
-    const unsigned long long mLo = n0 / D, mHi = (n0 + nIn) / D;
-    const size_t nOut = size_t(mHi - mLo);
+    const unsigned long long n0 = captures ? 0 : c->carry.n0;
+    const unsigned long long mLo = n0 / (unsigned long long)c->D;
+    const size_t nOut = decimatedCount(n0, nIn, c->D);
     if (nOutP) *nOutP = nOut;
     if (nIn == 0) return LORAHIP_OK;
     if (nOut && (out == nullptr || outStride < nOut)) return LORAHIP_E_INVALID;
     if (nOut > (size_t(1) << 30)) { setLastError("channeliser: more than 2^30 outputs per channel in one call"); return LORAHIP_E_INVALID; }
     ChanArgs a;
     a.chunk = wide; a.nChunk = (long long)nIn;
-    a.hist = c->dHist[c->cur].get(); a.histLen = captures ? 0 : c->HC;        // no history: samples before the capture read as 0
+    a.hist = c->carry.current(); a.histLen = captures ? 0 : c->HC;        // no history: samples before the capture read as 0
     a.n0 = (long long)n0;
     a.captureIn = (long long)captureStride; a.captureOut = (long long)(size_t(c->K) * outStride);
     a.taps = reinterpret_cast<const v2f *>(c->dTaps.get());
@@ -310,10 +289,9 @@ static int chanRun(lorahip_channelizer *c, const float2 *wide, const size_t nIn,
         LORAHIP_TRY(hipGetLastError());
     }
     if (captures) return LORAHIP_OK;
-    hipLaunchKernelGGL(chanHistory, dim3((c->HC + 255) / 256), dim3(256), 0, ctx->stream, a, c->dHist[c->cur ^ 1].get());
+    hipLaunchKernelGGL(carryHistory, dim3((c->HC + 255) / 256), dim3(256), 0, ctx->stream, a.chunk, a.nChunk, a.hist, a.histLen, a.n0, c->carry.next());
     LORAHIP_TRY(hipGetLastError());
-    c->cur ^= 1;
-    c->n0 += nIn;
+    c->carry.advance(nIn);
     return LORAHIP_OK;
 }
 
@@ -357,12 +335,20 @@ int lorahip_channelizer_create(lorahip_channelizer **out, lorahip_ctx *ctx, cons
     if (c == nullptr) return LORAHIP_E_NOMEM;
     c->ctx = ctx; c->K = int(n_channels); c->L = L; c->D = D; c->HC = L - 1 + D; c->QP = QP; c->RM = RM;
     c->nGroups = int((n_channels + CHAN_KG - 1) / CHAN_KG);
-    c->ldsBytes = lds; c->cur = 0; c->n0 = 0;
+    c->ldsBytes = lds;
 
     const size_t KP = size_t(c->nGroups) * CHAN_KG;
-    std::vector<unsigned long long> w(KP, 0);
-    std::vector<float2> g(size_t(c->nGroups) * size_t(L + 1) * CHAN_KG, make_float2(0.0f, 0.0f));
-    std::vector<unsigned> off(size_t(L) + 2, 0u);
+    std::vector<unsigned long long> w;
+    std::vector<float2> g, rot;
+    std::vector<unsigned> off;
+    try
+    {
+        w.assign(KP, 0);
+        g.assign(size_t(c->nGroups) * size_t(L + 1) * CHAN_KG, make_float2(0.0f, 0.0f));
+        off.assign(size_t(L) + 2, 0u);
+        rot.resize(KP * (1 + CHAN_THREADS));
+    }
+    catch (const std::bad_alloc &) { delete c; return LORAHIP_E_NOMEM; }
     for (int jr = 0; jr < L; jr++) off[size_t(jr)] = unsigned((jr % D) * QP + jr / D) * unsigned(sizeof(float2));
     for (size_t k = 0; k < n_channels; k++)
     {
@@ -377,7 +363,6 @@ int lorahip_channelizer_create(lorahip_channelizer **out, lorahip_ctx *ctx, cons
                 make_float2(float(double(taps[j]) * std::cos(ang)), float(double(taps[j]) * std::sin(ang)));
         }
     }
-    std::vector<float2> rot(KP * (1 + CHAN_THREADS));
     for (size_t k = 0; k < KP; k++)
         for (int t = 0; t <= CHAN_THREADS; t++)
         {
@@ -385,24 +370,8 @@ int lorahip_channelizer_create(lorahip_channelizer **out, lorahip_ctx *ctx, cons
             const double ang = 2.0 * M_PI * std::ldexp(double((long long)(w[k] * (unsigned long long)(t * D))), -64);
             rot[t == CHAN_THREADS ? k : KP + k * CHAN_THREADS + size_t(t)] = make_float2(float(std::cos(ang)), float(-std::sin(ang)));
         }
-    const DeviceGuard guard(ctx->device);
-    const size_t histBytes = size_t(c->HC) * sizeof(float2);
-    hipError_t e = c->dTaps.grow(g.size() * sizeof(float2));
-    if (e == hipSuccess) e = c->dTapOff.grow(off.size() * sizeof(unsigned));
-    if (e == hipSuccess) e = c->dW.grow(w.size() * sizeof(unsigned long long));
-    if (e == hipSuccess) e = c->dRot.grow(rot.size() * sizeof(float2));
-    if (e == hipSuccess) e = c->dHist[0].grow(histBytes);
-    if (e == hipSuccess) e = c->dHist[1].grow(histBytes);
-    if (e != hipSuccess) { delete c; return LORAHIP_E_NOMEM; }
-    e = hipMemcpy(c->dTaps.get(), g.data(), g.size() * sizeof(float2), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(c->dTapOff.get(), off.data(), off.size() * sizeof(unsigned), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(c->dW.get(), w.data(), w.size() * sizeof(unsigned long long), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(c->dRot.get(), rot.data(), rot.size() * sizeof(float2), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(c->dHist[0].get(), 0, histBytes);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { delete c; return hipFail(e, "channeliser table upload"); }
-    *out = c;
-    return LORAHIP_OK;
+    return uploadTables(out, c, "channeliser", size_t(c->HC), c->dTaps, g.data(), g.size(), c->dTapOff, off.data(), off.size(), c->dW, w.data(), w.size(),
+                        c->dRot, rot.data(), rot.size());
 }
 
 void lorahip_channelizer_destroy(lorahip_channelizer *c)
@@ -416,16 +385,13 @@ int lorahip_channelizer_reset(lorahip_channelizer *c)
 {
     if (c == nullptr) return LORAHIP_E_INVALID;
     const DeviceGuard guard(c->ctx->device);
-    LORAHIP_TRY(hipMemsetAsync(c->dHist[c->cur].get(), 0, size_t(c->HC) * sizeof(float2), c->ctx->stream));
-    c->n0 = 0;
+    LORAHIP_TRY(c->carry.reset(c->ctx->stream));
     return LORAHIP_OK;
 }
 
 size_t lorahip_channelizer_out_count(const lorahip_channelizer *c, const size_t n_in)
 {
-    if (c == nullptr) return 0;
-    const unsigned long long D = (unsigned long long)c->D;
-    return size_t((c->n0 + n_in) / D - c->n0 / D);
+    return c == nullptr ? 0 : decimatedCount(c->carry.n0, n_in, c->D);
 }
 
 int lorahip_channelizer_run(lorahip_channelizer *c, const float *wide_dev, const size_t n_in, float *out_dev,

@@ -38,9 +38,7 @@ struct lorahip_pfb
     lorahip::DevBuf<float> dTaps;               // [Lp] h[j], zeros from L on
     lorahip::DevBuf<float2> dTw;                // [bankTwiddles(M)] exp(-2 pi i k / M), k < M / 2; 5 * 2^a: the same for M / 5, then exp(-2 pi i n / M), n < M
     lorahip::DevBuf<int> dSel;                  // [K] where row i's bin stands after the transform: bankPlace(M, bins[i] mod M)
-    lorahip::DevBuf<float2> dHist[2];           // the HC samples before n0 (zeros before the start of the stream)
-    int cur;
-    unsigned long long n0;                      // samples consumed since the last reset
+    lorahip::StreamCarry carry;                 // the HC samples before n0
 };
 
 namespace lorahip {
@@ -63,17 +61,6 @@ struct PfbArgs
     long long nOut;
     int D, L, Lp, K, T, logT, span;
 };
-
-//! sample n of the stream (absolute index): from this call's chunk, from the history kept from earlier calls, or 0
-__device__ __forceinline__ float2 pfbSample(const PfbArgs &a, const long long n)
-{
-    const long long c = n - a.n0, h = c + a.histLen;
-    const float2 *src = c >= 0 ? a.chunk + c : a.hist + h;
-    const bool ok = c >= 0 ? c < a.nChunk : h >= 0;
-    float2 v = make_float2(0.0f, 0.0f);
-    if (ok) v = *src;
-    return v;
-}
 
 //! one folded sum from samples that lie in a row: xp = the newest sample of residue s, the older ones M apart below it; rounds = the
 //! number of taps r, r + M, ... below L
@@ -121,7 +108,7 @@ __global__ __launch_bounds__(PFB_THREADS) void pfbChannelize(const PfbArgs a)
         else
         {
 #pragma unroll 4
-            for (int i = tid; i < a.span; i += PFB_THREADS) xs[i] = pfbSample(a, tileStart + i);
+            for (int i = tid; i < a.span; i += PFB_THREADS) xs[i] = carriedSample(a.chunk, a.nChunk, a.hist, a.histLen, a.n0, tileStart + i);
         }
         __syncthreads();
     }
@@ -151,7 +138,7 @@ __global__ __launch_bounds__(PFB_THREADS) void pfbChannelize(const PfbArgs a)
             float re = 0.0f, im = 0.0f;
             for (int q = 0; q < rounds; q++)
             {
-                const float2 x = pfbSample(a, n - r - (long long)q * M);
+                const float2 x = carriedSample(a.chunk, a.nChunk, a.hist, a.histLen, a.n0, n - r - (long long)q * M);
                 const float h = hp[q * M];
                 re = __builtin_fmaf(h, x.x, re);
                 im = __builtin_fmaf(h, x.y, im);
@@ -176,13 +163,6 @@ __global__ __launch_bounds__(PFB_THREADS) void pfbChannelize(const PfbArgs a)
     }
 }
 
-//! the HC samples that precede the next call
-__global__ void pfbHistory(const PfbArgs a, float2 *newHist)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < a.histLen) newHist[i] = pfbSample(a, a.n0 + a.nChunk - a.histLen + i);
-}
-
 template <int M>
 static hipError_t pfbLaunch(const lorahip_pfb *p, const PfbArgs &a, const unsigned grid)
 {
@@ -205,9 +185,8 @@ static hipError_t pfbLaunch(const lorahip_pfb *p, const PfbArgs &a, const unsign
 static int pfbRun(lorahip_pfb *p, const float2 *wide, const size_t nIn, float2 *out, const size_t outStride, size_t *nOutP)
 {
     lorahip_ctx *ctx = p->ctx;
-    const unsigned long long D = (unsigned long long)p->D;
-    const unsigned long long mLo = p->n0 / D, mHi = (p->n0 + nIn) / D;
-    const size_t nOut = size_t(mHi - mLo);
+    const unsigned long long mLo = p->carry.n0 / (unsigned long long)p->D;
+    const size_t nOut = decimatedCount(p->carry.n0, nIn, p->D);
     if (nOutP) *nOutP = nOut;
     if (nIn == 0) return LORAHIP_OK;
     if (nOut && (out == nullptr || outStride < nOut)) { setLastError("polyphase channeliser: no output rows, or out_stride below the outputs of this call"); return LORAHIP_E_INVALID; }
@@ -217,8 +196,8 @@ static int pfbRun(lorahip_pfb *p, const float2 *wide, const size_t nIn, float2 *
     const DeviceGuard guard(ctx->device);
     PfbArgs a;
     a.chunk = wide; a.nChunk = (long long)nIn;
-    a.hist = p->dHist[p->cur].get(); a.histLen = p->HC;
-    a.n0 = (long long)p->n0;
+    a.hist = p->carry.current(); a.histLen = p->HC;
+    a.n0 = (long long)p->carry.n0;
     a.taps = p->dTaps.get(); a.tw = p->dTw.get(); a.sel = p->dSel.get();
     a.out = out; a.outStride = (long long)outStride;
     a.mLo = (long long)mLo; a.nOut = (long long)nOut;
@@ -228,10 +207,9 @@ static int pfbRun(lorahip_pfb *p, const float2 *wide, const size_t nIn, float2 *
         const hipError_t e = bankDispatch(p->M, BankCounts(), [&](const auto m) { return pfbLaunch<decltype(m)::value>(p, a, unsigned(nTiles)); });
         LORAHIP_TRY(e);
     }
-    hipLaunchKernelGGL(pfbHistory, dim3((p->HC + 255) / 256), dim3(256), 0, ctx->stream, a, p->dHist[p->cur ^ 1].get());
+    hipLaunchKernelGGL(carryHistory, dim3((p->HC + 255) / 256), dim3(256), 0, ctx->stream, a.chunk, a.nChunk, a.hist, a.histLen, a.n0, p->carry.next());
     LORAHIP_TRY(hipGetLastError());
-    p->cur ^= 1;
-    p->n0 += nIn;
+    p->carry.advance(nIn);
     return LORAHIP_OK;
 }
 
@@ -263,29 +241,21 @@ static int pfbCreate(const bool radix5, lorahip_pfb **out, lorahip_ctx *ctx, con
     p->span = int(span);                        // < 2^21
     p->staged = fixedLds + span * sizeof(float2) <= PFB_STAGE_LDS;
     p->ldsBytes = fixedLds + (p->staged ? span * sizeof(float2) : 0);
-    p->cur = 0; p->n0 = 0;
 
-    std::vector<float> h(size_t(p->Lp), 0.0f);
+    std::vector<float> h;
+    std::vector<float2> tw;
+    std::vector<int> sel;
+    try
+    {
+        h.assign(size_t(p->Lp), 0.0f);
+        tw = bankTwiddleTable(M, false);
+        sel.resize(n_sel);
+    }
+    catch (const std::bad_alloc &) { delete p; return LORAHIP_E_NOMEM; }
     for (size_t j = 0; j < n_taps; j++) h[j] = taps[j];
-    const std::vector<float2> tw = bankTwiddleTable(M, false);
-    std::vector<int> sel(n_sel);
     for (size_t i = 0; i < n_sel; i++) sel[i] = bankPlace(M, bins ? bankBin(M, bins[i]) : int(i));
-    const DeviceGuard guard(ctx->device);
-    const size_t histBytes = size_t(p->HC) * sizeof(float2);
-    hipError_t e = p->dTaps.grow(h.size() * sizeof(float));
-    if (e == hipSuccess) e = p->dTw.grow(tw.size() * sizeof(float2));
-    if (e == hipSuccess) e = p->dSel.grow(sel.size() * sizeof(int));
-    if (e == hipSuccess) e = p->dHist[0].grow(histBytes);
-    if (e == hipSuccess) e = p->dHist[1].grow(histBytes);
-    if (e != hipSuccess) { delete p; return LORAHIP_E_NOMEM; }
-    e = hipMemcpy(p->dTaps.get(), h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->dTw.get(), tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->dSel.get(), sel.data(), sel.size() * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(p->dHist[0].get(), 0, histBytes);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { delete p; return hipFail(e, "polyphase channeliser table upload"); }
-    *out = p;
-    return LORAHIP_OK;
+    return uploadTables(out, p, "polyphase channeliser", size_t(p->HC), p->dTaps, h.data(), h.size(), p->dTw, tw.data(), tw.size(),
+                        p->dSel, sel.data(), sel.size());
 }
 
 } // namespace lorahip
@@ -327,16 +297,13 @@ int lorahip_pfb_reset(lorahip_pfb *p)
 {
     if (p == nullptr) return LORAHIP_E_INVALID;
     const DeviceGuard guard(p->ctx->device);
-    LORAHIP_TRY(hipMemsetAsync(p->dHist[p->cur].get(), 0, size_t(p->HC) * sizeof(float2), p->ctx->stream));
-    p->n0 = 0;
+    LORAHIP_TRY(p->carry.reset(p->ctx->stream));
     return LORAHIP_OK;
 }
 
 size_t lorahip_pfb_out_count(const lorahip_pfb *p, const size_t n_in)
 {
-    if (p == nullptr) return 0;
-    const unsigned long long D = (unsigned long long)p->D;
-    return size_t((p->n0 + n_in) / D - p->n0 / D);
+    return p == nullptr ? 0 : decimatedCount(p->carry.n0, n_in, p->D);
 }
 
 int lorahip_pfb_run(lorahip_pfb *p, const float *wide_dev, const size_t n_in, float *out_dev, const size_t out_stride, size_t *n_out)

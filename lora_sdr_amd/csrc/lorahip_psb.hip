@@ -46,9 +46,7 @@ struct lorahip_psb
     lorahip::DevBuf<int> dBinRow;               // [K]
     lorahip::DevBuf<float> dBinGain;            // [K] the gain of that row
     lorahip::DevBuf<float2> dWs;                // [segment][M] u_s[m] of the segment in flight
-    lorahip::DevBuf<float2> dHist[2];           // [HC][M] u_s[m] of the HC input times before n0 (zeros before the start of the stream)
-    int cur;
-    unsigned long long n0;                      // input times consumed since the last reset
+    lorahip::StreamCarry carry;                 // [HC][M] u_s[m] of the HC input times before n0
 };
 
 namespace lorahip {
@@ -212,14 +210,13 @@ static int psbRun(lorahip_psb *p, const float2 *in, const size_t inStride, const
     for (size_t done = 0; done < nIn; )
     {
         const size_t cnt = nIn - done < seg ? nIn - done : seg;
-        a.in = in + done; a.cnt = int(cnt); a.m0 = (long long)p->n0;
-        a.hist = p->dHist[p->cur].get();
+        a.in = in + done; a.cnt = int(cnt); a.m0 = (long long)p->carry.n0;
+        a.hist = p->carry.current();
         a.out = out + done * U;
-        float2 *newHist = p->dHist[p->cur ^ 1].get();
+        float2 *newHist = p->carry.next();
         const hipError_t e = bankDispatch(p->M, BankCounts(), [&](const auto m) { return psbLaunch<decltype(m)::value>(p, a, newHist); });
         LORAHIP_TRY(e);
-        if (p->HC) p->cur ^= 1;
-        p->n0 += cnt;
+        p->carry.advance(cnt);
         done += cnt;
     }
     if (nOutP) *nOutP = nIn * U;
@@ -255,7 +252,6 @@ static int psbCreate(const bool radix5, lorahip_psb **out, lorahip_ctx *ctx, con
     p->ldsBytes = (size_t(p->T) * size_t(M + 1) + size_t(bankTwiddles(M))) * sizeof(float2);
     const size_t byWs = PSB_WS_POINTS / size_t(M), byOut = PSB_SEG_OUTPUTS / interp;
     p->seg = byWs < byOut ? byWs : byOut;
-    p->cur = 0; p->n0 = 0;
 
     std::vector<float2> tw;
     std::vector<int> start, row;
@@ -281,26 +277,8 @@ static int psbCreate(const bool radix5, lorahip_psb **out, lorahip_ctx *ctx, con
             g[size_t(e)] = gain ? gain[k] : 1.0f;
         }
     }
-    const DeviceGuard guard(ctx->device);
-    const size_t histBytes = size_t(p->HC) * size_t(M) * sizeof(float2);
-    hipError_t e = p->dTaps.grow(n_taps * sizeof(float));
-    if (e == hipSuccess) e = p->dTw.grow(tw.size() * sizeof(float2));
-    if (e == hipSuccess) e = p->dBinStart.grow(start.size() * sizeof(int));
-    if (e == hipSuccess) e = p->dBinRow.grow(row.size() * sizeof(int));
-    if (e == hipSuccess) e = p->dBinGain.grow(g.size() * sizeof(float));
-    if (e == hipSuccess) e = p->dHist[0].grow(histBytes);
-    if (e == hipSuccess) e = p->dHist[1].grow(histBytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); delete p; return LORAHIP_E_NOMEM; }
-    e = hipMemcpy(p->dTaps.get(), taps, n_taps * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->dTw.get(), tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->dBinStart.get(), start.data(), start.size() * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->dBinRow.get(), row.data(), row.size() * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->dBinGain.get(), g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess && histBytes) e = hipMemset(p->dHist[0].get(), 0, histBytes);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { delete p; return hipFail(e, "polyphase synthesiser table upload"); }
-    *out = p;
-    return LORAHIP_OK;
+    return uploadTables(out, p, "polyphase synthesiser", size_t(p->HC) * size_t(M), p->dTaps, taps, n_taps, p->dTw, tw.data(), tw.size(),
+                        p->dBinStart, start.data(), start.size(), p->dBinRow, row.data(), row.size(), p->dBinGain, g.data(), g.size());
 }
 
 } // namespace lorahip
@@ -342,8 +320,7 @@ int lorahip_psb_reset(lorahip_psb *p)
 {
     if (p == nullptr) return LORAHIP_E_INVALID;
     const DeviceGuard guard(p->ctx->device);
-    if (p->HC) LORAHIP_TRY(hipMemsetAsync(p->dHist[p->cur].get(), 0, size_t(p->HC) * size_t(p->M) * sizeof(float2), p->ctx->stream));
-    p->n0 = 0;
+    LORAHIP_TRY(p->carry.reset(p->ctx->stream));
     return LORAHIP_OK;
 }
 

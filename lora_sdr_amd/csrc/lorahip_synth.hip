@@ -15,7 +15,7 @@
 // the 256 places inside it): nothing depends on how the stream was cut into calls, and nothing drifts.
 // Stores: a lane's 8 outputs are 64 contiguous bytes, lanes lie U * 8 bytes apart: four 16-byte stores per lane, back to back
 // (DESIGN.md has the reasoning and what was measured).
-#include "lorahip_own.h"
+#include "lorahip_frontend.h"
 #include "lorahip_mixer.h"
 #include <cmath>
 #include <new>
@@ -29,9 +29,7 @@ struct lorahip_synthesizer
     lorahip::DevBuf<float2> dTaps;              // [nGroups*8][I][UP] (+ a pad row): g_k[p + i U] at [k][i][p], zero where p + i U >= L or p >= U
     lorahip::DevBuf<unsigned long long> dWU;    // [nGroups*8] w_k * U mod 2^64: the phase step of one input time
     lorahip::DevBuf<float2> dRot;               // [nGroups*8][256] e^{+2 pi i frac(w_k U t / 2^64)}
-    lorahip::DevBuf<float2> dHist[2];           // [K][HC] the HC input samples of every channel before n0 (zeros before the start)
-    int cur;
-    unsigned long long n0;                      // input samples per channel consumed since the last reset
+    lorahip::StreamCarry carry;                 // [K][HC] the HC input samples of every channel before n0
 };
 
 namespace lorahip {
@@ -210,12 +208,12 @@ static int synthRun(lorahip_synthesizer *s, const float2 *in, const size_t inStr
     if (inStride < nIn) { setLastError("synthesiser: in_stride is shorter than n_in"); return LORAHIP_E_INVALID; }
     const size_t nOut = nIn * size_t(s->U);
     if (nOut > (size_t(1) << 30)) { setLastError("synthesiser: more than 2^30 outputs in one call"); return LORAHIP_E_INVALID; }
-    const size_t nBlocks = size_t(s->nPB) * ((s->n0 % SYN_THREADS + nIn + SYN_THREADS - 1) / SYN_THREADS);
+    const size_t nBlocks = size_t(s->nPB) * ((s->carry.n0 % SYN_THREADS + nIn + SYN_THREADS - 1) / SYN_THREADS);
     if (nBlocks > 0x7fffffffu) { setLastError("synthesiser: tiles x phase blocks of one call exceed the launch grid"); return LORAHIP_E_INVALID; }
     SynthArgs a;
     a.in = in; a.inStride = (long long)inStride; a.nIn = (long long)nIn;
-    a.hist = s->dHist[s->cur].get();
-    a.n0 = (long long)s->n0;
+    a.hist = s->carry.current();
+    a.n0 = (long long)s->carry.n0;
     a.taps = reinterpret_cast<const v2f *>(s->dTaps.get());
     a.wU = s->dWU.get();
     a.laneRot = reinterpret_cast<const v2f *>(s->dRot.get());
@@ -229,11 +227,10 @@ static int synthRun(lorahip_synthesizer *s, const float2 *in, const size_t inStr
     if (s->HC)
     {
         const unsigned ky = unsigned(s->K < 65535 ? s->K : 65535), kz = unsigned((s->K + 65534) / 65535);
-        hipLaunchKernelGGL(synthHistory, dim3((s->HC + 255) / 256, ky, kz), dim3(256), 0, ctx->stream, a, s->dHist[s->cur ^ 1].get());
+        hipLaunchKernelGGL(synthHistory, dim3((s->HC + 255) / 256, ky, kz), dim3(256), 0, ctx->stream, a, s->carry.next());
         LORAHIP_TRY(hipGetLastError());
-        s->cur ^= 1;
     }
-    s->n0 += nIn;
+    s->carry.advance(nIn);
     if (nOutP) *nOutP = nOut;
     return LORAHIP_OK;
 }
@@ -272,7 +269,7 @@ int lorahip_synthesizer_create(lorahip_synthesizer **out, lorahip_ctx *ctx, cons
     s->ctx = ctx; s->K = int(n_channels); s->L = L; s->U = U; s->I = I; s->HC = HC; s->TS = TS; s->nBlk = nBlk;
     s->nPB = (U + SYN_P - 1) / SYN_P; s->UP = s->nPB * SYN_P;
     s->nGroups = int((n_channels + SYN_KG - 1) / SYN_KG);
-    s->ldsBytes = lds; s->cur = 0; s->n0 = 0;
+    s->ldsBytes = lds;
 
     const size_t KP = size_t(s->nGroups) * SYN_KG, UP = size_t(s->UP);
     std::vector<unsigned long long> wU;
@@ -301,22 +298,8 @@ int lorahip_synthesizer_create(lorahip_synthesizer **out, lorahip_ctx *ctx, cons
             rot[k * SYN_THREADS + size_t(t)] = make_float2(float(std::cos(ang)), float(std::sin(ang)));
         }
     }
-    const DeviceGuard guard(ctx->device);
-    const size_t histBytes = size_t(n_channels) * size_t(HC) * sizeof(float2);
-    hipError_t e = s->dTaps.grow(g.size() * sizeof(float2));
-    if (e == hipSuccess) e = s->dWU.grow(wU.size() * sizeof(unsigned long long));
-    if (e == hipSuccess) e = s->dRot.grow(rot.size() * sizeof(float2));
-    if (e == hipSuccess) e = s->dHist[0].grow(histBytes);
-    if (e == hipSuccess) e = s->dHist[1].grow(histBytes);
-    if (e != hipSuccess) { delete s; return LORAHIP_E_NOMEM; }
-    e = hipMemcpy(s->dTaps.get(), g.data(), g.size() * sizeof(float2), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(s->dWU.get(), wU.data(), wU.size() * sizeof(unsigned long long), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(s->dRot.get(), rot.data(), rot.size() * sizeof(float2), hipMemcpyHostToDevice);
-    if (e == hipSuccess && histBytes) e = hipMemset(s->dHist[0].get(), 0, histBytes);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { delete s; return hipFail(e, "synthesiser table upload"); }
-    *out = s;
-    return LORAHIP_OK;
+    return uploadTables(out, s, "synthesiser", size_t(n_channels) * size_t(HC), s->dTaps, g.data(), g.size(), s->dWU, wU.data(), wU.size(),
+                        s->dRot, rot.data(), rot.size());
 }
 
 void lorahip_synthesizer_destroy(lorahip_synthesizer *s)
@@ -330,8 +313,7 @@ int lorahip_synthesizer_reset(lorahip_synthesizer *s)
 {
     if (s == nullptr) return LORAHIP_E_INVALID;
     const DeviceGuard guard(s->ctx->device);
-    if (s->HC) LORAHIP_TRY(hipMemsetAsync(s->dHist[s->cur].get(), 0, size_t(s->K) * size_t(s->HC) * sizeof(float2), s->ctx->stream));
-    s->n0 = 0;
+    LORAHIP_TRY(s->carry.reset(s->ctx->stream));
     return LORAHIP_OK;
 }
 
