@@ -124,3 +124,51 @@ def test_fold_and_fft_is_the_direct_form_for_these_bin_counts(M, D, L):
     print("M %d D %d L %d: err / scale %.3g" % (M, D, L, err))
     assert err <= 1e-9
     assert float(np.abs(want).max()) > 0.0
+
+
+DEEP = ((1 << 31) + 12345, (1 << 32) + 54321)      # where tests/test_gpu_bank5_edges.py puts its noise
+
+
+@pytest.mark.parametrize("M,D,L", [(5, 8, 37), (40, 64, 323), (320, 512, 700)])
+def test_n0_is_that_many_explicit_zeros(M, D, L):
+    """channelize(x, n0 = k) is channelize(k zeros + x) without the outputs of the zeros: k a multiple of M and of D, a multiple of D
+    but not of M, and a multiple of neither; a short stream, all bins and some beyond +-M"""
+    rng = np.random.default_rng(M + D)
+    n = 3 * D + L + 5
+    x = rng.standard_normal(n) + 1j * rng.standard_normal(n)
+    h = rng.uniform(-1.0, 1.0, L)
+    bins = np.concatenate([np.arange(min(M, 12)), [M - 1, -1, -3 * M - 2, M + 4]]).astype(np.int64)
+    starts = (M * D, M * D + D, 2 * M + 3)
+    assert [(k % M == 0, k % D == 0) for k in starts] == [(True, True), (False, True), (False, False)]
+    assert np.array_equal(pd.channelize(x, M, D, h, bins, n0=0), pd.channelize(x, M, D, h, bins))
+    for k in starts:
+        got = pd.channelize(x, M, D, h, bins, n0=k)
+        want = pd.channelize(np.concatenate([np.zeros(k), x]), M, D, h, bins)[:, k // D:]
+        assert got.shape == want.shape == (bins.size, (k + n) // D - k // D)
+        assert np.array_equal(pd.out_times(n, D, k), np.arange(k // D, (k + n) // D))
+        err = float(np.abs(got - want).max()) / pd.scale(x, h)
+        print("M %d D %d L %d n0 %d: err / scale %.3g" % (M, D, L, k, err))
+        assert err <= 1e-12
+        assert float(np.abs(want).max()) > 0.0
+
+
+def test_the_deep_positions_can_show_a_32_bit_position():
+    """pure integers: 2^32 = 1 and 2^31 = 3 (mod 5), so a stream position cut to 32 bits (unsigned, from 2^32 on; signed, from 2^31
+    on) or to 31 bits moves every residue n mod M the definition takes -- at every sample of the stretches the GPU test compares, for
+    every radix-5 bin count. (For a power of two none of them moves.)"""
+    for n0 in DEEP:
+        n = n0 + np.arange(3 * 256 * 512 + 5, dtype=np.int64)          # beyond the longest stretch compared
+        assert n.dtype == np.int64 and int(n[-1]) == n0 + 3 * 256 * 512 + 4
+        cut = {"uint32": n & 0xFFFFFFFF, "int32": ((n + (1 << 31)) & 0xFFFFFFFF) - (1 << 31), "31 bits": n & 0x7FFFFFFF}
+        assert np.array_equal(cut["int32"], n.astype(np.int32).astype(np.int64))
+        for M in RADIX5:
+            true = pd.residues(n, M)
+            assert true.min() == 0 and true.max() == M - 1
+            assert int(true[0]) == n0 % M                              # Python's own integers
+            for name, t in cut.items():
+                if name == "uint32" and n0 < 1 << 32:
+                    assert np.array_equal(pd.residues(t, M), true)     # nothing is cut yet: the second position is there for this one
+                else:
+                    assert np.all(pd.residues(t, M) != true), (n0, M, name)
+        for M in (8, 64, 1024):
+            assert all(np.array_equal(pd.residues(t, M), pd.residues(n, M)) for t in cut.values())

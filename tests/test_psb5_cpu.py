@@ -114,3 +114,56 @@ def test_gather_fft_fold_is_the_direct_form_for_these_bin_counts(M, U, L):
     assert float(np.abs(want).max()) > 0.0
     if L < U:
         assert np.all(got.reshape(n, U)[:, L:] == 0)
+
+
+DEEP = ((1 << 31) + 12345, (1 << 32) + 54321)      # the input times where tests/test_gpu_bank5_edges.py puts its noise
+
+
+@pytest.mark.parametrize("M,U,L", [(5, 3, 20), (40, 64, 323), (320, 7, 150)])
+def test_n0_is_that_many_explicit_zeros(M, U, L):
+    """synthesize(rows, n0 = k) is synthesize(k zero input times + rows) without the outputs of the zeros: k a multiple of M, k not a
+    multiple of M, and k with k U no multiple of M either; and synthesize_at, the direct form with the same integer phase, gives the
+    same outputs at either position"""
+    rng = np.random.default_rng(M * 13 + U)
+    K, n = 7, 23
+    x = rng.standard_normal((K, n)) + 1j * rng.standard_normal((K, n))
+    h = rng.uniform(-1.0, 1.0, L)
+    g = rng.uniform(0.25, 2.0, K)
+    bins = rng.integers(-2 * M, 3 * M, K)
+    bins[1] = bins[0] + M                                     # two rows on one bin
+    starts = (3 * M, 3 * M + 1, 2 * M + 3)
+    assert [k % M == 0 for k in starts] == [True, False, False] and (starts[2] * U) % M != 0
+    assert np.array_equal(pd.synthesize(x, M, U, h, bins, g, n0=0), pd.synthesize(x, M, U, h, bins, g))
+    scale = sd.error_scale(x, h, U, g)
+    for k in (0,) + starts:
+        got = pd.synthesize(x, M, U, h, bins, g, n0=k)
+        want = pd.synthesize(np.concatenate([np.zeros((K, k)), x], axis=1), M, U, h, bins, g)[k * U:]
+        assert got.shape == want.shape == (n * U,)
+        at = pd.synthesize_at(x, M, U, h, bins, g, n=k * U + np.arange(n * U, dtype=np.int64), n0=k)
+        err = float(np.abs(got - want).max()) / scale
+        err_at = float(np.abs(at - want).max()) / scale
+        print("M %d U %d L %d n0 %d: err / scale %.3g, the direct form %.3g" % (M, U, L, k, err, err_at))
+        assert err <= 1e-12 and err_at <= 1e-12
+        assert float(np.abs(want).max()) > 0.0
+
+
+def test_the_deep_positions_can_show_a_32_bit_position():
+    """pure integers: the residue of output n = m U + p is (m U + p) mod M; with the input time m cut to 32 bits (unsigned, from
+    2^32 on; signed, from 2^31 on) or to 31 bits it moves by 2^32 U or 2^31 U, which is no multiple of 5 for the U = 3 of the GPU
+    test -- at every output of the stretches compared there, for M = 5 and 10. (U = 5 would hide it, and so would a power of two.)"""
+    U = 3
+    for m0 in DEEP:
+        m = m0 + np.arange(3 * 256 + 5, dtype=np.int64)
+        cut = {"uint32": m & 0xFFFFFFFF, "int32": ((m + (1 << 31)) & 0xFFFFFFFF) - (1 << 31), "31 bits": m & 0x7FFFFFFF}
+        assert np.array_equal(cut["int32"], m.astype(np.int32).astype(np.int64))
+        for M in (5, 10):
+            for p in range(U):
+                true = pd.residues(m * U + p, M)
+                assert int(true[0]) == (m0 * U + p) % M        # Python's own integers
+                for name, t in cut.items():
+                    if name == "uint32" and m0 < 1 << 32:
+                        assert np.array_equal(pd.residues(t * U + p, M), true)     # nothing is cut yet: the second position is there for this
+                    else:
+                        assert np.all(pd.residues(t * U + p, M) != true), (m0, M, p, name)
+            assert np.array_equal(pd.residues(cut["uint32"] * 5, M), pd.residues(m * 5, M))
+        assert all(np.array_equal(pd.residues(t * U, 64), pd.residues(m * U, 64)) for t in cut.values())
