@@ -535,6 +535,136 @@ __device__ __forceinline__ int laneScan(BIN bin, float &bestV, double &tot)
     return cj[0];
 }
 
+/***********************************************************************
+ * The same arg-max through 64-bit MAX KEYS (the launch-uniform batch kernels, FastCore::scan). |X|^2 = re*re + im*im is never
+ * negative unless it is NaN, so its bit pattern orders like its value, and a 64-bit pattern with sign bit 0 orders like the positive
+ * double it spells. The key of a bin is the register pair (lo, hi) = (last bin - bin, bits of |X|^2) read as a double: the maximum
+ * of the keys (v_max_f64, one instruction where the scan spends a compare and two selects) is the largest |X|^2 and, among equal
+ * ones, the largest lo = the LOWEST bin -- the reference's strict '>' from index 0 (LoRaDetector.hpp:43). An all-zero window
+ * yields bin 0 with value 0. Keys of small |X|^2 are fp64 subnormals: the kernels run with fp64 denormals kept (HIP's default,
+ * .amdhsa_float_denorm_mode_16_64 3). A NaN |X|^2 has a large pattern and would win where the reference never takes a NaN: the
+ * caller sends a wavefront that holds one to laneScan instead (see FastCore::scan).
+ **********************************************************************/
+// Which launch-uniform instances scan through keys, as bit masks over SF (tools/build_variant.py -DLORAHIP_SCAN_KEYS=0 is the A/B;
+// profiles/r07 has the pairs). SF7 and SF8 cleared the shipping bar; SF6 (bimodal run to run), SF9 (no difference) and SF10 (+1.8 %)
+// keep the compare-and-select scan.
+#ifndef LORAHIP_SCAN_KEYS
+#define LORAHIP_SCAN_KEYS 0x180         // bit SF: the launch-uniform instances of that SF scan through max keys
+#endif
+// Where the low key words live. Set: sixteen loop-invariant registers, |X|^2 is added straight into the register beside its word
+// (nothing per bin but the maximum) -- for an instance whose budget has the sixteen to spare (SF7: 142 -> 168 registers, the budget of
+// three wavefronts per SIMD, no scratch; SF8 / SF9 / SF10 would spill 68..152 B). Clear: one integer add per bin writes the word.
+#ifndef LORAHIP_SCAN_KEYS_INV
+#define LORAHIP_SCAN_KEYS_INV 0x080
+#endif
+__device__ __forceinline__ double maxKey(const double a, const double b)
+{
+    // (__builtin_fmax canonicalises both operands first under IEEE mode: three instructions a maximum)
+    double r;
+    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+//! (p.x + p.y, p.y + p.x)
+__device__ __forceinline__ v2f sumBothV(const v2f p)
+{
+    v2f r;
+    asm("v_pk_add_f32 %0, %1, %1 op_sel:[0,1] op_sel_hi:[1,0]" : "=v"(r) : "v"(p));
+    return r;
+}
+__device__ __forceinline__ double makeKey(const float v, const int lo) { return __hiloint2double(__float_as_int(v), lo); }
+
+/*! laneScan<CNT, 4> through keys: the same four fp64 total chains over consecutive quarters and the same pairwise merges (the
+ * total's bits do not change), the arg-max as a tree of key maxima -- a level's maxima are independent of each other, and the
+ * total's merges sit between the last levels, so that few asm results feed the very next instruction (the rule above mulLoV).
+ * lo(j) is the low key word of bin(j): larger for lower bins. SPLIT: lo(j) are loop-invariant registers of the caller (see
+ * LORAHIP_SCAN_KEYS_INV). Returns the lane's best key. */
+template <int CNT, bool SPLIT = false, class BIN, class LO>
+__device__ __forceinline__ double laneScanKeys(BIN bin, LO lo, double &tot)
+{
+    constexpr int CH = 4, PER = CNT / CH;
+    static_assert(CNT >= 2 * CH && (CNT & (CNT - 1)) == 0, "four chains over a power of two of bins");
+    double key[CNT], ct[CH];
+#pragma unroll
+    for (int k = 0; k < PER; k++)
+    {
+#ifdef LORAHIP_FMA
+#pragma unroll
+        for (int c = 0; c < CH; c++)
+        {
+            const int j = c * PER + k;
+            const v2f b = bin(j);
+            const float mag2 = __builtin_fmaf(b.x, b.x, b.y * b.y);
+            ct[c] = k ? ct[c] + (double)mag2 : (double)mag2;
+            key[j] = makeKey(mag2, lo(j));
+        }
+#else
+        // |X|^2 into BOTH halves of a register pair (x*x + y*y and y*y + x*x: the same sum): the high half is the key's value word
+        // where it stands, the low half feeds the total and then takes the index word. Four bins a round, so that no asm result
+        // feeds the next instruction.
+        v2f mm[CH];
+#pragma unroll
+        for (int c = 0; c < CH; c++) { const v2f b = bin(c * PER + k); mm[c] = b * b; }
+        if constexpr (SPLIT)
+        {
+            // the index words are the caller's loop-invariant registers: |X|^2 goes straight into the register beside its word
+            float m[CH];
+#pragma unroll
+            for (int c = 0; c < CH; c++) asm("v_add_f32 %0, %1, %2" : "=v"(m[c]) : "v"(mm[c].x), "v"(mm[c].y));
+#pragma unroll
+            for (int c = 0; c < CH; c++) ct[c] = k ? ct[c] + (double)m[c] : (double)m[c];
+#pragma unroll
+            for (int c = 0; c < CH; c++) key[c * PER + k] = makeKey(m[c], lo(c * PER + k));
+            continue;
+        }
+#pragma unroll
+        for (int c = 0; c < CH; c++) mm[c] = sumBothV(mm[c]);
+        // (a chain starts from its first addend: 0.0 + x == x, |X|^2 is never -0)
+#pragma unroll
+        for (int c = 0; c < CH; c++) ct[c] = k ? ct[c] + (double)mm[c].x : (double)mm[c].x;
+#pragma unroll
+        for (int c = 0; c < CH; c++) key[c * PER + k] = __hiloint2double(__float_as_int(mm[c].y), lo(c * PER + k));
+#endif
+    }
+#pragma unroll
+    for (int w = 1; w < CNT / 4; w <<= 1)
+#pragma unroll
+        for (int j = 0; j + w < CNT; j += 2 * w) key[j] = maxKey(key[j], key[j + w]);
+    // four keys left (0, CNT/4, CNT/2, 3 CNT/4)
+    key[0] = maxKey(key[0], key[CNT / 4]);
+    ct[0] += ct[1];
+    key[CNT / 2] = maxKey(key[CNT / 2], key[3 * CNT / 4]);
+    ct[2] += ct[3];
+    tot = ct[0] + ct[2];
+    return maxKey(key[0], key[CNT / 2]);
+}
+
+//! maximum of a key and groupSumF64 of a total over the aligned group of T lanes in one pass, results in every lane: per step the partners' words of both (DPP row permutations up to 16
+//! lanes, v_permlane16/32_swap above), one v_max_f64 and one v_add_f64 -- the two chains fill each other's wait states. The sum is
+//! groupSumF64's own pairing tree: the same bits.
+template <int T>
+__device__ __forceinline__ void groupMaxKeySumF64(double &key, double &tot)
+{
+#define LORAHIP_KEY_DPP(CTRL) { const unsigned kl_ = __builtin_amdgcn_mov_dpp((unsigned)__double2loint(key), CTRL, 0xf, 0xf, false), \
+                                               kh_ = __builtin_amdgcn_mov_dpp((unsigned)__double2hiint(key), CTRL, 0xf, 0xf, false), \
+                                               tl_ = __builtin_amdgcn_mov_dpp((unsigned)__double2loint(tot), CTRL, 0xf, 0xf, false), \
+                                               th_ = __builtin_amdgcn_mov_dpp((unsigned)__double2hiint(tot), CTRL, 0xf, 0xf, false); \
+                                key = maxKey(key, __hiloint2double((int)kh_, (int)kl_)); tot += __hiloint2double((int)th_, (int)tl_); }
+    if (T >= 2) LORAHIP_KEY_DPP(0xB1)       // quad_perm [1,0,3,2]
+    if (T >= 4) LORAHIP_KEY_DPP(0x4E)       // quad_perm [2,3,0,1]
+    if (T >= 8) LORAHIP_KEY_DPP(0x141)      // row_half_mirror
+    if (T >= 16) LORAHIP_KEY_DPP(0x140)     // row_mirror
+#undef LORAHIP_KEY_DPP
+#define LORAHIP_KEY_SWAP(SWAP) { const v2u kl_ = SWAP((unsigned)__double2loint(key), (unsigned)__double2loint(key), false, false), \
+                                           kh_ = SWAP((unsigned)__double2hiint(key), (unsigned)__double2hiint(key), false, false), \
+                                           tl_ = SWAP((unsigned)__double2loint(tot), (unsigned)__double2loint(tot), false, false), \
+                                           th_ = SWAP((unsigned)__double2hiint(tot), (unsigned)__double2hiint(tot), false, false); \
+                                 key = maxKey(__hiloint2double((int)kh_.x, (int)kl_.x), __hiloint2double((int)kh_.y, (int)kl_.y)); \
+                                 tot = __hiloint2double((int)th_.x, (int)tl_.x) + __hiloint2double((int)th_.y, (int)tl_.y); }
+    if (T >= 32) LORAHIP_KEY_SWAP(__builtin_amdgcn_permlane16_swap)
+    if (T >= 64) LORAHIP_KEY_SWAP(__builtin_amdgcn_permlane32_swap)
+#undef LORAHIP_KEY_SWAP
+}
+
 /*! laneScan with the total in fp32: the arg-max part is the reference's scan unchanged (same comparisons, same winner); the total is
  * only good for the streaming kernels' QUICK squelch estimate (squelchQuickF below), never for a value that leaves the kernel. */
 #ifndef LORAHIP_QUICK_SCAN_CHAINS

@@ -375,6 +375,37 @@ struct FastCore
                 for (int g = 0; g < NGL; g++) fftOut[(t + T * g) + (e << BL)] = vl[g][e];
         }
         // element j = e*NGL + g of the lane is bin (t + T g) + (e << BL): ascending in j
+        // (not the register-select neighbours, which keep the bins' registers alive across the scan, nor the 128-register budget of four
+        // wavefronts per SIMD -- profiling variants: they would spill)
+        if constexpr (CHAINS == 4 && ((LORAHIP_SCAN_KEYS >> LOG2N) & 1) != 0 && !C::NB_SELECT && C::WAVES_PER_SIMD <= 3)
+        {
+            // the launch-uniform instances: arg-max through max keys (lorahip_device.h). A bin's low key word is (N - 1) - bin =
+            // a compile-time constant per register minus the lane's t. INV: sixteen loop-invariant registers (the compiler hoists
+            // them). Else one add per bin on a register the compiler cannot see through -- or it hoists the words all the same
+            // and copies every |X|^2 beside them: the registers of the one form and the instructions of the other.
+            constexpr bool INV = ((LORAHIP_SCAN_KEYS_INV >> LOG2N) & 1) != 0;
+            if (INV) __builtin_amdgcn_sched_barrier(0);      // the stores of F first: moved down among the maxima they keep the bins' registers alive
+            int negT = -t;
+            if (!INV) asm volatile("" : "+v"(negT));
+            double laneKey = laneScanKeys<GL * NGL, INV>([&](const int j) { return vl[j % NGL][j / NGL]; },
+                                                    [&](const int j) { return ((N - 1) - (T * (j % NGL) + ((j / NGL) << BL))) + negT; }, tot);
+            // a lane's partial total is NaN exactly when one of its |X|^2 is (the addends are >= 0 or NaN: no Inf - Inf)
+            if (__any(tot != tot))
+            {
+                // cold: some window of this wavefront holds a NaN, which the reference's scan never takes -- the lanes' keys from the
+                // compare-and-select scan for the whole wavefront, over the lane's own bins read back from F where they are staged
+                // (so that the bins' registers are free while the keys are reduced)
+                constexpr bool FROM_F = STORE_F;
+                float v;
+                const int bestJ = laneScan<GL * NGL, CHAINS>([&](const int j) { return FROM_F ? F[(t + T * (j % NGL)) + ((j / NGL) << BL)] : vl[j % NGL][j / NGL]; }, v, tot);
+                laneKey = makeKey(v, v > 0.0f ? (N - 1) - ((t + T * (bestJ & (NGL - 1))) + ((bestJ / NGL) << BL)) : N - 1);
+            }
+            groupMaxKeySumF64<T>(laneKey, tot);
+            bestV = __int_as_float(__double2hiint(laneKey));
+            bestI = (N - 1) - __double2loint(laneKey);
+            if (!(bestV > 0.0f)) bestI = 0;
+            return;
+        }
         const int bestJ = laneScan<GL * NGL, CHAINS>([&](const int j) { return vl[j % NGL][j / NGL]; }, bestV, tot);
         bestI = (t + T * (bestJ & (NGL - 1))) + ((bestJ / NGL) << BL);
         if (!(bestV > 0.0f)) bestI = 0;

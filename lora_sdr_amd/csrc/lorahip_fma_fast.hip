@@ -5,6 +5,8 @@
 //
 // The whole translation unit lives in its own namespace (the kernels' mangled names must differ from the exact build's).
 #define LORAHIP_FMA 1
+// (the bin scan's index words by integer add at every SF: with sixteen of them in loop-invariant registers this build's SF7 instance spills 8 B)
+#define LORAHIP_SCAN_KEYS_INV 0
 #define lorahip lorahip_fma
 #include "lorahip_fast.hip"
 #undef lorahip
