@@ -85,18 +85,7 @@ static int fillContext(lorahip_ctx *ctx, const int device, const int sf)
     HostTables t;
     buildHostTables(sf, t, true);
     const size_t nb = ctx->N * sizeof(cf32);
-    {
-        // LORAHIP_PART_PRIORITY=1 (a measurement: profiles/r06): the stream of a context at SF11 / 12 above, at SF7 / 8 below the
-        // others -- in a mixed object the long windows' launches then get the device first and their tail starts earliest
-        static const bool byPrio = std::getenv("LORAHIP_PART_PRIORITY") != nullptr;
-        int least = 0, greatest = 0;
-        if (byPrio && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
-        {
-            const int prio = sf >= 11 ? greatest : (sf <= 8 ? least : (least + greatest) / 2);
-            LORAHIP_TRY(ctx->ownStream.ensure(hipStreamNonBlocking, &prio));
-        }
-        else LORAHIP_TRY(ctx->ownStream.ensure(hipStreamNonBlocking));
-    }
+    LORAHIP_TRY(ctx->ownStream.ensure(hipStreamNonBlocking));
     ctx->stream = ctx->ownStream.get();
     LORAHIP_TRY(ctx->ev0.ensure());
     LORAHIP_TRY(ctx->ev1.ensure());

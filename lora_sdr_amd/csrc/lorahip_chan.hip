@@ -197,16 +197,10 @@ __global__ __launch_bounds__(CHAN_THREADS) void channelize(const ChanArgs a)
         unsigned offB;
         g += 2 * CHAN_KG; op += 2;
         tapWait<RM>(gA, xA, offA);
-#ifdef LORAHIP_CHAN_EXP_NOLOAD
-        gB = gA; xB = xA; offB = offA;
-#else
         tapIssue<RM>(gB, xB, offB, g - CHAN_KG, op, lds0 + offA);
-#endif
         tapFma<RM>(acc, gA, xA);
         tapWait<RM>(gB, xB, offB);
-#ifndef LORAHIP_CHAN_EXP_NOLOAD
         tapIssue<RM>(gA, xA, offA, g, op + 1, lds0 + offB);
-#endif
         tapFma<RM>(acc, gB, xB);
     }
     tapWait<RM>(gA, xA, offA);                              // nothing may still be in flight when the registers are reused
@@ -321,7 +315,6 @@ int lorahip_channelizer_create(lorahip_channelizer **out, lorahip_ctx *ctx, cons
                                          // the sample is the same however the stream is cut
     // two output times per lane when the tile fits 64 KiB, one otherwise; the LDS limit is 160 KiB per workgroup
     int RM = 2, QP = 0;
-    if (const char *e = std::getenv("LORAHIP_CHAN_RM")) { if (std::atoi(e) == 1) RM = 1; }      // measurement hook
     size_t lds = 0;
     for (; RM >= 1; RM--)
     {

@@ -853,12 +853,7 @@ static int runStream(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
     }
 
     StreamLayout L;
-    long rowPad = 0;
-#ifdef LORAHIP_ALL_VARIANTS
-    // measurement hook of the profiling build only (tools/row_stride.sh): extra entries per symbol row; never fewer than cap + carryCap
-    if (const char *e = std::getenv("LORAHIP_SYM_PAD")) { const long v = std::atol(e); if (v >= 0 && v < (1 << 20)) rowPad = v; }
-#endif
-    L.make(B, cap, capPkt, dm->tracing, size_t(long(useDevCarry ? dm->carryCap : 0) + rowPad), dm->wantSignals);
+    L.make(B, cap, capPkt, dm->tracing, useDevCarry ? dm->carryCap : 0, dm->wantSignals);
     if (L.total > dm->sDev.bytes())
     {
         { const int rc = syncMirrors(dm); if (rc != LORAHIP_OK) return rc; }      // the pinned copy of the state goes away with the buffers
@@ -958,9 +953,6 @@ static int runStream(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
     // first launch of the run: every channel starts at sample 0, call 0 (unless the run continues the streams), behind its open packet's
     // symbols, and leaves the packet it is inside at the end in the carry rows
     a.flags = (cont ? 0 : 1) | (activate ? 2 : 0) | (useDevCarry ? 4 | 8 : 0);
-#if defined(LORAHIP_ALL_VARIANTS) || defined(LORAHIP_STREAM_PERSIST)
-    if (const char *e = std::getenv("LORAHIP_STREAM_BLOCKS")) a.maxBlocks = std::atoi(e);        // e.g. 512: two workgroups of 256 threads per CU
-#endif
     if (activate) dm->activatePending = false;        // applied by the kernel when it loads the state
     dm->devStateFresh = false;                        // until the run has completed
     dm->mirrorsStale = true;
@@ -1544,7 +1536,6 @@ static int residentStep(lorahip_demod *dm, const float *iqDev, const size_t rowS
         a.maxBlocks = 0; a.lanes = -1;
         a.res = R.ctl.get(); a.resHost = static_cast<ResidentHost *>(hostDev); a.resWatchdog = kResidentWatchdog; a.resRecStride = L.total;
         if (const char *e = std::getenv("LORAHIP_RESIDENT_DEBUG")) a.resDebug = unsigned(std::atoi(e));     // (the step whose stamps every wavefront leaves)
-        if (const char *e = std::getenv("LORAHIP_RESIDENT_SLEEP")) a.resSleep = std::atoi(e);             // (measurements: profiles/r06)
         // behind everything queued on the launch stream (the state of the run before, the cleared control block)
         LORAHIP_TRY(hipEventRecord(R.ev.get(), ctx->stream));
         LORAHIP_TRY(hipStreamWaitEvent(R.run.get(), R.ev.get(), 0));

@@ -115,9 +115,7 @@ __device__ __forceinline__ void frameStep(StreamState &st, const StreamArgs &s, 
     const int next = isFS ? (sync3 ? ST_DOWNCHIRP0 : ST_FRAMESYNC) : (isDA ? (post ? ST_FRAMESYNC : ST_DATASYMBOLS) : stateBefore + 1);
     const int downTable = sync3 ? 1 : (isD1 ? 0 : st.downTable);                                        // :212, :257
 
-#ifndef LORAHIP_TIMING_NO_RECORD_STORES     // timing-only build (profiles/r03): what the per-call record stores cost
     if (writer && isDA) o.symOut[o.nSym] = (short)value;                                                 // out[_symCount++] = value  :290
-#endif
     if (writer && post) { StreamPacket q; q.callIndex = st.callCount; q.len = symCount; o.pktOut[o.nPkt] = q; }   // postMessage  :295-298
     if (o.sigOut)                                                                                        // uniform over the launch
     {

@@ -7,29 +7,10 @@
 #include "lorahip_residentproto.h"
 #include <cstdlib>
 
-#ifndef STREAM_STAGE_BINS
-#define STREAM_STAGE_BINS 0       // untraced path: neighbours by register select (1: all bins staged in LDS whenever a channel is in FRAMESYNC; 1-1.7 % slower, profiles/r03)
-#endif
-#ifndef STREAM_SCAN_CHAINS
-#define STREAM_SCAN_CHAINS 1
-#endif
-#ifndef STREAM_TWLDS
-#define STREAM_TWLDS false      // last-phase twiddles from the LDS table instead of registers (A/B: frees ~30 registers)
-#endif
-#ifndef STREAM_TWLDS9
-#define STREAM_TWLDS9 false
-#endif
-#ifndef LORAHIP_RES_NOCOPY
-#define LORAHIP_RES_NOCOPY 1      // the resident receiver leaves the open packets' symbols in the carry rows (carryIn without the copy; the pack reads them there)
-#endif
-#ifndef STREAM_WPS
-#define STREAM_WPS 2            // wavefronts per SIMD the register budget is set for (3 = 168 VGPRs: A/B builds, profiles/r03)
-#endif
 namespace lorahip {
 
-//! PERSIST: a grid of at most s.maxBlocks workgroups, each looping over channel sets -- for launches over more channels than are
-//! resident at once. The loop costs registers (96 / 112 B of scratch at SF7 / SF9 against 20 / 28), so a launch that fits the
-//! device takes the instance without it (one workgroup per channel set).
+//! One workgroup per channel set: a loop over channel sets costs registers (96 / 112 B of scratch at SF7 / SF9 against 20 / 28), and a
+//! persistent grid built on it lost at SF7 to SF10 (profiles/r04/s22_*).
 //! RES: the resident receiver -- the launch stays, the steps arrive as messages (residentWait / residentStepEnd above). One workgroup
 //! per channel set, all of them resident at once (the launcher checks); s.flags carries the carry bits only.
 //! AHEAD: a channel takes TWO lane groups of the wavefront. The first evaluates the call's window as ever; the second, at the same
@@ -41,12 +22,12 @@ namespace lorahip {
 //! counted. For receivers with fewer channels than the device holds wavefronts (lorahip_stream_pairs.hip): a chain's time is the
 //! time of its passes, and this halves their number where the guess holds. Scheduling only: every call sees the operands it would
 //! have seen alone.
-template <class C, bool PERSIST, bool RES = false, bool AHEAD = false>
+template <class C, bool RES = false, bool AHEAD = false>
 __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD)
 demodStream(const StreamArgs s)
 {
-    static_assert(!(RES && PERSIST), "the resident receiver has one workgroup per channel set");
-    static_assert(!AHEAD || (!RES && !PERSIST && C::WPW >= 2 && C::PREFETCH == 0), "the look-ahead instances: one-launch grids, two lane groups per channel");
+    static_assert(C::PREFETCH == 0, "the window prefetch is not in this kernel (slower: profiles/r05/s6_lanes_prefetch_negative.txt)");
+    static_assert(!AHEAD || (!RES && C::WPW >= 2), "the look-ahead instances: one-launch grids, two lane groups per channel");
     typedef FastCore<C> K;
     constexpr int N = C::N, T = C::T, VEC = C::VEC, R = C::R, WPW = C::WPW;
     constexpr int LOG2T = C::LOG2T;
@@ -97,9 +78,7 @@ demodStream(const StreamArgs s)
     const auto uniI = [](const int v) { return UNI ? __builtin_amdgcn_readfirstlane(v) : v; };
     const auto uniF = [](const float v) { return UNI ? __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(v))) : v; };
 
-    // The grid is PERSISTENT: at most the resident number of workgroups (s.maxBlocks), each walking one set of WAVES * WPW channels
-    // after the other -- the tables above are loaded once, and a launch over more channels than fit the device does not run a second,
-    // half-empty round of workgroups. From here on the wavefronts of a workgroup are independent (no workgroup barrier below).
+    // From here on the wavefronts of a workgroup are independent (no workgroup barrier below).
     const unsigned nSets = (s.nChannels + WAVES * CPW - 1) / (WAVES * CPW);
     // RES: one turn of this loop per receiver step (otherwise exactly one turn). In a step the workgroup walks its channel sets --
     // blockIdx.x, + gridDim.x, ... like a persistent grid -- with the tables it staged once; a channel's state lives in s.state between the
@@ -173,7 +152,7 @@ demodStream(const StreamArgs s)
     }
     const int tc = AHEAD ? t + (roleB ? T : 0) : t;         // lane inside the channel's lanes, TC of them
     constexpr int TC = AHEAD ? 2 * T : T;
-    if (mine) o.carryIn(s, st, cc, tc, TC, !(RES && LORAHIP_RES_NOCOPY));                 // the packet the channel is inside: its symbols so far, from the carry rows
+    if (mine) o.carryIn(s, st, cc, tc, TC, !RES);          // the packet the channel is inside: its symbols so far, from the carry rows (RES: left there, the pack reads them in place)
     if (dbgW && step > 0u && setIdx == 0) s.res->dbg[(step - 1u) & 7u][2] = wall_clock64();
 
     // one window: LoRaDemod.cpp:157-166 + LoRaDetector::detect. Every lane of the wavefront takes part; groups
@@ -198,11 +177,6 @@ demodStream(const StreamArgs s)
 #define TMARK(i)
 #define TMARK_NOWAIT(i)
 #endif
-    // (instances with few points per lane -- the ones for receivers that leave the device partly empty, lorahip_stream_lanes.hip --
-    // keep the NEXT window's samples in registers: C::PREFETCH)
-    constexpr bool PF = C::PREFETCH != 0;
-    v2f xp[PF ? R : 1][PF ? VEC : 1];
-    long long pfOff = -1;
     // the near-threshold counters (StreamArgs::near): a window evaluated ahead is counted when -- and only if -- its call is made
     int nearAhead = 0;
     const auto noteNear = [&](const int which, const bool yes)
@@ -215,18 +189,7 @@ demodStream(const StreamArgs s)
     {
         v2f x[R][VEC];
         TMARK(5);
-        if constexpr (PF)
-        {
-            // the window that was asked for while the call before was still computing (below), if this call reads where that one
-            // guessed it would; the channels of the wave that guessed wrong load now (from lines the guess has brought closer)
-            const bool hit = on && off == pfOff;
-            if (!__all(hit || !on)) K::load(x, gIq + (on ? off : 0), t);
-#pragma unroll
-            for (int r = 0; r < R; r++)
-#pragma unroll
-                for (int u = 0; u < VEC; u++) x[r][u] = hit ? xp[r][u] : x[r][u];
-        }
-        else K::load(x, gIq + (on ? off : 0), t);
+        K::load(x, gIq + (on ? off : 0), t);
         const float d = err * (float)LORAHIP_FINE_STEPS;
         const bool moving = on && d != 0.0f;
         int *sIdx = reinterpret_cast<int *>(X) + wsub * N;
@@ -299,22 +262,7 @@ demodStream(const StreamArgs s)
 
         TMARK(2);
         v2f vl[NGL][GL];
-        K::fft(x, X, wsub, t, sTw, twR, vl, [&]()
-        {
-            if constexpr (PF)
-            {
-                // The chain of a channel exposes the latency of every window's load: call k + 1 reads where call k's result says.
-                // Mostly that is the next window (DATASYMBOLS, the down-chirps, a quiet or an aligned FRAMESYNC call consume N; the
-                // second window of a sync check is the next one too): ask for it now, with this window's samples in the FFT's
-                // registers, so that it arrives while this call computes. A wrong guess (FRAMESYNC on noise: N - value) costs the
-                // request, and the right window then overlaps the guessed one: its lines are already on their way.
-                const bool can = on && off + 2 * N <= base + len;
-                pfOff = can ? off + N : -1;
-                // (unconditional, from the head of the buffer where there is nothing to ask for: behind a branch the compiler no
-                // longer knows how many loads are in flight and waits for ALL of them at the next wait for an older one)
-                K::load(xp, gIq + (can ? off + N : 0), t);
-            }
-        }, &twM);
+        K::fft(x, X, wsub, t, sTw, twR, vl, []() {}, &twM);
         TMARK(3);
         v2f *F = X + wsub * FS;
         float bestV;
@@ -322,10 +270,9 @@ demodStream(const StreamArgs s)
         double tot;
         v2f l, r;
         value = 0;
-        const bool staged = full || (STREAM_STAGE_BINS && __any(on && wantFi != 0));       // bins to LDS for the neighbour fetch (else: register select)
         if (full)
         {
-            K::template scan<true, STREAM_SCAN_CHAINS>(vl, F, nullptr, t, bestV, bestI, tot);
+            K::template scan<true, 1>(vl, F, nullptr, t, bestV, bestI, tot);
             K::neighbours(vl, F, bestI, lane, t, l, r);
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -336,10 +283,10 @@ demodStream(const StreamArgs s)
         else
         {
             // no fp64 total on this path: the squelch estimate takes an fp32 one (scanQuick / squelchQuickF, whose `sure` band
-            // accounts for it); the exact total is summed only where the exact chain is evaluated
+            // accounts for it); the exact total is summed only where the exact chain is evaluated. The bins stay in registers and the
+            // neighbours come by register select (staging them in LDS was 1-1.7 % slower, profiles/r03)
             float totF;
-            if (staged) K::template scanQuick<true>(vl, F, t, bestV, bestI, totF);
-            else K::template scanQuick<false>(vl, F, t, bestV, bestI, totF);
+            K::template scanQuick<false>(vl, F, t, bestV, bestI, totF);
             TMARK(6);
             bool sure;
             squelched = squelchQuickF(bestV, totF, s.thresh, K::QUICK_REL_ERR, sure);
@@ -350,19 +297,13 @@ demodStream(const StreamArgs s)
             TMARK(7);
             if (__any(exact || logs || fi))
             {
-                if (staged) K::neighbours(vl, F, bestI, lane, t, l, r);
-                else K::template neighbours<true>(vl, F, bestI, lane, t, l, r);
-                if (staged)
-                {
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                }
+                K::template neighbours<true>(vl, F, bestI, lane, t, l, r);
                 if (__any(exact || logs))
                 {
                     // LoRaDetector.hpp:36-48's double total, in scan()'s association (the bins are still in registers)
                     {
                         float bv_;
-                        (void)laneScan<GL * NGL, STREAM_SCAN_CHAINS>([&](const int j) { return vl[j % NGL][j / NGL]; }, bv_, tot);
+                        (void)laneScan<GL * NGL, 1>([&](const int j) { return vl[j % NGL][j / NGL]; }, bv_, tot);
                         tot = groupSumF64<T>(tot);
                     }
                     tailValuesPaired(s.powerScale, bestV, tot, l, r, lane, power, powerAvg, fIndex);
@@ -397,7 +338,7 @@ demodStream(const StreamArgs s)
     int value0 = 0, fineIdxBefore0 = 0;
     float snr0 = 0.0f, fineErrBefore0 = 0.0f;
     const int slot = wavefrontSlot();
-    const bool lastRound = RES || PERSIST || !LORAHIP_PRIO_HOLD || blockIdx.x >= s.lastRoundFrom;
+    const bool lastRound = RES || !LORAHIP_PRIO_HOLD || blockIdx.x >= s.lastRoundFrom;
     holdPriority<LORAHIP_PRIO_ALTERNATE>(!lastRound);
     while (true)
     {
@@ -537,9 +478,7 @@ demodStream(const StreamArgs s)
                         st.fineTuneIndex = idxEndB;                                                          // :160-162
                         const int symCount = st.symCount + 1;
                         const bool post = (unsigned)symCount >= s.mtu || squelchedB;                         // :291
-#ifndef LORAHIP_TIMING_NO_RECORD_STORES
                         if (tc == 0) o.symOut[o.nSym] = (short)valueB;                                       // out[_symCount++] = value  :290
-#endif
                         if (tc == 0 && post) { StreamPacket q; q.callIndex = st.callCount; q.len = symCount; o.pktOut[o.nPkt] = q; }   // :295-298
                         o.nSym++; o.nPkt += post ? 1 : 0; o.calls++;
                         st.finefreqError = post ? 0.0f : st.finefreqError;                                   // :299
@@ -568,7 +507,7 @@ demodStream(const StreamArgs s)
                tsec[0], tsec[1], tsec[2], tsec[3], tsec[6], tsec[7], tsec[4], 0ull, tsec[8], tsec[9], tsec[5], o.calls, tPasses, (unsigned long long)__builtin_amdgcn_s_memtime() - tBegin);
 #endif
     // (RES: the step's packets leave first -- a packet's first symbols may still be in the carry row carryOut is about to overwrite)
-    if constexpr (RES && LORAHIP_RES_NOCOPY) residentPackOwn<C>(s, sR, step, (cset * WAVES + unsigned(wave)) * unsigned(WPW), o, mine, lane, st.state == ST_DATASYMBOLS ? st.symCount : 0);
+    if constexpr (RES) residentPackOwn<C>(s, sR, step, (cset * WAVES + unsigned(wave)) * unsigned(WPW), o, mine, lane, st.state == ST_DATASYMBOLS ? st.symCount : 0);
     o.carryOut(s, st, cc, tc, TC, mine);
     if (mine && tc == 0)
     {
@@ -581,12 +520,11 @@ demodStream(const StreamArgs s)
     }
     if constexpr (RES)
     {
-        if constexpr (!LORAHIP_RES_NOCOPY) residentPackOwn<C>(s, sR, step, (cset * WAVES + unsigned(wave)) * unsigned(WPW), o, mine, lane);
         resCalls += (mine && t == 0) ? o.calls : 0;
         resStopped = resStopped || (mine && len - st.pos >= 2 * N);        // stopped with samples left: a record buffer was full
         setIdx++;
     }
-    } while ((PERSIST || RES) && (cset += gridDim.x) < nSets);      // without PERSIST / RES there is no loop at all (it would cost registers)
+    } while (RES && (cset += gridDim.x) < nSets);      // without RES there is no loop at all (it would cost registers)
     if constexpr (!RES) break;
     else
     {
@@ -610,27 +548,16 @@ static hipError_t launchStreamCfg(const StreamArgs &args, hipStream_t stream)
 {
     constexpr int WAVES = 4;
     const size_t smem = size_t(C::TWN + C::N) * sizeof(float2) + size_t(WAVES) * C::XW * sizeof(float2) + FineDims<C::LOG2N>::BYTES;
-    static unsigned long long attrDone = 0, attrDoneP = 0;
+    static unsigned long long attrDone = 0;
     static PerDeviceCount resident;
     StreamArgs s = args;
     const unsigned perBlock = WAVES * (AHEAD ? C::WPW / 2 : C::WPW);
     const unsigned grid = (s.nChannels + perBlock - 1) / perBlock;
     if (grid == 0) return hipSuccess;
-#if defined(LORAHIP_ALL_VARIANTS) || defined(LORAHIP_STREAM_PERSIST)      // the persistent grid: profiling builds only (lorahip_demod.cpp::runStream)
-    if (!AHEAD && s.maxBlocks > 0 && grid > unsigned(s.maxBlocks))
-    {
-        const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(demodStream<C, true>), smem, attrDoneP);
-        if (e != hipSuccess) return e;
-        s.lastRoundFrom = 0;
-        hipLaunchKernelGGL((demodStream<C, true>), dim3(unsigned(s.maxBlocks)), dim3(WAVES * 64), smem, stream, s);
-        return hipGetLastError();
-    }
-#endif
-    (void)attrDoneP;
-    const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(demodStream<C, false, false, AHEAD>), smem, attrDone);
+    const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(demodStream<C, false, AHEAD>), smem, attrDone);
     if (e != hipSuccess) return e;
-    s.lastRoundFrom = lastRoundFrom(grid, residentWorkgroupsCached(resident, reinterpret_cast<const void *>(demodStream<C, false, false, AHEAD>), WAVES * 64, smem));
-    hipLaunchKernelGGL((demodStream<C, false, false, AHEAD>), dim3(grid), dim3(WAVES * 64), smem, stream, s);
+    s.lastRoundFrom = lastRoundFrom(grid, residentWorkgroupsCached(resident, reinterpret_cast<const void *>(demodStream<C, false, AHEAD>), WAVES * 64, smem));
+    hipLaunchKernelGGL((demodStream<C, false, AHEAD>), dim3(grid), dim3(WAVES * 64), smem, stream, s);
     return hipGetLastError();
 }
 
@@ -647,9 +574,9 @@ static hipError_t launchStreamResidentCfg(const StreamArgs &args, hipStream_t st
     const unsigned nSets = (args.nChannels + perBlock - 1) / perBlock;
     if (gridOut) *gridOut = 0;
     if (nSets == 0) return hipErrorNotSupported;
-    const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(demodStream<C, false, true>), smem, attrDone);
+    const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(demodStream<C, true>), smem, attrDone);
     if (e != hipSuccess) return e;
-    const int res = residentWorkgroupsCached(resident, reinterpret_cast<const void *>(demodStream<C, false, true>), WAVES * 64, smem);
+    const int res = residentWorkgroupsCached(resident, reinterpret_cast<const void *>(demodStream<C, true>), WAVES * 64, smem);
     if (res <= 0) return hipErrorNotSupported;
     // more channel sets than the device holds workgroups: every workgroup walks several per step, all workgroups the same number but
     // the last ones
@@ -657,7 +584,7 @@ static hipError_t launchStreamResidentCfg(const StreamArgs &args, hipStream_t st
     const unsigned grid = (nSets + perWg - 1) / perWg;
     if (grid > 4095u) return hipErrorNotSupported;
     if (gridOut) *gridOut = grid;
-    hipLaunchKernelGGL((demodStream<C, false, true>), dim3(grid), dim3(WAVES * 64), smem, stream, args);
+    hipLaunchKernelGGL((demodStream<C, true>), dim3(grid), dim3(WAVES * 64), smem, stream, args);
     return hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
 """bench.py's mixed_level3 section (BASELINE configs[3] as receivers behind one handle) by itself:  python tools/mixed_level3_probe.py
-(LORAHIP_PART_PRIORITY=1: the parts' streams by priority, long windows first; LORA_PROBE_LANES=-1: every part on its 16-points-per-lane
+(LORA_PROBE_LANES=-1: every part on its 16-points-per-lane
 geometry -- lorahip_demod_set_stream_lanes on the mixed handle -- instead of the lanes its own channel count would pick)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

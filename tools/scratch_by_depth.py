@@ -23,6 +23,6 @@ for l in txt:
     if s.startswith('scratch_load') or s.startswith('scratch_store'): res[kern][depth]+=1
     if s and not s.startswith(';') and not s.startswith('.') and not s.endswith(':'): insts[kern][depth]+=1
 for k in res:
-    if 'demodStream' in k and k.endswith('Lb0ELb1EEEvNS_10StreamArgsE'):
+    if 'demodStream' in k and k.endswith('Lb1ELb0EEEvNS_10StreamArgsE'):
         m=re.search(r'ILi(\d+)',k)
         print('SF'+m.group(1), 'scratch ops by loop depth', dict(sorted(res[k].items())), ' instructions by depth', dict(sorted(insts[k].items())))
