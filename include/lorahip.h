@@ -26,7 +26,8 @@
  *
  * Around the path (each behind its own entry points further down): the batched modulator + AWGN channel
  * (lorahip_mod_frames, lorahip_add_awgn), the batched decoder (lorahip_decode_packets) with the packet hand-off
- * lorahip_demod_packets_to_device, and the front-end channeliser (lorahip_channelizer_*).
+ * lorahip_demod_packets_to_device, and the front-end channeliser (lorahip_channelizer_*), which like the polyphase bank
+ * (lorahip_pfb_*) also takes the integer samples a radio delivers (sc16, sc8: the *_run_iq entry points, LORAHIP_IQ_*).
  *
  * Results: symbol indices and FFT bins are bit-identical to the reference CPU path
  * compiled without FMA contraction (the kernels evaluate kissfft's radix-4/2 DIT graph
@@ -814,6 +815,40 @@ void lorahip_pfb_destroy(lorahip_pfb *p);
 int lorahip_pfb_reset(lorahip_pfb *p);
 size_t lorahip_pfb_out_count(const lorahip_pfb *p, size_t n_in);
 int lorahip_pfb_run(lorahip_pfb *p, const float *wide_dev, size_t n_in, float *out_dev, size_t out_stride, size_t *n_out);
+
+/* -------------------------------------------------------------------------------------
+ * Integer IQ input for the two receive front ends above. Radios and recordings hand out pairs of 16-bit or 8-bit integers; the
+ * *_run_iq entry points take them as they are, so the link to the device and the wideband buffer carry 4 or 2 bytes a sample
+ * instead of 8 and no conversion pass runs: the kernels convert in the load. Definition, the only one: sample n of a chunk of
+ * format f is
+ *
+ *     x[n] = (scale * (float)I[n], scale * (float)Q[n])
+ *
+ * -- each component converted int -> float exactly, then multiplied by scale ONCE in fp32, an operation of its own (never fused
+ * into what follows) -- and everything after that is the cf32 definition of the object, operation for operation. Hence
+ * run_iq(ints, f, scale) gives, bit for bit, what run gives on the cf32 array scale * (float)ints, for every object, shape,
+ * chunking and stream position. The history an object keeps between calls holds converted samples: consecutive calls on one stream
+ * may change format and scale freely, and a stream fed partly as integers and partly through the plain run is bit-identical to the
+ * all-cf32 stream. scale is the caller's (2^-15 and 2^-7 map full scale to +-1); any finite value, 0 and negative ones included.
+ * wide_dev: n_in samples of I, Q pairs in the format's type, aligned to the sample size (4 / 2 / 8 bytes) and no more: any sample
+ * offset into a ring buffer will do. For run_captures_iq, capture_stride counts samples of the format.
+ * The limits, refusals, *n_out, stream-state rules and asynchrony are exactly those of lorahip_channelizer_run /
+ * lorahip_channelizer_run_captures / lorahip_pfb_run (lorahip_pfb_run_iq serves handles of lorahip_pfb_create and
+ * lorahip_pfb_create_radix5 alike). Refused in addition, with LORAHIP_E_INVALID and a lorahip_last_error() text ("channeliser:
+ * ...", "polyphase channeliser: ..."): an unknown format, a non-finite scale, LORAHIP_IQ_CF32 with scale != 1.0f, wide_dev not
+ * aligned to the sample size. A refusal consumes nothing and leaves the stream state untouched. LORAHIP_IQ_CF32 with scale 1.0f is
+ * the plain run. The transmit side (synthesisers) has no integer formats.
+ * ------------------------------------------------------------------------------------- */
+#define LORAHIP_IQ_CF32 0   /* float I, float Q: 8 bytes a sample; scale must be 1.0f; identical to the plain run */
+#define LORAHIP_IQ_SC16 1   /* int16 I, int16 Q: 4 bytes a sample */
+#define LORAHIP_IQ_SC8  2   /* int8 I, int8 Q: 2 bytes a sample */
+size_t lorahip_iq_sample_bytes(int format);    /* host only: 8 / 4 / 2, 0 for anything else */
+int lorahip_channelizer_run_iq(lorahip_channelizer *c, const void *wide_dev, int format, float scale, size_t n_in, float *out_dev,
+                               size_t out_stride, size_t *n_out);
+int lorahip_channelizer_run_captures_iq(lorahip_channelizer *c, const void *wide_dev, int format, float scale, size_t n_captures,
+                                        size_t capture_stride /* samples */, size_t n_in, float *out_dev, size_t out_stride, size_t *n_out);
+int lorahip_pfb_run_iq(lorahip_pfb *p, const void *wide_dev, int format, float scale, size_t n_in, float *out_dev, size_t out_stride,
+                       size_t *n_out);
 
 /* -------------------------------------------------------------------------------------
  * Polyphase synthesis filter bank: the transmit front end for a UNIFORM channel plan, K channel streams onto the grid fs / M

@@ -11,6 +11,7 @@ OK = 0
 SF_MIN, SF_MAX = 6, 12
 FINE_STEPS = 128
 CHIRP_UP, CHIRP_DOWN, CHIRP_NONE = 0, 1, 2
+IQ_CF32, IQ_SC16, IQ_SC8 = 0, 1, 2         # LORAHIP_IQ_*: the sample formats of the receive front ends
 
 _f32p = C.POINTER(C.c_float)
 
@@ -171,6 +172,10 @@ SIGNATURES = {
     "lorahip_channelizer_out_count": (C.c_size_t, [C.c_void_p, C.c_size_t]),
     "lorahip_channelizer_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "lorahip_channelizer_run_captures": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "lorahip_iq_sample_bytes": (C.c_size_t, [C.c_int]),
+    "lorahip_channelizer_run_iq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "lorahip_channelizer_run_captures_iq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                     C.POINTER(C.c_size_t)]),
     "lorahip_synthesizer_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "lorahip_synthesizer_destroy": (None, [C.c_void_p]),
     "lorahip_synthesizer_reset": (C.c_int, [C.c_void_p]),
@@ -184,6 +189,7 @@ SIGNATURES = {
     "lorahip_pfb_reset": (C.c_int, [C.c_void_p]),
     "lorahip_pfb_out_count": (C.c_size_t, [C.c_void_p, C.c_size_t]),
     "lorahip_pfb_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "lorahip_pfb_run_iq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "lorahip_psb_check": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
     "lorahip_psb_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "lorahip_psb_check_radix5": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),

@@ -471,6 +471,12 @@ class Channelizer(_Handle):
         """wide: 1-D complex64 device tensor (the next samples of the stream); returns the (K, n_out) complex64 tensor"""
         return _chan_run(self, "lorahip_channelizer_run", wide, out)
 
+    def run_int(self, wide, scale=None, out=None):
+        """run() on integer samples as a radio or a recording hands them out: wide an (n, 2) int16 or int8 device tensor (I, Q; it may
+        be buf[k:] of a larger tensor), sample = scale * (float)(I, Q) with scale None = 2^-15 / 2^-7. Converted in the kernel's load:
+        bit-identical to run() on the complex64 tensor scale * wide.float(), and free to alternate with run() on one stream."""
+        return _chan_run(self, "lorahip_channelizer_run_iq", wide, out, (scale,))
+
     def run_captures(self, wide):
         """wide: (S, n_in) complex64 device tensor of S independent captures -> (S, K, n_in // decim) tensor, one launch; every
         capture is processed like a fresh stream, the object's own stream state is left alone"""
@@ -478,14 +484,23 @@ class Channelizer(_Handle):
         if wide.dim() != 2 or wide.dtype != torch.complex64:
             raise ValueError("wide must be a (captures, samples) complex64 device tensor")
         wide = wide.contiguous()
+        return self._run_captures("lorahip_channelizer_run_captures", wide, (), int(wide.shape[1]))
+
+    def run_captures_int(self, wide, scale=None):
+        """run_captures() on integer samples: wide an (S, n_in, 2) int16 or int8 device tensor (captures a whole number of samples
+        apart: it may be buf[:, :n_in] of a larger tensor), scale as in run_int; bit-identical to run_captures() on scale * wide.float()"""
+        iq = _iq_args(wide, scale, 1)
+        return self._run_captures("lorahip_channelizer_run_captures_iq", wide, iq, int(wide.stride(0)) // 2 if wide.shape[0] > 1 and wide.numel() else int(wide.shape[1]))
+
+    def _run_captures(self, run, wide, iq, capture_stride):
+        import torch
         S, n_in = int(wide.shape[0]), int(wide.shape[1])
         n_out = n_in // self.decim
         out = torch.empty((S, self.n_channels, n_out), dtype=torch.complex64, device=wide.device)
         self._ctx.use_torch_stream()
         got = C.c_size_t()
-        check(self._lib.lorahip_channelizer_run_captures(self._h, C.c_void_p(wide.data_ptr()) if wide.numel() else None, S, n_in, n_in,
-                                                         C.c_void_p(out.data_ptr()) if out.numel() else None, n_out, C.byref(got)),
-              "lorahip_channelizer_run_captures")
+        check(getattr(self._lib, run)(self._h, C.c_void_p(wide.data_ptr()) if wide.numel() else None, *iq, S, capture_stride, n_in,
+                                      C.c_void_p(out.data_ptr()) if out.numel() else None, n_out, C.byref(got)), run)
         return out
 
 
@@ -533,13 +548,45 @@ def _plan_bins(n_bins, bins):
     return b64.astype(np.int32)
 
 
-def _chan_run(obj, run, wide, out):
-    """Channelizer.run and PolyphaseChannelizer.run: check wide and out, call the C entry point `run`, return the outputs it wrote"""
+def _iq_args(wide, scale, lead):
+    """The integer wideband tensor of run_int (lead = 0: (n, 2)) and run_captures_int (lead = 1: (S, n, 2)) checked, and the (format,
+    scale) arguments of the *_run_iq entry points: the format from the dtype, scale None = 2^-15 for int16 and 2^-7 for int8. The
+    last axis is I, Q; a sample is one element pair, so the tensor may start at any sample of a larger buffer (buf[k:])."""
     import torch
-    if wide.dim() != 1 or wide.dtype != torch.complex64:
-        raise ValueError("wide must be a 1-D complex64 device tensor")
-    wide = wide.contiguous()
-    n_out = obj.out_count(wide.numel())
+    formats = {torch.int16: (_lib.IQ_SC16, 2.0 ** -15), torch.int8: (_lib.IQ_SC8, 2.0 ** -7)}
+    shape = "(captures, samples, 2)" if lead else "(samples, 2)"
+    if (not _is_torch(wide) or not wide.is_cuda or wide.dtype not in formats or wide.dim() != lead + 2 or wide.shape[-1] != 2
+            or (wide.numel() and (wide.stride(-1) != 1 or wide.stride(-2) != 2))
+            or (lead and wide.numel() and wide.shape[0] > 1 and (wide.stride(0) % 2 or wide.stride(0) < 2 * wide.shape[1]))):
+        raise ValueError("wide must be a %s int16 or int8 device tensor, the last axis I, Q, with strides (2, 1)%s"
+                         % (shape, " and captures a whole number of samples apart" if lead else ""))
+    fmt, default = formats[wide.dtype]
+    if scale is None:
+        scale = default
+    try:
+        scale = float(scale)
+    except (TypeError, ValueError):
+        scale = float("nan")
+    with np.errstate(over="ignore"):
+        held = np.isfinite(np.float32(scale))
+    if not held:
+        raise ValueError("scale must be a finite real number that float32 holds (None: 2^-15 for int16, 2^-7 for int8)")
+    return fmt, C.c_float(scale)
+
+
+def _chan_run(obj, run, wide, out, int_scale=()):
+    """Channelizer.run / run_int and PolyphaseChannelizer.run / run_int: check wide and out, call the C entry point `run`, return the
+    outputs it wrote. int_scale = (scale,): wide is the integer tensor of run_int and `run` the *_run_iq entry point."""
+    import torch
+    if int_scale:
+        iq = _iq_args(wide, int_scale[0], 0)
+        n_in = int(wide.shape[0])
+    else:
+        if wide.dim() != 1 or wide.dtype != torch.complex64:
+            raise ValueError("wide must be a 1-D complex64 device tensor")
+        wide = wide.contiguous()
+        iq, n_in = (), wide.numel()
+    n_out = obj.out_count(n_in)
     if out is None:
         out = torch.empty((obj.n_channels, n_out), dtype=torch.complex64, device=wide.device)
     elif (out.dim() != 2 or out.shape[0] != obj.n_channels or out.shape[1] < n_out or out.dtype != torch.complex64
@@ -548,7 +595,7 @@ def _chan_run(obj, run, wide, out):
     obj._ctx.use_torch_stream()
     got = C.c_size_t()
     # the row stride is the tensor's own: `out` may be the columns [w, w + n) of a (K, capacity) buffer that fills chunk by chunk
-    check(getattr(obj._lib, run)(obj._h, C.c_void_p(wide.data_ptr()) if wide.numel() else None, wide.numel(),
+    check(getattr(obj._lib, run)(obj._h, C.c_void_p(wide.data_ptr()) if wide.numel() else None, *iq, n_in,
                                  C.c_void_p(out.data_ptr()) if out.numel() else None,
                                  int(out.stride(0)) if out.numel() and out.shape[0] > 1 else int(out.shape[1]), C.byref(got)), run)
     return out[:, :got.value]
@@ -648,6 +695,12 @@ class PolyphaseChannelizer(_PolyphaseBank):
         """wide: 1-D complex64 device tensor (the next samples of the stream); returns the (K, n_out) complex64 tensor (written into
         out if given: it may be the columns [w, w + n) of a (K, capacity) buffer)"""
         return _chan_run(self, "lorahip_pfb_run", wide, out)
+
+    def run_int(self, wide, scale=None, out=None):
+        """run() on integer samples: wide an (n, 2) int16 or int8 device tensor (I, Q; it may be buf[k:] of a larger tensor), sample =
+        scale * (float)(I, Q) with scale None = 2^-15 / 2^-7. Converted in the kernel's load: bit-identical to run() on the complex64
+        tensor scale * wide.float(), and free to alternate with run() on one stream. Serves the constructor, radix5 and for_plan."""
+        return _chan_run(self, "lorahip_pfb_run_iq", wide, out, (scale,))
 
 
 class Synthesizer(_Handle):

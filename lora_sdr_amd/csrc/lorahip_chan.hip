@@ -15,6 +15,8 @@
 //     16*RM v_pk_fma_f32;
 //   * the NCO is a 64-bit phase counter (w_k * n mod 2^64): exact wrap-around, no drift, and a stream cut into
 //     chunks gives the same bits as one call.
+// The chunk of a call is cf32, sc16 or sc8 (template argument S; lorahip_frontend.h has the definition): the conversion happens in the
+// staging load, the LDS and everything after it hold cf32. The cf32 instances are the code they were before the formats.
 #include "lorahip_frontend.h"
 #include "lorahip_mixer.h"
 #include <cmath>
@@ -38,9 +40,9 @@ namespace lorahip {
 constexpr int CHAN_THREADS = 256;
 constexpr int CHAN_KG = 8;          // channels per workgroup
 
-struct ChanArgs
+template <class S> struct ChanArgs
 {
-    const float2 *chunk;
+    const S *chunk;                 // this call's samples in their format (lorahip_frontend.h)
     long long nChunk;
     const float2 *hist;
     int histLen;
@@ -56,6 +58,7 @@ struct ChanArgs
     long long nOut;
     int K, L, D, QP, nGroups;
     long long captureIn, captureOut;    // batch of independent captures (blockIdx.y): sample / output-row strides, 0 for a stream
+    float scale;                    // of the integer formats
 };
 
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -107,7 +110,8 @@ __device__ __forceinline__ void tapFma(v2f (&acc)[RM][CHAN_KG], const TapCoef &G
 
 //! the common tile: wholly inside this call's chunk. Uniform base + 32-bit byte offsets (no 64-bit vector arithmetic),
 //! 8 loads in flight per lane and round; the LDS slot walks by a constant with one conditional wrap
-__device__ __forceinline__ void tileStageInside(float2 *xs, const float2 *chunkAt, const int D, const int QP, const int TI, const int t)
+template <class S>
+__device__ __forceinline__ void tileStageInside(float2 *xs, const S *chunkAt, const int D, const int QP, const int TI, const int t, const float scale)
 {
     const char *__restrict__ bp = reinterpret_cast<const char *>(chunkAt);
     const int dq = CHAN_THREADS / D, dp = CHAN_THREADS - dq * D;
@@ -118,7 +122,11 @@ __device__ __forceinline__ void tileStageInside(float2 *xs, const float2 *chunkA
     {
         float2 v[8];
 #pragma unroll
-        for (int u = 0; u < 8; u++) v[u] = *reinterpret_cast<const float2 *>(bp + min(unsigned(tt + u * CHAN_THREADS), unsigned(TI - 1)) * 8u);
+        for (int u = 0; u < 8; u++)
+        {
+            if constexpr (std::is_same<S, float2>::value) v[u] = *reinterpret_cast<const float2 *>(bp + min(unsigned(tt + u * CHAN_THREADS), unsigned(TI - 1)) * 8u);
+            else v[u] = iqLoad(reinterpret_cast<const S *>(bp + min(unsigned(tt + u * CHAN_THREADS), unsigned(TI - 1)) * unsigned(sizeof(S))), scale);
+        }
 #pragma unroll
         for (int u = 0; u < 8; u++)
         {
@@ -129,7 +137,8 @@ __device__ __forceinline__ void tileStageInside(float2 *xs, const float2 *chunkA
     }
 }
 //! any tile, fetch and store back to back: 8 loads in flight per lane and round
-__device__ __forceinline__ void tileStage(float2 *xs, const ChanArgs &a, const float2 *chunk, const long long tileStart, const int D, const int QP, const int TI, const int t)
+template <class S>
+__device__ __forceinline__ void tileStage(float2 *xs, const ChanArgs<S> &a, const S *chunk, const long long tileStart, const int D, const int QP, const int TI, const int t)
 {
     const int dq = CHAN_THREADS / D, dp = CHAN_THREADS - dq * D;
     for (int tt = t; tt < TI; tt += 8 * CHAN_THREADS)
@@ -137,7 +146,7 @@ __device__ __forceinline__ void tileStage(float2 *xs, const ChanArgs &a, const f
         float2 v[8];
         int q = tt / D, p = tt - q * D;
 #pragma unroll
-        for (int u = 0; u < 8; u++) v[u] = tt + u * CHAN_THREADS < TI ? carriedSample(chunk, a.nChunk, a.hist, a.histLen, a.n0, tileStart + tt + u * CHAN_THREADS) : make_float2(0.0f, 0.0f);
+        for (int u = 0; u < 8; u++) v[u] = tt + u * CHAN_THREADS < TI ? carriedSample(chunk, a.nChunk, a.hist, a.histLen, a.n0, tileStart + tt + u * CHAN_THREADS, a.scale) : make_float2(0.0f, 0.0f);
 #pragma unroll
         for (int u = 0; u < 8; u++)
         {
@@ -150,8 +159,8 @@ __device__ __forceinline__ void tileStage(float2 *xs, const ChanArgs &a, const f
 
 // One workgroup = one tile of 256*RM output times x one group of 8 channels; blockIdx.x = tile * nGroups + group: the groups
 // of a tile are neighbours in launch order and share the tile's input in L2.
-template <int RM>
-__global__ __launch_bounds__(CHAN_THREADS) void channelize(const ChanArgs a)
+template <int RM, class S>
+__global__ __launch_bounds__(CHAN_THREADS) void channelize(const ChanArgs<S> a)
 {
     extern __shared__ float2 xs[];
     constexpr int TM = CHAN_THREADS * RM;
@@ -164,9 +173,9 @@ __global__ __launch_bounds__(CHAN_THREADS) void channelize(const ChanArgs a)
     const long long mTile = (a.mLo / TM + (long long)(blockIdx.x / unsigned(a.nGroups))) * TM;
     const long long tileStart = (mTile + 1) * D - L;            // oldest sample of the tile's first output
     {
-        const float2 *chunk = a.chunk + (size_t)blockIdx.y * a.captureIn;       // this capture's samples (blockIdx.y = 0 for a stream)
+        const S *chunk = a.chunk + (size_t)blockIdx.y * a.captureIn;       // this capture's samples (blockIdx.y = 0 for a stream)
         const long long rel = tileStart - a.n0;
-        if (rel >= 0 && rel + TI <= a.nChunk) tileStageInside(xs, chunk + rel, D, QP, TI, t);
+        if (rel >= 0 && rel + TI <= a.nChunk) tileStageInside(xs, chunk + rel, D, QP, TI, t, a.scale);
         else tileStage(xs, a, chunk, tileStart, D, QP, TI, t);
     }
     __syncthreads();
@@ -235,11 +244,20 @@ __global__ __launch_bounds__(CHAN_THREADS) void channelize(const ChanArgs a)
     }
 }
 
-static unsigned long long gLdsMask[2] = {0, 0};
+template <int RM, class S>
+static hipError_t chanLaunch(const lorahip_channelizer *c, const ChanArgs<S> &a, const dim3 grid)
+{
+    static unsigned long long ldsMask;
+    const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(&channelize<RM, S>), 160 * 1024, ldsMask);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((channelize<RM, S>), grid, dim3(CHAN_THREADS), c->ldsBytes, c->ctx->stream, a);
+    return hipGetLastError();
+}
 
 //! captures == 0: the next nIn samples of THE stream (history and phase carried). captures > 0: that many independent captures of nIn
-//! samples each, every one from sample 0 with zero history; the stream state is not touched.
-static int chanRun(lorahip_channelizer *c, const float2 *wide, const size_t nIn, float2 *out, const size_t outStride, size_t *nOutP,
+//! samples each, every one from sample 0 with zero history; the stream state is not touched. S = the format of wide, scale its scale.
+template <class S>
+static int chanRun(lorahip_channelizer *c, const S *wide, const float scale, const size_t nIn, float2 *out, const size_t outStride, size_t *nOutP,
                    const size_t captures = 0, const size_t captureStride = 0)
 {
     lorahip_ctx *ctx = c->ctx;
@@ -251,8 +269,8 @@ static int chanRun(lorahip_channelizer *c, const float2 *wide, const size_t nIn,
     if (nIn == 0) return LORAHIP_OK;
     if (nOut && (out == nullptr || outStride < nOut)) return LORAHIP_E_INVALID;
     if (nOut > (size_t(1) << 30)) { setLastError("channeliser: more than 2^30 outputs per channel in one call"); return LORAHIP_E_INVALID; }
-    ChanArgs a;
-    a.chunk = wide; a.nChunk = (long long)nIn;
+    ChanArgs<S> a;
+    a.chunk = wide; a.scale = scale; a.nChunk = (long long)nIn;
     a.hist = c->carry.current(); a.histLen = captures ? 0 : c->HC;        // no history: samples before the capture read as 0
     a.n0 = (long long)n0;
     a.captureIn = (long long)captureStride; a.captureOut = (long long)(size_t(c->K) * outStride);
@@ -270,20 +288,10 @@ static int chanRun(lorahip_channelizer *c, const float2 *wide, const size_t nIn,
         const size_t nBlocks = size_t(c->nGroups) * ((mLo % TM + nOut + TM - 1) / TM);
         if (nBlocks > 0x7fffffffu) { setLastError("channeliser: channels x outputs of one call exceed the launch grid"); return LORAHIP_E_INVALID; }
         const dim3 grid((unsigned)nBlocks, (unsigned)(captures ? captures : 1));
-        if (c->RM == 2)
-        {
-            LORAHIP_TRY(ensureDynamicLds(reinterpret_cast<const void *>(&channelize<2>), 160 * 1024, gLdsMask[1]));
-            hipLaunchKernelGGL(channelize<2>, grid, dim3(CHAN_THREADS), c->ldsBytes, ctx->stream, a);
-        }
-        else
-        {
-            LORAHIP_TRY(ensureDynamicLds(reinterpret_cast<const void *>(&channelize<1>), 160 * 1024, gLdsMask[0]));
-            hipLaunchKernelGGL(channelize<1>, grid, dim3(CHAN_THREADS), c->ldsBytes, ctx->stream, a);
-        }
-        LORAHIP_TRY(hipGetLastError());
+        LORAHIP_TRY(c->RM == 2 ? chanLaunch<2>(c, a, grid) : chanLaunch<1>(c, a, grid));
     }
     if (captures) return LORAHIP_OK;
-    hipLaunchKernelGGL(carryHistory, dim3((c->HC + 255) / 256), dim3(256), 0, ctx->stream, a.chunk, a.nChunk, a.hist, a.histLen, a.n0, c->carry.next());
+    hipLaunchKernelGGL(carryHistory<S>, dim3((c->HC + 255) / 256), dim3(256), 0, ctx->stream, a.chunk, a.nChunk, a.hist, a.histLen, a.n0, c->carry.next(), a.scale);
     LORAHIP_TRY(hipGetLastError());
     c->carry.advance(nIn);
     return LORAHIP_OK;
@@ -387,11 +395,32 @@ size_t lorahip_channelizer_out_count(const lorahip_channelizer *c, const size_t 
     return c == nullptr ? 0 : decimatedCount(c->carry.n0, n_in, c->D);
 }
 
+size_t lorahip_iq_sample_bytes(const int format) { return iqSampleBytes(format); }
+
+int lorahip_channelizer_run_iq(lorahip_channelizer *c, const void *wide_dev, const int format, const float scale, const size_t n_in, float *out_dev,
+                               const size_t out_stride, size_t *n_out)
+{
+    if (c == nullptr || (n_in && wide_dev == nullptr)) return LORAHIP_E_INVALID;
+    if (iqCheck("channeliser", wide_dev, format, scale) != LORAHIP_OK) return LORAHIP_E_INVALID;
+    return iqDispatch(wide_dev, format, [&](const auto *wide) { return chanRun(c, wide, scale, n_in, reinterpret_cast<float2 *>(out_dev), out_stride, n_out); });
+}
+
 int lorahip_channelizer_run(lorahip_channelizer *c, const float *wide_dev, const size_t n_in, float *out_dev,
                             const size_t out_stride, size_t *n_out)
 {
     if (c == nullptr || (n_in && wide_dev == nullptr)) return LORAHIP_E_INVALID;
-    return chanRun(c, reinterpret_cast<const float2 *>(wide_dev), n_in, reinterpret_cast<float2 *>(out_dev), out_stride, n_out);
+    return chanRun(c, reinterpret_cast<const float2 *>(wide_dev), 1.0f, n_in, reinterpret_cast<float2 *>(out_dev), out_stride, n_out);
+}
+
+int lorahip_channelizer_run_captures_iq(lorahip_channelizer *c, const void *wide_dev, const int format, const float scale, const size_t n_captures,
+                                        const size_t capture_stride, const size_t n_in, float *out_dev, const size_t out_stride, size_t *n_out)
+{
+    if (c == nullptr || n_captures > 65535u || (n_captures && n_in && (wide_dev == nullptr || capture_stride < n_in))) return LORAHIP_E_INVALID;
+    if (iqCheck("channeliser", wide_dev, format, scale) != LORAHIP_OK) return LORAHIP_E_INVALID;
+    if (n_out) *n_out = n_in / size_t(c->D);
+    if (n_captures == 0 || n_in == 0) return LORAHIP_OK;
+    return iqDispatch(wide_dev, format, [&](const auto *wide)
+                      { return chanRun(c, wide, scale, n_in, reinterpret_cast<float2 *>(out_dev), out_stride, n_out, n_captures, capture_stride); });
 }
 
 int lorahip_channelizer_run_captures(lorahip_channelizer *c, const float *wide_dev, const size_t n_captures, const size_t capture_stride,
@@ -400,7 +429,7 @@ int lorahip_channelizer_run_captures(lorahip_channelizer *c, const float *wide_d
     if (c == nullptr || n_captures > 65535u || (n_captures && n_in && (wide_dev == nullptr || capture_stride < n_in))) return LORAHIP_E_INVALID;
     if (n_out) *n_out = n_in / size_t(c->D);
     if (n_captures == 0 || n_in == 0) return LORAHIP_OK;
-    return chanRun(c, reinterpret_cast<const float2 *>(wide_dev), n_in, reinterpret_cast<float2 *>(out_dev), out_stride, n_out, n_captures, capture_stride);
+    return chanRun(c, reinterpret_cast<const float2 *>(wide_dev), 1.0f, n_in, reinterpret_cast<float2 *>(out_dev), out_stride, n_out, n_captures, capture_stride);
 }
 
 } // extern "C"

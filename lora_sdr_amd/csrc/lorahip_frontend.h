@@ -1,9 +1,12 @@
 // What the four front ends (lorahip_chan.hip, lorahip_synth.hip, lorahip_pfb.hip, lorahip_psb.hip) have in common, stated once: the
 // state that carries one stream across calls, the output count of the decimators, the sample lookup and the history kernel of the two
-// channelisers, and the way an object's tables reach the device when it is created.
+// channelisers with the sample formats they read, and the way an object's tables reach the device when it is created.
 #pragma once
 #include "lorahip_own.h"
+#include <cmath>
+#include <cstdint>
 #include <string>
+#include <type_traits>
 
 namespace lorahip {
 
@@ -49,24 +52,82 @@ inline size_t decimatedCount(const unsigned long long n0, const size_t nIn, cons
     return size_t((n0 + nIn) / (unsigned long long)D - n0 / (unsigned long long)D);
 }
 
-//! sample n of the stream (absolute index): from this call's chunk, from the history kept from earlier calls, or 0
-__device__ __forceinline__ float2 carriedSample(const float2 *chunk, const long long nChunk, const float2 *hist, const int histLen,
-                                                const long long n0, const long long n)
+// The sample formats of the receive front ends (include/lorahip.h: LORAHIP_IQ_*). A chunk of format S holds one S per sample: float2
+// (cf32), short2 (sc16: int16 I, int16 Q) or char2 (sc8). The definition, stated once: x[n] = (scale * (float)I[n], scale * (float)Q[n])
+// -- the integer converted exactly, then ONE fp32 multiply per component, an operation of its own (-ffp-contract=off) -- and everything
+// after that is the cf32 definition, operation for operation. Only reads from the chunk convert: the history holds converted samples.
+// A format needs no alignment beyond its own size (4 / 2 / 8 bytes).
+
+//! the chunk's sample at p as cf32; the one place a format is read
+__device__ __forceinline__ float2 iqLoad(const float2 *p, const float) { return *p; }
+__device__ __forceinline__ float2 iqLoad(const short2 *p, const float scale)
+{
+    const short2 v = *p;
+    return make_float2(scale * float(v.x), scale * float(v.y));
+}
+__device__ __forceinline__ float2 iqLoad(const char2 *p, const float scale)
+{
+    const char2 v = *p;
+    return make_float2(scale * float(v.x), scale * float(v.y));
+}
+
+//! bytes of one sample of a LORAHIP_IQ_* format, 0 for anything else
+inline size_t iqSampleBytes(const int format)
+{
+    return format == LORAHIP_IQ_CF32 ? sizeof(float2) : format == LORAHIP_IQ_SC16 ? sizeof(short2) : format == LORAHIP_IQ_SC8 ? sizeof(char2) : 0;
+}
+
+//! what every *_run_iq refuses before it looks at anything else: LORAHIP_OK, or LORAHIP_E_INVALID and "<who>: ..." in lorahip_last_error
+inline int iqCheck(const std::string &who, const void *wide, const int format, const float scale)
+{
+    const size_t bytes = iqSampleBytes(format);
+    std::string why;
+    if (bytes == 0) why = "unknown sample format (LORAHIP_IQ_CF32, LORAHIP_IQ_SC16 or LORAHIP_IQ_SC8)";
+    else if (!std::isfinite(scale)) why = "scale must be finite";
+    else if (format == LORAHIP_IQ_CF32 && scale != 1.0f) why = "LORAHIP_IQ_CF32 takes scale 1";
+    else if (uintptr_t(wide) % bytes) why = "wide_dev must be aligned to the sample size (" + std::to_string(bytes) + " bytes)";
+    if (why.empty()) return LORAHIP_OK;
+    setLastError(who + ": " + why);
+    return LORAHIP_E_INVALID;
+}
+
+//! f(chunk) with wide as the sample type of `format` (one iqCheck has passed)
+template <class F> int iqDispatch(const void *wide, const int format, F &&f)
+{
+    if (format == LORAHIP_IQ_SC16) return f(static_cast<const short2 *>(wide));
+    if (format == LORAHIP_IQ_SC8) return f(static_cast<const char2 *>(wide));
+    return f(static_cast<const float2 *>(wide));
+}
+
+//! sample n of the stream (absolute index): from this call's chunk (format S, converted), from the history kept from earlier calls
+//! (cf32), or 0
+template <class S>
+__device__ __forceinline__ float2 carriedSample(const S *chunk, const long long nChunk, const float2 *hist, const int histLen,
+                                                const long long n0, const long long n, [[maybe_unused]] const float scale)
 {
     const long long c = n - n0, h = c + histLen;
-    const float2 *src = c >= 0 ? chunk + c : hist + h;
-    const bool ok = c >= 0 ? c < nChunk : h >= 0;
     float2 v = make_float2(0.0f, 0.0f);
-    if (ok) v = *src;
+    if constexpr (std::is_same<S, float2>::value)
+    {
+        const float2 *src = c >= 0 ? chunk + c : hist + h;
+        const bool ok = c >= 0 ? c < nChunk : h >= 0;
+        if (ok) v = *src;
+    }
+    else if (c >= 0)
+    {
+        if (c < nChunk) v = iqLoad(chunk + c, scale);
+    }
+    else if (h >= 0) v = hist[h];
     return v;
 }
 
 //! the histLen samples that precede the next call (the two channelisers launch it; internal linkage: every unit has its own)
-[[maybe_unused]] static __global__ void carryHistory(const float2 *chunk, const long long nChunk, const float2 *hist, const int histLen, const long long n0,
-                                    float2 *newHist)
+template <class S>
+static __global__ void carryHistory(const S *chunk, const long long nChunk, const float2 *hist, const int histLen, const long long n0,
+                                    float2 *newHist, const float scale)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < histLen) newHist[i] = carriedSample(chunk, nChunk, hist, histLen, n0, n0 + nChunk - histLen + i);
+    if (i < histLen) newHist[i] = carriedSample(chunk, nChunk, hist, histLen, n0, n0 + nChunk - histLen + i, scale);
 }
 
 inline hipError_t growTables() { return hipSuccess; }

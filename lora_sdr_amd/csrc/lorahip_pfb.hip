@@ -25,6 +25,9 @@
 //   * store: only the selected bins leave the LDS; lane = output time, so a row's run of a tile is T * 8 >= 128 bytes. Rows of the
 //     sums are M + 1 samples apart: the T lanes that read one bin of T rows hit T different banks (M + 1 odd; M = 5: 6 samples =
 //     12 banks apart, lanes 16 apart share a bank: two-way).
+// The chunk of a call is cf32, sc16 or sc8 (template argument S; lorahip_frontend.h has the definition): a staged span is converted
+// when it is copied, so the LDS holds cf32 for every format and the staging rule does not depend on it; an unstaged fold converts at
+// every tap read. The cf32 instances are the code they were before the formats.
 // The phase is the stream position modulo M -- integer arithmetic, no drift. M is a template constant: for the power-of-two banks
 // the divisions and remainders by it are shifts and masks, for the others multiplications.
 #include "lorahip_bank.h"
@@ -45,9 +48,9 @@ namespace lorahip {
 
 constexpr size_t PFB_STAGE_LDS = 80u << 10;     // sums + twiddles + input span up to this: two workgroups a compute unit
 
-struct PfbArgs
+template <class S> struct PfbArgs
 {
-    const float2 *chunk;
+    const S *chunk;                 // this call's samples in their format (lorahip_frontend.h)
     long long nChunk;
     const float2 *hist;
     int histLen;
@@ -60,18 +63,21 @@ struct PfbArgs
     long long mLo;                  // absolute index of the first output of this call
     long long nOut;
     int D, L, Lp, K, T, logT, span;
+    float scale;                    // of the integer formats
 };
 
 //! one folded sum from samples that lie in a row: xp = the newest sample of residue s, the older ones M apart below it; rounds = the
-//! number of taps r, r + M, ... below L
-template <int M>
-__device__ __forceinline__ float2 pfbFold(const float2 *xp, const float *hp, const int rounds)
+//! number of taps r, r + M, ... below L. S = float2 for the LDS copy (converted when it was staged), the chunk's format for the chunk
+template <int M, class S>
+__device__ __forceinline__ float2 pfbFold(const S *xp, const float *hp, const int rounds, const float scale)
 {
     float re = 0.0f, im = 0.0f;
 #pragma unroll 4
     for (int q = 0; q < rounds; q++)
     {
-        const float2 x = xp[-q * M];
+        float2 x;
+        if constexpr (std::is_same<S, float2>::value) x = xp[-q * M];
+        else x = iqLoad(xp - q * M, scale);
         const float h = hp[q * M];
         re = __builtin_fmaf(h, x.x, re);
         im = __builtin_fmaf(h, x.y, im);
@@ -79,8 +85,8 @@ __device__ __forceinline__ float2 pfbFold(const float2 *xp, const float *hp, con
     return make_float2(re, im);
 }
 
-template <int M, bool STAGED>
-__global__ __launch_bounds__(PFB_THREADS) void pfbChannelize(const PfbArgs a)
+template <int M, bool STAGED, class S>
+__global__ __launch_bounds__(PFB_THREADS) void pfbChannelize(const PfbArgs<S> a)
 {
     extern __shared__ float2 pfbLds[];
     constexpr bool POW2 = bankIsPow2(M);
@@ -101,14 +107,18 @@ __global__ __launch_bounds__(PFB_THREADS) void pfbChannelize(const PfbArgs a)
     {
         if (inside)
         {
-            const float2 *__restrict__ src = a.chunk + rel;
+            const S *__restrict__ src = a.chunk + rel;
 #pragma unroll 8
-            for (int i = tid; i < a.span; i += PFB_THREADS) xs[i] = src[i];
+            for (int i = tid; i < a.span; i += PFB_THREADS)
+            {
+                if constexpr (std::is_same<S, float2>::value) xs[i] = src[i];
+                else xs[i] = iqLoad(src + i, a.scale);
+            }
         }
         else
         {
 #pragma unroll 4
-            for (int i = tid; i < a.span; i += PFB_THREADS) xs[i] = carriedSample(a.chunk, a.nChunk, a.hist, a.histLen, a.n0, tileStart + i);
+            for (int i = tid; i < a.span; i += PFB_THREADS) xs[i] = carriedSample(a.chunk, a.nChunk, a.hist, a.histLen, a.n0, tileStart + i, a.scale);
         }
         __syncthreads();
     }
@@ -131,14 +141,14 @@ __global__ __launch_bounds__(PFB_THREADS) void pfbChannelize(const PfbArgs a)
         const float *hp = a.taps + r;
         const int rounds = POW2 ? (a.L - r + M - 1) >> LOGN : int(unsigned(a.L - r + M - 1) / unsigned(M));   // taps r, r + M, ... < L: the padding of the table is never multiplied (0 where r >= L)
         float2 acc;
-        if constexpr (STAGED) acc = pfbFold<M>(xs + at, hp, rounds);
-        else if (inside) acc = pfbFold<M>(a.chunk + rel + at, hp, rounds);
+        if constexpr (STAGED) acc = pfbFold<M>(xs + at, hp, rounds, 1.0f);
+        else if (inside) acc = pfbFold<M>(a.chunk + rel + at, hp, rounds, a.scale);
         else
         {
             float re = 0.0f, im = 0.0f;
             for (int q = 0; q < rounds; q++)
             {
-                const float2 x = carriedSample(a.chunk, a.nChunk, a.hist, a.histLen, a.n0, n - r - (long long)q * M);
+                const float2 x = carriedSample(a.chunk, a.nChunk, a.hist, a.histLen, a.n0, n - r - (long long)q * M, a.scale);
                 const float h = hp[q * M];
                 re = __builtin_fmaf(h, x.x, re);
                 im = __builtin_fmaf(h, x.y, im);
@@ -163,26 +173,27 @@ __global__ __launch_bounds__(PFB_THREADS) void pfbChannelize(const PfbArgs a)
     }
 }
 
-template <int M>
-static hipError_t pfbLaunch(const lorahip_pfb *p, const PfbArgs &a, const unsigned grid)
+template <int M, class S>
+static hipError_t pfbLaunch(const lorahip_pfb *p, const PfbArgs<S> &a, const unsigned grid)
 {
     static unsigned long long ldsMask[2];
     if (p->staged)
     {
-        const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(&pfbChannelize<M, true>), 160 * 1024, ldsMask[1]);
+        const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(&pfbChannelize<M, true, S>), 160 * 1024, ldsMask[1]);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((pfbChannelize<M, true>), dim3(grid), dim3(PFB_THREADS), p->ldsBytes, p->ctx->stream, a);
+        hipLaunchKernelGGL((pfbChannelize<M, true, S>), dim3(grid), dim3(PFB_THREADS), p->ldsBytes, p->ctx->stream, a);
     }
     else
     {
-        const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(&pfbChannelize<M, false>), 160 * 1024, ldsMask[0]);
+        const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(&pfbChannelize<M, false, S>), 160 * 1024, ldsMask[0]);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((pfbChannelize<M, false>), dim3(grid), dim3(PFB_THREADS), p->ldsBytes, p->ctx->stream, a);
+        hipLaunchKernelGGL((pfbChannelize<M, false, S>), dim3(grid), dim3(PFB_THREADS), p->ldsBytes, p->ctx->stream, a);
     }
     return hipGetLastError();
 }
 
-static int pfbRun(lorahip_pfb *p, const float2 *wide, const size_t nIn, float2 *out, const size_t outStride, size_t *nOutP)
+template <class S>
+static int pfbRun(lorahip_pfb *p, const S *wide, const float scale, const size_t nIn, float2 *out, const size_t outStride, size_t *nOutP)
 {
     lorahip_ctx *ctx = p->ctx;
     const unsigned long long mLo = p->carry.n0 / (unsigned long long)p->D;
@@ -194,8 +205,8 @@ static int pfbRun(lorahip_pfb *p, const float2 *wide, const size_t nIn, float2 *
     const size_t nTiles = nOut ? size_t((mLo & (unsigned long long)(p->T - 1)) + nOut + size_t(p->T) - 1) >> p->logT : 0;
     if (nTiles > 0x7fffffffu) { setLastError("polyphase channeliser: the outputs of one call exceed the launch grid"); return LORAHIP_E_INVALID; }
     const DeviceGuard guard(ctx->device);
-    PfbArgs a;
-    a.chunk = wide; a.nChunk = (long long)nIn;
+    PfbArgs<S> a;
+    a.chunk = wide; a.scale = scale; a.nChunk = (long long)nIn;
     a.hist = p->carry.current(); a.histLen = p->HC;
     a.n0 = (long long)p->carry.n0;
     a.taps = p->dTaps.get(); a.tw = p->dTw.get(); a.sel = p->dSel.get();
@@ -207,7 +218,7 @@ static int pfbRun(lorahip_pfb *p, const float2 *wide, const size_t nIn, float2 *
         const hipError_t e = bankDispatch(p->M, BankCounts(), [&](const auto m) { return pfbLaunch<decltype(m)::value>(p, a, unsigned(nTiles)); });
         LORAHIP_TRY(e);
     }
-    hipLaunchKernelGGL(carryHistory, dim3((p->HC + 255) / 256), dim3(256), 0, ctx->stream, a.chunk, a.nChunk, a.hist, a.histLen, a.n0, p->carry.next());
+    hipLaunchKernelGGL(carryHistory<S>, dim3((p->HC + 255) / 256), dim3(256), 0, ctx->stream, a.chunk, a.nChunk, a.hist, a.histLen, a.n0, p->carry.next(), a.scale);
     LORAHIP_TRY(hipGetLastError());
     p->carry.advance(nIn);
     return LORAHIP_OK;
@@ -310,7 +321,16 @@ int lorahip_pfb_run(lorahip_pfb *p, const float *wide_dev, const size_t n_in, fl
 {
     if (p == nullptr) return LORAHIP_E_INVALID;
     if (n_in && wide_dev == nullptr) { setLastError("polyphase channeliser: no input"); return LORAHIP_E_INVALID; }
-    return pfbRun(p, reinterpret_cast<const float2 *>(wide_dev), n_in, reinterpret_cast<float2 *>(out_dev), out_stride, n_out);
+    return pfbRun(p, reinterpret_cast<const float2 *>(wide_dev), 1.0f, n_in, reinterpret_cast<float2 *>(out_dev), out_stride, n_out);
+}
+
+int lorahip_pfb_run_iq(lorahip_pfb *p, const void *wide_dev, const int format, const float scale, const size_t n_in, float *out_dev, const size_t out_stride,
+                       size_t *n_out)
+{
+    if (p == nullptr) return LORAHIP_E_INVALID;
+    if (n_in && wide_dev == nullptr) { setLastError("polyphase channeliser: no input"); return LORAHIP_E_INVALID; }
+    if (iqCheck("polyphase channeliser", wide_dev, format, scale) != LORAHIP_OK) return LORAHIP_E_INVALID;
+    return iqDispatch(wide_dev, format, [&](const auto *wide) { return pfbRun(p, wide, scale, n_in, reinterpret_cast<float2 *>(out_dev), out_stride, n_out); });
 }
 
 } // extern "C"
