@@ -27,7 +27,9 @@
  * Around the path (each behind its own entry points further down): the batched modulator + AWGN channel
  * (lorahip_mod_frames, lorahip_add_awgn), the batched decoder (lorahip_decode_packets) with the packet hand-off
  * lorahip_demod_packets_to_device, and the front-end channeliser (lorahip_channelizer_*), which like the polyphase bank
- * (lorahip_pfb_*) also takes the integer samples a radio delivers (sc16, sc8: the *_run_iq entry points, LORAHIP_IQ_*).
+ * (lorahip_pfb_*) also takes the integer samples a radio delivers (sc16, sc8: the *_run_iq entry points, LORAHIP_IQ_*). On the
+ * transmit side the synthesiser (lorahip_synthesizer_*) and the polyphase synthesis bank (lorahip_psb_*) write the same integer
+ * formats, quantised in the store, through their own *_run_iq entry points ("Integer IQ output" below).
  *
  * Results: symbol indices and FFT bins are bit-identical to the reference CPU path
  * compiled without FMA contraction (the kernels evaluate kissfft's radix-4/2 DIT graph
@@ -837,7 +839,7 @@ int lorahip_pfb_run(lorahip_pfb *p, const float *wide_dev, size_t n_in, float *o
  * lorahip_pfb_create_radix5 alike). Refused in addition, with LORAHIP_E_INVALID and a lorahip_last_error() text ("channeliser:
  * ...", "polyphase channeliser: ..."): an unknown format, a non-finite scale, LORAHIP_IQ_CF32 with scale != 1.0f, wide_dev not
  * aligned to the sample size. A refusal consumes nothing and leaves the stream state untouched. LORAHIP_IQ_CF32 with scale 1.0f is
- * the plain run. The transmit side (synthesisers) has no integer formats.
+ * the plain run. The transmit side writes the same formats: "Integer IQ output for the two synthesisers" at the end of this file.
  * ------------------------------------------------------------------------------------- */
 #define LORAHIP_IQ_CF32 0   /* float I, float Q: 8 bytes a sample; scale must be 1.0f; identical to the plain run */
 #define LORAHIP_IQ_SC16 1   /* int16 I, int16 Q: 4 bytes a sample */
@@ -915,6 +917,43 @@ void lorahip_psb_destroy(lorahip_psb *p);
 int lorahip_psb_reset(lorahip_psb *p);
 size_t lorahip_psb_out_count(const lorahip_psb *p, size_t n_in);                       /* n_in * interp; 0 for NULL */
 int lorahip_psb_run(lorahip_psb *p, const float *in_dev, size_t in_stride, size_t n_in, float *wide_dev, size_t *n_out);
+
+/* -------------------------------------------------------------------------------------
+ * Integer IQ output for the two synthesisers above. DACs, SDR transmit ports and recordings take pairs of 16-bit or 8-bit integers;
+ * the *_run_iq entry points write them as they are, so the wideband buffer and the link from the device carry 4 or 2 bytes a sample
+ * instead of 8 and no conversion pass runs: the kernels quantise in the store. Definition, the only one: let y be the cf32 output
+ * sample of the object's definition above, operation for operation, and [lo, hi] = [-32768, 32767] (LORAHIP_IQ_SC16) or [-128, 127]
+ * (LORAHIP_IQ_SC8). For each component c of y:
+ *
+ *     1. t = scale * c        one fp32 multiply, an operation of its own: never fused with the sum before it or anything after it
+ *     2. r = rint(t)          in fp32: to nearest, ties to even
+ *     3. stored: 0 if r is NaN, lo if r < lo, hi if r > hi, (int)r otherwise (so +Inf gives hi, -Inf gives lo)
+ *     4. the component is CLIPPED if r is NaN or lies outside [lo, hi]
+ *
+ * Hence run_iq(rows, f, scale) stores, bit for bit, the same object's run(rows) quantised like this -- in numpy terms
+ * clip(nan_to_num(rint(float32(scale) * y), nan=0, posinf=hi, neginf=lo), lo, hi) as integers -- for every shape, chunking, stream
+ * position and output alignment. The state an object carries between calls stays cf32 and does not depend on the output format:
+ * consecutive calls on one stream may alternate between run, sc16 and sc8 with any scales, and each call's outputs are the
+ * quantisation of what run would have written at that stream position. The channel-rate rows stay cf32. scale is the caller's
+ * (32767 and 127 map +-1 to full scale without a clip); any finite value, 0 and negative ones included.
+ * wide_dev: room for *n_out samples of I, Q pairs in the format's type, aligned to the sample size (4 / 2 / 8 bytes) and no more: any
+ * sample offset into a ring buffer will do. Nothing outside the *n_out samples is written. *n_out counts samples.
+ * The limits, *n_out, stream-state rules and asynchrony are exactly those of lorahip_synthesizer_run / lorahip_psb_run
+ * (lorahip_psb_run_iq serves handles of lorahip_psb_create and lorahip_psb_create_radix5 alike; 2^30 outputs a call at most).
+ * Refused in addition, before anything else is looked at, with LORAHIP_E_INVALID, *n_out = 0 and a lorahip_last_error() text
+ * ("synthesiser: ...", "polyphase synthesiser: ..."): an unknown format, a non-finite scale, LORAHIP_IQ_CF32 with scale != 1.0f,
+ * wide_dev not aligned to the sample size. A refusal consumes nothing and leaves the stream state and the clip count untouched.
+ * LORAHIP_IQ_CF32 with scale 1.0f is the plain run and counts nothing.
+ * *_clipped: *count = the clipped components (I and Q counted separately) that the integer runs of this object have stored since
+ * create or the last *_reset. It synchronises the context's stream and does not clear the count; *_reset clears it. Every sample
+ * is bit-identical across chunkings, so the count of a stream is too. A NULL handle or a NULL count is LORAHIP_E_INVALID.
+ * ------------------------------------------------------------------------------------- */
+int lorahip_synthesizer_run_iq(lorahip_synthesizer *s, const float *in_dev, size_t in_stride, size_t n_in, void *wide_dev, int format,
+                               float scale, size_t *n_out);
+int lorahip_psb_run_iq(lorahip_psb *p, const float *in_dev, size_t in_stride, size_t n_in, void *wide_dev, int format, float scale,
+                       size_t *n_out);
+int lorahip_synthesizer_clipped(lorahip_synthesizer *s, unsigned long long *count);
+int lorahip_psb_clipped(lorahip_psb *p, unsigned long long *count);
 
 /* Measurement aid: one read-only streaming pass over n_bytes of device memory (pattern 0: linear
  * 16 B per lane; 1: the access shape of the tuned SF7 kernel). Time it with lorahip_timer_*; the

@@ -11,7 +11,7 @@ OK = 0
 SF_MIN, SF_MAX = 6, 12
 FINE_STEPS = 128
 CHIRP_UP, CHIRP_DOWN, CHIRP_NONE = 0, 1, 2
-IQ_CF32, IQ_SC16, IQ_SC8 = 0, 1, 2         # LORAHIP_IQ_*: the sample formats of the receive front ends
+IQ_CF32, IQ_SC16, IQ_SC8 = 0, 1, 2         # LORAHIP_IQ_*: the sample formats the receive front ends read and the synthesisers write
 
 _f32p = C.POINTER(C.c_float)
 
@@ -198,6 +198,10 @@ SIGNATURES = {
     "lorahip_psb_reset": (C.c_int, [C.c_void_p]),
     "lorahip_psb_out_count": (C.c_size_t, [C.c_void_p, C.c_size_t]),
     "lorahip_psb_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]),
+    "lorahip_synthesizer_run_iq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_size_t)]),
+    "lorahip_psb_run_iq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_size_t)]),
+    "lorahip_synthesizer_clipped": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
+    "lorahip_psb_clipped": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "lorahip_demod_activate": (C.c_int, [C.c_void_p]),
     "lorahip_demod_set_mode": (C.c_int, [C.c_void_p, C.c_int]),
     "lorahip_demod_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -601,15 +601,57 @@ def _chan_run(obj, run, wide, out, int_scale=()):
     return out[:, :got.value]
 
 
-def _synth_run(obj, run, rows, out):
-    """Synthesizer.run and PolyphaseSynthesizer.run: check rows and out, call the C entry point `run`, return the outputs it wrote"""
+def _iq_out_args(rows, n_channels, dtype, scale):
+    """The arguments of Synthesizer.run_int / PolyphaseSynthesizer.run_int checked before any call into the library, and the (format,
+    scale) arguments of the *_run_iq entry points of the transmit side: rows a (K, n) complex64 DEVICE tensor, the format from dtype
+    (torch.int16 / torch.int8), scale None = 32767 for int16 and 127 for int8 (|component| <= 1 never clips)."""
     import torch
-    if (rows.dim() != 2 or rows.dtype != torch.complex64 or rows.shape[0] != obj.n_channels
+    formats = {torch.int16: (_lib.IQ_SC16, 32767.0), torch.int8: (_lib.IQ_SC8, 127.0)}
+    if dtype not in formats:
+        raise ValueError("dtype must be torch.int16 or torch.int8")
+    fmt, default = formats[dtype]
+    if scale is None:
+        scale = default
+    try:
+        scale = float(scale)
+    except (TypeError, ValueError):
+        scale = float("nan")
+    with np.errstate(over="ignore"):
+        held = np.isfinite(np.float32(scale))
+    if not held:
+        raise ValueError("scale must be a finite real number that float32 holds (None: 32767 for int16, 127 for int8)")
+    if (not _is_torch(rows) or not rows.is_cuda or rows.dim() != 2 or rows.dtype != torch.complex64 or rows.shape[0] != n_channels
+            or (rows.numel() and (rows.stride(1) != 1 or (rows.shape[0] > 1 and rows.stride(0) < rows.shape[1])))):
+        raise ValueError("rows must be a (K, n) complex64 device tensor with unit column stride (rows may be a slice of a wider buffer)")
+    return fmt, C.c_float(scale)
+
+
+def _iq_out_buffer(out, dtype, n_out, device):
+    """the (>= n_out, 2) integer tensor run_int writes: `out` checked (a device tensor of `dtype`, the last axis I, Q, strides (2, 1);
+    it may start at any sample of a larger buffer: buf[k:]), or a new one"""
+    import torch
+    if out is None:
+        return torch.empty((n_out, 2), dtype=dtype, device=device)
+    if (not _is_torch(out) or not out.is_cuda or out.dtype != dtype or out.dim() != 2 or out.shape[1] != 2 or out.shape[0] < n_out
+            or (out.numel() and (out.stride(1) != 1 or out.stride(0) != 2))):
+        raise ValueError("out must be a (>= n * interp, 2) device tensor of dtype %s, the last axis I, Q, with strides (2, 1)" % dtype)
+    return out
+
+
+def _synth_run(obj, run, rows, out, int_format=()):
+    """Synthesizer.run / run_int and PolyphaseSynthesizer.run / run_int: check rows and out, call the C entry point `run`, return the
+    outputs it wrote. int_format = (dtype, scale): the integer output of run_int and `run` the *_run_iq entry point."""
+    import torch
+    if int_format:
+        iq = _iq_out_args(rows, obj.n_channels, *int_format)
+    elif (rows.dim() != 2 or rows.dtype != torch.complex64 or rows.shape[0] != obj.n_channels
             or (rows.numel() and (rows.stride(1) != 1 or (rows.shape[0] > 1 and rows.stride(0) < rows.shape[1])))):
         raise ValueError("rows must be a (K, n) complex64 device tensor with unit column stride (rows may be a slice of a wider buffer)")
     n_in = int(rows.shape[1])
     n_out = obj.out_count(n_in)
-    if out is None:
+    if int_format:
+        out = _iq_out_buffer(out, int_format[0], n_out, rows.device)
+    elif out is None:
         out = torch.empty(n_out, dtype=torch.complex64, device=rows.device)
     elif out.dim() != 1 or out.dtype != torch.complex64 or out.numel() < n_out or (out.numel() and out.stride(0) != 1):
         raise ValueError("out must be a 1-D complex64 tensor of >= n * interp samples with unit stride")
@@ -618,8 +660,16 @@ def _synth_run(obj, run, rows, out):
     # the row stride is the tensor's own: `rows` may be a column slice of a (K, capacity) buffer
     check(getattr(obj._lib, run)(obj._h, C.c_void_p(rows.data_ptr()) if rows.numel() else None,
                                  int(rows.stride(0)) if rows.numel() and rows.shape[0] > 1 else n_in, n_in,
-                                 C.c_void_p(out.data_ptr()) if out.numel() else None, C.byref(got)), run)
+                                 C.c_void_p(out.data_ptr()) if out.numel() else None, *(iq if int_format else ()), C.byref(got)), run)
     return out[:got.value]
+
+
+def _synth_clipped(obj, entry):
+    """Synthesizer.clipped / PolyphaseSynthesizer.clipped: the count the C entry point reports (it waits for the context's stream)"""
+    obj._ctx.use_torch_stream()
+    n = C.c_ulonglong()
+    check(getattr(obj._lib, entry)(obj._h, C.byref(n)), entry)
+    return int(n.value)
 
 
 class _PolyphaseBank(_Handle):
@@ -735,6 +785,20 @@ class Synthesizer(_Handle):
         [a, a + n) of a wider buffer); returns the 1-D complex64 tensor of n * interp wideband samples (written into out if given)"""
         return _synth_run(self, "lorahip_synthesizer_run", rows, out)
 
+    def run_int(self, rows, dtype=None, scale=None, out=None):
+        """run() with the wideband output as integers, as a DAC, an SDR transmit port or a recording takes them: returns the (n * interp,
+        2) device tensor of dtype torch.int16 (the default) or torch.int8, last axis I, Q (written into out if given: a (>= n * interp,
+        2) tensor of that dtype with strides (2, 1), which may be buf[k:] of a larger buffer). Each component is scale * c, rounded to
+        nearest (ties to even) and saturated, NaN -> 0; scale None = 32767 / 127. Quantised in the kernel's store: bit-identical to
+        run()'s output quantised that way (include/lorahip.h), and free to alternate with run() on one stream. clipped() counts."""
+        import torch
+        return _synth_run(self, "lorahip_synthesizer_run_iq", rows, out, (torch.int16 if dtype is None else dtype, scale))
+
+    def clipped(self):
+        """components (I and Q counted separately) that run_int saturated or found NaN since the object was made or reset; waits for
+        the stream"""
+        return _synth_clipped(self, "lorahip_synthesizer_clipped")
+
 
 class PolyphaseSynthesizer(_PolyphaseBank):
     """The synthesiser for a uniform channel plan: row k goes to centre bins[k] / n_bins cycles per OUTPUT sample (n_bins a power of
@@ -766,6 +830,18 @@ class PolyphaseSynthesizer(_PolyphaseBank):
         """rows: (K, n) complex64 device tensor with unit column stride (the next n samples of every channel; may be the columns
         [a, a + n) of a wider buffer); returns the 1-D complex64 tensor of n * interp wideband samples (written into out if given)"""
         return _synth_run(self, "lorahip_psb_run", rows, out)
+
+    def run_int(self, rows, dtype=None, scale=None, out=None):
+        """run() with the wideband output as integers: the (n * interp, 2) device tensor of dtype torch.int16 (the default) or
+        torch.int8, last axis I, Q; dtype, scale and out as in Synthesizer.run_int. Quantised in the kernel's store: bit-identical to
+        run()'s output quantised by the definition in include/lorahip.h. Serves the constructor, radix5 and for_plan."""
+        import torch
+        return _synth_run(self, "lorahip_psb_run_iq", rows, out, (torch.int16 if dtype is None else dtype, scale))
+
+    def clipped(self):
+        """components (I and Q counted separately) that run_int saturated or found NaN since the object was made or reset; waits for
+        the stream"""
+        return _synth_clipped(self, "lorahip_psb_clipped")
 
 
 class LoRaDetector(_Handle):

@@ -1,6 +1,7 @@
 // What the four front ends (lorahip_chan.hip, lorahip_synth.hip, lorahip_pfb.hip, lorahip_psb.hip) have in common, stated once: the
 // state that carries one stream across calls, the output count of the decimators, the sample lookup and the history kernel of the two
-// channelisers with the sample formats they read, and the way an object's tables reach the device when it is created.
+// channelisers with the sample formats they read, the integer formats the two synthesisers store with their clip counter, and the way an
+// object's tables reach the device when it is created.
 #pragma once
 #include "lorahip_own.h"
 #include <cmath>
@@ -71,13 +72,79 @@ __device__ __forceinline__ float2 iqLoad(const char2 *p, const float scale)
     return make_float2(scale * float(v.x), scale * float(v.y));
 }
 
+// The same formats on the transmit side (include/lorahip.h, "Integer IQ output", has the definition; nothing here restates it
+// differently): a synthesiser's cf32 output sample y is stored as float2 as it is, or per component as t = scale * c (ONE fp32 multiply,
+// an operation of its own), r = rint(t) (v_rndne_f32: ties to even), then 0 for NaN, lo for r < lo, hi for r > hi, (int)r otherwise;
+// a component is clipped when r is NaN or outside [lo, hi].
+
+//! one component by that definition; clipped counts it when it clips
+template <int LO, int HI> __device__ __forceinline__ int iqQuantize(const float c, const float scale, unsigned &clipped)
+{
+    const float r = rintf(scale * c);
+    const bool nan = r != r, low = r < float(LO), high = r > float(HI);
+    clipped += unsigned(nan | low | high);
+    return nan ? 0 : low ? LO : high ? HI : int(r);
+}
+//! sample y in the format of *p, quantised: the one place a format is written
+__device__ __forceinline__ float2 iqPack(const float2 *, const float2 y, const float, unsigned &) { return y; }
+__device__ __forceinline__ short2 iqPack(const short2 *, const float2 y, const float scale, unsigned &clipped)
+{
+    const int i = iqQuantize<-32768, 32767>(y.x, scale, clipped), q = iqQuantize<-32768, 32767>(y.y, scale, clipped);
+    return make_short2(short(i), short(q));
+}
+__device__ __forceinline__ char2 iqPack(const char2 *, const float2 y, const float scale, unsigned &clipped)
+{
+    const int i = iqQuantize<-128, 127>(y.x, scale, clipped), q = iqQuantize<-128, 127>(y.y, scale, clipped);
+    return make_char2((signed char)i, (signed char)q);
+}
+//! *p = y in p's format; clipped grows by the lane's clipped components (never for float2)
+template <class S> __device__ __forceinline__ void iqStore(S *p, const float2 y, const float scale, unsigned &clipped)
+{
+    *p = iqPack(p, y, scale, clipped);
+}
+
+//! The clipped components of a wavefront (per lane < 2^BITS) go to *counter: bit b of every lane's count is one ballot, so lanes that
+//! have left the kernel count nothing; then ONE lane adds, and no lane where the wavefront clipped nothing. Call it where the lanes
+//! that stored have come together again.
+template <int BITS> __device__ __forceinline__ void iqCountClipped(unsigned long long *counter, const unsigned clipped)
+{
+    unsigned total = 0;
+#pragma unroll
+    for (int b = 0; b < BITS; b++) total += unsigned(__popcll(__ballot(int((clipped >> b) & 1u)))) << b;
+    const int lane = int(__lane_id());
+    if (total && lane == __builtin_amdgcn_readfirstlane(lane)) atomicAdd(counter, (unsigned long long)total);
+}
+
+//! the clip counter of a synthesiser: 8 bytes on the device, allocated and zeroed by the first integer run (an object that only ever
+//! writes cf32 allocates what it always did), zeroed again by reset
+struct ClipCount
+{
+    DevBuf<unsigned long long> dev;
+    //! before an integer run is launched on `stream`
+    hipError_t ensure(hipStream_t stream)
+    {
+        if (dev.get()) return hipSuccess;
+        const hipError_t e = dev.grow(sizeof(unsigned long long));
+        return e != hipSuccess ? e : hipMemsetAsync(dev.get(), 0, sizeof(unsigned long long), stream);
+    }
+    hipError_t reset(hipStream_t stream) { return dev.get() ? hipMemsetAsync(dev.get(), 0, sizeof(unsigned long long), stream) : hipSuccess; }
+    //! the count of everything launched on `stream` so far (synchronises it)
+    hipError_t read(hipStream_t stream, unsigned long long *count) const
+    {
+        *count = 0;
+        const hipError_t e = dev.get() ? hipMemcpyAsync(count, dev.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost, stream) : hipSuccess;
+        return e != hipSuccess ? e : hipStreamSynchronize(stream);
+    }
+};
+
 //! bytes of one sample of a LORAHIP_IQ_* format, 0 for anything else
 inline size_t iqSampleBytes(const int format)
 {
     return format == LORAHIP_IQ_CF32 ? sizeof(float2) : format == LORAHIP_IQ_SC16 ? sizeof(short2) : format == LORAHIP_IQ_SC8 ? sizeof(char2) : 0;
 }
 
-//! what every *_run_iq refuses before it looks at anything else: LORAHIP_OK, or LORAHIP_E_INVALID and "<who>: ..." in lorahip_last_error
+//! what every *_run_iq refuses before it looks at anything else: LORAHIP_OK, or LORAHIP_E_INVALID and "<who>: ..." in lorahip_last_error.
+//! wide is the chunk a channeliser reads or the buffer a synthesiser writes: the same four rules hold for both directions.
 inline int iqCheck(const std::string &who, const void *wide, const int format, const float scale)
 {
     const size_t bytes = iqSampleBytes(format);
@@ -97,6 +164,13 @@ template <class F> int iqDispatch(const void *wide, const int format, F &&f)
     if (format == LORAHIP_IQ_SC16) return f(static_cast<const short2 *>(wide));
     if (format == LORAHIP_IQ_SC8) return f(static_cast<const char2 *>(wide));
     return f(static_cast<const float2 *>(wide));
+}
+//! the same for the buffer a synthesiser writes
+template <class F> int iqDispatch(void *wide, const int format, F &&f)
+{
+    if (format == LORAHIP_IQ_SC16) return f(static_cast<short2 *>(wide));
+    if (format == LORAHIP_IQ_SC8) return f(static_cast<char2 *>(wide));
+    return f(static_cast<float2 *>(wide));
 }
 
 //! sample n of the stream (absolute index): from this call's chunk (format S, converted), from the history kept from earlier calls

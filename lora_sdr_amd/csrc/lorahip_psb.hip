@@ -31,6 +31,10 @@
 // The three kernels are templates on M, like the receive bank's. M = 5 * 2^a: the transform is lorahip_pfbfft5.h with the conjugate
 // tables -- one radix-5 stage, then five radix-2 transforms of N = M / 5 points, residue 5 k + r left at r N + bitrev(k) --, and the
 // divisions and remainders by M are by a compile-time constant where the powers of two have shifts and masks.
+// psbFold is also a template on the output sample type S (lorahip_frontend.h: float2, short2 = sc16, char2 = sc8): the fold is the same
+// sequence of FMAs, the lane's one output becomes an 8-, 4- or 2-byte store, quantised by the definition in include/lorahip.h, and the
+// integer instances add their clipped components to the object's counter, one atomic per wavefront at most. The workspace and the
+// history stay cf32, and a segment's output pointer advances in samples of S.
 #include "lorahip_bank.h"
 #include <new>
 
@@ -47,6 +51,7 @@ struct lorahip_psb
     lorahip::DevBuf<float> dBinGain;            // [K] the gain of that row
     lorahip::DevBuf<float2> dWs;                // [segment][M] u_s[m] of the segment in flight
     lorahip::StreamCarry carry;                 // [HC][M] u_s[m] of the HC input times before n0
+    lorahip::ClipCount clipped;                 // components the integer runs clipped since create / reset
 };
 
 namespace lorahip {
@@ -67,8 +72,10 @@ struct PsbArgs
     const float2 *tw;
     float2 *ws;
     const float2 *hist;
-    float2 *out;                    // the segment's first output
+    void *out;                      // the segment's first output, samples of psbFold's S
     int U, L, HC, T, logT;
+    unsigned long long *clipped;    // the integer instances of psbFold count here; float2 ignores both
+    float scale;
 };
 
 //! u_s of input time m0 + c (c >= -HC): from this segment's workspace or from the history kept from earlier segments and calls
@@ -126,7 +133,7 @@ __global__ __launch_bounds__(PFB_THREADS) void psbTransform(const PsbArgs a)
     }
 }
 
-template <int M>
+template <int M, class S>
 __global__ __launch_bounds__(PSB_FOLD_THREADS) void psbFold(const PsbArgs a)
 {
     const unsigned U = unsigned(a.U);
@@ -147,7 +154,13 @@ __global__ __launch_bounds__(PSB_FOLD_THREADS) void psbFold(const PsbArgs a)
         re = __builtin_fmaf(h, u.x, re);
         im = __builtin_fmaf(h, u.y, im);
     }
-    a.out[o] = make_float2(re, im);
+    if constexpr (std::is_same<S, float2>::value) static_cast<float2 *>(a.out)[o] = make_float2(re, im);
+    else
+    {
+        unsigned clipped = 0;                       // <= 2 a lane; the lanes past the end have left and count nothing
+        iqStore(static_cast<S *>(a.out) + o, make_float2(re, im), a.scale, clipped);
+        iqCountClipped<2>(a.clipped, clipped);
+    }
 }
 
 //! the transforms of the HC input times that precede the next segment
@@ -162,7 +175,7 @@ __global__ void psbHistory(const PsbArgs a, float2 *newHist)
     newHist[idx] = psbU<M>(a, a.cnt - a.HC + h, s);         // >= -HC
 }
 
-template <int M>
+template <int M, class S>
 static hipError_t psbLaunch(const lorahip_psb *p, const PsbArgs &a, float2 *newHist)
 {
     static unsigned long long ldsMask;
@@ -173,7 +186,7 @@ static hipError_t psbLaunch(const lorahip_psb *p, const PsbArgs &a, float2 *newH
     hipLaunchKernelGGL((psbTransform<M>), dim3(tiles), dim3(PFB_THREADS), p->ldsBytes, st, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     const unsigned long long nOut = (unsigned long long)a.cnt * (unsigned long long)a.U;        // <= 2^30
-    hipLaunchKernelGGL((psbFold<M>), dim3(unsigned((nOut + PSB_FOLD_THREADS - 1) / PSB_FOLD_THREADS)), dim3(PSB_FOLD_THREADS), 0, st, a);
+    hipLaunchKernelGGL((psbFold<M, S>), dim3(unsigned((nOut + PSB_FOLD_THREADS - 1) / PSB_FOLD_THREADS)), dim3(PSB_FOLD_THREADS), 0, st, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (a.HC)
     {
@@ -184,7 +197,9 @@ static hipError_t psbLaunch(const lorahip_psb *p, const PsbArgs &a, float2 *newH
     return e;
 }
 
-static int psbRun(lorahip_psb *p, const float2 *in, const size_t inStride, const size_t nIn, float2 *out, size_t *nOutP)
+//! out in the format S; scale is what the integer formats multiply by
+template <class S>
+static int psbRun(lorahip_psb *p, const float2 *in, const size_t inStride, const size_t nIn, S *out, const float scale, size_t *nOutP)
 {
     lorahip_ctx *ctx = p->ctx;
     if (nOutP) *nOutP = 0;
@@ -207,6 +222,8 @@ static int psbRun(lorahip_psb *p, const float2 *in, const size_t inStride, const
     a.binStart = p->dBinStart.get(); a.binRow = p->dBinRow.get(); a.binGain = p->dBinGain.get();
     a.taps = p->dTaps.get(); a.tw = p->dTw.get(); a.ws = p->dWs.get();
     a.U = p->U; a.L = p->L; a.HC = p->HC; a.T = p->T; a.logT = p->logT;
+    if constexpr (!std::is_same<S, float2>::value) LORAHIP_TRY(p->clipped.ensure(ctx->stream));
+    a.clipped = p->clipped.dev.get(); a.scale = scale;
     for (size_t done = 0; done < nIn; )
     {
         const size_t cnt = nIn - done < seg ? nIn - done : seg;
@@ -214,7 +231,7 @@ static int psbRun(lorahip_psb *p, const float2 *in, const size_t inStride, const
         a.hist = p->carry.current();
         a.out = out + done * U;
         float2 *newHist = p->carry.next();
-        const hipError_t e = bankDispatch(p->M, BankCounts(), [&](const auto m) { return psbLaunch<decltype(m)::value>(p, a, newHist); });
+        const hipError_t e = bankDispatch(p->M, BankCounts(), [&](const auto m) { return psbLaunch<decltype(m)::value, S>(p, a, newHist); });
         LORAHIP_TRY(e);
         p->carry.advance(cnt);
         done += cnt;
@@ -321,6 +338,7 @@ int lorahip_psb_reset(lorahip_psb *p)
     if (p == nullptr) return LORAHIP_E_INVALID;
     const DeviceGuard guard(p->ctx->device);
     LORAHIP_TRY(p->carry.reset(p->ctx->stream));
+    LORAHIP_TRY(p->clipped.reset(p->ctx->stream));
     return LORAHIP_OK;
 }
 
@@ -332,7 +350,24 @@ size_t lorahip_psb_out_count(const lorahip_psb *p, const size_t n_in)
 int lorahip_psb_run(lorahip_psb *p, const float *in_dev, const size_t in_stride, const size_t n_in, float *wide_dev, size_t *n_out)
 {
     if (p == nullptr) return LORAHIP_E_INVALID;
-    return psbRun(p, reinterpret_cast<const float2 *>(in_dev), in_stride, n_in, reinterpret_cast<float2 *>(wide_dev), n_out);
+    return psbRun(p, reinterpret_cast<const float2 *>(in_dev), in_stride, n_in, reinterpret_cast<float2 *>(wide_dev), 1.0f, n_out);
+}
+
+int lorahip_psb_run_iq(lorahip_psb *p, const float *in_dev, const size_t in_stride, const size_t n_in, void *wide_dev, const int format,
+                       const float scale, size_t *n_out)
+{
+    if (p == nullptr) return LORAHIP_E_INVALID;
+    if (n_out) *n_out = 0;
+    if (iqCheck("polyphase synthesiser", wide_dev, format, scale) != LORAHIP_OK) return LORAHIP_E_INVALID;
+    return iqDispatch(wide_dev, format, [&](auto *wide) { return psbRun(p, reinterpret_cast<const float2 *>(in_dev), in_stride, n_in, wide, scale, n_out); });
+}
+
+int lorahip_psb_clipped(lorahip_psb *p, unsigned long long *count)
+{
+    if (p == nullptr || count == nullptr) return LORAHIP_E_INVALID;
+    const DeviceGuard guard(p->ctx->device);
+    LORAHIP_TRY(p->clipped.read(p->ctx->stream, count));
+    return LORAHIP_OK;
 }
 
 } // extern "C"

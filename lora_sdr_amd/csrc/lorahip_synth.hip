@@ -15,6 +15,13 @@
 // the 256 places inside it): nothing depends on how the stream was cut into calls, and nothing drifts.
 // Stores: a lane's 8 outputs are 64 contiguous bytes, lanes lie U * 8 bytes apart: four 16-byte stores per lane, back to back
 // (DESIGN.md has the reasoning and what was measured).
+// The kernel is a template on the output sample type S (`Out` inside the kernel; lorahip_frontend.h: float2, short2 = sc16, char2 =
+// sc8); nothing before the store depends on it. A lane's 8 outputs are 8 * sizeof(S) contiguous bytes = 64 / 32 / 16, lanes lie
+// U * sizeof(S) bytes apart. The rule of the wide path, for every S: vec16 = (U * sizeof(S)) % 16 == 0 and the output pointer is
+// 16-byte aligned -- then every lane's first output of a full phase block is, and the lane writes four / two / one 16-byte stores.
+// U even (cf32), U % 4 == 0 (sc16), U % 8 == 0 (sc8). Otherwise, and in a partial phase block, one store per sample, guarded by
+// p0 + p < U. The integer instances quantise by the definition in include/lorahip.h (iqPack) and add their clipped components to the
+// object's counter, one atomic per wavefront at most (iqCountClipped).
 #include "lorahip_frontend.h"
 #include "lorahip_mixer.h"
 #include <cmath>
@@ -30,6 +37,7 @@ struct lorahip_synthesizer
     lorahip::DevBuf<unsigned long long> dWU;    // [nGroups*8] w_k * U mod 2^64: the phase step of one input time
     lorahip::DevBuf<float2> dRot;               // [nGroups*8][256] e^{+2 pi i frac(w_k U t / 2^64)}
     lorahip::StreamCarry carry;                 // [K][HC] the HC input samples of every channel before n0
+    lorahip::ClipCount clipped;                 // components the integer runs clipped since create / reset
 };
 
 namespace lorahip {
@@ -47,8 +55,10 @@ struct SynthArgs
     const v2f *taps;
     const unsigned long long *wU;
     const v2f *laneRot;
-    float2 *out;
+    void *out;                      // samples of the kernel's S
     int K, L, U, I, UP, nPB, TS, nBlk, HC, nGroups, vec16;
+    unsigned long long *clipped;    // the integer instances count here; float2 ignores both
+    float scale;
 };
 
 //! sample m of channel ch (absolute index): from this call's rows, from the history kept from earlier calls, or 0
@@ -91,7 +101,7 @@ __device__ __forceinline__ void synthFma(v2f (&acc)[SYN_P], const v16f &G, const
 }
 
 // blockIdx.x = tile * nPB + phase block: the phase blocks of a tile are neighbours in launch order and share the tile's input in L2
-__global__ __launch_bounds__(SYN_THREADS) void synthesize(const SynthArgs a)
+template <class Out> __global__ __launch_bounds__(SYN_THREADS) void synthesize(const SynthArgs a)
 {
     extern __shared__ float2 synLds[];
     v2f *xs = reinterpret_cast<v2f *>(synLds);                  // [8][TS] rotated samples, then [nBlk][8] block phases
@@ -173,18 +183,45 @@ __global__ __launch_bounds__(SYN_THREADS) void synthesize(const SynthArgs a)
 #pragma unroll
     for (int p = 0; p < SYN_P; p++)
         if (p0 + p >= a.L) acc[p] = (v2f){0.0f, 0.0f};          // a phase without a tap: exactly 0 whatever the input holds
-    float2 *o = a.out + (mLoc * a.U + p0);                      // 64-bit: 2^30 outputs are 2^33 bytes
-    if (a.vec16 && p0 + SYN_P <= a.U)
+    Out *o = static_cast<Out *>(a.out) + (mLoc * a.U + p0);         // 64-bit: 2^30 outputs are 2^33 bytes
+    if constexpr (std::is_same<Out, float2>::value)
     {
+        if (a.vec16 && p0 + SYN_P <= a.U)
+        {
 #pragma unroll
-        for (int p = 0; p < SYN_P; p += 2)
-            *reinterpret_cast<float4 *>(o + p) = make_float4(acc[p].x, acc[p].y, acc[p + 1].x, acc[p + 1].y);
+            for (int p = 0; p < SYN_P; p += 2)
+                *reinterpret_cast<float4 *>(o + p) = make_float4(acc[p].x, acc[p].y, acc[p + 1].x, acc[p + 1].y);
+        }
+        else
+        {
+#pragma unroll
+            for (int p = 0; p < SYN_P; p++)
+                if (p0 + p < a.U) o[p] = make_float2(acc[p].x, acc[p].y);
+        }
     }
     else
     {
+        unsigned clipped = 0;                                   // <= 16 a lane
+        if (a.vec16 && p0 + SYN_P <= a.U)
+        {
+            constexpr int PER = 16 / int(sizeof(Out));            // samples per 16-byte store: 4 (sc16), 8 (sc8)
+            struct alignas(16) Line { Out v[PER]; };
 #pragma unroll
-        for (int p = 0; p < SYN_P; p++)
-            if (p0 + p < a.U) o[p] = make_float2(acc[p].x, acc[p].y);
+            for (int p = 0; p < SYN_P; p += PER)
+            {
+                Line line;
+#pragma unroll
+                for (int q = 0; q < PER; q++) line.v[q] = iqPack(o, make_float2(acc[p + q].x, acc[p + q].y), a.scale, clipped);
+                *reinterpret_cast<Line *>(o + p) = line;
+            }
+        }
+        else
+        {
+#pragma unroll
+            for (int p = 0; p < SYN_P; p++)
+                if (p0 + p < a.U) iqStore(o + p, make_float2(acc[p].x, acc[p].y), a.scale, clipped);
+        }
+        iqCountClipped<5>(a.clipped, clipped);                  // the lanes of both paths are together again (the path is the block's)
     }
 }
 
@@ -196,10 +233,11 @@ __global__ void synthHistory(const SynthArgs a, float2 *newHist)
     if (h < a.HC && ch < a.K) newHist[(long long)ch * a.HC + h] = synthSample(a, ch, a.n0 + a.nIn - a.HC + h);
 }
 
-static unsigned long long gSynthLdsMask = 0;
-
-static int synthRun(lorahip_synthesizer *s, const float2 *in, const size_t inStride, const size_t nIn, float2 *out, size_t *nOutP)
+//! out in the format S; scale is what the integer formats multiply by
+template <class S>
+static int synthRun(lorahip_synthesizer *s, const float2 *in, const size_t inStride, const size_t nIn, S *out, const float scale, size_t *nOutP)
 {
+    static unsigned long long ldsMask = 0;
     lorahip_ctx *ctx = s->ctx;
     const DeviceGuard guard(ctx->device);
     if (nOutP) *nOutP = 0;
@@ -220,9 +258,11 @@ static int synthRun(lorahip_synthesizer *s, const float2 *in, const size_t inStr
     a.out = out;
     a.K = s->K; a.L = s->L; a.U = s->U; a.I = s->I; a.UP = s->UP; a.nPB = s->nPB; a.TS = s->TS; a.nBlk = s->nBlk; a.HC = s->HC;
     a.nGroups = s->nGroups;
-    a.vec16 = (s->U % 2 == 0 && uintptr_t(out) % 16 == 0) ? 1 : 0;
-    LORAHIP_TRY(ensureDynamicLds(reinterpret_cast<const void *>(&synthesize), 160 * 1024, gSynthLdsMask));
-    hipLaunchKernelGGL(synthesize, dim3((unsigned)nBlocks), dim3(SYN_THREADS), s->ldsBytes, ctx->stream, a);
+    a.vec16 = ((size_t(s->U) * sizeof(S)) % 16 == 0 && uintptr_t(out) % 16 == 0) ? 1 : 0;
+    if constexpr (!std::is_same<S, float2>::value) LORAHIP_TRY(s->clipped.ensure(ctx->stream));
+    a.clipped = s->clipped.dev.get(); a.scale = scale;
+    LORAHIP_TRY(ensureDynamicLds(reinterpret_cast<const void *>(&synthesize<S>), 160 * 1024, ldsMask));
+    hipLaunchKernelGGL(synthesize<S>, dim3((unsigned)nBlocks), dim3(SYN_THREADS), s->ldsBytes, ctx->stream, a);
     LORAHIP_TRY(hipGetLastError());
     if (s->HC)
     {
@@ -314,6 +354,7 @@ int lorahip_synthesizer_reset(lorahip_synthesizer *s)
     if (s == nullptr) return LORAHIP_E_INVALID;
     const DeviceGuard guard(s->ctx->device);
     LORAHIP_TRY(s->carry.reset(s->ctx->stream));
+    LORAHIP_TRY(s->clipped.reset(s->ctx->stream));
     return LORAHIP_OK;
 }
 
@@ -326,7 +367,24 @@ int lorahip_synthesizer_run(lorahip_synthesizer *s, const float *in_dev, const s
                             size_t *n_out)
 {
     if (s == nullptr) return LORAHIP_E_INVALID;
-    return synthRun(s, reinterpret_cast<const float2 *>(in_dev), in_stride, n_in, reinterpret_cast<float2 *>(wide_dev), n_out);
+    return synthRun(s, reinterpret_cast<const float2 *>(in_dev), in_stride, n_in, reinterpret_cast<float2 *>(wide_dev), 1.0f, n_out);
+}
+
+int lorahip_synthesizer_run_iq(lorahip_synthesizer *s, const float *in_dev, const size_t in_stride, const size_t n_in, void *wide_dev,
+                               const int format, const float scale, size_t *n_out)
+{
+    if (s == nullptr) return LORAHIP_E_INVALID;
+    if (n_out) *n_out = 0;
+    if (iqCheck("synthesiser", wide_dev, format, scale) != LORAHIP_OK) return LORAHIP_E_INVALID;
+    return iqDispatch(wide_dev, format, [&](auto *wide) { return synthRun(s, reinterpret_cast<const float2 *>(in_dev), in_stride, n_in, wide, scale, n_out); });
+}
+
+int lorahip_synthesizer_clipped(lorahip_synthesizer *s, unsigned long long *count)
+{
+    if (s == nullptr || count == nullptr) return LORAHIP_E_INVALID;
+    const DeviceGuard guard(s->ctx->device);
+    LORAHIP_TRY(s->clipped.read(s->ctx->stream, count));
+    return LORAHIP_OK;
 }
 
 } // extern "C"
