@@ -126,15 +126,7 @@ detectFast(const DetectArgs a, const FastTables ft, const unsigned nSets)
     __syncthreads();
 
     // which window sets this wave walks: set = first, first + waveCount, ... < last
-    unsigned waveId = blockIdx.x * WAVES + wave, waveCount = gridDim.x * WAVES, setEnd = nSets;
-    if (C::XCD_CONTIG && gridDim.x >= 8 && (gridDim.x & 7) == 0)
-    {
-        // workgroups are dealt round-robin to the 8 XCDs: give each XCD one contiguous eighth of the batch
-        const unsigned xcd = blockIdx.x & 7, perXcd = (nSets + 7) / 8;
-        waveCount = (gridDim.x >> 3) * WAVES;
-        waveId = xcd * perXcd + (blockIdx.x >> 3) * WAVES + wave;
-        setEnd = (xcd + 1) * perXcd < nSets ? (xcd + 1) * perXcd : nSets;
-    }
+    const unsigned waveId = blockIdx.x * WAVES + wave, waveCount = gridDim.x * WAVES;
     int pending = 0;                                       // tail records waiting in tr
 
     v2f xn[R][VEC];
@@ -144,14 +136,14 @@ detectFast(const DetectArgs a, const FastTables ft, const unsigned nSets)
         const unsigned wc_ = w_ < a.nWindows ? w_ : a.nWindows - 1;
         K::load(xn, gIq + (a.offsets ? a.offsets[wc_] : (long long)wc_ * a.stride), t);
     };
-    if (C::PREFETCH && waveId < setEnd) issueLoads(waveId);
+    if (C::PREFETCH && waveId < nSets) issueLoads(waveId);
     const v2f fconst0 = gFine[0];
 
     const int prioSlot = wavefrontSlot();
 #ifdef LORAHIP_WG_TIMELINE
     tlLoop = wall_clock64();
 #endif
-    for (unsigned set = waveId; set < setEnd; set += waveCount)
+    for (unsigned set = waveId; set < nSets; set += waveCount)
     {
 #ifdef LORAHIP_WG_TIMELINE
         tlSets++;
@@ -175,7 +167,6 @@ detectFast(const DetectArgs a, const FastTables ft, const unsigned nSets)
         for (int r = 0; r < R; r++)
 #pragma unroll
             for (int u = 0; u < VEC; u++) x[r][u] = xn[r][u];
-        if (C::PREFETCH == 2) issueLoads(set + waveCount < setEnd ? set + waveCount : nSets - 1);
 
         // ---- fine-tune indices of this lane's samples for windows whose index moves (LoRaDemod.cpp:160-162): closed form
         // (lorahip_fine.h); a wave that holds a window where the form does not apply walks the exact chain instead
@@ -261,7 +252,7 @@ detectFast(const DetectArgs a, const FastTables ft, const unsigned nSets)
         // ---- phases / exchanges; the next set's samples go in flight once phase 0's inputs are staged and land
         // while this set is transformed (past the end: re-read the last set, harmless and branch-free)
         v2f vl[NGL][GL];
-        K::fft(x, X, wsub, t, sTw, twR, vl, [&]() { if (C::PREFETCH == 1) issueLoads(set + waveCount < setEnd ? set + waveCount : nSets - 1); }, &twM);
+        K::fft(x, X, wsub, t, sTw, twR, vl, [&]() { if (C::PREFETCH) issueLoads(set + waveCount < nSets ? set + waveCount : nSets - 1); }, &twM);
 
         // ---- scan (LoRaDetector.hpp:36-48); final bins into the (now free) exchange region for the neighbour fetch
         v2f *F = X + wsub * FS;
@@ -341,14 +332,6 @@ static hipError_t launchOne(const DetectArgs &a, const FastTables &ft, hipStream
     return hipGetLastError();
 }
 
-template <class C>
-static hipError_t launchCfg(const DetectArgs &a, const FastTables &ft, hipStream_t stream)
-{
-    const bool uni = a.chirpSel == nullptr && a.fineErr == nullptr;
-    if (a.decOut || a.fftOut) return launchOne<C, true, false>(a, ft, stream);
-    return uni ? launchOne<C, false, true>(a, ft, stream) : launchOne<C, false, false>(a, ft, stream);
-}
-
 /***********************************************************************
  * configurations: the geometry of an SF is fixed (lanes per window, vector width, phases, the exchange-0 LDS layout found
  * with tools/lds_conflicts.py); what varies between the selectable variants is a set of options.
@@ -363,47 +346,27 @@ template <> struct Geo<10> { enum { LOG2T = 6, VEC = 1, NPH = 3, PB1 = 4, PB2 = 
 
 enum : unsigned
 {
-    W2 = 1u << 0, W4 = 1u << 1,         // waves per SIMD the register budget is set for (default 3)
-    CH_REG = 1u << 2,                    // chirp values of the lane's sample positions in registers (default: LDS copy of the table)
-    TW_REG = 1u << 3,                    // last-phase twiddles in registers (default: LDS table)
-    PF_NONE = 1u << 4, PF_EARLY = 1u << 5,   // next set's loads: none / at the top of the set (default: after the dechirp)
-    NT = 1u << 6,                        // non-temporal IQ loads
-    NB_SEL = 1u << 7,                    // peak's neighbours by register select (default: bins staged in LDS)
-    X1_SWAP = 1u << 8,                   // exchange 1 by row swaps / DPP (SF9, SF10)
-    TWM_REG = 1u << 9,                   // middle-phase twiddles in registers
-    XCD = 1u << 10,                      // XCD-contiguous walk over the batch
-    W1 = 1u << 11                        // one wave per SIMD: the 512-register budget (what does not fit 256 lands in AGPRs, not scratch)
+    W2 = 1u << 0,                        // register budget set for two waves per SIMD (default: three)
+    CH_REG = 1u << 1,                    // chirp values of the lane's sample positions in registers (default: LDS copy of the table)
+    TW_REG = 1u << 2,                    // last-phase twiddles in registers (default: LDS table)
+    PF_NONE = 1u << 3,                   // next set's loads at the top of their own set (default: in flight since the previous set's dechirp)
+    NT = 1u << 4,                        // non-temporal IQ loads
+    X1_SWAP = 1u << 5,                   // exchange 1 by row swaps / DPP (SF9, SF10)
+    TWM_REG = 1u << 6                    // middle-phase twiddles in registers
 };
 template <int SF, unsigned O>
-using Fast = FastCfg<SF, Geo<SF>::LOG2T, Geo<SF>::VEC, Geo<SF>::NPH, Geo<SF>::PB1, Geo<SF>::PB2, (O & W2) ? 2 : (O & W4) ? 4 : 3,
-                     Geo<SF>::ROT, Geo<SF>::PAD, Geo<SF>::S, Geo<SF>::D, !(O & CH_REG), !(O & TW_REG), (O & PF_NONE) ? 0 : (O & PF_EARLY) ? 2 : 1,
-                     (O & NT) != 0, (O & NB_SEL) != 0, (O & X1_SWAP) != 0, (O & TWM_REG) != 0, (O & XCD) != 0>;
+using Fast = FastCfg<SF, Geo<SF>::LOG2T, Geo<SF>::VEC, Geo<SF>::NPH, Geo<SF>::PB1, Geo<SF>::PB2, 0, (O & W2) ? 2 : 3,
+                     Geo<SF>::ROT, Geo<SF>::PAD, Geo<SF>::S, Geo<SF>::D, 8, !(O & CH_REG), !(O & TW_REG), !(O & PF_NONE),
+                     (O & X1_SWAP) != 0, (O & NT) != 0, (O & TWM_REG) != 0>;
 
 // second SF9 geometry: 16 lanes x 32 points, two phases [R2,4,4] X [4,4] -- one LDS exchange, no exchange 1; at the 256-register budget of
 // two waves per SIMD. +3.6 % on launch-uniform batches, -6 % where every window carries its own settings (spills): the default picks per call
 template <unsigned O>
-using Fast9b = FastCfg<9, 4, 1, 2, 5, 9, (O & W2) ? 2 : (O & W4) ? 4 : 3, 0, 1, 0, 0, !(O & CH_REG), !(O & TW_REG), (O & PF_NONE) ? 0 : (O & PF_EARLY) ? 2 : 1,
-                       (O & NT) != 0, (O & NB_SEL) != 0, false, false, false>;
+using Fast9b = FastCfg<9, 4, 1, 2, 5, 9, 0, (O & W2) ? 2 : 3, 0, 1, 0, 0, 8, !(O & CH_REG), !(O & TW_REG), !(O & PF_NONE), false, (O & NT) != 0>;
 
-// SF11 inside one wavefront: 64 lanes x 32 points, phases [R2,4,4] X [4] X [4,4], both exchanges wave-local (no workgroup barrier)
-template <unsigned O>
-using Fast11q = FastCfg<11, 6, 1, 3, 5, 7, (O & W1) ? 1 : (O & W2) ? 2 : (O & W4) ? 4 : 3, 0, 1, 0, 0, !(O & CH_REG), !(O & TW_REG), (O & PF_NONE) ? 0 : (O & PF_EARLY) ? 2 : 1,
-                        (O & NT) != 0, (O & NB_SEL) != 0, false, (O & TWM_REG) != 0, false>;
-
-// one LDS exchange less for the long windows, as two-phase geometries of 64 points per lane (profiling variants;
-// profiles/r03/README.md has their register / scratch / LDS-instruction counts and the A/B):
-//   SF10: 16 lanes x 64 points, [4,4,4] X [4,4]            (4 windows per wavefront)
-//   SF11: 32 lanes x 64 points, [R2,4,4] X [4,4,4]         (2 windows per wavefront)
-//   SF12: 64 lanes x 64 points, [4,4,4] X [4,4,4]          (1 window per wavefront, no workgroup barrier)
-template <unsigned O>
-using Fast10b = FastCfg<10, 4, 1, 2, 6, 10, (O & W1) ? 1 : (O & W2) ? 2 : 3, 0, 1, 0, 0, !(O & CH_REG), !(O & TW_REG), (O & PF_NONE) ? 0 : (O & PF_EARLY) ? 2 : 1,
-                        (O & NT) != 0, (O & NB_SEL) != 0, false, false, false>;
-template <unsigned O>
-using Fast11b = FastCfg<11, 5, 2, 2, 5, 11, (O & W1) ? 1 : (O & W2) ? 2 : 3, 0, 1, 0, 0, !(O & CH_REG), !(O & TW_REG), (O & PF_NONE) ? 0 : (O & PF_EARLY) ? 2 : 1,
-                        (O & NT) != 0, (O & NB_SEL) != 0, false, false, false>;
-template <unsigned O>
-using Fast12b = FastCfg<12, 6, 1, 2, 6, 12, (O & W1) ? 1 : (O & W2) ? 2 : 3, 0, 1, 0, 0, !(O & CH_REG), !(O & TW_REG), (O & PF_NONE) ? 0 : (O & PF_EARLY) ? 2 : 1,
-                        (O & NT) != 0, (O & NB_SEL) != 0, false, false, false>;
+// Retired geometries (the parent of the commit that removed them has the code): SF11 inside one wavefront, 64 lanes x 32 points
+// (profiles/r01/s8_variants.txt, its last table), and the two-phase geometries of 64 points per lane for SF10 / SF11 / SF12
+// (profiles/r03/README.md: registers, scratch, LDS instructions and the A/B). None beat the kernels that ship.
 
 bool fastAvailable(const int sf) { return sf >= 6 && sf <= 10; }
 
@@ -426,11 +389,7 @@ static bool layoutOk()
 
 bool fastLayoutsOk()
 {
-    bool ok = layoutOk<Fast<6, 0>>() && layoutOk<Fast<7, 0>>() && layoutOk<Fast<8, 0>>() && layoutOk<Fast<9, 0>>() && layoutOk<Fast9b<0>>() && layoutOk<Fast<10, 0>>();
-#ifdef LORAHIP_ALL_VARIANTS
-    ok = ok && layoutOk<Fast11q<0>>() && layoutOk<Fast10b<0>>() && layoutOk<Fast11b<0>>() && layoutOk<Fast12b<0>>();
-#endif
-    return ok;
+    return layoutOk<Fast<6, 0>>() && layoutOk<Fast<7, 0>>() && layoutOk<Fast<8, 0>>() && layoutOk<Fast<9, 0>>() && layoutOk<Fast9b<0>>() && layoutOk<Fast<10, 0>>();
 }
 
 /***********************************************************************
@@ -454,19 +413,15 @@ static hipError_t launchByShape(const DetectArgs &a, const FastTables &ft, hipSt
     return uni ? launchOne<UNI_CFG, false, true>(a, ft, stream) : launchOne<MOVING_CFG, false, false>(a, ft, stream);
 }
 
-// (the option sets of the per-window-settings instances of SF7 / SF10 as macros: A/B builds, tools/build_variant.py -DLORAHIP_SF10_MOVING=...)
-#ifndef LORAHIP_SF7_MOVING
-#define LORAHIP_SF7_MOVING (CH_REG | NT)
-#endif
-#ifndef LORAHIP_SF10_MOVING
-#define LORAHIP_SF10_MOVING (W2 | CH_REG | TW_REG | NT | X1_SWAP | TWM_REG)
-#endif
 struct FastVariant { int sf, variant; FastLaunch launch; };
-#define V(SF, N, OPTS) { SF, N, &launchCfg<Fast<SF, (OPTS)>> }
 // What ships: per SF the default (0) and ONE alternative -- variant 10, every table (chirp, twiddles) read from LDS, the option
-// set the streaming demodulator's kernels run with -- beside the generic kernel (1, lorahip_kernels.hip). The losers of the
-// round-1 tuning (profiles/r01/s8_variants.txt keeps every A/B pair) are compiled only with -DLORAHIP_ALL_VARIANTS
-// (python -m lora_sdr_amd.build --all-variants), under their old numbers.
+// set the streaming demodulator's kernels run with -- beside the generic kernel (1, lorahip_kernels.hip). Every other number
+// runs the default (launchFast below).
+// Retired option sets (the parent of the commit that removed them has the code and their old numbers): the round-1 tuning,
+// with four waves per SIMD, the early prefetch, register-select neighbours and the XCD-contiguous walk among its losers
+// (profiles/r01/s8_variants.txt keeps every A/B pair); the round-2 sets for batches with per-window settings
+// (profiles/r02/s3_explore_moving_variants.txt); the round-4 retune under rotating priorities (profiles/r04); and the other
+// option sets tried for the per-window-settings instances of SF7 and SF10 (profiles/r06/s32_*: both lost).
 static const FastVariant kFastVariants[] = {
     // The debug-port instances (dec / fft outputs, 3x the traffic: not occupancy-bound) and, from SF8 up, the per-window-settings
     // instances run at the 256-register budget of two waves per SIMD: at three (168 registers) they spilled up to 296 B (SF9 / SF10
@@ -475,7 +430,7 @@ static const FastVariant kFastVariants[] = {
 #ifndef LORAHIP_FMA      // (the contracted build carries the defaults only)
     { 6, 10, &launchByShape<Fast<6, CH_REG | NT>, Fast<6, CH_REG | NT>, Fast<6, W2 | CH_REG | NT>> },
 #endif
-    { 7, 0, &launchByShape<Fast<7, CH_REG | NT>, Fast<7, LORAHIP_SF7_MOVING>, Fast<7, W2 | CH_REG | NT>> },   // default
+    { 7, 0, &launchByShape<Fast<7, CH_REG | NT>, Fast<7, CH_REG | NT>, Fast<7, W2 | CH_REG | NT>> },   // default
 #ifndef LORAHIP_FMA
     { 7, 10, &launchByShape<Fast<7, 0>, Fast<7, 0>, Fast<7, W2>> },
 #endif
@@ -492,40 +447,11 @@ static const FastVariant kFastVariants[] = {
     { 9, 10, &launchByShape<Fast<9, 0>, Fast<9, W2>, Fast<9, W2>> },
 #endif
     // default SF10: per-window settings at two waves per SIMD with the middle-phase twiddles in registers too
-    { 10, 0, &launchByShape<Fast<10, CH_REG | TW_REG | NT | X1_SWAP>, Fast<10, LORAHIP_SF10_MOVING>, Fast<10, W2>> },   // (debug ports: every table from LDS, no scratch)
+    { 10, 0, &launchByShape<Fast<10, CH_REG | TW_REG | NT | X1_SWAP>, Fast<10, W2 | CH_REG | TW_REG | NT | X1_SWAP | TWM_REG>, Fast<10, W2>> },   // (debug ports: every table from LDS, no scratch)
 #ifndef LORAHIP_FMA
     { 10, 10, &launchByShape<Fast<10, 0>, Fast<10, W2>, Fast<10, W2>> },
 #endif
-#ifdef LORAHIP_ALL_VARIANTS
-    V(6, 7, TW_REG), V(6, 8, NT), V(6, 11, CH_REG | NT), V(6, 12, CH_REG | TW_REG | NT), V(6, 15, CH_REG | TW_REG | NT | PF_NONE),
-    V(7, 2, PF_NONE), V(7, 3, W2), V(7, 4, W4 | PF_NONE), V(7, 5, W2 | CH_REG | TW_REG), V(7, 6, PF_EARLY), V(7, 7, TW_REG),
-    V(7, 8, NT), V(7, 9, TW_REG | NT), V(7, 11, CH_REG | NT), V(7, 12, W2 | CH_REG | TW_REG | NT),
-    V(7, 13, CH_REG | NT | NB_SEL), V(7, 14, CH_REG | NT | XCD), V(7, 15, CH_REG | TW_REG | NT | PF_NONE), V(7, 16, CH_REG | TW_REG | NT | PF_NONE | NB_SEL),
-    V(7, 17, W4 | CH_REG | NT | PF_NONE),
-    V(8, 6, PF_EARLY), V(8, 7, TW_REG), V(8, 8, NT), V(8, 9, TW_REG | NT), V(8, 11, CH_REG | TW_REG | NT),
-    V(8, 13, CH_REG | TW_REG | NT | NB_SEL), V(8, 15, CH_REG | TW_REG | NT | PF_NONE), V(8, 17, W4 | CH_REG | NT | PF_NONE),
-    V(9, 6, PF_EARLY), V(9, 7, TW_REG), V(9, 8, NT), V(9, 9, TW_REG | NT), V(9, 11, CH_REG | TW_REG | NT),
-    V(9, 12, CH_REG | TW_REG | NT | X1_SWAP), V(9, 13, CH_REG | TW_REG | NT | NB_SEL), V(9, 15, CH_REG | TW_REG | NT | X1_SWAP | TWM_REG | PF_NONE),
-    V(9, 16, W2 | CH_REG | TW_REG | NT | X1_SWAP | TWM_REG),
-    { 9, 20, &launchCfg<Fast9b<W2 | CH_REG | TW_REG | NT>> }, { 9, 21, &launchCfg<Fast9b<W2 | NT>> }, { 9, 22, &launchCfg<Fast9b<W2 | TW_REG | NT>> },
-    { 9, 23, &launchCfg<Fast9b<W2 | CH_REG | NT>> }, { 9, 24, &launchCfg<Fast9b<W2 | CH_REG | TW_REG | NT | PF_NONE>> },
-    // SF11 per wavefront (the default SF11 kernel is lorahip_wide.hip's)
-    { 11, 20, &launchCfg<Fast11q<W2 | NT | PF_NONE>> }, { 11, 21, &launchCfg<Fast11q<W2 | TW_REG | NT | PF_NONE>> },
-    { 11, 22, &launchCfg<Fast11q<W2 | CH_REG | TW_REG | NT | PF_NONE>> }, { 11, 23, &launchCfg<Fast11q<W2 | NT>> },
-    { 11, 24, &launchCfg<Fast11q<W2 | TW_REG | TWM_REG | NT | PF_NONE>> },
-    // round 3: two-phase geometries of 64 points per lane (all tables from LDS: 64 points leave no registers for them)
-    { 10, 25, &launchCfg<Fast10b<W2 | NT | PF_NONE>> }, { 10, 26, &launchCfg<Fast10b<W1 | NT | PF_NONE>> },
-    { 11, 25, &launchCfg<Fast11b<W2 | NT | PF_NONE>> }, { 11, 26, &launchCfg<Fast11b<W1 | NT | PF_NONE>> },
-    { 12, 25, &launchCfg<Fast12b<W2 | NT | PF_NONE>> }, { 12, 26, &launchCfg<Fast12b<W1 | NT | PF_NONE>> },
-    V(10, 6, PF_EARLY), V(10, 7, TW_REG), V(10, 8, NT), V(10, 9, TW_REG | NT), V(10, 11, CH_REG | TW_REG | NT),
-    V(10, 12, CH_REG | TW_REG | NT | X1_SWAP), V(10, 13, CH_REG | TW_REG | NT | NB_SEL), V(10, 14, CH_REG | TW_REG | NT | NB_SEL | X1_SWAP),
-    V(10, 15, CH_REG | TW_REG | NT | X1_SWAP | TWM_REG | PF_NONE), V(10, 16, W2 | CH_REG | TW_REG | NT | X1_SWAP | TWM_REG),
-    // round 2: the defaults at the 256-register budget of two waves per SIMD (the per-window-settings kernels spill at three)
-    V(7, 30, W2 | CH_REG | NT), V(8, 30, W2 | CH_REG | TW_REG | NT), V(9, 30, W2 | CH_REG | TW_REG | NT | X1_SWAP), V(9, 31, CH_REG | TW_REG | NT | X1_SWAP),
-    V(10, 30, W2 | CH_REG | TW_REG | NT | X1_SWAP), V(10, 31, W2 | CH_REG | TW_REG | NT | X1_SWAP | PF_NONE), V(8, 31, W2 | CH_REG | TW_REG | NT | PF_NONE),
-#endif
 };
-#undef V
 
 hipError_t launchFast(const int sf, const int variant, const DetectArgs &a, const FastTables &ft, hipStream_t stream)
 {

@@ -12,17 +12,17 @@ namespace lorahip {
  *   index n_low = VEC*t+u at element offset rotr(n_low, X0ROT)*(WPW*R+X0PAD) + ((n_low>>X0S)&1)*X0D,
  *   the WPW windows of a wave side by side inside the row (stride R), so that the writers' ds_write_b64
  *   groups and the readers' ds_read_b64 groups each tile the LDS banks exactly once.
+ *   The geometry comes first (PB3_: 0 below four phases; X1PAD_: the row pad of exchange 1, unused with two phases), the
+ *   options after it; the last three are off in most instances and default to that.
  **********************************************************************/
-template <int LOG2N_, int LOG2T_, int VEC_, int NPH_, int PB1_, int PB2_, int WAVES_PER_SIMD_,
-          int X0ROT_, int X0PAD_, int X0S_, int X0D_, bool CH_LDS_, bool TW_ALL_LDS_, int PREFETCH_, bool NT_ = false, bool NB_SELECT_ = false, bool X1_SWAP_ = false, bool TW_MID_REG_ = false, bool XCD_CONTIG_ = false,
-          int PB3_ = 0, int X1PAD_ = 8>
+template <int LOG2N_, int LOG2T_, int VEC_, int NPH_, int PB1_, int PB2_, int PB3_, int WAVES_PER_SIMD_,
+          int X0ROT_, int X0PAD_, int X0S_, int X0D_, int X1PAD_, bool CH_LDS_, bool TW_ALL_LDS_, bool PREFETCH_,
+          bool X1_SWAP_ = false, bool NT_ = false, bool TW_MID_REG_ = false>
 struct FastCfg
 {
-    static constexpr int PREFETCH = PREFETCH_;        // next window set's loads: 0 none (loaded at the top), 1 issued after the dechirp of this set, 2 at the top of this set
-    static constexpr bool XCD_CONTIG = XCD_CONTIG_;   // workgroups of one XCD (blockIdx mod 8) walk one contiguous eighth of the batch (else: sets interleaved over all workgroups)
+    static constexpr bool PREFETCH = PREFETCH_;       // next window set's loads issued after the dechirp of this set (else: loaded at the top of their own set)
     static constexpr bool TW_MID_REG = TW_MID_REG_;   // middle-phase twiddles (they depend on the lane only) in registers instead of LDS reads per window
     static constexpr bool X1_SWAP = X1_SWAP_;         // exchange 1 as a 4x4 transpose between the wave's 16-lane rows and registers (v_permlane16/32_swap), no LDS
-    static constexpr bool NB_SELECT = NB_SELECT_;     // peak's neighbours by register select + lane shuffle instead of staging all bins in LDS
     static constexpr bool NT = NT_;                   // non-temporal hint on the IQ loads (read once, never reused)
     static constexpr bool CH_LDS = CH_LDS_;           // chirp table read from LDS per window (else loop-invariant registers)
     static constexpr bool TW_ALL_LDS = TW_ALL_LDS_;   // last-phase twiddles from the LDS table too (else registers)
@@ -60,7 +60,6 @@ struct FastCfg
     static constexpr int X1 = G1 * R + X1PAD_;                  // row pad of the position-indexed exchange (tools/lds_conflicts_lanes.py)
     static constexpr int X1ROWS = N / (G1 * R);                 // rows of 2^PB2 positions (+8 pad) per window
     static constexpr int X1ELEMS = NPH_ >= 3 ? WPW * X1ROWS * X1 : 0;   // per wave
-    static constexpr int XELEMS = (X0ELEMS > X1ELEMS ? X0ELEMS : X1ELEMS) + (N > X0ELEMS ? N - X0ELEMS : 0) / 2 * 0;
     //! twiddle entries staged in LDS: all stages below the last phase, or every stage
     static constexpr int TW_LDS = twStageOffset(LOG2N_, TW_ALL_LDS_ ? LOG2N_ : bound(NPH_ - 1));
     static constexpr int CH_ELEMS = CH_LDS_ ? N : 0;
@@ -360,7 +359,7 @@ struct FastCore
     static __device__ __forceinline__ void scan(const v2f (&vl)[NGL][GL], v2f *F, v2f *fftOut, const int t,
                                                 float &bestV, int &bestI, double &tot)
     {
-        if (!C::NB_SELECT && STORE_F)
+        if (STORE_F)
         {
 #pragma unroll
             for (int e = 0; e < GL; e++)
@@ -375,9 +374,8 @@ struct FastCore
                 for (int g = 0; g < NGL; g++) fftOut[(t + T * g) + (e << BL)] = vl[g][e];
         }
         // element j = e*NGL + g of the lane is bin (t + T g) + (e << BL): ascending in j
-        // (not the register-select neighbours, which keep the bins' registers alive across the scan, nor the 128-register budget of four
-        // wavefronts per SIMD -- profiling variants: they would spill)
-        if constexpr (CHAINS == 4 && ((LORAHIP_SCAN_KEYS >> LOG2N) & 1) != 0 && !C::NB_SELECT && C::WAVES_PER_SIMD <= 3)
+        // (CHAINS == 4 is what the batch kernel's launch-uniform instances ask for; every other caller takes the compare-and-select scan below)
+        if constexpr (CHAINS == 4 && ((LORAHIP_SCAN_KEYS >> LOG2N) & 1) != 0)
         {
             // the launch-uniform instances: arg-max through max keys (lorahip_device.h). A bin's low key word is (N - 1) - bin =
             // a compile-time constant per register minus the lane's t. INV: sixteen loop-invariant registers (the compiler hoists
@@ -421,7 +419,7 @@ struct FastCore
     template <bool STORE_F>
     static __device__ __forceinline__ void scanQuick(const v2f (&vl)[NGL][GL], v2f *F, const int t, float &bestV, int &bestI, float &totF)
     {
-        if (!C::NB_SELECT && STORE_F)
+        if (STORE_F)
         {
 #pragma unroll
             for (int e = 0; e < GL; e++)
@@ -435,8 +433,9 @@ struct FastCore
         totF = groupSumF32<T>(totF);
     }
 
-    //! bins k-1 and k+1 of the window's peak k (LoRaDetector.hpp:56-57), valid in every lane of the window
-    template <bool FROM_REGS = C::NB_SELECT>
+    //! bins k-1 and k+1 of the window's peak k (LoRaDetector.hpp:56-57), valid in every lane of the window: read back from F where
+    //! scan() staged the bins, or (FROM_REGS, the streaming kernels' untraced path) by register select and lane shuffle
+    template <bool FROM_REGS = false>
     static __device__ __forceinline__ void neighbours(const v2f (&vl)[NGL][GL], const v2f *F, const int bestI, const int lane, const int t,
                                                       v2f &leftBin, v2f &rightBin)
     {

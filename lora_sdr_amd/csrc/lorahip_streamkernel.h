@@ -26,7 +26,7 @@ template <class C, bool RES = false, bool AHEAD = false>
 __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD)
 demodStream(const StreamArgs s)
 {
-    static_assert(C::PREFETCH == 0, "the window prefetch is not in this kernel (slower: profiles/r05/s6_lanes_prefetch_negative.txt)");
+    static_assert(!C::PREFETCH, "the window prefetch is not in this kernel (slower: profiles/r05/s6_lanes_prefetch_negative.txt)");
     static_assert(!AHEAD || (!RES && C::WPW >= 2), "the look-ahead instances: one-launch grids, two lane groups per channel");
     typedef FastCore<C> K;
     constexpr int N = C::N, T = C::T, VEC = C::VEC, R = C::R, WPW = C::WPW;

@@ -18,15 +18,12 @@
 #include "lorahip_framemachine.h"
 #include "lorahip_residentproto.h"
 
-#ifndef SCAN_CHAINS_WIDE
-#define SCAN_CHAINS_WIDE 1
-#endif
-#ifndef STREAM_WIDE_PREFETCH
-#define STREAM_WIDE_PREFETCH 0  // 1: demodStreamWide requests the window at off + N while this one is transformed. Measured 2-3 % SLOWER (profiles/r04/s10_*): kept as the A/B
-#endif
 namespace lorahip {
 
-template <int LOG2N_, int VEC_, int MINW_, int X0ROT_, int X0PAD_, int X0S_, int X0D_, bool CH_LDS_, bool TW_ALL_LDS_, bool PREFETCH_ = true, bool NT_ = false, int WPB_ = 0,
+constexpr int SCAN_CHAINS_WIDE = 1;     // independent compare-and-select chains of a lane's 16-bin scan (laneScan)
+
+// The chirp values of a lane's sample positions and the last-phase twiddles live in registers; the twiddles of the first two phases in LDS.
+template <int LOG2N_, int VEC_, int MINW_, int X0ROT_, int X0PAD_, int X0S_, int X0D_, bool PREFETCH_ = true, bool NT_ = false, int WPB_ = 0,
           bool INPLACE_ = false, int X0S2_ = 0, int X0D2_ = 0>
 struct WideCfg
 {
@@ -40,7 +37,6 @@ struct WideCfg
     static constexpr int BPC = MINW_ * 256 / BLOCK;             // workgroups per CU at MINW waves per SIMD
     static constexpr int WPWIN = T / 64;                        // wavefronts per window
     static constexpr int MINW = MINW_;
-    static constexpr bool CH_LDS = CH_LDS_, TW_ALL_LDS = TW_ALL_LDS_;
     static constexpr bool NT = NT_;                             // non-temporal hint on the IQ loads
     static constexpr bool INPLACE = INPLACE_;                   // the middle phase writes its results back where it read its inputs:
                                                                 // no barrier between the two, the last phase reads the exchange-0 layout
@@ -60,9 +56,8 @@ struct WideCfg
     static constexpr int X1ELEMS = INPLACE_ ? 0 : 16 * X1;
     static constexpr int XE = X0ELEMS > X1ELEMS ? X0ELEMS : X1ELEMS;
     static constexpr int XW = ((XE * 2 > N ? XE : (N + 1) / 2) + 1) & ~1;   // v2f per window; also holds N ints
-    static constexpr int TW_LDS = twStageOffset(LOG2N_, TW_ALL_LDS_ ? LOG2N_ : B2);
+    static constexpr int TW_LDS = twStageOffset(LOG2N_, B2);          // twiddle entries staged in LDS: the stages below the last phase
     static constexpr int TWN = (TW_LDS + 1) & ~1;
-    static constexpr int CH_ELEMS = CH_LDS_ ? N : 0;
 };
 
 struct RedRec { float v; int i; double tot; };
@@ -126,7 +121,7 @@ struct WideSmem
     //! everything but the split fine-tune tables (16-byte multiple: the tables follow)
     static constexpr size_t base()
     {
-        return (size_t(C::TWN + C::CH_ELEMS + C::WPB * C::XW) * sizeof(float2) + 4 * sizeof(RedRec) + size_t(C::WPB) * 2 * sizeof(float2) + sizeof(TailRec) + size_t(C::WPB) * 12 * sizeof(int) + 15) & ~size_t(15);
+        return (size_t(C::TWN + C::WPB * C::XW) * sizeof(float2) + 4 * sizeof(RedRec) + size_t(C::WPB) * 2 * sizeof(float2) + sizeof(TailRec) + size_t(C::WPB) * 12 * sizeof(int) + 15) & ~size_t(15);
     }
     static constexpr size_t bytes(const bool withFine) { return base() + (withFine ? FineDims<C::LOG2N>::BYTES : 0); }
 };
@@ -142,8 +137,7 @@ detectWide(const DetectArgs a, const FastTables ft, const unsigned nSets)
 
     extern __shared__ __attribute__((aligned(16))) char smemRaw[];
     v2f *sTw = reinterpret_cast<v2f *>(smemRaw);                         // [TWN]
-    v2f *sCh = sTw + C::TWN;                                             // [CH_ELEMS]
-    v2f *sX = sCh + C::CH_ELEMS;                                         // [WPB][XW]
+    v2f *sX = sTw + C::TWN;                                              // [WPB][XW]
     RedRec *sRed = reinterpret_cast<RedRec *>(sX + WPB * C::XW);         // [4]: one per wavefront
     v2f *sNb = reinterpret_cast<v2f *>(sRed + 4);                        // [WPB][2]: bins left/right of the peak
     TailRec &tr = *reinterpret_cast<TailRec *>(sNb + WPB * 2);
@@ -166,8 +160,7 @@ detectWide(const DetectArgs a, const FastTables ft, const unsigned nSets)
     for (int i = tid; i < C::TW_LDS; i += C::BLOCK) sTw[i] = reinterpret_cast<const v2f *>(ft.twStage)[i];
 
     // register twiddles of the last phase (klow = t there)
-    v2f twR[C::TW_ALL_LDS ? 1 : SLOTS];
-    if (!C::TW_ALL_LDS)
+    v2f twR[SLOTS];
     {
         int slot = 0;
 #pragma unroll
@@ -177,9 +170,9 @@ detectWide(const DetectArgs a, const FastTables ft, const unsigned nSets)
             {
                 const int k = t + (kl << B2);
                 const int base = twStageOffset(LOG2N, b) + k;
-                twR[C::TW_ALL_LDS ? 0 : slot] = reinterpret_cast<const v2f *>(ft.twStage)[base];
-                twR[C::TW_ALL_LDS ? 0 : slot + 1] = reinterpret_cast<const v2f *>(ft.twStage)[base + (1 << b)];
-                twR[C::TW_ALL_LDS ? 0 : slot + 2] = reinterpret_cast<const v2f *>(ft.twStage)[base + (2 << b)];
+                twR[slot] = reinterpret_cast<const v2f *>(ft.twStage)[base];
+                twR[slot + 1] = reinterpret_cast<const v2f *>(ft.twStage)[base + (1 << b)];
+                twR[slot + 2] = reinterpret_cast<const v2f *>(ft.twStage)[base + (2 << b)];
                 slot += 3;
             }
     }
@@ -191,26 +184,15 @@ detectWide(const DetectArgs a, const FastTables ft, const unsigned nSets)
     // chirp table values of this lane's sample positions: _upChirpTable = conj(_downChirpTable) (LoRaDemod.cpp:103-104)
     const bool perWindowSel = !UNI && a.chirpSel != nullptr;
     const float s0 = (!perWindowSel && a.chirpSelAll == LORAHIP_CHIRP_UP) ? -1.0f : 1.0f;
-    v2f ch[C::CH_LDS ? 1 : R][C::CH_LDS ? 1 : VEC];
-    if (C::CH_LDS)
-    {
-        for (int i = tid; i < N; i += C::BLOCK)
+    v2f ch[R][VEC];
+#pragma unroll
+    for (int r = 0; r < R; r++)
+#pragma unroll
+        for (int u = 0; u < VEC; u++)
         {
-            const v2f c = gDown[i];
-            sCh[i] = MAKE2(c.x, s0 * c.y);
+            const v2f c = gDown[VEC * t + u + VEC * T * r];
+            ch[r][u] = MAKE2(c.x, s0 * c.y);
         }
-    }
-    else
-    {
-#pragma unroll
-        for (int r = 0; r < (C::CH_LDS ? 0 : R); r++)
-#pragma unroll
-            for (int u = 0; u < VEC; u++)
-            {
-                const v2f c = gDown[VEC * t + u + VEC * T * r];
-                ch[C::CH_LDS ? 0 : r][C::CH_LDS ? 0 : u] = MAKE2(c.x, s0 * c.y);
-            }
-    }
     __syncthreads();
 
     // coalesced window load: VEC*8 bytes per lane, a wavefront covers 512 or 1024 contiguous bytes, R rows
@@ -324,24 +306,8 @@ detectWide(const DetectArgs a, const FastTables ft, const unsigned nSets)
         v2f cw[R][VEC];
 #pragma unroll
         for (int r = 0; r < R; r++)
-        {
-            if (C::CH_LDS)
-            {
-                const v2f *p = sCh + VEC * t + VEC * T * r;
-                if (VEC == 2)
-                {
-                    const v4f q = *reinterpret_cast<const v4f *>(p);
-                    cw[r][0] = MAKE2(q.x, q.y);
-                    cw[r][VEC - 1] = MAKE2(q.z, q.w);
-                }
-                else cw[r][0] = *p;
-            }
-            else
-            {
 #pragma unroll
-                for (int u = 0; u < VEC; u++) cw[r][u] = ch[C::CH_LDS ? 0 : r][C::CH_LDS ? 0 : u];
-            }
-        }
+            for (int u = 0; u < VEC; u++) cw[r][u] = ch[r][u];
         if (UNI || (!perWindowSel && !anyMoving))
         {
             if (a.chirpSelAll != LORAHIP_CHIRP_NONE)
@@ -444,8 +410,7 @@ detectWide(const DetectArgs a, const FastTables ft, const unsigned nSets)
 #pragma unroll
             for (int e = 0; e < 16; e++) vl[e] = X[e * C::X1 + t];
         }
-        if (C::TW_ALL_LDS) runPhase<LOG2N, B2, LOG2N, false>(vl, t, sTw, nullptr);
-        else runPhase<LOG2N, B2, LOG2N, true>(vl, 0, nullptr, twR);
+        runPhase<LOG2N, B2, LOG2N, true>(vl, 0, nullptr, twR);
 
         // ---- scan (LoRaDetector.hpp:36-48): bin = t + T*e, ascending in e ----------------------
         if (DBG && a.fftOut && active)
@@ -527,14 +492,6 @@ static hipError_t launchOneWide(const DetectArgs &a, const FastTables &ft, hipSt
     return hipGetLastError();
 }
 
-template <class C>
-static hipError_t launchCfgWide(const DetectArgs &a, const FastTables &ft, hipStream_t stream)
-{
-    const bool uni = a.chirpSel == nullptr && a.fineErr == nullptr;
-    if (a.decOut || a.fftOut) return launchOneWide<C, true, false>(a, ft, stream);
-    return uni ? launchOneWide<C, false, true>(a, ft, stream) : launchOneWide<C, false, false>(a, ft, stream);
-}
-
 /***********************************************************************
  * configurations: geometry per SF x layout (the plain padded exchange-0 layout, or the swizzled one the in-place middle
  * phase needs -- both found with tools/lds_conflicts.py), plus an option mask.
@@ -548,18 +505,16 @@ template <> struct WGeo<12, true>  { enum { VEC = 1, ROT = 0, PAD = 1, S = 6, D 
 
 enum : unsigned
 {
-    WW2 = 1u << 0, WW4 = 1u << 1,       // waves per SIMD the register budget is set for (default 3)
-    WCH_LDS = 1u << 2,                   // chirp values from an LDS copy of the table (default: registers)
-    WTW_LDS = 1u << 3,                   // last-phase twiddles from the LDS table (default: registers)
-    WPF_NONE = 1u << 4,                  // no register prefetch of the next window
-    WNT = 1u << 5,                       // non-temporal IQ loads
-    WONE = 1u << 6,                      // one window per workgroup (SF11: 128 threads)
-    WINPLACE = 1u << 7                   // in-place middle phase (3 barriers per window instead of 4)
+    WW2 = 1u << 0,                       // register budget set for two waves per SIMD (default: three)
+    WPF_NONE = 1u << 1,                  // no register prefetch of the next window
+    WNT = 1u << 2,                       // non-temporal IQ loads
+    WONE = 1u << 3,                      // one window per workgroup (SF11: 128 threads)
+    WINPLACE = 1u << 4                   // in-place middle phase (3 barriers per window instead of 4)
 };
 template <int SF, unsigned O>
-using Wide = WideCfg<SF, WGeo<SF, (O & WINPLACE) != 0>::VEC, (O & WW2) ? 2 : (O & WW4) ? 4 : 3,
+using Wide = WideCfg<SF, WGeo<SF, (O & WINPLACE) != 0>::VEC, (O & WW2) ? 2 : 3,
                      WGeo<SF, (O & WINPLACE) != 0>::ROT, WGeo<SF, (O & WINPLACE) != 0>::PAD, WGeo<SF, (O & WINPLACE) != 0>::S,
-                     WGeo<SF, (O & WINPLACE) != 0>::D, (O & WCH_LDS) != 0, (O & WTW_LDS) != 0, !(O & WPF_NONE), (O & WNT) != 0,
+                     WGeo<SF, (O & WINPLACE) != 0>::D, !(O & WPF_NONE), (O & WNT) != 0,
                      (O & WONE) ? 1 : 0, (O & WINPLACE) != 0, WGeo<SF, (O & WINPLACE) != 0>::S2, WGeo<SF, (O & WINPLACE) != 0>::D2>;
 
 // streaming demodulator configurations (demodStreamWide below): one channel per workgroup, in-place middle phase
@@ -593,9 +548,13 @@ bool wideLayoutsOk();
  **********************************************************************/
 typedef hipError_t (*WideLaunch)(const DetectArgs &, const FastTables &, hipStream_t);
 struct WideVariant { int sf, variant; WideLaunch launch; bool (*layoutOk)(); };
-#define V(SF, N, OPTS) { SF, N, &launchCfgWide<Wide<SF, (OPTS)>>, &layoutOk<Wide<SF, (OPTS)>> }
 // ships: the default (0) and one alternative per SF (10: the plain exchange-0 layout, four barriers per window, register
-// prefetch); the rest of the round-1 A/B set only with -DLORAHIP_ALL_VARIANTS (profiles/r01/s8_variants.txt)
+// prefetch); every other number runs the default (launchWide below).
+// Retired option sets (the parent of the commit that removed them has the code and their old numbers): the rest of the round-1 A/B
+// set, with four waves per SIMD and the chirp values / last-phase twiddles read from LDS among its losers
+// (profiles/r01/s8_variants.txt); the round-2 sets at two waves per SIMD (profiles/r02/s3_explore_moving_variants.txt); and round 4's
+// two-waves-per-SIMD kernels with the chirp values from an LDS copy (profiles/r04).
+
 //! defaults by call shape, like lorahip_fast.hip's: per-window settings (moving fine-tune index) at two waves per SIMD
 template <class UNI_CFG, class MOVING_CFG>
 static hipError_t launchWideByShape(const DetectArgs &a, const FastTables &ft, hipStream_t stream)
@@ -620,20 +579,7 @@ static const WideVariant kWideVariants[] = {
 #ifndef LORAHIP_FMA
     { 12, 10, &launchWideByShape<Wide<12, 0>, Wide<12, WW2>>, &layoutOk<Wide<12, 0>> },
 #endif
-#ifdef LORAHIP_ALL_VARIANTS
-    V(11, 2, WW2), V(11, 3, WW2 | WCH_LDS), V(11, 4, WW2 | WTW_LDS), V(11, 5, WW2 | WCH_LDS | WTW_LDS), V(11, 6, WW4 | WPF_NONE),
-    V(11, 7, WPF_NONE), V(11, 8, WNT), V(11, 9, WPF_NONE | WNT), V(11, 11, WPF_NONE | WNT | WONE), V(11, 12, WNT | WONE),
-    V(11, 13, WPF_NONE | WNT | WONE | WINPLACE), V(11, 14, WPF_NONE | WNT | WINPLACE),
-    V(12, 2, WW2), V(12, 3, WW2 | WCH_LDS), V(12, 4, WW2 | WTW_LDS), V(12, 5, WW2 | WCH_LDS | WTW_LDS), V(12, 6, WW4 | WPF_NONE),
-    V(12, 7, WPF_NONE), V(12, 8, WNT), V(12, 9, WPF_NONE | WNT), V(12, 13, WPF_NONE | WNT | WINPLACE), V(12, 14, WNT | WINPLACE),
-    // round 2: the defaults at the 256-register budget of two waves per SIMD
-    V(11, 30, WW2 | WPF_NONE | WNT | WONE | WINPLACE), V(11, 31, WW2 | WNT | WINPLACE), V(11, 29, WW2 | WNT | WONE | WINPLACE),
-    V(12, 30, WW2 | WNT | WINPLACE), V(12, 31, WW2 | WPF_NONE | WNT | WINPLACE),
-    // round 4: the two-waves-per-SIMD kernels with the chirp values from an LDS copy (32 registers back: no scratch)
-    V(11, 32, WW2 | WNT | WONE | WINPLACE | WCH_LDS), V(12, 32, WW2 | WNT | WINPLACE | WCH_LDS), V(12, 33, WW2 | WPF_NONE | WNT | WINPLACE | WCH_LDS),
-#endif
 };
-#undef V
 
 bool wideLayoutsOk()
 {
@@ -686,7 +632,7 @@ demodStreamWide(const StreamArgs s)
 #ifdef LORAHIP_WG_TIMELINE
     const unsigned long long tl0 = wall_clock64();
 #endif
-    static_assert(C::INPLACE && C::WPB == 1 && !C::CH_LDS && !C::TW_ALL_LDS, "stream configs: one channel per workgroup, in-place middle phase");
+    static_assert(C::INPLACE && C::WPB == 1, "stream configs: one channel per workgroup, in-place middle phase");
     constexpr int N = C::N, T = C::T, VEC = C::VEC, R = C::R, WPWIN = C::WPWIN;
     constexpr int LOG2N = C::LOG2N, LOG2T = C::LOG2T, B1 = C::B1, B2 = C::B2, HB = C::HB;
     constexpr int SLOTS = lastPhaseSlots<LOG2N, B2, LOG2N>();
@@ -808,14 +754,8 @@ demodStreamWide(const StreamArgs s)
     // Signals without a trace (lorahip_demod_set_signals): the DOWNCHIRP1 call of a packet takes the traced path (`full`), see demodStream
     const bool traced = s.calls != nullptr;
     const bool sig = s.sigOut != nullptr;
-    // The window's samples are PREFETCHED: most calls consume N samples (both down-chirp states, every data symbol, a squelched
-    // FRAMESYNC window; the second sync window sits at pos + N too), so the window at off + N is requested as soon as this one's
-    // samples have left their registers for phase 0 -- the loads stay in flight across the window's barriers (which wait for LDS
-    // only) and hide the HBM latency the frame machine otherwise exposes once per call. A call that consumed something else
-    // (N - value while acquiring, the quarter chirp) finds another offset than the prefetched one and loads its own window.
+    // (Requesting the window at off + N while this one is transformed measured 2-3 % slower, profiles/r04/s10_*: every call loads its own.)
     v2f x[R][VEC];
-    long long preOff = -1;                                   // workgroup-uniform: which window x holds (or is about to hold)
-    const long long endOff = base + len;
     auto loadWindow = [&](const long long off)
     {
         const v2f *win = gIq + off;                          // scalar base, per-lane offsets
@@ -835,7 +775,7 @@ demodStreamWide(const StreamArgs s)
     auto detect = [&](const bool all, const bool wantSq, const int wantFi, const long long off, const bool downTable, const int idx0, const float err,
                       int &value, float &power, float &powerAvg, float &fIndex, int &idxEnd, bool &squelched)
     {
-        if (!STREAM_WIDE_PREFETCH || off != preOff) loadWindow(off);
+        loadWindow(off);
         const float d = err * (float)LORAHIP_FINE_STEPS;
         const bool moving = d != 0.0f;                       // workgroup-uniform
         int *sIdx = reinterpret_cast<int *>(X);
@@ -887,12 +827,6 @@ demodStreamWide(const StreamArgs s)
         for (int r = 0; r < R; r++)
 #pragma unroll
             for (int u = 0; u < VEC; u++) v0[u][Plan<LOG2N>::pos(VEC * T * r) & (R - 1)] = x[r][u];
-        if (STREAM_WIDE_PREFETCH)
-        {
-            // x is free: the next window, speculatively (it must lie inside the stream: the call's own 2N are checked, the third N is not)
-            if (off + 2 * N <= endOff) { preOff = off + N; loadWindow(preOff); }
-            else preOff = -1;
-        }
 #pragma unroll
         for (int u = 0; u < VEC; u++) runPhase<LOG2N, 0, B1, false>(v0[u], 0, sTw, nullptr);
 #pragma unroll

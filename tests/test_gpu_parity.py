@@ -309,7 +309,8 @@ def test_golden_detector_kat(gpu, golden, sf):
 
 
 # the kernel variants the library ships (lorahip_set_variant): 0 = tuned default, 1 = generic kernel, 10 = the one alternative per
-# SF; the round-1 A/B zoo is compiled only with -DLORAHIP_ALL_VARIANTS (profiles/r01/s8_variants.txt is its record)
+# SF. Every other number runs the SF's default: the A/B option sets of the tuning rounds are retired (DESIGN.md has the list and
+# where each measurement lives)
 VARIANTS = {sf: [0, 1, 10] for sf in range(6, 13)}
 
 
@@ -339,6 +340,31 @@ def test_steady_state_kernels_all_variants(gpu, oracle, sf):
     o2 = oracle.detect_batch(sf, iq[:1500], chirp_sel=1, want_fft=True, nthreads=8)
     g2 = ctx.detect_batch(d[:1500], chirp_sel_all=L.CHIRP_DOWN, want_fft=True)
     check(o2, g2, where="steady-dbg sf%d" % sf)
+
+
+@pytest.mark.parametrize("sf", [7, 9, 11])
+def test_retired_variant_numbers_run_the_default(gpu, sf):
+    """numbers that once selected A/B option sets (17, 26, 31) are accepted and compute exactly what variant 0 computes: at SF7
+    (the fast kernels), SF9 (two geometries behind one default) and SF11 (the wide kernels)"""
+    import lora_sdr_amd as L
+    rng = np.random.default_rng(400 + sf)
+    iq, _ = make_iq(rng, sf, 300, snr_db=-5.0 if sf >= 9 else 5.0)
+    d = gpu.from_numpy(iq).cuda()
+    ctx = L.Context(sf)
+
+    def run(v):
+        ctx.set_variant(v)
+        g = ctx.detect_batch(d, chirp_sel_all=L.CHIRP_UP)
+        gpu.cuda.synchronize()
+        return {k: to_np(g[k]).tobytes() for k in ("sym", "power", "powerAvg", "fIndex")}
+
+    ref = run(0)
+    assert len(ref["sym"]) == 300 * 2 and len(ref["power"]) == 300 * 4
+    for v in (17, 26, 31):
+        got = run(v)
+        for k in ref:
+            assert got[k] == ref[k], "%s of variant %d differs from variant 0 at sf%d" % (k, v, sf)
+    ctx.set_variant(0)
 
 
 @pytest.mark.parametrize("sf", [7, 8, 9, 10, 11, 12])

@@ -7,7 +7,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from lora_sdr_amd.build import FLAGS, SOURCES, CSRC, HERE, OBJDIR, build_lib
 name = sys.argv[1]
-extra = [a for a in sys.argv[2:] if a.startswith("-")]
+extra = [a for a in sys.argv[2:] if a.startswith("-") and a != "--only"]
 only = [a for a in sys.argv[2:] if not a.startswith("-")]
 build_lib()                                     # the shipped objects are current
 objdir = os.path.join(HERE, "build_" + name)
