@@ -233,7 +233,7 @@ int lorahip_detector_detect(lorahip_detector *det, size_t *index, float *power, 
                             float *f_index, float *fft_out);
 
 /* -------------------------------------------------------------------------------------
- * Level 3: B channels of the LoRaDemod block (declared here, see lorahip_demod.cpp).
+ * Level 3: B channels of the LoRaDemod block (declared here, see lorahip_demod.cpp and the lorahip_demod_*.cpp units beside it).
  *
  * What "identical to the reference block" means here: symbol values and FFT bins are bit-exact by construction; power, powerAvg and
  * fIndex equal the CPU build's to float rounding (<= 2e-5 dB / 2e-6 bins: the logarithms and the fp64 sum are evaluated in a

@@ -285,7 +285,7 @@ hipError_t launchStreamResident(int sf, const StreamArgs &s, hipStream_t stream,
 hipError_t launchStreamResidentWide(int sf, const StreamArgs &s, hipStream_t stream, unsigned *grid);    // SF11 / SF12 (lorahip_wide.hip)
 bool streamLanesAvailable(int sf, int log2Lanes);
 int streamLanesChosen(int sf, unsigned nChannels, int forced, unsigned otherWaves = 0);
-//! wavefronts the other parts of a mixed object put on this part's device at 16 points per lane (lorahip_rx.cpp -> lorahip_demod.cpp)
+//! wavefronts the other parts of a mixed object put on this part's device at 16 points per lane (lorahip_rx.cpp -> lorahip_demod.cpp; read by lorahip_demod_stream.cpp::lanesArg)
 void demodSetCoResidentWaves(lorahip_demod *dm, unsigned waves);
 hipError_t launchStreamLanes(int sf, int log2Lanes, const StreamArgs &s, hipStream_t stream);
 //! a lanes code with this bit: the AHEAD instance over windows of 2^(code & 15) lanes (lorahip_stream_pairs.hip) -- a channel takes two such
@@ -361,7 +361,7 @@ int hipFail(hipError_t e, const char *what);
 
 namespace lorahip {
 //! A level-3 object over several (device, SF) parts behind one lorahip_demod handle (lorahip_rx.cpp; lorahip_demod_create_mixed).
-//! The entry points of lorahip_demod.cpp hand over to it when the handle carries one; it speaks global channel numbers.
+//! The entry points of lorahip_demod.cpp and lorahip_demod_ports.cpp hand over to it when the handle carries one; it speaks global channel numbers.
 class Composite
 {
 public:

@@ -9,8 +9,8 @@
 // host until every channel has fewer than 2N samples left (or has filled its record buffer: the launch is
 // resumable from the saved per-channel state).
 //
-// Numerics are those of the batch kernels (same FastCore, same tables); the state machine is the one of
-// lorahip_demod.cpp's host path, which tests pin against the verbatim LoRaDemod.cpp.
+// Numerics are those of the batch kernels (same FastCore, same tables); the state machine is lorahip_framestep.h::frameStep, the
+// function the host path of lorahip_demod_rounds.cpp runs too, which tests pin against the verbatim LoRaDemod.cpp.
 #include "lorahip_streamkernel.h"
 #include "lorahip_streamcfg.h"
 #include <cstddef>
