@@ -104,7 +104,8 @@ __device__ __forceinline__ void bfly4(float2 &f0, float2 &f1, float2 &f2, float2
 }
 
 //! kf_bfly4 whose three twiddles are twiddle(0) = (1,0): x*(1,0) == x as a value for finite x
-//! (only the sign of a zero can differ, which never reaches a non-zero result or |.|^2)
+//! (only the sign of a zero can differ, which never reaches a non-zero result or |.|^2; the instances that show bins on a debug
+//! port multiply: runPhase's UNITMUL, lorahip_fft.h)
 __device__ __forceinline__ void bfly4unit(float2 &f0, float2 &f1, float2 &f2, float2 &f3)
 {
     bfly4core(f0, f1, f2, f3, f1, f2, f3);

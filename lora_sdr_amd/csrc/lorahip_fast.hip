@@ -252,7 +252,7 @@ detectFast(const DetectArgs a, const FastTables ft, const unsigned nSets)
         // ---- phases / exchanges; the next set's samples go in flight once phase 0's inputs are staged and land
         // while this set is transformed (past the end: re-read the last set, harmless and branch-free)
         v2f vl[NGL][GL];
-        K::fft(x, X, wsub, t, sTw, twR, vl, [&]() { if (C::PREFETCH) issueLoads(set + waveCount < nSets ? set + waveCount : nSets - 1); }, &twM);
+        K::template fft<DBG>(x, X, wsub, t, sTw, twR, vl, [&]() { if (C::PREFETCH) issueLoads(set + waveCount < nSets ? set + waveCount : nSets - 1); }, &twM);
 
         // ---- scan (LoRaDetector.hpp:36-48); final bins into the (now free) exchange region for the neighbour fetch
         v2f *F = X + wsub * FS;

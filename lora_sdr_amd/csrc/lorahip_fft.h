@@ -31,18 +31,27 @@ __host__ __device__ constexpr int rev4(int x, const int bits)
  *   TWL  : LDS stage-major table (stages below the last phase)
  *   twR  : register twiddles of the last phase (slot order = stage, kl, q)
  *   klow : position bits below LO of this group (0 in phase 0)
+ *   UNITMUL : phase 0 (never the LAST one) multiplies by twiddle(0) = (1, 0) as kissfft does instead of skipping it (the
+ *          debug-port instances: the product differs from its operand in the sign of a zero and, for an infinite operand, by
+ *          Inf * 0 = NaN)
  **********************************************************************/
-template <int LOG2N, int LO, int HI, bool LAST>
+template <int LOG2N, int LO, int HI, bool LAST, bool UNITMUL = false>
 __device__ __forceinline__ void runPhase(v2f (&v)[1 << (HI - LO)], const int klow,
                                          const v2f *__restrict__ TWL, const v2f *twR)
 {
     constexpr int G = 1 << (HI - LO);
     constexpr bool R2 = (LO == 0) && (LOG2N & 1);
+    static_assert(!UNITMUL || !LAST, "twiddle(0) comes from the LDS table");
     if (R2)
     {
         // innermost radix-2 stage, m = 1: twiddle(0) = (1,0)
 #pragma unroll
-        for (int i = 0; i < G / 2; i++) bfly2unitv(v[2 * i], v[2 * i + 1]);
+        for (int i = 0; i < G / 2; i++)
+        {
+            // the table's own twiddle(0): kissfft's is (1, -0) (the sine of -0), and the sign of that zero tells in the product
+            if (UNITMUL) v[2 * i + 1] = cmulv(v[2 * i + 1], TWL[twStageOffset(LOG2N, 1)]);
+            bfly2unitv(v[2 * i], v[2 * i + 1]);
+        }
     }
     int slot = 0;
 #pragma unroll
@@ -54,7 +63,7 @@ __device__ __forceinline__ void runPhase(v2f (&v)[1 << (HI - LO)], const int klo
         for (int kl = 0; kl < nkl; kl++)
         {
             v2f t1, t2, t3;
-            const bool unit = (LO == 0) && (kl == 0);
+            const bool unit = !UNITMUL && (LO == 0) && (kl == 0);
             if (!unit)
             {
                 if (LAST)

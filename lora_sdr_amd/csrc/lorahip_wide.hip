@@ -358,7 +358,7 @@ detectWide(const DetectArgs a, const FastTables ft, const unsigned nSets)
         // next set's samples go in flight now (past the end: re-read the last set, harmless and branch-free)
         if (C::PREFETCH) issueLoads(set + gridDim.x < nSets ? set + gridDim.x : nSets - 1);
 #pragma unroll
-        for (int u = 0; u < VEC; u++) runPhase<LOG2N, 0, B1, false>(v0[u], 0, sTw, nullptr);
+        for (int u = 0; u < VEC; u++) runPhase<LOG2N, 0, B1, false, DBG>(v0[u], 0, sTw, nullptr);
 
         // ---- exchange 0 ----------------------------------------------------------------------
 #pragma unroll

@@ -367,7 +367,7 @@ def test_retired_variant_numbers_run_the_default(gpu, sf):
     ctx.set_variant(0)
 
 
-@pytest.mark.parametrize("sf", [7, 8, 9, 10, 11, 12])
+@pytest.mark.parametrize("sf", [6, 7, 8, 9, 10, 11, 12])
 def test_per_window_settings_at_scale(gpu, oracle, sf):
     """per-window chirp selection, fine-tune start index and error on batches large enough that every persistent wave /
     workgroup runs many window sets (the index chain's LDS scratch aliases the exchange region of the previous set)"""
@@ -375,7 +375,7 @@ def test_per_window_settings_at_scale(gpu, oracle, sf):
     rng = np.random.default_rng(300 + sf)
     N = 1 << sf
     M = 128 * N
-    W = {7: 60013, 8: 30011, 9: 12007, 10: 6007, 11: 3001, 12: 1801}[sf]
+    W = {6: 60013, 7: 60013, 8: 30011, 9: 12007, 10: 6007, 11: 3001, 12: 1801}[sf]
     iq, _ = make_iq(rng, sf, W, snr_db=0.0 if sf >= 9 else 6.0)
     sel = rng.integers(0, 3, W).astype(np.int32)
     err = np.where(rng.random(W) < 0.5, 0.0, rng.uniform(-2.5, 2.5, W)).astype(np.float32)
@@ -484,7 +484,9 @@ def test_inputs_at_the_edges_of_fp32(gpu, oracle, sf):
     ONE deliberate difference, stated in DESIGN.md section 2: kissfft multiplies by the twiddle (1, 0) where the kernels skip the
     multiplication, and Inf * 0 = NaN -- in a window that holds an INFINITE sample some bin components are Inf here and NaN in
     the reference. Every bin of such a window is non-finite either way (a non-finite sample leaves the two dechirp
-    multiplications with a NaN component), so |X|^2 is NaN for every bin in both and everything detect() returns is the same."""
+    multiplications with a NaN component), so |X|^2 is NaN for every bin in both and everything detect() returns is the same.
+    (The debug-port instances, which this test runs, have since been made to multiply -- profiles/r13 -- and give the reference's
+    pattern there too; the allowance stays as stated, for the kernels that skip.)"""
     import lora_sdr_amd as L
     rng = np.random.default_rng(50 + sf)
     N, W = 1 << sf, 36
