@@ -308,7 +308,7 @@ StreamArgs makeStreamArgs(const lorahip_demod *dm, const float *iqDev, const Str
     // at every SF but 11: the dispatcher hands a free slot the next set. A PERSISTENT grid (the resident number of workgroups, each
     // looping over sets) lost there even with the alternating priority (profiles/r04/s22_*: SF7 32768 channels 0.34 against 0.44,
     // SF9 0.36 against 0.40; SF8 / 10 / 12 equal) -- the loop costs the wave-per-channel-set kernels registers -- and is the default
-    // only where one-by-one placement leaves slots unusable: SF11 (lorahip_wide.hip::launchStreamWideCfg).
+    // only where one-by-one placement leaves slots unusable: SF11 (lorahip_stream_wide.hip::launchStreamWideCfg).
     a.maxBlocks = dm->streamGrid; a.lanes = lanesArg(dm); a.lastRoundFrom = 0;
     return a;
 }

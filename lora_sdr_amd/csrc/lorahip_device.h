@@ -20,7 +20,7 @@ namespace lorahip {
 // in a tail where the late ones run alone, latency-bound, on half-empty SIMDs. rotatePriority(), once per work() call / window set,
 // hands the SIMD's priority round on a clock counter its wavefronts see alike (s_setprio): they advance at the same rate and
 // finish together. Measured (profiles/r04/s22_*, s23_*): level-3 kernels +3-9 % at SF7-10, +6 % at SF12, +27 % at SF11 together
-// with the persistent grid (lorahip_wide.hip); the half period (2^16 / 2^18 clocks: 27 / 110 us) does not matter within the
+// with the persistent grid (lorahip_stream_wide.hip); the half period (2^16 / 2^18 clocks: 27 / 110 us) does not matter within the
 // noise, 2^14 is too short.
 // Only wavefronts that are NOT REPLACED when they finish take part (the last resident set of a grid, every wavefront of a persistent
 // one): earlier workgroups hold a priority above them, oldest first as the hardware has it -- one of two finishes early and its slot

@@ -1,5 +1,5 @@
 // FFT building blocks shared by the tuned kernels (lorahip_fast.hip: a window inside one wavefront;
-// lorahip_wide.hip: a window across the wavefronts of a workgroup). Numerics contract: lorahip_device.h.
+// lorahip_widecore.h: a window across the wavefronts of a workgroup). Numerics contract: lorahip_device.h.
 #pragma once
 #include "lorahip_device.h"
 #include "lorahip_fine.h"

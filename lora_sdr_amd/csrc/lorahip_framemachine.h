@@ -1,7 +1,7 @@
 // The LoRaDemod frame state machine (lorahip_framestep.h::frameStep) as the streaming kernels run it: per work() call, in the
 // registers of every lane that owns the channel (replicated, so no broadcast is needed); the writer lane appends the
 // symbol / packet / trace records -- into the arrays of StreamOut, below. Shared by lorahip_stream.hip (a channel per T <= 64
-// lanes) and lorahip_wide.hip (a channel per workgroup).
+// lanes) and lorahip_stream_wide.hip (a channel per workgroup).
 #pragma once
 #include "lorahip_device.h"
 #include "lorahip_framestep.h"

@@ -1,6 +1,6 @@
 // The LoRaDemod frame state machine (LoRaDemod.cpp:176-312): ONE work() call, written once. The streaming kernels run it in the
 // registers of every lane that owns the channel (lorahip_framemachine.h has their record arrays, lorahip_stream.hip and
-// lorahip_wide.hip the loops around it); the host-driven rounds run it between two batch launches
+// lorahip_stream_wide.hip the loops around it); the host-driven rounds run it between two batch launches
 // (lorahip_demod_rounds.cpp::runRounds). Nothing here is device-only: the .cpp units include it too. Tests pin it against the
 // verbatim LoRaDemod.cpp through both.
 #pragma once

@@ -1,6 +1,6 @@
 // The resident receiver's protocol on the device: the step messages (host ring -> relay wavefronts -> mirrors -> LDS), a wavefront's own
 // packets and signals into the step's rows, the end of a step and its report. Shared by the RES instances of demodStream
-// (lorahip_streamkernel.h: SF7-10) and of demodStreamWide (lorahip_wide.hip: SF11 / SF12). ResidentMsg / ResidentCtl / ResidentHost:
+// (lorahip_streamkernel.h: SF7-10) and of demodStreamWide (lorahip_stream_wide.hip: SF11 / SF12). ResidentMsg / ResidentCtl / ResidentHost:
 // lorahip_internal.h; the host side: lorahip_demod_resident.cpp::residentStep; the protocol in words: INTEGRATION.md section 4.
 #pragma once
 #include "lorahip_framemachine.h"

@@ -1,5 +1,5 @@
 """Readable register / scratch table of the kernels of a translation unit (after tools/kernel_resources.py left its .s in /tmp):
-    python tools/kernel_table.py lorahip_wide.hip [name substring]"""
+    python tools/kernel_table.py lorahip_wide.hip | lorahip_stream_wide.hip [name substring]"""
 import re, subprocess, sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 f = sys.argv[1]; key = sys.argv[2] if len(sys.argv) > 2 else ""

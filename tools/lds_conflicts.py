@@ -133,7 +133,7 @@ if __name__ == "__main__":
 
 
 def exch0_wide(LOG2N, VEC, off):
-    """wide kernels (lorahip_wide.hip): T = N/16 lanes per window (whole wavefronts), one X region per window.
+    """wide kernels (lorahip_widecore.h: detectWide in lorahip_wide.hip, demodStreamWide in lorahip_stream_wide.hip): T = N/16 lanes per window (whole wavefronts), one X region per window.
     off(n_low) -> element offset of the row start."""
     N = 1 << LOG2N
     T = N // 16

@@ -1,5 +1,5 @@
 """When and where the wavefronts of a batch launch (detectFast, SF6-10) ran: start, end of set-up, end, sets walked.
-Needs the profiling build:   python tools/build_variant.py tl -DLORAHIP_WG_TIMELINE lorahip_fast.hip lorahip_wide.hip
+Needs the profiling build:   python tools/build_variant.py tl -DLORAHIP_WG_TIMELINE lorahip_fast.hip lorahip_stream_wide.hip
     LORAHIP_LIB=lora_sdr_amd/liblorahip_tl.so python tools/wave_timeline.py <sf> [moving]"""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -24,7 +24,7 @@ for p in range(3):
     assert lib.lorahip_debug_wave_timeline(tl.ctypes.data, tl.nbytes) == 0
     tl = tl[tl[:, 1] != 0]
     if len(tl) == 0:
-        raise SystemExit("no records: the build lacks -DLORAHIP_WG_TIMELINE, or this SF runs lorahip_wide.hip's kernels (SF11 / SF12), which are not instrumented")
+        raise SystemExit("no records: the build lacks -DLORAHIP_WG_TIMELINE, or this SF runs lorahip_wide.hip's batch kernels (SF11 / SF12), which are not instrumented")
     t0, t1 = tl[:, 0].astype(np.float64) * 0.01, tl[:, 1].astype(np.float64) * 0.01
     setup = (tl[:, 3] >> np.uint64(32)).astype(np.float64) * 0.01
     sets = (tl[:, 3] & np.uint64(0xffffffff)).astype(np.int64)

@@ -1,5 +1,5 @@
 """When and where the workgroups of a streaming launch (demodStreamWide, SF11 / SF12: one channel per workgroup) ran.
-Needs the profiling build:   python tools/build_variant.py tl -DLORAHIP_WG_TIMELINE --only lorahip_wide.hip
+Needs the profiling build:   python tools/build_variant.py tl -DLORAHIP_WG_TIMELINE --only lorahip_stream_wide.hip
     LORAHIP_LIB=lora_sdr_amd/liblorahip_tl.so python tools/wg_timeline.py <sf> <channels> [passes]
 Per pass: the kernel's span, the spread of workgroup durations and start times, how many workgroups each compute unit ran, and the
 time the compute units spent with fewer workgroups than they can hold (the tail of a grid of few, long workgroups)."""
