@@ -177,10 +177,12 @@ struct FastCore
 
     //! dechirped samples x -> FFT bins vl (lane t holds bins (t + T*g) + 2^BL * e). X = the wave's exchange
     //! region. `mid` is called once phase 0's inputs are staged (the batch kernel issues its prefetch there).
-    //! UNITMUL: runPhase's (the bins are kissfft's bit for bit, signs of zeros and NaN patterns included)
+    //! UNITMUL: runPhase's (the bins are kissfft's bit for bit, signs of zeros and NaN patterns included); unitRt: the same chosen at
+    //! run time, wave-uniform (the streaming kernels' second pass over a window whose bins came out non-finite)
     template <bool UNITMUL = false, class MID>
     static __device__ __forceinline__ void fft(const v2f (&x)[R][VEC], v2f *X, const int wsub, const int t,
-                                               const v2f *sTw, const TwR &twR, v2f (&vl)[NGL][GL], MID mid, const TwM *twMp = nullptr)
+                                               const v2f *sTw, const TwR &twR, v2f (&vl)[NGL][GL], MID mid, const TwM *twMp = nullptr,
+                                               const bool unitRt = false)
     {
         // ---- phase 0: bits [0, B1) in registers, one group per u -----------------------------
         // register r holds sample index high part a = r; its work-array position low bits are rev(a)
@@ -191,7 +193,11 @@ struct FastCore
             for (int u = 0; u < VEC; u++) v0[u][Plan<LOG2N>::pos(VEC * T * r) & (R - 1)] = x[r][u];
         mid();
 #pragma unroll
-        for (int u = 0; u < VEC; u++) runPhase<LOG2N, 0, B1, false, UNITMUL>(v0[u], 0, sTw, nullptr);
+        for (int u = 0; u < VEC; u++)
+        {
+            if (!UNITMUL && unitRt) runPhase<LOG2N, 0, B1, false, true>(v0[u], 0, sTw, nullptr);
+            else runPhase<LOG2N, 0, B1, false, UNITMUL>(v0[u], 0, sTw, nullptr);
+        }
 
         // ---- exchange 0: one row per n_low = VEC*t+u, the wave's windows side by side ----------
         {

@@ -154,9 +154,11 @@ demodStreamWide(const StreamArgs s)
     const bool traced = s.calls != nullptr;
     const bool sig = s.sigOut != nullptr;
     // (Requesting the window at off + N while this one is transformed measured 2-3 % slower, profiles/r04/s10_*: every call loads its own.)
+    // unitTw: the pass repeats a window whose total came out non-finite, with phase 0's products by twiddle(0) carried out (see
+    // demodStream, lorahip_streamkernel.h). Returns whether the window has to be repeated so (workgroup-uniform; nothing is valid then).
     v2f x[R][VEC];
-    auto detect = [&](const bool all, const bool wantSq, const int wantFi, const long long off, const bool downTable, const int idx0, const float err,
-                      int &value, float &power, float &powerAvg, float &fIndex, int &idxEnd, bool &squelched)
+    auto detect = [&](const bool all, const bool wantSq, const int wantFi, const long long off, const bool downTable, const int idx0, const float err, const bool unitTw,
+                      int &value, float &power, float &powerAvg, float &fIndex, int &idxEnd, bool &squelched) -> bool
     {
         Core::load(x, gIq + off, t);                         // scalar base, per-lane offsets
         const float d = err * (float)LORAHIP_FINE_STEPS;
@@ -174,7 +176,7 @@ demodStreamWide(const StreamArgs s)
             idxEnd = uniI(fineEndIndex(idx0, pl, LOG2N, LOG2N + 7));
             // the closed form can only reach the value M under the modulus M + 1 (lorahip_fine.h): no vote, no barrier otherwise
             usedChain = !pl.regular || ((pl.mod != (unsigned)M && !pl.sat) && __syncthreads_or(ymax == (unsigned)M));
-            if (t == 0 && nearStep(d)) atomicAdd(s.near + 1, 1u);                    // counted, not changed (lorahip_internal.h)
+            if (!unitTw && t == 0 && nearStep(d)) atomicAdd(s.near + 1, 1u);         // counted (once), not changed (lorahip_internal.h)
             if (usedChain)
             {
                 idxEnd = uniI(fineChainBlock<T, M>(idx0, d, t, t >> 6, sIdx, sChain));
@@ -203,7 +205,7 @@ demodStreamWide(const StreamArgs s)
 
         // phase 0 -> exchange 0 -> phase 1 in place -> last phase: lane t holds bins t + T*e
         v2f vl[16];
-        Core::fft(x, X, t, sTw, twR, vl);
+        Core::fft(x, X, t, sTw, twR, vl, unitTw);
 
         // scan (LoRaDetector.hpp:36-48). Without a trace the total only feeds the quick squelch estimate: fp32 then (laneScanQuick,
         // squelchQuickF); the fp64 total is summed where the exact chain is evaluated (below)
@@ -215,6 +217,7 @@ demodStreamWide(const StreamArgs s)
         bestI = uniI(bestI);
         bestV = uniF(bestV);
         tot = __hiloint2double(uniI(__double2hiint(tot)), uniI(__double2loint(tot)));
+        if (!unitTw && (__double2hiint(tot) & 0x7ff00000) == 0x7ff00000) return true;      // Inf or NaN: some bin is
         value = bestI;
         bool needLogs = all, needFi = all;
         if (!all)
@@ -257,12 +260,14 @@ demodStreamWide(const StreamArgs s)
             }
             else fIndex = uniF(fIndexPaired(bestV, sNb[0], sNb[1], lane));
         }
+        return false;
     };
 
     // A FRAMESYNC call that is sync'd and matches the first sync word looks at a SECOND window (LoRaDemod.cpp:183-206): it is taken
     // in the next pass of the loop (`pend`), so that the kernel holds ONE instance of the window code, not two -- nothing is written
     // and nothing is consumed in between, and the limits checked for the first pass cover the whole call (same scheme as demodStream).
     bool pend = false;
+    bool unitTw = false;                                    // this pass repeats the last one's window (nothing was committed)
     int value0 = 0, fineIdxBefore0 = 0;
     float snr0 = 0.0f, fineErrBefore0 = 0.0f;
     const int slot = wavefrontSlot();
@@ -280,8 +285,9 @@ demodStreamWide(const StreamArgs s)
         bool squelched;
         // window 0 of a call (:157-172), or window 1 of a parked one (:189-206: `int ft = _fineTuneIndex` starts from the committed
         // index and is not committed itself)
-        detect(traced || (sig && !second && st.state == ST_DOWNCHIRP1), !second && (fs || st.state == ST_DATASYMBOLS), second ? 2 : (fs ? 1 : 0), base + st.pos + (second ? N : 0), st.downTable != 0,
-               st.fineTuneIndex, st.finefreqError, value, power, powerAvg, fIndex, idxEnd, squelched);
+        unitTw = detect(traced || (sig && !second && st.state == ST_DOWNCHIRP1), !second && (fs || st.state == ST_DATASYMBOLS), second ? 2 : (fs ? 1 : 0), base + st.pos + (second ? N : 0), st.downTable != 0,
+                        st.fineTuneIndex, st.finefreqError, unitTw, value, power, powerAvg, fIndex, idxEnd, squelched);
+        if (unitTw) continue;
         float snr = power - powerAvg;                                                   // :173 (squelched = snr < thresh, :174, comes from detect)
         if (!second) st.fineTuneIndex = idxEnd;                                         // :160-162
         bool syncd = !squelched && (st.prevValue + 4) / 8 == 0;                        // :183

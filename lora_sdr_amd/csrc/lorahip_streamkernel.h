@@ -179,13 +179,20 @@ demodStream(const StreamArgs s)
 #endif
     // the near-threshold counters (StreamArgs::near): a window evaluated ahead is counted when -- and only if -- its call is made
     int nearAhead = 0;
-    const auto noteNear = [&](const int which, const bool yes)
+    // (again: the pass repeats its windows, see unitTw below -- what the first time round counted at once is not counted twice)
+    const auto noteNear = [&](const int which, const bool yes, const bool again = false)
     {
         if (AHEAD && roleB) nearAhead |= yes ? 1 << which : 0;
-        else if (yes) atomicAdd(s.near + which, 1u);
+        else if (yes && !again) atomicAdd(s.near + which, 1u);
     };
+    // The FFT skips kissfft's multiplications by twiddle(0) = (1, -0) in phase 0: the identity on finite values, but Inf * 0 = NaN. A
+    // FINITE sample beyond 2.4e38 can leave the dechirp with an infinite component and no NaN; kissfft's leaf product makes that a NaN
+    // (every |X|^2 of the window NaN: index 0), the skipped one leaves bins of a clean Inf that win the arg-max (profiles/r15). So when
+    // the total of a window is not finite -- every bin an Inf or a NaN reaches tells there -- detect() returns true before anything
+    // is counted or consumed, and the wavefront repeats the pass (nothing was committed) with the products carried out (unitTw): the
+    // reference's bins, Inf / NaN pattern included, for the window that needs it and the same values for the others.
     auto detect = [&](const bool full, const bool on, const bool wantSq, const bool wantLogs, const int wantFi, const long long off, const bool downTable, const int idx0, const float err,
-                      int &value, float &power, float &powerAvg, float &fIndex, int &idxEnd, bool &squelched)
+                      const bool unitTw, int &value, float &power, float &powerAvg, float &fIndex, int &idxEnd, bool &squelched) -> bool
     {
         v2f x[R][VEC];
         TMARK(5);
@@ -216,7 +223,7 @@ demodStream(const StreamArgs s)
                 __builtin_amdgcn_wave_barrier();
             }
             if (moving) idxEnd = e;
-            noteNear(1, moving && t == 0 && nearStep(d));                            // counted, not changed (lorahip_internal.h)
+            noteNear(1, moving && t == 0 && nearStep(d), unitTw);                    // counted, not changed (lorahip_internal.h)
         }
         TMARK_NOWAIT(0);
         TMARK(1);
@@ -262,7 +269,7 @@ demodStream(const StreamArgs s)
 
         TMARK(2);
         v2f vl[NGL][GL];
-        K::fft(x, X, wsub, t, sTw, twR, vl, []() {}, &twM);
+        K::fft(x, X, wsub, t, sTw, twR, vl, []() {}, &twM, unitTw);
         TMARK(3);
         v2f *F = X + wsub * FS;
         float bestV;
@@ -273,6 +280,7 @@ demodStream(const StreamArgs s)
         if (full)
         {
             K::template scan<true, 1>(vl, F, nullptr, t, bestV, bestI, tot);
+            if (!unitTw && __any(on && (__double2hiint(tot) & 0x7ff00000) == 0x7ff00000)) return true;      // Inf or NaN: some bin is
             K::neighbours(vl, F, bestI, lane, t, l, r);
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -287,6 +295,7 @@ demodStream(const StreamArgs s)
             // neighbours come by register select (staging them in LDS was 1-1.7 % slower, profiles/r03)
             float totF;
             K::template scanQuick<false>(vl, F, t, bestV, bestI, totF);
+            if (!unitTw && __any(on && (__float_as_uint(totF) & 0x7f800000u) == 0x7f800000u)) return true;
             TMARK(6);
             bool sure;
             squelched = squelchQuickF(bestV, totF, s.thresh, K::QUICK_REL_ERR, sure);
@@ -319,6 +328,7 @@ demodStream(const StreamArgs s)
         fIndex = uniF(fIndex); power = uniF(power); powerAvg = uniF(powerAvg);
         idxEnd = uniI(idxEnd);
         TMARK(4);
+        return false;
     };
 
 #ifdef LORAHIP_STREAM_TIMING
@@ -332,6 +342,7 @@ demodStream(const StreamArgs s)
     // slot of the next pass -- while the other channels do their next calls -- and completes the frame machine step. Nothing is
     // written and nothing is consumed in between, and the limits checked for the first pass cover the whole call.
     bool pend = false;
+    bool unitTw = false;                                    // this pass repeats the last one's windows (nothing was committed)
     bool fsPlain = false;                                   // AHEAD: the channel's last FRAMESYNC call consumed N and left the fine-tune state alone
     float planErr = __uint_as_float(0x7fc00000u);           // AHEAD: the error planStepN / planMod were derived from (NaN: none yet)
     unsigned planStepN = 0u, planMod = 0u;                  //        N q mod M' and M' of lorahip_fine.h's closed form (planMod 0: the form does not apply)
@@ -396,9 +407,10 @@ demodStream(const StreamArgs s)
         // untraced path (the same operations on the same operands as the traced path's: the same bits) -- for the channels that are in
         // that call, not, as the traced path would, the fp64 scan and both logarithms for every channel of the wavefront whenever one
         // of them is there (SF7: 8 channels per wavefront, 0.378 -> of the roofline with signals kept against 0.442 without, round 5)
-        detect(all, onG, firstG && (stG == ST_FRAMESYNC || stG == ST_DATASYMBOLS), sig && onG && firstG && stG == ST_DOWNCHIRP1, firstG ? (stG == ST_FRAMESYNC ? 1 : 0) : 2,
-               roleB ? base + posAhead : here, st.downTable != 0, roleB ? idxAhead : st.fineTuneIndex,
-               st.finefreqError, value, power, powerAvg, fIndex, idxEnd, squelched);
+        unitTw = detect(all, onG, firstG && (stG == ST_FRAMESYNC || stG == ST_DATASYMBOLS), sig && onG && firstG && stG == ST_DOWNCHIRP1, firstG ? (stG == ST_FRAMESYNC ? 1 : 0) : 2,
+                        roleB ? base + posAhead : here, st.downTable != 0, roleB ? idxAhead : st.fineTuneIndex,
+                        st.finefreqError, unitTw, value, power, powerAvg, fIndex, idxEnd, squelched);
+        if (unitTw) continue;
         // AHEAD: the two groups of a channel tell each other what they found (the channel's state is replicated in both)
         int valueB = 0, idxEndB = 0;
         float powerB = 0.0f, powerAvgB = 0.0f, fIndexB = 0.0f;

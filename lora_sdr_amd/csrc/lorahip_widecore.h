@@ -238,7 +238,10 @@ struct WideCore
 
     //! dechirped samples x -> FFT bins vl (lane t holds bins t + T*e), in-place middle phase (C::INPLACE): three barriers' worth of
     //! detectWide's window body without its prefetch and deferred tail work
-    static __device__ __forceinline__ void fft(const v2f (&x)[R][VEC], v2f *X, const int t, const v2f *sTw, const TwR &twR, v2f (&vl)[16])
+    //! unit: phase 0 multiplies by twiddle(0) as kissfft does (runPhase's UNITMUL), workgroup-uniform: the streaming kernels' second pass
+    //! over a window whose bins came out non-finite
+    static __device__ __forceinline__ void fft(const v2f (&x)[R][VEC], v2f *X, const int t, const v2f *sTw, const TwR &twR, v2f (&vl)[16],
+                                               const bool unit = false)
     {
         static_assert(C::INPLACE, "the swizzled exchange-0 layout");
         // ---- phase 0: bits [0, B1) in registers, one group per u -----------------------------
@@ -248,7 +251,11 @@ struct WideCore
 #pragma unroll
             for (int u = 0; u < VEC; u++) v0[u][Plan<LOG2N>::pos(VEC * T * r) & (R - 1)] = x[r][u];
 #pragma unroll
-        for (int u = 0; u < VEC; u++) runPhase<LOG2N, 0, B1, false>(v0[u], 0, sTw, nullptr);
+        for (int u = 0; u < VEC; u++)
+        {
+            if (unit) runPhase<LOG2N, 0, B1, false, true>(v0[u], 0, sTw, nullptr);
+            else runPhase<LOG2N, 0, B1, false>(v0[u], 0, sTw, nullptr);
+        }
 
         // ---- exchange 0 ----------------------------------------------------------------------
 #pragma unroll

@@ -35,6 +35,19 @@ def compare_channel(tr, ref_calls):
             assert abs(a["power"] - b["power"]) <= TOL_DB
 
 
+def compare_channel_by_class(tr, ref_calls, where):
+    """compare_channel for streams with non-finite values in their calls: power and fIndex of the same class (NaN, +Inf, -Inf, finite),
+    the finite ones within compare_channel's bounds or two float ulps"""
+    assert len(tr) == len(ref_calls), where
+    for i, (a, b) in enumerate(zip(tr, ref_calls)):
+        assert (a["consumed"], a["state_before"], a["value"]) == (b["consumed"], b["state"], b["value"]), "%s call %d" % (where, i)
+        for ka, kb, tol in (("power", "power", TOL_DB), ("f_index", "fIndex", 2e-6)):
+            va, vb = float(a[ka]), float(b[kb])
+            assert (np.isnan(va), np.isposinf(va), np.isneginf(va)) == (np.isnan(vb), np.isposinf(vb), np.isneginf(vb)), "%s call %d %s" % (where, i, ka)
+            if np.isfinite(vb):
+                assert abs(va - vb) <= max(tol, 2 * float(np.spacing(np.float32(abs(vb))))), "%s call %d %s" % (where, i, ka)
+
+
 MODES = [1, 2]     # 1 = streaming kernel (frame machine on the device), 2 = host-driven lock-step rounds
 
 
@@ -834,15 +847,7 @@ def test_streams_with_non_finite_and_extreme_samples(gpu, oracle, sf, mode):
                 continue
             where = "sf%d mode %d channel %d traced %d" % (sf, mode, c, traced)
             if traced:
-                tr = d.trace(c)
-                assert len(tr) == len(r["calls"]), where
-                for i, (a, b) in enumerate(zip(tr, r["calls"])):
-                    assert (a["consumed"], a["state_before"], a["value"]) == (b["consumed"], b["state"], b["value"]), "%s call %d" % (where, i)
-                    for ka, kb, tol in (("power", "power", TOL_DB), ("f_index", "fIndex", 2e-6)):
-                        va, vb = float(a[ka]), float(b[kb])
-                        assert (np.isnan(va), np.isposinf(va), np.isneginf(va)) == (np.isnan(vb), np.isposinf(vb), np.isneginf(vb)), "%s call %d %s" % (where, i, ka)
-                        if np.isfinite(vb):
-                            assert abs(va - vb) <= max(tol, 2 * float(np.spacing(np.float32(abs(vb))))), "%s call %d %s" % (where, i, ka)
+                compare_channel_by_class(d.trace(c), r["calls"], where)
             assert d.consumed(c) == int(sum(x["consumed"] for x in r["calls"])), where
             mine = [p[2] for p in pk if p[0] == c]
             assert len(mine) == len(r["packets"]), where
