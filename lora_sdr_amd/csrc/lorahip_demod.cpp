@@ -18,21 +18,10 @@ using namespace lorahip::demod;
 
 namespace lorahip { namespace demod {
 
-//! the next run's streams: n_channels x spc samples, `stride` apart. An append run continues every channel's stream where the last
-//! append run left it (unless there was none: create, rewind, any other kind of run in between); any other run begins new streams.
-void placeUniform(lorahip_demod *dm, const size_t spc, const size_t stride, const bool append)
-{
-    dm->uniform = true; dm->uniSpc = spc; dm->uniStride = stride; dm->geomApplied = false;
-    if (!append || dm->appendFresh) dm->posOnDevice = false;
-    if (!append) dm->appendFresh = true;
-    dm->append = append;
-}
-
 //! the next run's streams: channel c's n[c] samples from sample baseOf(c) of the device buffer on, each a new stream
 template <class BaseOf> static void placeSegments(lorahip_demod *dm, const size_t *n, const BaseOf &baseOf)
 {
-    dm->uniform = false; dm->geomApplied = true; dm->posOnDevice = false;
-    dm->append = false; dm->appendFresh = true;
+    dm->home.placedSegments();
     for (size_t c = 0; c < dm->B; c++)
     {
         Channel &k = dm->ch[c];
@@ -49,7 +38,7 @@ static int runAny(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
     // the port replay reads the per-call trace; a trace the caller did not ask for lives for this run only (it must neither grow
     // without bound in a long-running receiver nor show up in lorahip_demod_get_trace / _trace_len / _get_labels)
     const bool internalTrace = dm->portsOn && !dm->userTracing;
-    const bool cont = dm->append && !dm->appendFresh;
+    const bool cont = dm->home.continues();
     if (internalTrace || (dm->portsOn && cont)) { const int rc = syncMirrors(dm); if (rc != LORAHIP_OK) return rc; }
     if (internalTrace) for (auto &k : dm->ch) { k.trace.clear(); k.traceSymCount0 = k.symCount; }
     if (dm->portsOn) for (auto &k : dm->ch) k.runStart = cont ? k.pos : 0;      // where the port replay starts reading
@@ -62,7 +51,7 @@ static int runAny(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
     if (!stream) { dm->kernelMs = 0.0; dm->lastLaunches = 0; }       // what the accessors say of a host-driven run
     int rc = stream ? runStream(dm, iqDev, roundsOut) : runRounds(dm, iqDev, roundsOut);
     if (rc == LORAHIP_OK && dm->portsOn) rc = fillPorts(dm, iqDev);
-    if (rc == LORAHIP_OK && dm->append) { dm->appendFresh = false; dm->appendPrev = dm->uniSpc; }    // the next append run continues this one
+    if (rc == LORAHIP_OK) dm->home.runCompleted();                      // the next append run continues this one
     if (internalTrace) for (auto &k : dm->ch) { std::vector<lorahip_work_result>().swap(k.trace); k.traceStart = 0; }
     return rc;
 }
@@ -322,7 +311,7 @@ int lorahip_demod_activate(lorahip_demod *dm)
     // activate() resets only _state and _chirpTable (:139-143); everything else keeps the
     // constructor / zero state, or whatever the previous activation left. While the state lives on the device (streaming mode)
     // the reset travels with the next launch as a flag; the mirrors get it when they are next brought up to date.
-    if (dm->devStateFresh) dm->activatePending = true;
+    if (dm->home.deviceCurrent()) dm->home.activateDeferred();
     else
     {
         const int rc = syncMirrors(dm);
@@ -340,7 +329,7 @@ int lorahip_demod_run_device(lorahip_demod *dm, const float *iq_dev, const size_
     { const int rc = refuseWhilePiped(dm); if (rc != LORAHIP_OK) return rc; }         // before anything of the object changes
     // n_channels streams of equal length back to back: the placement is two numbers, not 3 * n_channels (ch[].base / len / pos are
     // filled only for the paths that read them, applyGeometry)
-    placeUniform(dm, samples_per_channel, samples_per_channel, false);
+    dm->home.placedUniform(samples_per_channel, samples_per_channel, false);
     return runAny(dm, iq_dev, rounds);
 }
 
@@ -349,10 +338,10 @@ int lorahip_demod_run_device_append(lorahip_demod *dm, const float *iq_dev, cons
     if (dm == nullptr || n_valid > row_stride || (n_valid && iq_dev == nullptr)) return LORAHIP_E_INVALID;
     if (dm->comp) { setLastError("append runs are per part: lorahip_demod_part_handle"); return LORAHIP_E_INVALID; }
     { const int rc = refuseWhilePiped(dm); if (rc != LORAHIP_OK) return rc; }
-    if (!dm->appendFresh && n_valid < dm->appendPrev) { setLastError("an append run was given fewer samples than the one before it (lorahip_demod_rewind starts a new stream)"); return LORAHIP_E_INVALID; }
+    if (dm->home.appendBegun() && n_valid < dm->home.prevValid()) { setLastError("an append run was given fewer samples than the one before it (lorahip_demod_rewind starts a new stream)"); return LORAHIP_E_INVALID; }
     // every channel's stream is the first n_valid samples of its row; a channel continues at its own read position (the device's
     // copy of the state holds it: nothing is uploaded per run)
-    placeUniform(dm, n_valid, row_stride, true);
+    dm->home.placedUniform(n_valid, row_stride, true);
     return runAny(dm, iq_dev, rounds);
 }
 
@@ -361,7 +350,7 @@ int lorahip_demod_rewind(lorahip_demod *dm)
     if (dm == nullptr) return LORAHIP_E_INVALID;
     if (dm->comp) { for (size_t i = 0; i < dm->comp->numParts(); i++) (void)lorahip_demod_rewind(dm->comp->part(i)); return LORAHIP_OK; }
     { const int rc = refuseWhilePiped(dm); if (rc != LORAHIP_OK) return rc; }
-    dm->appendFresh = true; dm->appendPrev = 0;
+    dm->home.rewound();
     return LORAHIP_OK;
 }
 
@@ -698,7 +687,7 @@ static int flushResume(lorahip_demod *dm, const lorahip_packet_rows *rows, const
                        size_t *nPackets, int64_t *calls)
 {
     const int64_t calls0 = dm->workCalls;
-    int rc = lorahip_demod_run_device_append(dm, dm->stepIq, dm->stepStride, dm->appendPrev, nullptr);
+    int rc = lorahip_demod_run_device_append(dm, dm->stepIq, dm->stepStride, dm->home.prevValid(), nullptr);
     if (rc != LORAHIP_OK) return rc;
     if (calls) *calls = c0 + (dm->workCalls - calls0);
     if (rows == nullptr) { lorahip_demod_clear_packets(dm); return LORAHIP_OK; }
@@ -788,7 +777,7 @@ void lorahip_demod_clear_packets(lorahip_demod *dm)
     {
         // records still on the device: they can simply be dropped unless a channel is inside a packet -- the symbols it has
         // received so far open the first packet of the next run
-        if (P.anyOpen && !dm->devCarryValid) (void)drainPending(dm);
+        if (P.anyOpen && !dm->home.carryRowsValid()) (void)drainPending(dm);
         else P.valid = false;                                   // (with the open packets kept on the device nothing is lost)
     }
     dm->packets.clear();
@@ -810,17 +799,25 @@ int lorahip_demod_near_threshold(const lorahip_demod *dm, int64_t *near_squelch,
     return LORAHIP_OK;
 }
 
+//! where the read positions are: the pinned copy's states, fetched first (nullptr if that failed; *rc says how), or -- *rc
+//! LORAHIP_OK and nullptr -- the mirrors
+static const StreamState *pinnedPositions(const lorahip_demod *dm, int *rc)
+{
+    *rc = LORAHIP_OK;
+    if (!(dm->home.readPinnedPos() && dm->sHost.get())) return nullptr;
+    lorahip_demod *m = const_cast<lorahip_demod *>(dm);
+    *rc = ensureHead(m);
+    return *rc == LORAHIP_OK ? hostStates(m) : nullptr;
+}
+
 int64_t lorahip_demod_consumed(const lorahip_demod *dm, const size_t channel)
 {
     if (dm == nullptr || channel >= dm->B) return LORAHIP_E_INVALID;
     if (dm->comp) return dm->comp->consumed(channel);
-    if (dm->mirrorsStale && dm->posOnDevice && dm->sHost.get())
-    {
-        lorahip_demod *m = const_cast<lorahip_demod *>(dm);
-        if (ensureHead(m) != LORAHIP_OK) return LORAHIP_E_HIP;
-        return int64_t(hostStates(m)[channel].pos);
-    }
-    if (!dm->posOnDevice && dm->uniform && !dm->geomApplied) return 0;     // placement set, nothing run on it yet
+    int rc;
+    if (const StreamState *hs = pinnedPositions(dm, &rc)) return int64_t(hs[channel].pos);
+    if (rc != LORAHIP_OK) return LORAHIP_E_HIP;
+    if (dm->home.placementUntouched()) return 0;
     return int64_t(dm->ch[channel].pos);
 }
 
@@ -836,11 +833,7 @@ int lorahip_demod_consumed_all(const lorahip_demod *dm, int64_t *out)
     }
     // the one read that can fail -- the per-channel state back from the device -- up front: an error is the call's, not a negative
     // entry a caller would take for "nothing consumed"
-    if (dm->mirrorsStale && dm->posOnDevice && dm->sHost.get())
-    {
-        const int rc = ensureHead(const_cast<lorahip_demod *>(dm));
-        if (rc != LORAHIP_OK) return rc;
-    }
+    { int rc; (void)pinnedPositions(dm, &rc); if (rc != LORAHIP_OK) return rc; }
     for (size_t c = 0; c < dm->B; c++)
     {
         out[c] = lorahip_demod_consumed(dm, c);

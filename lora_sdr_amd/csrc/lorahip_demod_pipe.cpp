@@ -15,21 +15,16 @@ namespace lorahip { namespace demod {
  * for a packet. Anything else takes the ordinary step (which establishes exactly that). */
 bool steadyAppend(const lorahip_demod *dm, const size_t rowStride, const size_t nValid)
 {
-    return usesStreamKernel(dm) && !dm->tracing && !dm->portsOn && !dm->activatePending && dm->sDev.get() != nullptr && dm->append && !dm->appendFresh &&
-           dm->uniStride == rowStride && nValid >= dm->appendPrev && dm->dCarry.get() != nullptr && dm->mtu + 1 <= dm->carryCap;
+    return usesStreamKernel(dm) && !dm->tracing && !dm->portsOn && !dm->home.activateWaiting() && dm->sDev.get() != nullptr && dm->home.continues() &&
+           dm->home.stride() == rowStride && nValid >= dm->home.prevValid() && dm->dCarry.get() != nullptr && dm->mtu + 1 <= dm->carryCap;
 }
 
 //! ... and to enter either mode: the state and the open packets' symbols on the device, no records of a launch left there
-bool stateOnDevice(const lorahip_demod *dm) { return dm->devStateFresh && (dm->devCarryValid || !dm->lastSum.anyOpen) && !dm->pending.valid; }
+bool stateOnDevice(const lorahip_demod *dm) { return dm->home.mayEnter(dm->lastSum.anyOpen != 0, dm->pending.valid); }
 
 //! a pipelined or resident step has been given the first nValid samples of rows rowStride apart: an append run over those rows, after
 //! which the pinned copy of the state and the mirrors lag behind the device
-void noteSteadyStep(lorahip_demod *dm, const size_t rowStride, const size_t nValid)
-{
-    placeUniform(dm, nValid, rowStride, true);
-    dm->appendPrev = nValid;
-    dm->mirrorsStale = true; dm->headStale = true;
-}
+void noteSteadyStep(lorahip_demod *dm, const size_t rowStride, const size_t nValid) { dm->home.steadyStep(rowStride, nValid); }
 
 //! a pipelined or resident receiver has been left: the object is as a streaming run leaves it -- the state (and the open packets'
 //! symbols) on the device, the pinned copy and the mirrors behind. (Its steps are not timed one by one: an event pair per step is two
@@ -37,8 +32,7 @@ void noteSteadyStep(lorahip_demod *dm, const size_t rowStride, const size_t nVal
 void leaveStateOnDevice(lorahip_demod *dm)
 {
     dm->kernelMs = 0.0;
-    dm->devStateFresh = true; dm->posOnDevice = true; dm->mirrorsStale = true; dm->headStale = true;
-    dm->devCarryValid = true; dm->hostCarryStale = true;
+    dm->home.givenBack();
     dm->pending.valid = false;
 }
 
@@ -208,7 +202,7 @@ int pipeStep(lorahip_demod *dm, const float *iqDev, const size_t rowStride, cons
         LORAHIP_TRY(P.entry.ensure(hipEventDisableTiming));
         LORAHIP_TRY(P.side.ensure(hipStreamNonBlocking));
         P.active = true; P.k = 0; P.pending[0] = P.pending[1] = false; P.held[0] = P.held[1] = false;
-        dm->devStateFresh = false;                    // until the pipeline is flushed, only it knows where the state stands
+        dm->home.takenOver();                         // until the pipeline is flushed, only it knows where the state stands
     }
     const int set = int(P.k & 1);
     if (nPackets) *nPackets = 0;
@@ -230,9 +224,9 @@ int pipeStep(lorahip_demod *dm, const float *iqDev, const size_t rowStride, cons
         if (rc != LORAHIP_OK) return rc;
         delivered = true;
     }
-    const size_t prevValid = dm->appendPrev;
+    const size_t prevValid = dm->home.prevValid();
     size_t cap, capPkt;
-    streamCapacity(dm, nValid - dm->appendPrev + 2 * N, cap, capPkt);
+    streamCapacity(dm, nValid - prevValid + 2 * N, cap, capPkt);
     StreamLayout L;
     L.make(B, cap, capPkt, false, dm->carryCap, dm->wantSignals);
     // (this set's last use, step k - 2, was packed during step k - 1's call, stream-ordered before kernel k - 1: freeing waits for it)

@@ -80,7 +80,7 @@ void residentAbort(lorahip_demod *dm)
     __atomic_store_n(&R.host->abort, 1u, __ATOMIC_RELEASE);
     (void)hipStreamSynchronize(R.run.get());
     R.active = false; R.unavailable = true;
-    dm->devStateFresh = false;                        // the steps' bookkeeping is incomplete: nothing on the device is trusted
+    dm->home.aborted();                               // the steps' bookkeeping is incomplete: the state on the device is not trusted (the carry flags stay: Home::aborted)
 }
 
 int residentFlush(lorahip_demod *dm, size_t *nPackets, int64_t *calls)
@@ -213,7 +213,7 @@ int residentStep(lorahip_demod *dm, const float *iqDev, const size_t rowStride, 
         LORAHIP_TRY(R.ev.ensure(hipEventDisableTiming));
         // a step's records: sized for a step as long as this one (a longer one fills them, stops the channel and the next step resumes it)
         size_t cap, capPkt;
-        streamCapacity(dm, nValid - dm->appendPrev + 2 * N, cap, capPkt);
+        streamCapacity(dm, nValid - dm->home.prevValid() + 2 * N, cap, capPkt);
         StreamLayout L;
         L.make(B, cap, capPkt, false, dm->carryCap, dm->wantSignals);
         // (RES_RING sets of record arrays: a step writes set step & 3 -- StreamArgs::resRecStride)
@@ -248,12 +248,12 @@ int residentStep(lorahip_demod *dm, const float *iqDev, const size_t rowStride, 
             if (__atomic_load_n(&R.host->arrivedAll, __ATOMIC_ACQUIRE) == 0u)
             {
                 residentAbort(dm);
-                dm->devStateFresh = true;             // (no step was taken: the state on the device is what it was)
+                dm->home.censusFailed();              // (no step was taken: the state on the device is what it was)
                 return LORAHIP_OK;
             }
         }
         dm->stepIq = iqDev; dm->stepStride = rowStride;
-        dm->devStateFresh = false;                    // until the kernel has left, only it knows where the state stands
+        dm->home.takenOver();                         // until the kernel has left, only it knows where the state stands
     }
     handled = true;
     {

@@ -76,14 +76,14 @@ static int launchRound(lorahip_demod *dm, const float *iqDev, const size_t n)
 //! ch[].base / len / pos of a uniform run (filled only for the paths that read them: host-driven rounds, the port replay)
 void applyGeometry(lorahip_demod *dm)
 {
-    if (dm->geomApplied) return;
-    const bool cont = dm->append && !dm->appendFresh;           // an append run continues at the mirrors' read positions (synced by the caller)
+    if (dm->home.geometryCurrent()) return;
+    const bool cont = dm->home.continues();                     // an append run continues at the mirrors' read positions (synced by the caller)
     for (size_t c = 0; c < dm->B; c++)
     {
-        dm->ch[c].base = c * dm->uniStride; dm->ch[c].len = dm->uniSpc;
+        dm->ch[c].base = c * dm->home.stride(); dm->ch[c].len = dm->home.spc();
         if (!cont) { dm->ch[c].pos = 0; dm->ch[c].callCount = 0; }
     }
-    dm->geomApplied = true;
+    dm->home.geometryApplied();
 }
 
 //! frameStep<2^sf> on the host: the call whose detect results stand in r (the first pass filled it), its record into r -- o.out points
@@ -112,9 +112,8 @@ int runRounds(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
     const size_t N = dm->N, B = dm->B;
     { const int rc = syncMirrors(dm); if (rc != LORAHIP_OK) return rc; }       // (a failed fetch of the open packets' symbols: nothing is invalidated)
     applyGeometry(dm);
-    if (!(dm->append && !dm->appendFresh)) for (auto &k : dm->ch) k.callCount = 0;
-    dm->devStateFresh = false;                                  // the mirrors are about to change: the device copy goes stale
-    dm->devCarryValid = false;                                  // ... and so do the open packets' symbols it holds (syncMirrors fetched them)
+    if (!dm->home.continues()) for (auto &k : dm->ch) k.callCount = 0;
+    dm->home.roundsBegin();                                     // the mirrors are about to change: the device's copies go stale (syncMirrors fetched the open packets)
     const DeviceGuard guard(dm->ctx->device);
     const Round hr = carve(dm->h.get(), B);
     std::vector<uint32_t> live, second;

@@ -9,6 +9,7 @@
 #pragma once
 #include "lorahip_own.h"
 #include "lorahip_framestep.h"
+#include "lorahip_demod_home.h"
 #include <chrono>
 #include <vector>
 
@@ -197,28 +198,17 @@ struct lorahip_demod
     lorahip::DevBuf<char> dPort;     // scratch of the port replay: window descriptors, replayed fft / dec windows
     int64_t nNearSquelch, nNearStep; // decisions float rounding could flip, since activate() (lorahip_demod_near_threshold)
     // Streaming mode keeps the per-channel frame-machine state ON THE DEVICE between runs (its pinned copy in sHost is what the host
-    // reads); the Channel mirrors above are brought up to date only when somebody needs them (host-driven rounds, ports, accessors)
-    bool devStateFresh;              // the device holds the current state: the next streaming run need not upload it
-    bool mirrorsStale;               // ch[].state .. ch[].pos lag behind the pinned copy of the device state
-    bool activatePending;            // activate() since the last run, not yet applied to the device state / the mirrors
-    bool uniform; size_t uniSpc;     // the streams of the current run are n_channels x uniSpc samples, uniStride apart (lorahip_demod_run_device[_append])
-    size_t uniStride;
-    bool append;                     // the current run continues every channel's stream where the last append run left it
-    bool appendFresh = true;         // ... unless nothing has been appended yet (create, rewind, any other kind of run in between)
-    size_t appendPrev;               // samples per channel the last append run was given
-    bool headStale;                  // the pinned copy of the per-channel state and counts (sHost) lags the device: ensureHead() fetches it
-    lorahip::StreamSummary lastSum;  // of the last streaming launch (valid while devStateFresh)
+    // reads); the Channel mirrors above are brought up to date only when somebody needs them (host-driven rounds, ports, accessors).
+    // The symbols of open packets stay in the carry rows below likewise. Which copy is current, and the placement of the next run's
+    // streams: lorahip_demod_home.h
+    lorahip::demod::Home home;
+    lorahip::StreamSummary lastSum;  // of the last streaming launch (valid while home.deviceCurrent())
     unsigned nearSeen[2];            // the kernels' running near-threshold counters as last read
-    bool geomApplied = true;         // ch[].base / len / pos hold the current run's placement
-    bool posOnDevice;                // the pinned state copy's `pos` belongs to the CURRENT placement (a streaming run filled it; a new
-                                     // lorahip_demod_run[_device] call invalidates it: its streams start at sample 0)
     bool portCountsDirty = true;     // ch[].portFft / portDec / portRaw may be non-zero
     // The symbols of the packet a channel is INSIDE when a streaming run ends stay on the device too: the kernel leaves them in dCarry
     // and copies them to the head of the channel's symbol row at the start of the next run, then appends behind them -- a packet
     // that spans runs is assembled without the host (the running receiver: lorahip_demod_run_device_segments + packets_to_device).
     lorahip::DevBuf<short> dCarry; size_t carryCap; // [B][carryCap]
-    bool devCarryValid;              // dCarry holds the open packets of the state on the device
-    bool hostCarryStale;             // ch[].outSymbols lack what the runs since the last drain received (implies devCarryValid)
     size_t callsPerWindowQ8 = 288;   // streaming runs: work() calls per N samples the record buffers are sized for, in 1/256 (adapts, see runStream;
                                      // 1.125 to begin with)
     lorahip::demod::PendingLaunch pending; // records of the last streaming launch still on the device
@@ -231,7 +221,6 @@ struct lorahip_demod
 namespace lorahip { namespace demod {
 
 // lorahip_demod.cpp
-void placeUniform(lorahip_demod *dm, size_t spc, size_t stride, bool append);
 int drained(const lorahip_demod *dm);
 
 // lorahip_demod_rounds.cpp

@@ -69,12 +69,12 @@ StreamLayout headLayout(const lorahip_demod *dm)
 //! only its summary; whoever needs the arrays -- the Channel mirrors, consumed(), a drain of the records -- asks here first.
 int ensureHead(lorahip_demod *dm)
 {
-    if (!dm->headStale || dm->sHost.get() == nullptr || dm->sDev.get() == nullptr) return LORAHIP_OK;
+    if (!dm->home.headLags() || dm->sHost.get() == nullptr || dm->sDev.get() == nullptr) return LORAHIP_OK;
     const StreamLayout L = headLayout(dm);
     const DeviceGuard guard(dm->ctx->device);
     LORAHIP_TRY(hipMemcpyAsync(dm->sHost.get() + L.oState, dm->sDev.get() + L.oState, L.oPkt - L.oState, hipMemcpyDeviceToHost, dm->ctx->stream));
     LORAHIP_TRY(hipStreamSynchronize(dm->ctx->stream));
-    dm->headStale = false;
+    dm->home.headFetched();
     return LORAHIP_OK;
 }
 
@@ -171,7 +171,7 @@ int drainPending(lorahip_demod *dm)
     const int rc = drainLaunch(dm, P.lay);
     if (rc != LORAHIP_OK) return rc;
     P.valid = false;
-    dm->hostCarryStale = false;                       // drainLaunch has written the open packets' symbols of this launch into the mirrors
+    dm->home.pendingDrained();                        // drainLaunch has written the open packets' symbols of this launch into the mirrors
     orderNewPackets(dm, P.firstNewPacket, P.rounds);
     P.drainMs = std::chrono::duration<double>(Clock::now() - t0).count() * 1e3;
     static const bool timing = std::getenv("LORAHIP_DEMOD_TIMING") != nullptr;
@@ -187,11 +187,11 @@ StreamState *hostStates(lorahip_demod *dm)
 //! the open packets' symbols the device holds (dCarry) into the mirrors' outSymbols; the mirrors' state must be current
 static int fetchCarry(lorahip_demod *dm)
 {
-    if (!dm->hostCarryStale) return LORAHIP_OK;
+    if (!dm->home.openPacketsLag()) return LORAHIP_OK;
     const size_t B = dm->B, cap = dm->carryCap;
     bool any = false;
     for (size_t c = 0; c < B && !any; c++) any = dm->ch[c].state == ST_DATASYMBOLS && dm->ch[c].symCount != 0;
-    if (any && dm->dCarry.get() && dm->devCarryValid)
+    if (any && dm->dCarry.get() && dm->home.carryRowsValid())
     {
         const DeviceGuard guard(dm->ctx->device);
         std::vector<short> rows;
@@ -207,7 +207,7 @@ static int fetchCarry(lorahip_demod *dm)
             std::memcpy(k.outSymbols.data(), rows.data() + c * cap, n * sizeof(short));
         }
     }
-    dm->hostCarryStale = false;
+    dm->home.openPacketsFetched();
     return LORAHIP_OK;
 }
 
@@ -215,7 +215,7 @@ static int fetchCarry(lorahip_demod *dm)
 int syncMirrors(lorahip_demod *dm)
 {
     { const int rc = refuseWhilePiped(dm); if (rc != LORAHIP_OK) return rc; }
-    if (dm->mirrorsStale && dm->sHost.get())
+    if (dm->home.mirrorsLag() && dm->sHost.get())
     {
         { const int rc = ensureHead(dm); if (rc != LORAHIP_OK) return rc; }
         const StreamState *hs = hostStates(dm);
@@ -224,18 +224,17 @@ int syncMirrors(lorahip_demod *dm)
             Channel &k = dm->ch[c];
             const StreamState &st = hs[c];
             fromStreamState(k, st);
-            if (dm->posOnDevice) { k.pos = size_t(st.pos); k.callCount = st.callCount; }
+            if (dm->home.pinnedPosCurrent()) { k.pos = size_t(st.pos); k.callCount = st.callCount; }
         }
     }
-    dm->mirrorsStale = false;
-    // before a deferred activate() hides which channels were inside a packet. A failed copy leaves hostCarryStale set and the
+    dm->home.mirrorsSynced();
+    // before a deferred activate() hides which channels were inside a packet. A failed copy leaves the mirrors' symbols lagging and the
     // device's copy valid: the caller must not invalidate it (it returns the error instead)
     { const int rc = fetchCarry(dm); if (rc != LORAHIP_OK) return rc; }
-    if (dm->activatePending)
+    if (dm->home.activateWaiting())
     {
         for (auto &k : dm->ch) { k.state = ST_FRAMESYNC; k.downTable = false; }     // activate() (:139-143), deferred
-        dm->activatePending = false;
-        dm->devStateFresh = false;                      // the device copy does not have it: the next streaming run uploads
+        dm->home.activateAppliedToMirrors();            // the device copy does not have it: the next streaming run uploads
     }
     return LORAHIP_OK;
 }
@@ -290,7 +289,7 @@ StreamArgs makeStreamArgs(const lorahip_demod *dm, const float *iqDev, const Str
     const StreamLayout H = headLayout(dm);
     StreamArgs a{};
     a.iq = reinterpret_cast<const float2 *>(iqDev);
-    a.uniformStride = (long long)dm->uniStride;
+    a.uniformStride = (long long)dm->home.stride();
     a.state = reinterpret_cast<StreamState *>(dm->sDev.get() + H.oState);
     a.near = reinterpret_cast<unsigned *>(dm->sDev.get() + H.oNear);
     a.carry = dm->dCarry.get(); a.carryCap = int(dm->carryCap);
@@ -325,10 +324,11 @@ int runStream(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
     typedef std::chrono::steady_clock Clock;
     const Clock::time_point t0 = Clock::now();
     double tDev = 0, tAsm = 0;
-    const bool cont = dm->append && !dm->appendFresh;           // the channels continue where the last append run left them
+    const bool cont = dm->home.continues();                     // the channels continue where the last append run left them
     // an append run works through what is new since the last one plus what that one left (fewer than 2N samples per channel)
-    size_t maxLen = dm->uniform ? (cont && dm->appendPrev <= dm->uniSpc ? dm->uniSpc - dm->appendPrev + 2 * N : dm->uniSpc) : 0;
-    if (!dm->uniform) for (size_t c = 0; c < B; c++) if (dm->ch[c].len - dm->ch[c].pos > maxLen) maxLen = dm->ch[c].len - dm->ch[c].pos;
+    const Home &pl = dm->home;
+    size_t maxLen = pl.isUniform() ? (cont && pl.prevValid() <= pl.spc() ? pl.spc() - pl.prevValid() + 2 * N : pl.spc()) : 0;
+    if (!pl.isUniform()) for (size_t c = 0; c < B; c++) if (dm->ch[c].len - dm->ch[c].pos > maxLen) maxLen = dm->ch[c].len - dm->ch[c].pos;
     size_t cap, capPkt;
     streamCapacity(dm, maxLen, cap, capPkt);
 
@@ -339,7 +339,7 @@ int runStream(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
     if (useDevCarry && dm->mtu + 1 > dm->carryCap)
     {
         { const int rc = syncMirrors(dm); if (rc != LORAHIP_OK) return rc; }      // what the device holds of open packets goes to the mirrors first
-        dm->carryCap = 0; dm->devCarryValid = false;
+        dm->carryCap = 0; dm->home.carryRowsRegrown();
         const size_t rows = dm->mtu + 1 < 64 ? 64 : dm->mtu + 1;
         LORAHIP_TRY(dm->dCarry.grow(B * rows * sizeof(short)));      // (more rows than it has: the old block goes, then the new one is made)
         dm->carryCap = rows;
@@ -350,8 +350,7 @@ int runStream(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
     if (L.total > dm->sDev.bytes())
     {
         { const int rc = syncMirrors(dm); if (rc != LORAHIP_OK) return rc; }      // the pinned copy of the state goes away with the buffers
-        dm->devStateFresh = false;
-        dm->headStale = false;                       // (syncMirrors has read what there was)
+        dm->home.recordBuffersRegrown();             // (syncMirrors has read what there was)
         // a quarter more than this run needs: the chunks of a running receiver differ by the remainders they start with, and every
         // growth costs two allocations and an upload of the state
         LORAHIP_TRY(regrowPair(dm->sDev, L.total + L.total / 4, dm->sHost, L.oPkt, hipHostMallocDefault));   // the host mirrors only the head: placement, state, counts
@@ -371,14 +370,14 @@ int runStream(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
     // 72 bytes: the state is where the last run left it on the device, the placement of uniform streams is computed by the kernel,
     // an activate() in between travels as a flag, the open packets' symbols are in the device's carry rows, and what the host needs
     // to know of the last run is its summary (streamSummary). The per-channel state and counts are fetched when somebody asks.
-    const bool resident = dm->devStateFresh;
-    const bool activate = resident && dm->activatePending;
+    const bool resident = dm->home.deviceCurrent();
+    const bool activate = resident && dm->home.activateWaiting();
     if (resident)
     {
         // symbols of packets that are still being received when the run starts: the last summary says whether there are any
         if (!activate && dm->lastSum.anyOpen && dm->lastSum.openSyms > 0) { anyCarryIn = true; maxCarry = size_t(dm->lastSum.maxOpen); }
         // which channels, and how many symbols each, only matters where the HOST hands them on
-        const bool perChannel = anyCarryIn && (!useDevCarry || maxCarry >= dm->carryCap || !dm->devCarryValid);
+        const bool perChannel = anyCarryIn && (!useDevCarry || maxCarry >= dm->carryCap || !dm->home.carryRowsValid());
         if (perChannel)
         {
             { const int rc = ensureHead(dm); if (rc != LORAHIP_OK) return rc; }
@@ -403,7 +402,7 @@ int runStream(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
             if (carry[c] > maxCarry) maxCarry = carry[c];
         }
         LORAHIP_TRY(hipMemcpyAsync(d + L.oState, h + L.oState, L.oN - L.oState, hipMemcpyHostToDevice, ctx->stream));
-        dm->headStale = false;                        // the pinned copy IS what the device is being given
+        dm->home.stateUploaded();                     // the pinned copy IS what the device is being given
     }
     // Where do the symbols of those packets come from? From the device's own copy (the carry rows: the kernel copies a channel's open
     // packet to the head of its symbol row and appends behind it, so the host sees packets without a past), unless a packet is
@@ -411,7 +410,7 @@ int runStream(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
     if (useDevCarry && maxCarry >= dm->carryCap) useDevCarry = false;
     if (useDevCarry)
     {
-        if (anyCarryIn && !dm->devCarryValid)
+        if (anyCarryIn && !dm->home.carryRowsValid())
         {
             // the mirrors hold them (a host-driven run, or a resumed one, came before): up they go
             const size_t cc = dm->carryCap;
@@ -427,12 +426,12 @@ int runStream(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
     }
     else
     {
-        if (dm->hostCarryStale) { const int rc = syncMirrors(dm); if (rc != LORAHIP_OK) return rc; }      // (a deferred activate() then travels with the state upload: see syncMirrors)
+        if (dm->home.openPacketsLag()) { const int rc = syncMirrors(dm); if (rc != LORAHIP_OK) return rc; }      // (a deferred activate() then travels with the state upload: see syncMirrors)
         if (anyCarryIn)
             for (size_t c = 0; c < B; c++) if (carry[c] && dm->ch[c].outSymbols.size() < carry[c]) dm->ch[c].outSymbols.resize(carry[c], 0);
-        dm->devCarryValid = false;
+        dm->home.carryRowsBypassed();
     }
-    if (!dm->uniform)
+    if (!pl.isUniform())
     {
         for (size_t c = 0; c < B; c++) { hBase[c] = (long long)dm->ch[c].base; hLen[c] = (long long)dm->ch[c].len; }
         LORAHIP_TRY(hipMemcpyAsync(d, h, L.oState, hipMemcpyHostToDevice, ctx->stream));       // base, len
@@ -441,13 +440,12 @@ int runStream(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
     StreamArgs a = makeStreamArgs(dm, iqDev, L, d);
     a.base = reinterpret_cast<const long long *>(d + L.oBase);
     a.len = reinterpret_cast<const long long *>(d + L.oLen);
-    a.uniformLen = dm->uniform ? (long long)dm->uniSpc : -1;
+    a.uniformLen = pl.isUniform() ? (long long)pl.spc() : -1;
     // first launch of the run: every channel starts at sample 0, call 0 (unless the run continues the streams), behind its open packet's
     // symbols, and leaves the packet it is inside at the end in the carry rows
     a.flags = (cont ? 0 : 1) | (activate ? 2 : 0) | (useDevCarry ? 4 | 8 : 0);
-    if (activate) dm->activatePending = false;        // applied by the kernel when it loads the state
-    dm->devStateFresh = false;                        // until the run has completed
-    dm->mirrorsStale = true;
+    if (activate) dm->home.activateRidesLaunch();     // applied by the kernel when it loads the state
+    dm->home.runBegins();                             // (before the first launch: a failed one leaves the device distrusted)
 
     const size_t firstNewPacket = dm->packets.size();
     const Clock::time_point t1 = Clock::now();
@@ -474,7 +472,7 @@ int runStream(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
                                         direct ? static_cast<StreamSummary *>(sumDev) : reinterpret_cast<StreamSummary *>(d + L.oSum), ctx->stream));
         if (!direct) LORAHIP_TRY(hipMemcpyAsync(h + L.oSum, d + L.oSum, sizeof(StreamSummary), hipMemcpyDeviceToHost, ctx->stream));
         LORAHIP_TRY(hipStreamSynchronize(ctx->stream));
-        dm->headStale = true;                         // the pinned copy of the per-channel state and counts lags the device now
+        dm->home.launchSummarised();                  // the pinned copy of the per-channel state and counts lags the device now
         { float ms = 0.0f; if (hipEventElapsedTime(&ms, dm->evK0.get(), dm->evK1.get()) == hipSuccess) dm->kernelMs += ms; }
         const Clock::time_point tb = Clock::now();
         tDev += std::chrono::duration<double>(tb - ta).count();
@@ -511,15 +509,10 @@ int runStream(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
         const size_t q8 = (runCalls * 256 / (maxLen / N)) * 5 / 4 + 16;
         if (q8 > dm->callsPerWindowQ8) dm->callsPerWindowQ8 = q8 > size_t(256) * 64 ? size_t(256) * 64 : q8;
     }
-    dm->devStateFresh = true;                         // the device holds the current state; the pinned copy (headStale) and the mirrors lag
-    dm->posOnDevice = true;
-    if (useDevCarry && launches == 1)
-    {
-        // the packets the channels are inside now: the kernel left the last symCount entries of their symbol rows in the carry rows
-        dm->devCarryValid = true;
-        dm->hostCarryStale = lastPending;             // a drain (traced runs) has brought the mirrors' outSymbols up to date already
-    }
-    else { dm->devCarryValid = false; dm->hostCarryStale = false; }      // a resumed run: its launches handed the symbols on through the mirrors
+    // the device holds the current state; the pinned copy and the mirrors lag. The packets the channels are inside now: the kernel
+    // left the last symCount entries of their symbol rows in the carry rows (a drain -- traced runs -- has brought the mirrors'
+    // outSymbols up to date already), unless the run was resumed: its launches handed the symbols on through the mirrors
+    dm->home.runEnded(!(useDevCarry && launches == 1) ? Home::THROUGH_MIRRORS : lastPending ? Home::CARRY_RECORDS_PENDING : Home::CARRY_RECORDS_DRAINED);
     PendingLaunch &P = dm->pending;
     if (lastPending)
     {
