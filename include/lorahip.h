@@ -955,6 +955,65 @@ int lorahip_psb_run_iq(lorahip_psb *p, const float *in_dev, size_t in_stride, si
 int lorahip_synthesizer_clipped(lorahip_synthesizer *s, unsigned long long *count);
 int lorahip_psb_clipped(lorahip_psb *p, unsigned long long *count);
 
+/* -------------------------------------------------------------------------------------
+ * Rational-rate resampler: K rows of complex64 at one rate -> the same rows at up / down times that rate (lorahip_resamp.hip). The
+ * block between the rate a radio delivers and the rates the four front ends above take (2.4 Msps x 5/6 = 2 Msps in front of a
+ * channeliser of decim 16; 61.44 Msps x 25/24 = 64 Msps in front of lorahip_pfb_create_radix5(320, 512); 1.28 Msps rows x 25/256 =
+ * 125 kHz in front of the demodulator; the same objects in reverse behind the synthesisers). K = 1 is a wideband stream, K > 1 the
+ * rows a channeliser writes or a synthesiser reads. NOT a reference component.
+ * Definition (x_k[n] = row k of the stream since the last reset, x_k[n<0] = 0, U = up, D = down, L = n_taps, h = taps, real):
+ *
+ *     t_m    = (m + 1) D - 1                        (output m sits at this instant of the U-times zero-stuffed stream)
+ *     y_k[m] = sum_{j<L, (t_m - j) mod U == 0, t_m - j >= 0} h[j] x_k[(t_m - j) / U]
+ *
+ * i.e. zero-stuff by U, low-pass with h, keep every D-th sample. After N input samples per row exactly floor(N U / D) outputs per row
+ * exist: a call of n_in samples at stream position n0 writes floor((n0 + n_in) U / D) - floor(n0 U / D) outputs per row -- possibly 0,
+ * the same count for every row --, which is what lorahip_resampler_out_count answers for the next call. With U = 1 this is the
+ * channeliser's definition at frequency 0, with D = 1 the synthesiser's for one row at frequency 0 and gain 1 (the same values within
+ * the tolerance all three are held to, not bit for bit). Pass U * design_lowpass(max(U, D), L) for unit passband gain and a cutoff
+ * at the lower of the two Nyquist rates.
+ * Evaluated in fp32: with p = t_m mod U, c = floor(t_m / U), T = ceil(L / U) and the taps padded with zeros to T whole rounds of U,
+ * each component of y_k[m] is ONE chain of T fused multiply-adds acc = fma(h[p + i U], x_k[c - i], acc) over i = 0 .. T - 1 from
+ * acc = 0. Nothing in it depends on how the stream was cut into calls: arbitrary chunks give bit-identical outputs to one call. The
+ * stream position is a 64-bit counter; n0 U, t_m and the row addressing are evaluated in 64 bits.
+ * Non-finite samples follow the synthesiser's rule: the products with the padding ARE formed, so a NaN or Inf in x_k[c] makes
+ * non-finite exactly the outputs m of row k with floor(t_m / U) - T < c <= floor(t_m / U); every other output and every other row
+ * is untouched. A phase without a tap (p >= L, possible when L < U) gives exact zeros whatever the input holds.
+ * run(): row k of the input is the n_in complex64 samples at in_dev + 2*k*in_stride floats (in_stride in samples >= n_in), row k of
+ * the output goes to out_dev + 2*k*out_stride floats (out_stride in samples >= the output count); *n_out = the count. Asynchronous
+ * on the context's stream. Between calls the object keeps the stream position and the T - 1 trailing samples of every row (nothing
+ * when L <= U).
+ * run_iq(): the input rows are LORAHIP_IQ_CF32, LORAHIP_IQ_SC16 or LORAHIP_IQ_SC8 samples (in_stride counts samples of the format;
+ * the definition, alignment and refusals of "Integer IQ input" above), converted in the kernel's load: bit-identical to run() on
+ * scale * (float)ints, and free to alternate with run() on one stream. The output stays cf32.
+ * reset(): a new stream at position 0. reset_at(position): a new stream whose samples before `position` are zeros and whose first
+ * sample is number `position` (<= 2^52): a capture that stays phase-aligned with an earlier recording.
+ * Limits: up and down 1..1024 each, n_taps 1..65536, n_rows 1..65535*8, stream position + n_in <= 2^52; lorahip_resampler_check
+ * answers for the first four without a device (LORAHIP_OK, or LORAHIP_E_INVALID and a lorahip_last_error() text). A workgroup keeps
+ * the input span of its tile in LDS: with U' = U / gcd, D' = D / gcd, one row of a tile of NS output steps x PB = min(U', 32) phases
+ * spans (NS - 1) D' + T + ceil((PB - 1) D / U) + 1 samples, rounded up to a multiple of D', next to its NS PB outputs; NS is a power
+ * of two, 64 .. 512 where that fits 64 KiB, 64 where it fits 160 KiB (20480 samples), and halves down to 1 where it does not, so
+ * every up / down is served and the bound is on the taps alone: T = ceil(n_taps / up) <= 16384 always fits; beyond that D' decides, and what does not fit is refused by _check and
+ * _create. Limits of one call (a longer stream is fed in several calls): at most 2^30 outputs per row, and tiles x phase blocks =
+ * (outputs / (NS U') + 2) * ceil(U' / 32) at most 2^31 - 1 and times the up to 512 threads of a workgroup below 2^32 (the launch
+ * grid; the second binds only where NS < 64, since a workgroup of 512 threads then makes fewer than 512 outputs: at NS = 1 and
+ * 32 phases, 16 threads per output and calls of up to 2^28 outputs). Anything beyond a limit, a NULL pointer (in_dev with
+ * n_in > 0, out_dev with outputs to write) or a stride shorter than its count is refused with LORAHIP_E_INVALID and a
+ * lorahip_last_error() text that begins "resampler", consumes nothing and leaves the stream state untouched.
+ * ------------------------------------------------------------------------------------- */
+typedef struct lorahip_resampler lorahip_resampler;
+int lorahip_resampler_check(size_t up, size_t down, size_t n_taps, size_t n_rows);     /* host only */
+int lorahip_resampler_create(lorahip_resampler **out, lorahip_ctx *ctx, size_t n_rows, size_t up, size_t down, const float *taps,
+                             size_t n_taps);
+void lorahip_resampler_destroy(lorahip_resampler *r);
+int lorahip_resampler_reset(lorahip_resampler *r);
+int lorahip_resampler_reset_at(lorahip_resampler *r, uint64_t position);
+size_t lorahip_resampler_out_count(const lorahip_resampler *r, size_t n_in);           /* of the next call; 0 for NULL and past 2^52 */
+int lorahip_resampler_run(lorahip_resampler *r, const float *in_dev, size_t in_stride, size_t n_in, float *out_dev, size_t out_stride,
+                          size_t *n_out);
+int lorahip_resampler_run_iq(lorahip_resampler *r, const void *in_dev, int format, float scale, size_t in_stride, size_t n_in,
+                             float *out_dev, size_t out_stride, size_t *n_out);
+
 /* Measurement aid: one read-only streaming pass over n_bytes of device memory (pattern 0: linear
  * 16 B per lane; 1: the access shape of the tuned SF7 kernel). Time it with lorahip_timer_*; the
  * result is the practical HBM ceiling the roofline fraction can be compared with. */

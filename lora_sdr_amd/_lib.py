@@ -202,6 +202,14 @@ SIGNATURES = {
     "lorahip_psb_run_iq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_size_t)]),
     "lorahip_synthesizer_clipped": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "lorahip_psb_clipped": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
+    "lorahip_resampler_check": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
+    "lorahip_resampler_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "lorahip_resampler_destroy": (None, [C.c_void_p]),
+    "lorahip_resampler_reset": (C.c_int, [C.c_void_p]),
+    "lorahip_resampler_reset_at": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "lorahip_resampler_out_count": (C.c_size_t, [C.c_void_p, C.c_size_t]),
+    "lorahip_resampler_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "lorahip_resampler_run_iq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "lorahip_demod_activate": (C.c_int, [C.c_void_p]),
     "lorahip_demod_set_mode": (C.c_int, [C.c_void_p, C.c_int]),
     "lorahip_demod_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -601,6 +601,14 @@ def _chan_run(obj, run, wide, out, int_scale=()):
     return out[:, :got.value]
 
 
+def _is_cf32_rows(t, n_rows, min_cols=0):
+    """t is an (n_rows, >= min_cols) complex64 DEVICE tensor with unit column stride (its rows may be a column slice of a wider
+    buffer): what the synthesisers and the resampler take as rows, and the resampler also as out"""
+    import torch
+    return (_is_torch(t) and t.is_cuda and t.dim() == 2 and t.dtype == torch.complex64 and t.shape[0] == n_rows and t.shape[1] >= min_cols
+            and not (t.numel() and (t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]))))
+
+
 def _iq_out_args(rows, n_channels, dtype, scale):
     """The arguments of Synthesizer.run_int / PolyphaseSynthesizer.run_int checked before any call into the library, and the (format,
     scale) arguments of the *_run_iq entry points of the transmit side: rows a (K, n) complex64 DEVICE tensor, the format from dtype
@@ -620,8 +628,7 @@ def _iq_out_args(rows, n_channels, dtype, scale):
         held = np.isfinite(np.float32(scale))
     if not held:
         raise ValueError("scale must be a finite real number that float32 holds (None: 32767 for int16, 127 for int8)")
-    if (not _is_torch(rows) or not rows.is_cuda or rows.dim() != 2 or rows.dtype != torch.complex64 or rows.shape[0] != n_channels
-            or (rows.numel() and (rows.stride(1) != 1 or (rows.shape[0] > 1 and rows.stride(0) < rows.shape[1])))):
+    if not _is_cf32_rows(rows, n_channels):
         raise ValueError("rows must be a (K, n) complex64 device tensor with unit column stride (rows may be a slice of a wider buffer)")
     return fmt, C.c_float(scale)
 
@@ -644,8 +651,7 @@ def _synth_run(obj, run, rows, out, int_format=()):
     import torch
     if int_format:
         iq = _iq_out_args(rows, obj.n_channels, *int_format)
-    elif (rows.dim() != 2 or rows.dtype != torch.complex64 or rows.shape[0] != obj.n_channels
-            or (rows.numel() and (rows.stride(1) != 1 or (rows.shape[0] > 1 and rows.stride(0) < rows.shape[1])))):
+    elif not _is_cf32_rows(rows, obj.n_channels):
         raise ValueError("rows must be a (K, n) complex64 device tensor with unit column stride (rows may be a slice of a wider buffer)")
     n_in = int(rows.shape[1])
     n_out = obj.out_count(n_in)
@@ -842,6 +848,84 @@ class PolyphaseSynthesizer(_PolyphaseBank):
         """components (I and Q counted separately) that run_int saturated or found NaN since the object was made or reset; waits for
         the stream"""
         return _synth_clipped(self, "lorahip_psb_clipped")
+
+
+class Resampler(_Handle):
+    """K rows of complex64 at one rate -> the same rows at up / down times that rate: zero-stuff by up, low-pass with the real taps,
+    keep every down-th sample (include/lorahip.h has the definition). The block between the rate a radio delivers and the rates the
+    front ends take: Resampler(ctx, 5, 6, taps) turns 2.4 Msps into the 2 Msps of a Channelizer(decim=16), Resampler(ctx, 25, 24, taps)
+    61.44 Msps into the 64 Msps of PolyphaseChannelizer.radix5(320, 512), Resampler(ctx, 25, 256, taps, n_rows=K) rows at 1.28 Msps
+    into the 125 kHz LoRaDemod reads; behind a Synthesizer the same objects run the other way. Pass Resampler.design(up, down, n_taps)
+    for unit passband gain. Stateful: consecutive run() calls continue one stream (position and filter history carried, bit-identical
+    to one call; a call may give 0 outputs), reset() starts a new one."""
+
+    _destroy = "lorahip_resampler_destroy"
+
+    def __init__(self, ctx, up, down, taps, n_rows=1):
+        super().__init__()
+        self._ctx = ctx                                                  # borrowed: device and stream
+        t = np.ascontiguousarray(taps, np.float32).reshape(-1)
+        check(self._lib.lorahip_resampler_create(C.byref(self._h), ctx._h, int(n_rows), int(up), int(down), t.ctypes.data, t.size),
+              "lorahip_resampler_create")
+        self.n_rows, self.up, self.down, self.n_taps = int(n_rows), int(up), int(down), int(t.size)
+
+    @staticmethod
+    def design(up, down, n_taps):
+        """taps for Resampler(ctx, up, down, taps): up * design_lowpass(max(up, down), n_taps) -- unit passband gain, cutoff at the
+        lower of the two Nyquist rates"""
+        return (float(up) * design_lowpass(max(int(up), int(down)), n_taps)).astype(np.float32)
+
+    def reset(self, position=0):
+        """a new stream; position > 0: one whose samples before `position` are zeros and whose first sample is number `position`
+        (a capture that stays phase-aligned with an earlier recording)"""
+        check(self._lib.lorahip_resampler_reset_at(self._h, int(position)), "lorahip_resampler_reset_at")
+
+    def out_count(self, n_in):
+        """outputs per row the next run() of n_in samples per row gives"""
+        return int(self._lib.lorahip_resampler_out_count(self._h, int(n_in)))
+
+    def run(self, rows, out=None):
+        """rows: (K, n) complex64 device tensor with unit column stride (the next n samples of every row; may be the columns
+        [a, a + n) of a wider buffer); for n_rows == 1 a 1-D tensor is taken and a 1-D tensor returned. Returns the (K, n_out)
+        complex64 tensor (written into out if given: it may be the columns [w, w + n_out) of a (K, capacity) buffer)."""
+        return self._run("lorahip_resampler_run", rows, out, ())
+
+    def run_int(self, rows, scale=None, out=None):
+        """run() on integer samples: rows a (K, n, 2) int16 or int8 device tensor (I, Q; rows a whole number of samples apart; (n, 2)
+        for n_rows == 1), sample = scale * (float)(I, Q) with scale None = 2^-15 / 2^-7. Converted in the kernel's load: bit-identical
+        to run() on the complex64 tensor scale * rows.float(), and free to alternate with run() on one stream."""
+        flat = _is_torch(rows) and rows.dim() == 2 and self.n_rows == 1
+        if flat:
+            rows = rows[None]
+        return self._run("lorahip_resampler_run_iq", rows, out, _iq_args(rows, scale, 1), flat)
+
+    def _run(self, run, rows, out, iq, flat=False):
+        import torch
+        if not iq:
+            flat = _is_torch(rows) and rows.dim() == 1 and self.n_rows == 1
+            if flat:
+                rows = rows[None]
+            if not _is_cf32_rows(rows, self.n_rows):
+                raise ValueError("rows must be a (n_rows, n) complex64 device tensor with unit column stride (rows may be a slice of a wider buffer)")
+        elif rows.shape[0] != self.n_rows:
+            raise ValueError("rows must hold n_rows = %d rows" % self.n_rows)
+        n_in = int(rows.shape[1])
+        in_stride = (int(rows.stride(0)) // (2 if iq else 1)) if rows.numel() and rows.shape[0] > 1 else n_in
+        n_out = self.out_count(n_in)
+        if out is None:
+            out = torch.empty((self.n_rows, n_out), dtype=torch.complex64, device=rows.device)
+        else:
+            if flat and _is_torch(out) and out.dim() == 1:
+                out = out[None]
+            if not _is_cf32_rows(out, self.n_rows, n_out):
+                raise ValueError("out must be a (K, >= n_out) complex64 device tensor with unit column stride (rows may be a slice of a wider buffer)")
+        self._ctx.use_torch_stream()
+        got = C.c_size_t()
+        check(getattr(self._lib, run)(self._h, C.c_void_p(rows.data_ptr()) if rows.numel() else None, *iq, in_stride, n_in,
+                                      C.c_void_p(out.data_ptr()) if out.numel() else None,
+                                      int(out.stride(0)) if out.numel() and out.shape[0] > 1 else int(out.shape[1]), C.byref(got)), run)
+        res = out[:, :got.value]
+        return res[0] if flat else res
 
 
 class LoRaDetector(_Handle):

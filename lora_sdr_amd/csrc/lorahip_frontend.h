@@ -1,7 +1,8 @@
 // What the four front ends (lorahip_chan.hip, lorahip_synth.hip, lorahip_pfb.hip, lorahip_psb.hip) have in common, stated once: the
 // state that carries one stream across calls, the output count of the decimators, the sample lookup and the history kernel of the two
 // channelisers with the sample formats they read, the integer formats the two synthesisers store with their clip counter, and the way an
-// object's tables reach the device when it is created.
+// object's tables reach the device when it is created. The rational-rate resampler (lorahip_resamp.hip) carries its rows with the same
+// StreamCarry, reads them through iqLoad / carriedSample and uploads its taps with uploadTables.
 #pragma once
 #include "lorahip_own.h"
 #include <cmath>
