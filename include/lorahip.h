@@ -1000,9 +1000,26 @@ int lorahip_psb_clipped(lorahip_psb *p, unsigned long long *count);
  * 32 phases, 16 threads per output and calls of up to 2^28 outputs). Anything beyond a limit, a NULL pointer (in_dev with
  * n_in > 0, out_dev with outputs to write) or a stride shorter than its count is refused with LORAHIP_E_INVALID and a
  * lorahip_last_error() text that begins "resampler", consumes nothing and leaves the stream state untouched.
+ * lorahip_resampler_plan(): the tiling _create would choose for (up, down, n_taps, n_rows), host only like _check and refused exactly
+ * where _check refuses (*plan is then all zeros). For tests and tuning: which branch of the kernel a shape lands on is read, not guessed.
  * ------------------------------------------------------------------------------------- */
 typedef struct lorahip_resampler lorahip_resampler;
+typedef struct lorahip_resampler_tiling
+{
+    size_t ns;              /* NS: output steps of one tile per phase, a power of two 1..512 */
+    size_t rg;              /* RG: rows one workgroup serves, 1, 2, 4 or 8 (selects the kernel instance) */
+    size_t pb;              /* PB: output phases of one workgroup, min(U', 32) */
+    size_t n_phase_blocks;  /* workgroups per tile and row group, ceil(U' / PB) */
+    size_t ti;              /* TI: input samples one workgroup stages per row, (NS - 1) D' + T + ceil((PB - 1) D / U) + 1 */
+    size_t qp;              /* QP: slots per D' phase of the staged span in LDS, odd, D' QP >= TI */
+    size_t waves;           /* wavefronts per workgroup, 1..8 */
+    size_t lds_bytes;       /* dynamic LDS of one workgroup, RG (D' QP + NS PB) 8 */
+    size_t t;               /* T = ceil(n_taps / up): fused multiply-adds per output component */
+    size_t up_reduced;      /* U' = up / gcd(up, down) */
+    size_t down_reduced;    /* D' = down / gcd(up, down) */
+} lorahip_resampler_tiling;
 int lorahip_resampler_check(size_t up, size_t down, size_t n_taps, size_t n_rows);     /* host only */
+int lorahip_resampler_plan(size_t up, size_t down, size_t n_taps, size_t n_rows, lorahip_resampler_tiling *plan);   /* host only */
 int lorahip_resampler_create(lorahip_resampler **out, lorahip_ctx *ctx, size_t n_rows, size_t up, size_t down, const float *taps,
                              size_t n_taps);
 void lorahip_resampler_destroy(lorahip_resampler *r);

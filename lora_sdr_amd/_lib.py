@@ -52,6 +52,11 @@ class DemodPorts(C.Structure):
                 ("host_buffers", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ResamplerTiling(C.Structure):
+    """struct lorahip_resampler_tiling"""
+    _fields_ = [(n, C.c_size_t) for n in ("ns", "rg", "pb", "n_phase_blocks", "ti", "qp", "waves", "lds_bytes", "t", "up_reduced", "down_reduced")]
+
+
 class PacketRows(C.Structure):
     """struct lorahip_packet_rows"""
     _fields_ = [("struct_size", C.c_size_t), ("syms_dev", C.c_void_p), ("sym_stride", C.c_size_t), ("nsyms_dev", C.c_void_p),
@@ -203,6 +208,7 @@ SIGNATURES = {
     "lorahip_synthesizer_clipped": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "lorahip_psb_clipped": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "lorahip_resampler_check": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
+    "lorahip_resampler_plan": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p]),
     "lorahip_resampler_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t]),
     "lorahip_resampler_destroy": (None, [C.c_void_p]),
     "lorahip_resampler_reset": (C.c_int, [C.c_void_p]),

@@ -875,6 +875,14 @@ class Resampler(_Handle):
         lower of the two Nyquist rates"""
         return (float(up) * design_lowpass(max(int(up), int(down)), n_taps)).astype(np.float32)
 
+    @staticmethod
+    def plan(up, down, n_taps, n_rows=1):
+        """the tiling Resampler(ctx, up, down, taps of n_taps, n_rows) runs on (lorahip_resampler_plan; no device needed): a dict with
+        the fields of struct lorahip_resampler_tiling in include/lorahip.h. Raises LoraHipError where the constructor would."""
+        t = _lib.ResamplerTiling()
+        check(load().lorahip_resampler_plan(int(up), int(down), int(n_taps), int(n_rows), C.byref(t)), "lorahip_resampler_plan")
+        return {name: int(getattr(t, name)) for name, _ in t._fields_}
+
     def reset(self, position=0):
         """a new stream; position > 0: one whose samples before `position` are zeros and whose first sample is number `position`
         (a capture that stays phase-aligned with an earlier recording)"""

@@ -380,6 +380,19 @@ int lorahip_resampler_check(const size_t up, const size_t down, const size_t n_t
     return LORAHIP_E_INVALID;
 }
 
+int lorahip_resampler_plan(const size_t up, const size_t down, const size_t n_taps, const size_t n_rows, lorahip_resampler_tiling *plan)
+{
+    if (plan == nullptr) { setLastError("resampler: NULL argument"); return LORAHIP_E_INVALID; }
+    *plan = lorahip_resampler_tiling();
+    ResampPlan p;
+    std::string why;
+    if (!resampPlan(up, down, n_taps, n_rows, p, why)) { setLastError("resampler: " + why); return LORAHIP_E_INVALID; }
+    plan->ns = size_t(p.NS); plan->rg = size_t(p.RG); plan->pb = size_t(p.PB); plan->n_phase_blocks = size_t(p.nPB);
+    plan->ti = size_t(p.TI); plan->qp = size_t(p.QP); plan->waves = size_t(p.nWaves); plan->lds_bytes = p.ldsBytes;
+    plan->t = size_t(p.T); plan->up_reduced = size_t(p.Up); plan->down_reduced = size_t(p.Dp);
+    return LORAHIP_OK;
+}
+
 int lorahip_resampler_create(lorahip_resampler **out, lorahip_ctx *ctx, const size_t n_rows, const size_t up, const size_t down, const float *taps,
                              const size_t n_taps)
 {

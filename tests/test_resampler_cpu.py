@@ -15,7 +15,7 @@ from conftest import ROOT
 import resampler_def as rd
 import synthesizer_def as sd
 
-SYMBOLS = ["lorahip_resampler_check", "lorahip_resampler_create", "lorahip_resampler_destroy", "lorahip_resampler_reset",
+SYMBOLS = ["lorahip_resampler_check", "lorahip_resampler_plan", "lorahip_resampler_create", "lorahip_resampler_destroy", "lorahip_resampler_reset",
            "lorahip_resampler_reset_at", "lorahip_resampler_out_count", "lorahip_resampler_run", "lorahip_resampler_run_iq"]
 
 SHAPES = [(5, 6, 192), (6, 5, 192), (25, 24, 800), (24, 25, 800), (25, 256, 4096), (125, 128, 4000), (1, 8, 64), (8, 1, 64), (1, 1, 1)]
@@ -142,8 +142,12 @@ def test_symbols_and_entry_points(tmp_path):
                    "int main(void) {\n"
                    "    lorahip_resampler *r = 0;\n"
                    "    float h = 1.0f; size_t n = 7;\n"
+                   "    lorahip_resampler_tiling t;\n"
                    "    if (lorahip_resampler_check(5, 6, 192, 1) != LORAHIP_OK) return 1;\n"
                    "    if (lorahip_resampler_check(5, 1025, 192, 1) != LORAHIP_E_INVALID) return 2;\n"
+                   "    if (lorahip_resampler_plan(5, 6, 192, 1, &t) != LORAHIP_OK || t.up_reduced != 5 || t.down_reduced != 6 || t.t != 39) return 9;\n"
+                   "    if (lorahip_resampler_plan(5, 1025, 192, 1, &t) != LORAHIP_E_INVALID || t.ns != 0) return 10;\n"
+                   "    if (lorahip_resampler_plan(5, 6, 192, 1, 0) != LORAHIP_E_INVALID) return 11;\n"
                    "    if (lorahip_resampler_create(&r, 0, 1, 5, 6, &h, 1) != LORAHIP_E_INVALID || r != 0) return 3;\n"
                    "    if (lorahip_resampler_out_count(0, 5) != 0) return 4;\n"
                    "    if (lorahip_resampler_run(0, 0, 0, 0, 0, 0, &n) != LORAHIP_E_INVALID) return 5;\n"
