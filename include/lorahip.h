@@ -256,9 +256,12 @@ void lorahip_demod_destroy(lorahip_demod *d);
  *   lorahip_demod_run_device_segments       all channels' segments in ONE device buffer (objects on one device)
  *   lorahip_demod_run_device_segments_multi iq_dev[n_devices]: channel c's segment lies in the buffer of ITS device slot
  *                                           (lorahip_demod_part_of / lorahip_demod_part say which)
+ * lorahip_demod_packets_to_device works on a handle whose parts all lie on ONE device (several slots naming it count as one): the rows
+ * of all parts in the queue's order, global channel numbers in channel_dev, for ONE lorahip_decode_packets_cfgs launch whose table says
+ * "configuration of channel".
  * Not offered on such a handle (LORAHIP_E_INVALID; use the part's own handle, lorahip_demod_part_handle): lorahip_demod_run_device,
- * the append runs, lorahip_demod_packets_to_device (one decoder configuration per SF), lorahip_demod_set_stream when the object
- * spans several devices; debug ports only for one SF and host buffers. lorahip_demod_kernel_ms / _last_launches report the maximum
+ * the append runs and receiver steps, lorahip_demod_packets_to_device and lorahip_demod_set_stream when the object spans several
+ * devices (the rows of one decoder launch live on one device); debug ports only for one SF and host buffers. lorahip_demod_kernel_ms / _last_launches report the maximum
  * over the parts, lorahip_demod_work_calls / _near_threshold the sums. On a plain object the part accessors report one part. */
 int lorahip_demod_create_mixed(lorahip_demod **d, const int *devices, size_t n_devices, const int32_t *channel_sf, size_t n_channels);
 size_t lorahip_demod_num_channels(const lorahip_demod *d);
@@ -492,7 +495,12 @@ int lorahip_demod_get_packets(const lorahip_demod *d, int32_t *channels, int64_t
  * the host queue). Otherwise the rows come from the host queue in lorahip_demod_get_packets' order. Either way: packet p's
  * symbols at syms_dev + p*sym_stride (zero padded), its length in nsyms_dev[p] -- a packet longer than sym_stride keeps its true
  * length there and lorahip_decode_packets() reports -2 for it --, its channel in channel_dev[p] (nullable). *n_packets = number of
- * queued packets (also when cap_packets is too small: LORAHIP_E_INVALID then). Does not clear the queue. */
+ * queued packets (also when cap_packets is too small: LORAHIP_E_INVALID then). Does not clear the queue.
+ * On a handle of lorahip_demod_create_mixed whose parts all lie on one device: the parts' rows one after the other in the queue's
+ * order (device slot ascending, SF ascending inside a slot), each part's rows in the order this entry gives for that part alone (a
+ * part whose records are still the only copy is packed on the device, on its own stream; the others come from their host queues);
+ * channel_dev holds GLOBAL channel numbers (each part's rows are renumbered on the device from its local-to-global table);
+ * *n_packets = the total over the parts; the rows are complete when the call returns. Over several devices: LORAHIP_E_INVALID. */
 int lorahip_demod_packets_to_device(lorahip_demod *d, uint16_t *syms_dev, size_t sym_stride, int32_t *nsyms_dev, int32_t *channel_dev,
                                     size_t cap_packets, size_t *n_packets);
 void lorahip_demod_clear_packets(lorahip_demod *d);
@@ -620,6 +628,38 @@ int lorahip_decode_packets(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfg, con
 int lorahip_decode_packets_host(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfg, const uint16_t *syms, size_t sym_stride,
                                 const int32_t *nsyms, size_t n_packets, uint8_t *out, size_t out_stride, int32_t *out_len,
                                 int32_t *dropped);
+/* The same launch with the configuration PER PACKET (a receiver over several SFs and coding rates: lorahip_demod_create_mixed ->
+ * lorahip_demod_packets_to_device -> here): packet p is decoded under cfgs[i] exactly as lorahip_decode_packets decodes it under that
+ * configuration -- the same bytes, out_len and dropped, and the same bytes left untouched behind them.
+ *   i = index_dev[p] with table_dev == NULL, else i = table_dev[index_dev[p]] (index_dev = the hand-off's channel_dev, table_dev[n_table]
+ *       = configuration of channel). out_len_dev[p] = -3, dropped_dev[p] = 0 and nothing written to the packet's output row where
+ *       index_dev[p] lies outside [0, n_table) or i outside [0, n_cfgs). -1 and -2 keep their meaning; the row rule behind -2 is each
+ *       packet's own configuration's.
+ *   cfgs: n_cfgs = 1..64 entries in HOST memory, read before the call returns (they travel in the kernel's arguments: nothing is
+ *       allocated or uploaded). LORAHIP_E_INVALID with nothing launched: n_cfgs 0 or > 64, ANY entry that lorahip_decode_packets would
+ *       refuse (whether or not a packet uses it), index_dev NULL with n_packets > 0, table_dev set with n_table 0 (or n_table >
+ *       0x7fffffff), and the row and stride limits above. n_packets 0 is no work.
+ *   One launch has one lane count per packet and one LDS slice per packet, those of the entry that needs most (lorahip_decode_plan below):
+ *       a table that holds an implicit-header entry with a data_length of thousands of bytes runs few packets per workgroup for ALL its
+ *       packets. Accepted: give such packets a launch of their own where that matters. */
+int lorahip_decode_packets_cfgs(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfgs, size_t n_cfgs, const int32_t *index_dev,
+                                const int32_t *table_dev, size_t n_table, const uint16_t *syms_dev, size_t sym_stride,
+                                const int32_t *nsyms_dev, size_t n_packets, uint8_t *out_dev, size_t out_stride, int32_t *out_len_dev,
+                                int32_t *dropped_dev);
+/* ... with every buffer (index and table too) in HOST memory, as lorahip_decode_packets_host; synchronous */
+int lorahip_decode_packets_cfgs_host(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfgs, size_t n_cfgs, const int32_t *index,
+                                     const int32_t *table, size_t n_table, const uint16_t *syms, size_t sym_stride, const int32_t *nsyms,
+                                     size_t n_packets, uint8_t *out, size_t out_stride, int32_t *out_len, int32_t *dropped);
+/* What a launch over rows of sym_stride symbols under these configurations runs on (host only, no device touched; the launches call the
+ * same function): a packet's symbols, codewords and nibbles live in an LDS slice of its lane group, sized by what the configuration can
+ * need -- (sym_cap * 2 + 2 * cw_cap + 15) & ~15 bytes; lanes_per_packet is 8 / 16 / 32 / 64 for the largest sym_cap <= 48 / <= 96 / <= 200 /
+ * above; packets_per_workgroup = min(256 / lanes_per_packet, 160 KiB / lds_slice_bytes). sym_cap, cw_cap and the slice are the largest
+ * over the entries. With n_cfgs == 1: what lorahip_decode_packets launches. Refused like lorahip_decode_packets_cfgs (*plan zeroed). */
+typedef struct lorahip_decode_tiling {
+    size_t struct_size;     /* = sizeof(lorahip_decode_tiling), set by the caller */
+    int32_t lanes_per_packet, sym_cap, cw_cap, lds_slice_bytes, packets_per_workgroup, reserved;
+} lorahip_decode_tiling;
+int lorahip_decode_plan(const lorahip_decoder_cfg *cfgs, size_t n_cfgs, size_t sym_stride, lorahip_decode_tiling *plan);   /* host only */
 /* the longest row (symbols): sym_stride <= this (16384). A packet of ANY length up to its row decodes as the reference decodes it: the
  * reference de-interleaves every codeword of a message but only those the announced length needs reach the output (LoRaDecoder.cpp:
  * 315-361) -- at most 2 * 260 with an explicit header --, so the kernel's working set follows the configuration, not the packet. A packet

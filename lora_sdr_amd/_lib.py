@@ -57,6 +57,12 @@ class ResamplerTiling(C.Structure):
     _fields_ = [(n, C.c_size_t) for n in ("ns", "rg", "pb", "n_phase_blocks", "ti", "qp", "waves", "lds_bytes", "t", "up_reduced", "down_reduced")]
 
 
+class DecodeTiling(C.Structure):
+    """struct lorahip_decode_tiling"""
+    _fields_ = [("struct_size", C.c_size_t)] + [(n, C.c_int32) for n in ("lanes_per_packet", "sym_cap", "cw_cap", "lds_slice_bytes",
+                                                                          "packets_per_workgroup", "reserved")]
+
+
 class PacketRows(C.Structure):
     """struct lorahip_packet_rows"""
     _fields_ = [("struct_size", C.c_size_t), ("syms_dev", C.c_void_p), ("sym_stride", C.c_size_t), ("nsyms_dev", C.c_void_p),
@@ -162,6 +168,11 @@ SIGNATURES = {
                                         C.c_void_p, C.c_void_p]),
     "lorahip_decode_packets_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                              C.c_void_p, C.c_void_p]),
+    "lorahip_decode_packets_cfgs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                             C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "lorahip_decode_packets_cfgs_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                  C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "lorahip_decode_plan": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
     "lorahip_decode_max_symbols": (C.c_int, []),
     "lorahip_decode_max_data_length": (C.c_int, []),
     "lorahip_encode_num_symbols": (C.c_long, [C.c_void_p, C.c_size_t]),

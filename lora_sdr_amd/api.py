@@ -1357,7 +1357,9 @@ class LoRaDemod(_Handle):
         """The queued packets as device tensors in the decoder's input layout -- (P, stride) int16 symbols (zero padded), (P,) int32
         lengths, (P,) int32 channels -- ready for LoRaDecoder.decode_batch(); no per-packet Python work. Straight after a
         work() of the streaming mode the packets never visit the host (rows ordered by channel, then time); otherwise the
-        rows follow packets()'s order. stride defaults to the MTU."""
+        rows follow packets()'s order. stride defaults to the MTU. On a mixed object whose parts share one device: the parts' rows
+        one after the other in packets()'s order, each part's as above, with global channel numbers -- the input of
+        LoRaDecoderSet.decode_batch(syms, nsyms, index=channels, table=decoder of channel); over several devices: refused."""
         import torch
         n = int(self._lib.lorahip_demod_num_packets(self._h))
         dev = torch.device("cuda", int(self._device))
@@ -1544,6 +1546,99 @@ class LoRaDecoder:
             if out_len[i] < 0:
                 res.append(None)
             elif self._cfg.interleaving:
+                res.append(out[i, :out_len[i]].copy())
+            else:
+                res.append(out[i, :2 * out_len[i]].view(np.uint16).copy())
+        return res
+
+
+class LoRaDecoderSet:
+    """1..64 configured LoRaDecoder objects as ONE launch whose packets each pick their decoder (lorahip_decode_packets_cfgs): the
+    decoder of a receiver over several SFs and coding rates. The configurations are copied at construction (later setter calls on
+    the decoders do not reach the set). Packet p is decoded exactly as decoders[i].decode_batch would decode it, i = index[p], or
+    table[index[p]] with a table (index = the channels LoRaDemod.packets_device() returns, table = decoder of channel); out_len is -3
+    where there is no such decoder. One launch has one LDS slice per packet, the largest any member needs: a member without a
+    header and with a data length of thousands of bytes slows every packet of the launch (LoRaDecoderSet.plan)."""
+
+    def __init__(self, decoders, device=0):
+        decoders = list(decoders)
+        if not 1 <= len(decoders) <= 64:
+            raise ValueError("LoRaDecoderSet: 1..64 decoders")
+        self._ctx = Context(7, device=device)             # device + stream only
+        self._cfgs = self._table(decoders)
+        self._dropped = 0
+
+    @staticmethod
+    def _table(decoders):
+        cfgs = (DecoderCfg * len(decoders))()
+        for i, d in enumerate(decoders):
+            C.memmove(C.byref(cfgs[i]), C.byref(d._cfg), C.sizeof(DecoderCfg))
+        return cfgs
+
+    @staticmethod
+    def plan(decoders, sym_stride):
+        """what a launch of these decoders over rows of sym_stride symbols runs on (lorahip_decode_plan; no device needed): a dict with
+        the fields of struct lorahip_decode_tiling in include/lorahip.h. Raises LoraHipError where decode_batch would."""
+        decoders = list(decoders)
+        cfgs = LoRaDecoderSet._table(decoders) if decoders else None
+        t = _lib.DecodeTiling(C.sizeof(_lib.DecodeTiling))
+        check(load().lorahip_decode_plan(cfgs, len(decoders), int(sym_stride), C.byref(t)), "lorahip_decode_plan")
+        return dict((f, int(getattr(t, f))) for f, _ in _lib.DecodeTiling._fields_ if f not in ("struct_size", "reserved"))
+
+    def getDropped(self): return self._dropped
+    def activate(self): self._dropped = 0
+
+    def decode_batch(self, syms, nsyms, index, table=None):
+        """syms: (P, stride) int16/uint16, nsyms: (P,) int32, index: (P,) int32, table: (T,) int32 or None -- device tensors ->
+        (out uint8 (P, out_stride), out_len int32 (P,), dropped int32 (P,)) device tensors, as LoRaDecoder.decode_batch"""
+        import torch
+        if syms.dim() != 2 or syms.dtype not in (torch.int16, torch.uint16) or nsyms.dtype != torch.int32:
+            raise ValueError("syms must be (P, stride) 16-bit, nsyms (P,) int32 device tensors")
+        P, stride = int(syms.shape[0]), int(syms.shape[1])
+        if index.dtype != torch.int32 or index.numel() != P or nsyms.numel() != P or (table is not None and table.dtype != torch.int32):
+            raise ValueError("index must be (P,) int32, table (T,) int32 device tensors")
+        syms, nsyms, index = syms.contiguous(), nsyms.contiguous(), index.contiguous()
+        table = None if table is None else table.contiguous()
+        out_stride = 2 * (stride + 8)
+        out = torch.zeros((P, out_stride), dtype=torch.uint8, device=syms.device)
+        out_len = torch.empty(P, dtype=torch.int32, device=syms.device)
+        dropped = torch.empty(P, dtype=torch.int32, device=syms.device)
+        self._ctx.use_torch_stream()
+        check(self._ctx._lib.lorahip_decode_packets_cfgs(self._ctx._h, self._cfgs, len(self._cfgs), _dptr(index),
+                                                         None if table is None else _dptr(table), 0 if table is None else int(table.numel()),
+                                                         _dptr(syms), stride, _dptr(nsyms), P, _dptr(out), out_stride, _dptr(out_len), _dptr(dropped)),
+              "lorahip_decode_packets_cfgs")
+        return out, out_len, dropped
+
+    def work(self, packets, index):
+        """list of symbol arrays and the decoder of each -> list of bytes arrays (None where the block posts nothing), as
+        LoRaDecoder.work; raises where a packet has no decoder (-3) or does not fit the rows (-2)"""
+        import torch
+        P = len(packets)
+        if len(index) != P:
+            raise ValueError("LoRaDecoderSet.work(): one index per packet")
+        if P == 0:
+            return []
+        stride = max(8, max(len(p) for p in packets))
+        host = np.zeros((P, stride), np.uint16)
+        for i, p in enumerate(packets):
+            host[i, :len(p)] = np.asarray(p).astype(np.uint16)
+        n = np.array([len(p) for p in packets], np.int32)
+        idx = np.asarray(index, np.int64)
+        dev = torch.device("cuda", self._ctx.device)
+        out, out_len, dropped = self.decode_batch(torch.from_numpy(host.view(np.int16)).to(dev), torch.from_numpy(n).to(dev),
+                                                  torch.from_numpy(np.clip(idx, -1, 2 ** 31 - 1).astype(np.int32)).to(dev))
+        out, out_len, dropped = out.cpu().numpy(), out_len.cpu().numpy(), dropped.cpu().numpy()
+        self._dropped += int(dropped.sum())
+        res = []
+        for i in range(P):
+            if out_len[i] == -3:
+                raise ValueError("LoRaDecoderSet.work(): packet %d names decoder %d of %d" % (i, int(idx[i]), len(self._cfgs)))
+            if out_len[i] == -2:
+                raise ValueError("LoRaDecoderSet.work(): packet %d does not fit its row" % i)
+            if out_len[i] < 0:
+                res.append(None)
+            elif self._cfgs[int(idx[i])].interleaving:
                 res.append(out[i, :out_len[i]].copy())
             else:
                 res.append(out[i, :2 * out_len[i]].view(np.uint16).copy())

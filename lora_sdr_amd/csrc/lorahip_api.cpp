@@ -435,13 +435,10 @@ int lorahip_add_awgn(lorahip_ctx *ctx, float *iq_dev, const size_t n_samples, co
     return LORAHIP_OK;
 }
 
-int lorahip_decode_packets(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfg, const uint16_t *syms_dev, const size_t sym_stride,
-                           const int32_t *nsyms_dev, const size_t n_packets, uint8_t *out_dev, const size_t out_stride,
-                           int32_t *out_len_dev, int32_t *dropped_dev)
+//! what lorahip_decode_packets refuses of a configuration (host arithmetic only): shared with the table launch and lorahip_decode_plan
+static int decoderCfgOk(const lorahip_decoder_cfg *cfg)
 {
-    if (ctx == nullptr || cfg == nullptr || cfg->struct_size != sizeof(lorahip_decoder_cfg)) return LORAHIP_E_INVALID;
-    if (n_packets == 0) return LORAHIP_OK;
-    if (!syms_dev || !nsyms_dev || !out_dev || !out_len_dev || !dropped_dev || n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
+    if (cfg->struct_size != sizeof(lorahip_decoder_cfg)) return LORAHIP_E_INVALID;
     if (cfg->sf < 1 || cfg->sf > LORAHIP_SF_MAX || cfg->ppm < 0 || cfg->ppm > cfg->sf || cfg->rdd < 0 || cfg->rdd > 4 || cfg->data_length < 0) return LORAHIP_E_INVALID;
     // An explicit header occupies the first 5 codewords of the first (PPM-codeword) block: with fewer than 5 bits per symbol the
     // reference whitens `PPM - 5` (an unsigned short: ~65535) codewords past its buffer (LoRaDecoder.cpp:235, undefined behaviour).
@@ -451,7 +448,6 @@ int lorahip_decode_packets(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfg, con
         setLastError("explicit header needs a symbol size (PPM) of at least 5 bits");
         return LORAHIP_E_INVALID;
     }
-    if (sym_stride == 0 || sym_stride > size_t(decodeMaxSymbols()) || (out_stride & 1) || out_stride < 2 * (sym_stride + 8)) return LORAHIP_E_INVALID;
     // without a header the length of every packet is the setter's: what the decoder's tables reach bounds it (the reference has no bound;
     // a LoRa length field is one byte). Refused loudly -- never a packet silently not decoded.
     if (!cfg->explicit_hdr && cfg->interleaving && cfg->data_length > decodeMaxDataLength())
@@ -459,6 +455,29 @@ int lorahip_decode_packets(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfg, con
         setLastError("data_length beyond what this build decodes (lorahip_decode_max_data_length())");
         return LORAHIP_E_INVALID;
     }
+    return LORAHIP_OK;
+}
+
+static bool decodeRowsOk(const size_t sym_stride, const size_t out_stride)
+{
+    return !(sym_stride == 0 || sym_stride > size_t(decodeMaxSymbols()) || (out_stride & 1) || out_stride < 2 * (sym_stride + 8));
+}
+
+static DecodeCfg decodeCfgOf(const lorahip_decoder_cfg &c)
+{
+    const DecodeCfg d = { c.sf, c.ppm, c.rdd, c.crcc, c.interleaving, c.error_check, c.explicit_hdr, c.hdr, c.data_length, 0, 0 };
+    return d;
+}
+
+int lorahip_decode_packets(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfg, const uint16_t *syms_dev, const size_t sym_stride,
+                           const int32_t *nsyms_dev, const size_t n_packets, uint8_t *out_dev, const size_t out_stride,
+                           int32_t *out_len_dev, int32_t *dropped_dev)
+{
+    if (ctx == nullptr || cfg == nullptr || cfg->struct_size != sizeof(lorahip_decoder_cfg)) return LORAHIP_E_INVALID;
+    if (n_packets == 0) return LORAHIP_OK;
+    if (!syms_dev || !nsyms_dev || !out_dev || !out_len_dev || !dropped_dev || n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
+    { const int rc = decoderCfgOk(cfg); if (rc != LORAHIP_OK) return rc; }
+    if (!decodeRowsOk(sym_stride, out_stride)) return LORAHIP_E_INVALID;
     const DeviceGuard guard(ctx->device);
     DecodeArgs a;
     a.syms = syms_dev; a.nsyms = nsyms_dev; a.out = out_dev; a.outLen = out_len_dev; a.dropped = dropped_dev;
@@ -503,6 +522,93 @@ int lorahip_decode_packets_host(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfg
     std::memcpy(out, h + pOut.off, pOut.bytes);
     std::memcpy(out_len, h + pLen.off, pLen.bytes);
     std::memcpy(dropped, h + pDrop.off, pDrop.bytes);
+    return LORAHIP_OK;
+}
+
+//! the argument checks of the table launch and of the plan query that need no device
+static int decodeCfgsOk(const lorahip_decoder_cfg *cfgs, const size_t n_cfgs)
+{
+    if (cfgs == nullptr || n_cfgs == 0 || n_cfgs > size_t(LORAHIP_DEC_MAX_CFGS)) return LORAHIP_E_INVALID;
+    for (size_t i = 0; i < n_cfgs; i++) { const int rc = decoderCfgOk(cfgs + i); if (rc != LORAHIP_OK) return rc; }
+    return LORAHIP_OK;
+}
+
+int lorahip_decode_packets_cfgs(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfgs, const size_t n_cfgs, const int32_t *index_dev,
+                                const int32_t *table_dev, const size_t n_table, const uint16_t *syms_dev, const size_t sym_stride,
+                                const int32_t *nsyms_dev, const size_t n_packets, uint8_t *out_dev, const size_t out_stride,
+                                int32_t *out_len_dev, int32_t *dropped_dev)
+{
+    if (ctx == nullptr) return LORAHIP_E_INVALID;
+    { const int rc = decodeCfgsOk(cfgs, n_cfgs); if (rc != LORAHIP_OK) return rc; }
+    if ((table_dev != nullptr && n_table == 0) || n_table > 0x7fffffffu || !decodeRowsOk(sym_stride, out_stride)) return LORAHIP_E_INVALID;
+    if (n_packets == 0) return LORAHIP_OK;
+    if (!index_dev || !syms_dev || !nsyms_dev || !out_dev || !out_len_dev || !dropped_dev || n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
+    DecodeCfg tab[LORAHIP_DEC_MAX_CFGS];
+    for (size_t i = 0; i < n_cfgs; i++) tab[i] = decodeCfgOf(cfgs[i]);
+    const DeviceGuard guard(ctx->device);
+    DecodeArgs a = {};
+    a.syms = syms_dev; a.nsyms = nsyms_dev; a.out = out_dev; a.outLen = out_len_dev; a.dropped = dropped_dev;
+    a.nPackets = unsigned(n_packets); a.symStride = int(sym_stride); a.outStride = int(out_stride);
+    LORAHIP_TRY(launchDecodeCfgs(a, tab, n_cfgs, index_dev, table_dev, int(n_table), ctx->variant, ctx->stream));
+    return LORAHIP_OK;
+}
+
+int lorahip_decode_packets_cfgs_host(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfgs, const size_t n_cfgs, const int32_t *index,
+                                     const int32_t *table, const size_t n_table, const uint16_t *syms, const size_t sym_stride,
+                                     const int32_t *nsyms, const size_t n_packets, uint8_t *out, const size_t out_stride, int32_t *out_len,
+                                     int32_t *dropped)
+{
+    if (ctx == nullptr) return LORAHIP_E_INVALID;
+    { const int rc = decodeCfgsOk(cfgs, n_cfgs); if (rc != LORAHIP_OK) return rc; }
+    if ((table != nullptr && n_table == 0) || n_table > 0x7fffffffu || !decodeRowsOk(sym_stride, out_stride)) return LORAHIP_E_INVALID;
+    if (n_packets == 0) return LORAHIP_OK;
+    if (!index || !syms || !nsyms || !out || !out_len || !dropped || n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
+    const DeviceGuard guard(ctx->device);
+    struct Piece { size_t off, bytes; };
+    size_t cur = 0;
+    auto carve = [&cur](const size_t bytes) { Piece p = { cur, bytes }; cur += (bytes + 255) & ~size_t(255); return p; };
+    const Piece pSym = carve(n_packets * sym_stride * sizeof(uint16_t));
+    const Piece pN = carve(n_packets * sizeof(int32_t));
+    const Piece pIdx = carve(n_packets * sizeof(int32_t));
+    const Piece pTab = carve(table ? n_table * sizeof(int32_t) : 0);
+    const size_t inBytes = cur;
+    const Piece pOut = carve(n_packets * out_stride);
+    const Piece pLen = carve(n_packets * sizeof(int32_t));
+    const Piece pDrop = carve(n_packets * sizeof(int32_t));
+    { const int rc = growStage(ctx, cur, cur); if (rc != LORAHIP_OK) return rc; }
+    char *d = ctx->dStage.get(), *h = ctx->hStage.get();
+    std::memcpy(h + pSym.off, syms, pSym.bytes);
+    std::memcpy(h + pN.off, nsyms, pN.bytes);
+    std::memcpy(h + pIdx.off, index, pIdx.bytes);
+    if (table) std::memcpy(h + pTab.off, table, pTab.bytes);
+    // the output rows travel both ways: a packet without an entry (-3) leaves its row as the caller had it
+    std::memcpy(h + pOut.off, out, pOut.bytes);
+    LORAHIP_TRY(hipMemcpyAsync(d, h, pOut.off + pOut.bytes, hipMemcpyHostToDevice, ctx->stream));
+    const int rc = lorahip_decode_packets_cfgs(ctx, cfgs, n_cfgs, reinterpret_cast<const int32_t *>(d + pIdx.off),
+                                               table ? reinterpret_cast<const int32_t *>(d + pTab.off) : nullptr, n_table,
+                                               reinterpret_cast<const uint16_t *>(d + pSym.off), sym_stride, reinterpret_cast<const int32_t *>(d + pN.off),
+                                               n_packets, reinterpret_cast<uint8_t *>(d + pOut.off), out_stride, reinterpret_cast<int32_t *>(d + pLen.off),
+                                               reinterpret_cast<int32_t *>(d + pDrop.off));
+    if (rc != LORAHIP_OK) return rc;
+    LORAHIP_TRY(hipMemcpyAsync(h + inBytes, d + inBytes, cur - inBytes, hipMemcpyDeviceToHost, ctx->stream));
+    LORAHIP_TRY(hipStreamSynchronize(ctx->stream));
+    std::memcpy(out, h + pOut.off, pOut.bytes);
+    std::memcpy(out_len, h + pLen.off, pLen.bytes);
+    std::memcpy(dropped, h + pDrop.off, pDrop.bytes);
+    return LORAHIP_OK;
+}
+
+int lorahip_decode_plan(const lorahip_decoder_cfg *cfgs, const size_t n_cfgs, const size_t sym_stride, lorahip_decode_tiling *plan)
+{
+    if (plan == nullptr || plan->struct_size != sizeof(lorahip_decode_tiling)) return LORAHIP_E_INVALID;
+    *plan = lorahip_decode_tiling();
+    plan->struct_size = sizeof(lorahip_decode_tiling);
+    { const int rc = decodeCfgsOk(cfgs, n_cfgs); if (rc != LORAHIP_OK) return rc; }
+    if (sym_stride == 0 || sym_stride > size_t(decodeMaxSymbols())) return LORAHIP_E_INVALID;
+    DecodeCfg tab[LORAHIP_DEC_MAX_CFGS];
+    for (size_t i = 0; i < n_cfgs; i++) tab[i] = decodeCfgOf(cfgs[i]);
+    const DecodeTiling t = decodePlan(tab, n_cfgs, int(sym_stride));
+    plan->lanes_per_packet = t.lanes; plan->sym_cap = t.symCap; plan->cw_cap = t.cwCap; plan->lds_slice_bytes = t.slice; plan->packets_per_workgroup = t.perBlock;
     return LORAHIP_OK;
 }
 

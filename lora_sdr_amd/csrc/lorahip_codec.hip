@@ -167,10 +167,40 @@ __device__ void diagonalDeinterleave(const unsigned short *symbols, const int nu
 
 } // namespace
 
-__global__ void __launch_bounds__(64) decodePackets(const DecodeArgs a)
+/*! The settings of a table launch (lorahip_decode_packets_cfgs), by value in the kernel arguments: packet p runs under e[i], i = index[p], or
+ * table[index[p]] with a table (a receiver: index = the channel the hand-off wrote, table = configuration of channel). An index[p] outside
+ * the table, or an i outside [0, nCfgs), is outcome -3: the packet is not looked at. The caps are the slice entry i needs (decodePlan). */
+struct DecodeCfgTable
 {
-    const unsigned p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= a.nPackets) return;
+    const int *index, *table;
+    int nTable, nCfgs;
+    DecodeCfg e[LORAHIP_DEC_MAX_CFGS];
+};
+
+//! packet p's entry of the table, -1 where there is none
+__device__ __forceinline__ int cfgIndexOf(const DecodeCfgTable &tab, const unsigned p)
+{
+    int i = tab.index[p];
+    if (tab.table != nullptr)
+    {
+        if (i < 0 || i >= tab.nTable) return -1;
+        i = tab.table[i];
+    }
+    return (i < 0 || i >= tab.nCfgs) ? -1 : i;
+}
+
+//! the rows of the launch with entry e as their settings: what the decoder bodies below read as `a`
+__device__ __forceinline__ DecodeArgs withCfg(const DecodeArgs &rows, const DecodeCfg &e)
+{
+    DecodeArgs a = rows;
+    a.sf = e.sf; a.ppm = e.ppm; a.rdd = e.rdd; a.crcc = e.crcc; a.interleaving = e.interleaving;
+    a.errorCheck = e.errorCheck; a.explicitHdr = e.explicitHdr; a.hdr = e.hdr; a.dataLength = e.dataLength;
+    return a;
+}
+
+//! packet p under the settings in `a`: launch-uniform scalars in decodePackets, the packet's own in decodePacketsCfgs
+__device__ __forceinline__ void decodeOnePacket(const DecodeArgs a, const unsigned p)
+{
     const int nsyms = a.nsyms[p];
     const unsigned short *in = a.syms + (size_t)p * a.symStride;
     unsigned char *out = a.out + (size_t)p * a.outStride;
@@ -307,6 +337,13 @@ __global__ void __launch_bounds__(64) decodePackets(const DecodeArgs a)
     a.dropped[p] = dropped;
 }
 
+__global__ void __launch_bounds__(64) decodePackets(const DecodeArgs a)
+{
+    const unsigned p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= a.nPackets) return;
+    decodeOnePacket(a, p);
+}
+
 
 /***********************************************************************
  * group-per-packet decoder
@@ -390,13 +427,17 @@ template <int G> __device__ __forceinline__ bool groupAny(const bool p)
  * any length the demodulator can produce decodes like the reference decodes it. */
 struct DecodeCaps { int symCap, cwCap; };
 
+/*! One packet per group of G lanes under the settings in `a` and the caps of THOSE settings; `slice` is the launch's distance between two
+ * groups' LDS (>= what the caps need). decodeGroup hands in its kernel arguments, so every setting is a launch-uniform scalar there;
+ * decodeGroupCfgs hands in the packet's own entry of the table, the same for every lane of a group (the lanes of a group share p): whatever
+ * is group-uniform below stays so, and no barrier stands under a condition (the `go` flag), so the 256 threads meet at every one of them
+ * whatever their packets' settings are. known = false (no such entry): the packet is reported as -3 and nothing of it is read or written. */
 template <int G>
-__global__ void __launch_bounds__(256) decodeGroup(const DecodeArgs a, const DecodeCaps caps, const int perBlock)
+__device__ __forceinline__ void decodeGroupBody(const DecodeArgs a, const DecodeCaps caps, const int slice, const int perBlock, const bool known)
 {
     // per packet: symCap Gray-coded symbols (u16), then the codewords (u8), then the nibbles (u8), 16-byte aligned slices
     extern __shared__ __attribute__((aligned(16))) unsigned char smemDec[];
     const int symCap = caps.symCap, cwCap = caps.cwCap;
-    const int slice = ((symCap * 2 + 2 * cwCap + 15) & ~15);
     const int g = threadIdx.x / G, t = threadIdx.x % G;
     unsigned short *sSym = reinterpret_cast<unsigned short *>(smemDec + (size_t)g * slice);
     unsigned char *sCw = smemDec + (size_t)g * slice + symCap * 2;
@@ -419,7 +460,7 @@ __global__ void __launch_bounds__(256) decodeGroup(const DecodeArgs a, const Dec
     const int symLoad = numSymbols < symCap ? numSymbols : symCap;                           // what of it this slice holds
     const int cwLoad = numCodewords + 4 < cwCap ? numCodewords + 4 : cwCap;
     // group-uniform early outs (:202 throws, :208 too short)
-    bool go = have && !(PPM > sf || nsyms < LORAHIP_N_HDR_SYMBOLS);
+    bool go = have && known && !(PPM > sf || nsyms < LORAHIP_N_HDR_SYMBOLS);
 
     // ---- Gray code with rounding to the symbol size (:218-222) --------------------------------------------------------
     if (go && !a.interleaving && nsyms > a.symStride) { outLen = -2; go = false; }           // every symbol is output: the row must hold them all
@@ -589,13 +630,19 @@ __global__ void __launch_bounds__(256) decodeGroup(const DecodeArgs a, const Dec
     }
     if (have && t == 0)
     {
-        a.outLen[p] = outLen;
+        a.outLen[p] = known ? outLen : -3;
         a.dropped[p] = dropped;
     }
 }
 
+template <int G>
+__global__ void __launch_bounds__(256) decodeGroup(const DecodeArgs a, const DecodeCaps caps, const int perBlock)
+{
+    decodeGroupBody<G>(a, caps, ((caps.symCap * 2 + 2 * caps.cwCap + 15) & ~15), perBlock, true);
+}
+
 //! the slice a configuration needs (see DecodeCaps): the symbols / codewords that can reach the output, or the whole row if that is less
-static DecodeCaps decodeCaps(const DecodeArgs &a)
+static DecodeCaps decodeCaps(const DecodeCfg &a, const int symStride)
 {
     const int PPM = a.ppm == 0 ? a.sf : a.ppm, bs = 4 + a.rdd;
     const long long bytesMax = a.explicitHdr ? 255 + 5 : (long long)a.dataLength + 2;
@@ -603,7 +650,7 @@ static DecodeCaps decodeCaps(const DecodeArgs &a)
     if (cEnd < PPM + 1) cEnd = PPM + 1;
     const long long nBlocks = (cEnd + PPM - 1) / PPM + 1;
     const long long symNeed = LORAHIP_N_HDR_SYMBOLS + nBlocks * bs;
-    const long long symRow = ((a.symStride + 7 + 8) / bs + 1) * bs + LORAHIP_N_HDR_SYMBOLS;       // the row, rounded up to whole blocks
+    const long long symRow = ((symStride + 7 + 8) / bs + 1) * bs + LORAHIP_N_HDR_SYMBOLS;         // the row, rounded up to whole blocks
     DecodeCaps c;
     c.symCap = int(symNeed < symRow ? symNeed : symRow);
     // codewords of those symbols (+ the 4 zero entries behind numCodewords the nibble loop may read, + nibble offsets)
@@ -611,21 +658,46 @@ static DecodeCaps decodeCaps(const DecodeArgs &a)
     return c;
 }
 
-template <int G>
-static hipError_t launchDecodeGroup(const DecodeArgs &a, const DecodeCaps &caps, hipStream_t stream)
+/* What a launch over rows of symStride symbols under these settings runs on -- the one place that decides it, for the uniform launch (one
+ * entry), the table launch and lorahip_decode_plan. Every entry gets the caps of ITS settings (its group lays out its slice with them); the
+ * launch has ONE lane count and ONE slice: the lanes by the largest symCap (n symbols make about n * PPM / (4 + rdd) codewords), the slice
+ * the largest entry's, and as many packets per workgroup as fit 160 KiB of LDS (0: not even one -- the entry points bound data_length, so
+ * this cannot happen). A table with one long entry therefore runs few packets per workgroup for ALL its packets. */
+DecodeTiling decodePlan(DecodeCfg *cfgs, const size_t nCfgs, const int symStride)
 {
-    const size_t slice = size_t((caps.symCap * 2 + 2 * caps.cwCap + 15) & ~15);
-    const size_t ldsMax = 160 * 1024;
-    unsigned perBlock = 256 / G;
-    if (slice > ldsMax) return hipErrorInvalidValue;                // (lorahip_decode_packets bounds data_length: cannot happen)
-    if (slice * perBlock > ldsMax) perBlock = unsigned(ldsMax / slice);
-    const size_t smem = slice * perBlock;
+    DecodeTiling t = { 0, 0, 0, 0, 0 };
+    for (size_t i = 0; i < nCfgs; i++)
+    {
+        const DecodeCaps c = decodeCaps(cfgs[i], symStride);
+        cfgs[i].symCap = c.symCap; cfgs[i].cwCap = c.cwCap;
+        const int slice = (c.symCap * 2 + 2 * c.cwCap + 15) & ~15;
+        t.symCap = c.symCap > t.symCap ? c.symCap : t.symCap;
+        t.cwCap = c.cwCap > t.cwCap ? c.cwCap : t.cwCap;
+        t.slice = slice > t.slice ? slice : t.slice;
+    }
+    t.lanes = t.symCap <= 48 ? 8 : t.symCap <= 96 ? 16 : t.symCap <= 200 ? 32 : 64;
+    const int ldsMax = 160 * 1024;
+    t.perBlock = 256 / t.lanes;
+    if (t.slice * t.perBlock > ldsMax) t.perBlock = ldsMax / t.slice;
+    return t;
+}
+
+static DecodeCfg cfgOf(const DecodeArgs &a)
+{
+    const DecodeCfg c = { a.sf, a.ppm, a.rdd, a.crcc, a.interleaving, a.errorCheck, a.explicitHdr, a.hdr, a.dataLength, 0, 0 };
+    return c;
+}
+
+template <int G>
+static hipError_t launchDecodeGroup(const DecodeArgs &a, const DecodeTiling &t, hipStream_t stream)
+{
+    const DecodeCaps caps = { t.symCap, t.cwCap };
     static unsigned long long attrDone = 0;
     {
-        const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(decodeGroup<G>), ldsMax, attrDone);
+        const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(decodeGroup<G>), 160 * 1024, attrDone);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((decodeGroup<G>), dim3((a.nPackets + perBlock - 1) / perBlock), dim3(256), smem, stream, a, caps, int(perBlock));
+    hipLaunchKernelGGL((decodeGroup<G>), dim3((a.nPackets + t.perBlock - 1) / t.perBlock), dim3(256), size_t(t.slice) * t.perBlock, stream, a, caps, t.perBlock);
     return hipGetLastError();
 }
 
@@ -637,12 +709,13 @@ hipError_t launchDecode(const DecodeArgs &a, const int variant, hipStream_t stre
         hipLaunchKernelGGL(decodePackets, dim3((a.nPackets + 63) / 64), dim3(64), 0, stream, a);
         return hipGetLastError();
     }
-    // lanes per packet by what a packet can need: n symbols make about n * PPM / (4 + rdd) codewords
-    const DecodeCaps caps = decodeCaps(a);
-    if (caps.symCap <= 48) return launchDecodeGroup<8>(a, caps, stream);
-    if (caps.symCap <= 96) return launchDecodeGroup<16>(a, caps, stream);
-    if (caps.symCap <= 200) return launchDecodeGroup<32>(a, caps, stream);
-    return launchDecodeGroup<64>(a, caps, stream);
+    DecodeCfg c = cfgOf(a);
+    const DecodeTiling t = decodePlan(&c, 1, a.symStride);
+    if (t.perBlock < 1) return hipErrorInvalidValue;                // (lorahip_decode_packets bounds data_length: cannot happen)
+    if (t.lanes == 8) return launchDecodeGroup<8>(a, t, stream);
+    if (t.lanes == 16) return launchDecodeGroup<16>(a, t, stream);
+    if (t.lanes == 32) return launchDecodeGroup<32>(a, t, stream);
+    return launchDecodeGroup<64>(a, t, stream);
 }
 
 /***********************************************************************
@@ -837,6 +910,81 @@ hipError_t launchEncode(const EncodeArgs &a, hipStream_t stream)
     if (rowSyms <= 96) return launchEncodeGroup<16>(a, caps, stream);
     if (rowSyms <= 200) return launchEncodeGroup<32>(a, caps, stream);
     return launchEncodeGroup<64>(a, caps, stream);
+}
+
+/***********************************************************************
+ * the decoder with the settings per packet (lorahip_decode_packets_cfgs): the kernels above over a table, and the hand-off's channel remap.
+ * Behind the uniform kernels on purpose: those stay the functions they were, in the order they were.
+ **********************************************************************/
+__global__ void __launch_bounds__(64) decodePacketsCfgs(const DecodeArgs rows, const DecodeCfgTable tab)
+{
+    const unsigned p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= rows.nPackets) return;
+    const int i = cfgIndexOf(tab, p);
+    if (i < 0) { rows.outLen[p] = -3; rows.dropped[p] = 0; return; }
+    decodeOnePacket(withCfg(rows, tab.e[i]), p);
+}
+
+
+template <int G>
+__global__ void __launch_bounds__(256) decodeGroupCfgs(const DecodeArgs rows, const DecodeCfgTable tab, const int slice, const int perBlock)
+{
+    const int g = threadIdx.x / G;
+    const unsigned p = blockIdx.x * perBlock + g;
+    const int i = (g < perBlock && p < rows.nPackets) ? cfgIndexOf(tab, p) : 0;     // (an idle group: any entry, it does nothing)
+    const DecodeCfg &e = tab.e[i < 0 ? 0 : i];
+    const DecodeCaps caps = { e.symCap, e.cwCap };
+    decodeGroupBody<G>(withCfg(rows, e), caps, slice, perBlock, i >= 0);
+}
+
+template <int G>
+static hipError_t launchDecodeGroupCfgs(const DecodeArgs &rows, const DecodeCfgTable &tab, const DecodeTiling &t, hipStream_t stream)
+{
+    static unsigned long long attrDone = 0;
+    {
+        const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(decodeGroupCfgs<G>), 160 * 1024, attrDone);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((decodeGroupCfgs<G>), dim3((rows.nPackets + t.perBlock - 1) / t.perBlock), dim3(256), size_t(t.slice) * t.perBlock, stream, rows, tab,
+                       t.slice, t.perBlock);
+    return hipGetLastError();
+}
+
+hipError_t launchDecodeCfgs(const DecodeArgs &rows, const DecodeCfg *cfgs, const size_t nCfgs, const int *index, const int *table, const int nTable,
+                            const int variant, hipStream_t stream)
+{
+    if (rows.nPackets == 0) return hipSuccess;
+    if (nCfgs == 0 || nCfgs > size_t(LORAHIP_DEC_MAX_CFGS)) return hipErrorInvalidValue;
+    DecodeCfgTable tab;
+    tab.index = index; tab.table = table; tab.nTable = nTable; tab.nCfgs = int(nCfgs);
+    for (size_t i = 0; i < size_t(LORAHIP_DEC_MAX_CFGS); i++) tab.e[i] = cfgs[i < nCfgs ? i : 0];      // (no entry of the argument block is left unset)
+    const DecodeTiling t = decodePlan(tab.e, nCfgs, rows.symStride);
+    if (variant == 1)
+    {
+        hipLaunchKernelGGL(decodePacketsCfgs, dim3((rows.nPackets + 63) / 64), dim3(64), 0, stream, rows, tab);
+        return hipGetLastError();
+    }
+    if (t.perBlock < 1) return hipErrorInvalidValue;                // (lorahip_decode_packets_cfgs bounds data_length: cannot happen)
+    if (t.lanes == 8) return launchDecodeGroupCfgs<8>(rows, tab, t, stream);
+    if (t.lanes == 16) return launchDecodeGroupCfgs<16>(rows, tab, t, stream);
+    if (t.lanes == 32) return launchDecodeGroupCfgs<32>(rows, tab, t, stream);
+    return launchDecodeGroupCfgs<64>(rows, tab, t, stream);
+}
+
+//! channel_dev[j] = globalOf[channel_dev[j]] for the n rows one part of a mixed handle packed (lorahip_rx.cpp: the hand-off speaks global channels)
+__global__ void __launch_bounds__(256) remapChannels(int *chan, const int *globalOf, const unsigned n, const int nLocal)
+{
+    const unsigned j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const int c = chan[j];
+    if (c >= 0 && c < nLocal) chan[j] = globalOf[c];
+}
+
+hipError_t launchRemapChannels(int *chan, const int *globalOf, const size_t n, const size_t nLocal, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(remapChannels, dim3(unsigned((n + 255) / 256)), dim3(256), 0, stream, chan, globalOf, unsigned(n), int(nLocal));
+    return hipGetLastError();
 }
 
 // rows: the de-whitening takes its length as a uint16_t in the reference (LoRaCodes.hpp: Sx1272ComputeWhiteningLfsr), i.e. messages of

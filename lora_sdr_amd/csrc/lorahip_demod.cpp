@@ -512,7 +512,7 @@ static int packetsToDevice(lorahip_demod *dm, uint16_t *syms_dev, const size_t s
                            const size_t cap_packets, size_t *n_packets, const bool sync)
 {
     if (dm == nullptr) return LORAHIP_E_INVALID;
-    if (dm->comp) { setLastError("packets on the device are per part (one decoder per SF): lorahip_demod_part_handle"); return LORAHIP_E_INVALID; }
+    if (dm->comp) return dm->comp->packetsToDevice(syms_dev, sym_stride, nsyms_dev, channel_dev, cap_packets, n_packets);   // (always complete on return)
     {
         // The records of the last streaming launch are still on the device and nothing else is queued: pack them there
         // (rows: channels ascending, time ascending inside a channel). A channel that entered the launch inside a packet found
@@ -566,6 +566,33 @@ int lorahip_demod_packets_to_device(lorahip_demod *dm, uint16_t *syms_dev, const
 {
     return packetsToDevice(dm, syms_dev, sym_stride, nsyms_dev, channel_dev, cap_packets, n_packets, true);
 }
+
+} // extern "C"
+
+namespace lorahip {
+int demodPacketsToDeviceQueued(lorahip_demod *dm, uint16_t *symsDev, const size_t symStride, int32_t *nsymsDev, int32_t *channelDev, const size_t capPackets,
+                               size_t *nPackets, const int32_t *globalOf, const size_t nLocal)
+{
+    if (dm == nullptr || dm->comp) return LORAHIP_E_INVALID;
+    size_t n = 0;
+    const int rc = packetsToDevice(dm, symsDev, symStride, nsymsDev, channelDev, capPackets, &n, false);
+    if (nPackets) *nPackets = n;
+    if (rc != LORAHIP_OK || n == 0 || channelDev == nullptr || globalOf == nullptr) return rc;
+    const DeviceGuard guard(dm->ctx->device);
+    LORAHIP_TRY(launchRemapChannels(channelDev, globalOf, n, nLocal, dm->ctx->stream));     // (behind the rows on the same stream, whichever path wrote them)
+    return LORAHIP_OK;
+}
+
+int demodStreamSync(lorahip_demod *dm)
+{
+    if (dm == nullptr || dm->comp) return LORAHIP_E_INVALID;
+    const DeviceGuard guard(dm->ctx->device);
+    LORAHIP_TRY(hipStreamSynchronize(dm->ctx->stream));
+    return LORAHIP_OK;
+}
+} // namespace lorahip
+
+extern "C" {
 
 /*! The signals of the run just made (an ordinary receiver step) into the registered signal rows from row `first` on: packed on the
  * device from the last launch's records while they are the only ones (the packets' device path), else from the host queue. Stream

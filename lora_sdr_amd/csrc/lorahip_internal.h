@@ -251,6 +251,17 @@ struct DecodeArgs
     int sf, ppm, rdd, crcc, interleaving, errorCheck, explicitHdr, hdr, dataLength;
 };
 hipError_t launchDecode(const DecodeArgs &a, int variant, hipStream_t stream);   // variant 1: the lane-per-packet checker
+//! one entry of a table launch: the nine settings of DecodeArgs, then the LDS caps decodePlan() works out for them
+struct DecodeCfg { int sf, ppm, rdd, crcc, interleaving, errorCheck, explicitHdr, hdr, dataLength, symCap, cwCap; };
+constexpr int LORAHIP_DEC_MAX_CFGS = 64;        // entries of a table: they travel by value in the kernel arguments (64 * 44 bytes)
+//! what a decoder launch runs on (lorahip_decode_plan): lanes per packet, the largest caps, the LDS slice of a group, packets per workgroup
+struct DecodeTiling { int lanes, symCap, cwCap, slice, perBlock; };
+DecodeTiling decodePlan(DecodeCfg *cfgs, size_t nCfgs, int symStride);          // fills every entry's caps; host only
+//! the rows of `rows` (its nine settings are not read), packet p under cfgs[index[p]] or cfgs[table[index[p]]]; outcome -3 without such an entry
+hipError_t launchDecodeCfgs(const DecodeArgs &rows, const DecodeCfg *cfgs, size_t nCfgs, const int *index, const int *table, int nTable,
+                            int variant, hipStream_t stream);
+//! chan[j] = globalOf[chan[j]], j < n (the packet hand-off of a mixed handle)
+hipError_t launchRemapChannels(int *chan, const int *globalOf, size_t n, size_t nLocal, hipStream_t stream);
 int decodeMaxSymbols();
 int decodeMaxDataLength();
 
@@ -380,6 +391,7 @@ public:
     int getPacket(size_t i, int32_t *channel, int64_t *round, size_t *len, int16_t *out, size_t cap) const;
     int getPackets(int32_t *channels, int64_t *rounds, int64_t *lens, size_t capPackets, int16_t *syms, size_t capSyms) const;
     int getSignals(int32_t *channels, int64_t *rounds, int32_t *errors, float *powers, float *snrs, size_t cap) const;
+    int packetsToDevice(uint16_t *symsDev, size_t symStride, int32_t *nsymsDev, int32_t *channelDev, size_t capPackets, size_t *nPackets);
     void clearPackets();
     int64_t consumed(size_t c) const; int consumedAll(int64_t *out) const;
     int64_t workCalls() const; double kernelMs() const; int lastLaunches() const; int nearThreshold(int64_t *sq, int64_t *st) const;
@@ -393,6 +405,13 @@ private:
     struct Impl;
     Impl *p;
 };
+
+//! a part's share of a mixed handle's packet hand-off (lorahip_demod.cpp): lorahip_demod_packets_to_device of the plain object `dm`, then
+//! channel_dev[j] = globalOf[channel_dev[j]] (globalOf: nLocal entries on the device) behind it on the object's stream. The device path
+//! returns with both queued, not waited for: demodStreamSync() ends it.
+int demodPacketsToDeviceQueued(lorahip_demod *dm, uint16_t *symsDev, size_t symStride, int32_t *nsymsDev, int32_t *channelDev, size_t capPackets,
+                               size_t *nPackets, const int32_t *globalOf, size_t nLocal);
+int demodStreamSync(lorahip_demod *dm);
 
 //! n host pieces -> device memory back to back from dDst, asynchronous on ctx->stream (pinned pieces by DMA straight away, the
 //! others through the context's double-buffered pinned staging); the caller synchronises the stream

@@ -7,7 +7,7 @@
 // its own level-2 context and HIP stream. Every part has a host thread that issues its runs, so the parts of one device overlap on
 // it and the devices run side by side. Nothing here touches the data path: a part's channels go through the very kernels a
 // single-SF object's would, and every accessor maps global channel numbers to (part, local channel).
-#include "lorahip_internal.h"
+#include "lorahip_own.h"
 #include <algorithm>
 #include <condition_variable>
 #include <cstring>
@@ -55,6 +55,7 @@ struct Composite::Impl
         lorahip_demod *d = nullptr;
         int device = 0, deviceSlot = 0, sf = 0;
         std::vector<uint32_t> chan;             // global channel numbers, ascending
+        DevBuf<int32_t> dGlobalOf;              // the same on the part's device, made by the first packet hand-off (packetsToDevice)
         PartWorker *w = nullptr;
     };
     std::vector<Part> parts;
@@ -75,6 +76,9 @@ struct Composite::Impl
                 if (p.w->th.joinable()) p.w->th.join();
                 delete p.w;
             }
+            // (only where a hand-off made the table: a part whose creation failed may name a device that does not exist, and a failed
+            // hipSetDevice would stay behind as this thread's last HIP error for the next launch to find)
+            if (p.dGlobalOf.get() != nullptr) { const DeviceGuard guard(p.device); p.dGlobalOf.reset(); }
             if (p.d) lorahip_demod_destroy(p.d);
         }
     }
@@ -319,6 +323,57 @@ int Composite::getSignals(int32_t *channels, int64_t *rounds, int32_t *errors, f
             at += n;
         }
         return LORAHIP_OK;
+    }
+    catch (const std::bad_alloc &) { setLastError("out of host memory"); return LORAHIP_E_NOMEM; }        // nothing may cross the C ABI
+}
+
+/* The queued packets of every part as the rows of ONE decoder launch (lorahip_decode_packets_cfgs, table = configuration of channel): the
+ * parts one after the other in the queue's order, each through the plain object's hand-off into its share of the rows -- packed on the
+ * device, on the part's own stream, where its records are still the only copy; from its host queue otherwise -- and renumbered there from
+ * local to global channels (the channels of one SF are not contiguous globally: a table per part, uploaded once). Nothing is waited for
+ * until every part's work is queued; the rows are complete on return. */
+int Composite::packetsToDevice(uint16_t *symsDev, const size_t symStride, int32_t *nsymsDev, int32_t *channelDev, const size_t capPackets, size_t *nPackets)
+{
+    Impl &I = *p;
+    for (const Impl::Part &q : I.parts)
+        if (q.device != I.parts[0].device)
+        {
+            setLastError("lorahip_demod_packets_to_device: the object spans several devices, and the rows of one decoder launch live on one device "
+                         "(per part: lorahip_demod_part_handle)");
+            return LORAHIP_E_INVALID;
+        }
+    const size_t total = numPackets();
+    if (nPackets) *nPackets = total;
+    if (total == 0) return LORAHIP_OK;
+    if (symsDev == nullptr || nsymsDev == nullptr || symStride == 0 || symStride > 0x7fffffffu || capPackets < total) return LORAHIP_E_INVALID;
+    const DeviceGuard guard(I.parts[0].device);
+    try
+    {
+    for (Impl::Part &q : I.parts)                       // (before anything is queued: a failure here leaves nothing in flight)
+        if (channelDev != nullptr && q.dGlobalOf.get() == nullptr)
+        {
+            const std::vector<int32_t> tab(q.chan.begin(), q.chan.end());
+            LORAHIP_TRY(q.dGlobalOf.grow(tab.size() * sizeof(int32_t)));
+            const hipError_t e = hipMemcpy(q.dGlobalOf.get(), tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+            if (e != hipSuccess) { q.dGlobalOf.reset(); return hipFail(e, "hipMemcpy (local-to-global channel table)"); }
+        }
+    size_t at = 0;
+    int rc = LORAHIP_OK;
+    std::vector<Impl::Part *> queued;
+    queued.reserve(I.parts.size());                     // (no allocation once work is in flight)
+    for (Impl::Part &q : I.parts)
+    {
+        const size_t n = lorahip_demod_num_packets(q.d);
+        if (n == 0) continue;
+        size_t got = 0;
+        rc = demodPacketsToDeviceQueued(q.d, symsDev + at * symStride, symStride, nsymsDev + at, channelDev ? channelDev + at : nullptr, n, &got,
+                                        q.dGlobalOf.get(), q.chan.size());
+        if (rc != LORAHIP_OK) break;
+        queued.push_back(&q);
+        at += n;
+    }
+    for (Impl::Part *q : queued) { const int src = demodStreamSync(q->d); if (rc == LORAHIP_OK) rc = src; }
+    return rc;
     }
     catch (const std::bad_alloc &) { setLastError("out of host memory"); return LORAHIP_E_NOMEM; }        // nothing may cross the C ABI
 }
