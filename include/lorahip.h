@@ -722,6 +722,52 @@ int lorahip_mod_frames_var(lorahip_ctx *ctx, float *iq_dev, size_t frame_stride,
                            const int32_t *nsyms_dev, size_t n_frames, size_t max_nsyms, unsigned char sync, float ampl, size_t padding);
 
 /* -------------------------------------------------------------------------------------
+ * The transmit side of a receiver over several SFs and coding rates (the mirror of lorahip_decode_packets_cfgs): the encoder with the
+ * configuration PER PACKET, and the modulator with SF, channel row and start sample PER FRAME.
+ *
+ * lorahip_encode_packets_cfgs: packet p is encoded under cfgs[i] exactly as lorahip_encode_packets encodes it under that configuration --
+ * the same symbols, the same nsyms (-1 and -2 included), the same zeros behind the packet up to sym_stride.
+ *   i = index_dev[p] with table_dev == NULL, else i = table_dev[index_dev[p]]. nsyms_dev[p] = -3 and an all-zero row where index_dev[p]
+ *       lies outside [0, n_table) or i outside [0, n_cfgs).
+ *   cfgs: n_cfgs = 1..64 entries in HOST memory, read before the call returns (they travel in the kernel's arguments: nothing is
+ *       allocated or uploaded). LORAHIP_E_INVALID with nothing launched: n_cfgs 0 or > 64, ANY entry that lorahip_encode_packets would
+ *       refuse (whether or not a packet uses it), index_dev NULL with n_packets > 0, table_dev set with n_table 0 (or n_table >
+ *       0x7fffffff), and the stride limits of lorahip_encode_packets. n_packets 0 is no work.
+ *   One launch has one lane count per packet and one LDS slice per packet, those of the entry that needs most over the rows of the launch;
+ *       each packet's group lays its slice out by its own entry.
+ * ------------------------------------------------------------------------------------- */
+int lorahip_encode_packets_cfgs(lorahip_ctx *ctx, const lorahip_encoder_cfg *cfgs, size_t n_cfgs, const int32_t *index_dev,
+                                const int32_t *table_dev, size_t n_table, const uint8_t *bytes_dev, size_t byte_stride,
+                                const int32_t *nbytes_dev, size_t n_packets, uint16_t *syms_dev, size_t sym_stride, int32_t *nsyms_dev);
+/* ... with every buffer (index and table too) in HOST memory, as lorahip_encode_packets_host; synchronous */
+int lorahip_encode_packets_cfgs_host(lorahip_ctx *ctx, const lorahip_encoder_cfg *cfgs, size_t n_cfgs, const int32_t *index,
+                                     const int32_t *table, size_t n_table, const uint8_t *bytes, size_t byte_stride, const int32_t *nbytes,
+                                     size_t n_packets, uint16_t *syms, size_t sym_stride, int32_t *nsyms);
+/* lorahip_mod_frames_sched: frame f is the BODY of the frame lorahip_mod_frames produces at SF sf_dev[f] for the first nsyms_dev[f] symbols
+ * at syms_dev + f*sym_stride -- everything before the zero padding: 10 up-chirps, 2 sync chirps, 2 1/4 down-chirps, the data chirps;
+ * lorahip_mod_body_len(sf, nsyms) = 14.25 N + nsyms N samples (0 outside SF 6..12) --, one float phase accumulator from 0
+ * (tests/modulator_def.py), amplitude ampl_dev[f] (ampl where ampl_dev is NULL), symbols as given (a symbol >= N is not masked). It is
+ * stored at samples [start_dev[f], start_dev[f] + body_len) of row row_dev[f] of iq_dev (n_rows rows of row_len complex64 samples, row_stride
+ * samples apart). NOTHING ELSE IS WRITTEN: the silence between the frames is the caller's. Every written sample is bit-identical to the one
+ * lorahip_mod_frames writes for the same symbols, SF, sync and amplitude. ctx supplies the device and the stream only (any SF).
+ *   status_dev[f] (may be NULL), checked in this order; a frame with a status != 0 writes nothing:
+ *        0  written
+ *       -1  nsyms_dev[f] < 1 or > sym_stride (the encoder's -1, -2 and -3 end here)
+ *       -3  sf_dev[f] outside 6..12, or row_dev[f] outside [0, n_rows)
+ *       -2  the body does not lie inside [0, row_len)
+ *   Frames of one launch MUST NOT OVERLAP: in an overlap every sample holds the value of one of the frames (not their sum), which one is
+ *       not defined. Not detected.
+ *   lanes: the lanes of a wavefront that share a frame -- 4, 16, 64, or 0 = chosen by n_frames; the samples do not
+ *       depend on it. With 4 / 16 the frames of a wavefront are neighbours in the order given and it runs as long as its longest frame.
+ *   LORAHIP_E_INVALID, nothing launched: a null pointer (status_dev and ampl_dev excepted) with n_frames > 0, row_len > row_stride,
+ *       sym_stride 0 or > lorahip_decode_max_symbols(), lanes not one of 0, 4, 16, 64, n_rows or n_frames > 0x7fffffff. */
+size_t lorahip_mod_body_len(int sf, size_t nsyms);
+int lorahip_mod_frames_sched(lorahip_ctx *ctx, float *iq_dev, size_t n_rows, size_t row_stride, size_t row_len,
+                             const uint16_t *syms_dev, size_t sym_stride, const int32_t *nsyms_dev, const int32_t *sf_dev,
+                             const int32_t *row_dev, const int64_t *start_dev, const float *ampl_dev, size_t n_frames,
+                             unsigned char sync, float ampl, int lanes, int32_t *status_dev);
+
+/* -------------------------------------------------------------------------------------
  * Front-end channeliser (the step before the path: SURVEY.md section 8f #4). NOT a reference component: the
  * reference's topologies put Pothos' /comms/rotate and a decimating FIR in front of every LoRaDemod block; this
  * does that for K channels of one wideband stream at once and writes the [channel][time] layout

@@ -289,6 +289,37 @@ class Context(_Handle):
                                            int(padding)), "lorahip_mod_frames")
         return iq
 
+    def mod_frames_sched(self, syms, nsyms, sf, row, start, out, ampl=1.0, ampl_of=None, sync=0x12, lanes=0):
+        """Frames of different SF into channel rows (lorahip_mod_frames_sched): frame f is the body -- preamble, sync, down-chirps and the
+        first nsyms[f] data chirps, lorahip_mod_body_len(sf[f], nsyms[f]) samples -- of the frame mod_frames makes at SF sf[f], written at
+        out[row[f], start[f]:start[f] + body]. Nothing else of `out` is touched; frames must not overlap.
+
+        syms: (F, stride) 16-bit, nsyms / sf / row: (F,) int32, start: (F,) int64, ampl_of: (F,) float32 or None (`ampl` for every frame) --
+        device tensors; out: a (n_rows, row_len) complex64 device tensor whose rows are contiguous (a row stride above row_len is fine).
+        lanes: 0 (by the frame count), 4, 16 or 64 lanes of a wavefront per frame. The context's own SF plays no part.
+        Returns status, (F,) int32: 0 written, -1 no usable symbol count, -2 the body does not fit the row, -3 no such SF or row."""
+        import torch
+        if syms.dim() != 2 or syms.dtype not in (torch.int16, torch.uint16):
+            raise ValueError("syms must be a (n_frames, stride) 16-bit integer device tensor")
+        F, S = int(syms.shape[0]), int(syms.shape[1])
+        for name, v, dt in (("nsyms", nsyms, torch.int32), ("sf", sf, torch.int32), ("row", row, torch.int32), ("start", start, torch.int64)):
+            if v.dtype != dt or v.numel() != F:
+                raise ValueError("%s must be a (n_frames,) %s device tensor" % (name, str(dt).replace("torch.", "")))
+        if ampl_of is not None and (ampl_of.dtype != torch.float32 or ampl_of.numel() != F):
+            raise ValueError("ampl_of must be a (n_frames,) float32 device tensor")
+        if out.dim() != 2 or out.dtype != torch.complex64 or (out.shape[1] > 1 and out.stride(1) != 1) or \
+                (out.shape[0] > 1 and out.stride(0) < out.shape[1]) or not out.is_cuda:
+            raise ValueError("out must be a (n_rows, row_len) complex64 device tensor with contiguous rows")
+        syms, nsyms, sf, row, start = syms.contiguous(), nsyms.contiguous(), sf.contiguous(), row.contiguous(), start.contiguous()
+        ampl_of = None if ampl_of is None else ampl_of.contiguous()
+        status = torch.empty(F, dtype=torch.int32, device=syms.device)
+        self.use_torch_stream()
+        row_stride = int(out.stride(0)) if out.shape[0] > 1 else int(out.shape[1])
+        check(self._lib.lorahip_mod_frames_sched(self._h, C.c_void_p(out.data_ptr()), int(out.shape[0]), row_stride, int(out.shape[1]), _dptr(syms), S,
+                                                 _dptr(nsyms), _dptr(sf), _dptr(row), _dptr(start), None if ampl_of is None else _dptr(ampl_of), F,
+                                                 int(sync) & 0xff, float(ampl), int(lanes), _dptr(status)), "lorahip_mod_frames_sched")
+        return status
+
     def add_awgn(self, iq, sigma, seed=0):
         """complex AWGN (per-component sigma) added in place to a complex64 device tensor"""
         self.use_torch_stream()
@@ -1751,6 +1782,152 @@ def transmit(payloads, sf=10, cr="4/8", sync=0x12, ampl=1.0, padding=1, sigma=0.
         if own:
             ctx.synchronize()                  # the context's tables must outlive the queued work
         return iq, nsyms
+    finally:
+        if own:
+            ctx.close()
+
+
+class LoRaEncoderSet:
+    """1..64 configured LoRaEncoder objects as ONE launch whose packets each pick their encoder (lorahip_encode_packets_cfgs): the
+    encoder of a transmitter over several SFs and coding rates, the mirror of LoRaDecoderSet. The configurations are copied at
+    construction (later setter calls on the encoders do not reach the set). Packet p is encoded exactly as encoders[i].encode_batch
+    would encode it, i = index[p], or table[index[p]] with a table; nsyms is -3 and the row zero where there is no such encoder."""
+
+    def __init__(self, encoders, device=0, ctx=None):
+        encoders = list(encoders)
+        if not 1 <= len(encoders) <= 64:
+            raise ValueError("LoRaEncoderSet: 1..64 encoders")
+        self._ctx = ctx if ctx is not None else Context(7, device=device)   # device + stream only
+        self._cfgs = (EncoderCfg * len(encoders))()
+        for i, e in enumerate(encoders):
+            C.memmove(C.byref(self._cfgs[i]), C.byref(e._cfg), C.sizeof(EncoderCfg))
+
+    def __len__(self):
+        return len(self._cfgs)
+
+    def _on(self, ctx):
+        """the same table launched through another context (its device and stream)"""
+        other = LoRaEncoderSet.__new__(LoRaEncoderSet)
+        other._ctx, other._cfgs = ctx, self._cfgs
+        return other
+
+    @property
+    def spread_factors(self):
+        """the SF of every member, in order"""
+        return [int(c.sf) for c in self._cfgs]
+
+    def num_symbols(self, i, n_bytes):
+        """symbols of a message of n_bytes bytes under member i (host arithmetic), as LoRaEncoder.num_symbols"""
+        return int(self._ctx._lib.lorahip_encode_num_symbols(C.byref(self._cfgs[int(i)]), int(n_bytes)))
+
+    def max_symbols(self, n_bytes):
+        """the largest num_symbols(i, n_bytes) over the members (at least 8): the symbol stride that holds any message of n_bytes bytes"""
+        return max(8, max(self.num_symbols(i, n_bytes) for i in range(len(self._cfgs))))
+
+    def encode_batch(self, data, nbytes, index, table=None, sym_stride=None):
+        """data: (P, stride) uint8, nbytes: (P,) int32, index: (P,) int32, table: (T,) int32 or None -- device tensors -> (syms
+        uint16-as-int16 (P, sym_stride), nsyms int32 (P,)) device tensors, queued on the torch stream. sym_stride defaults to what a
+        message of `stride` bytes needs under the member that makes most of it."""
+        import torch
+        if data.dim() != 2 or data.dtype != torch.uint8 or nbytes.dtype != torch.int32 or nbytes.numel() != data.shape[0]:
+            raise ValueError("data must be a (P, stride) uint8, nbytes a (P,) int32 device tensor")
+        P, stride = int(data.shape[0]), int(data.shape[1])
+        if index.dtype != torch.int32 or index.numel() != P or (table is not None and table.dtype != torch.int32):
+            raise ValueError("index must be (P,) int32, table (T,) int32 device tensors")
+        data, nbytes, index = data.contiguous(), nbytes.contiguous(), index.contiguous()
+        table = None if table is None else table.contiguous()
+        if sym_stride is None:
+            sym_stride = self.max_symbols(min(stride, self._ctx._lib.lorahip_encode_max_bytes()))
+        syms = torch.empty((P, int(sym_stride)), dtype=torch.int16, device=data.device)
+        nsyms = torch.empty(P, dtype=torch.int32, device=data.device)
+        self._ctx.use_torch_stream()
+        check(self._ctx._lib.lorahip_encode_packets_cfgs(self._ctx._h, self._cfgs, len(self._cfgs), _dptr(index),
+                                                         None if table is None else _dptr(table), 0 if table is None else int(table.numel()),
+                                                         C.c_void_p(data.data_ptr()), stride, _dptr(nbytes), P, _dptr(syms), int(sym_stride),
+                                                         _dptr(nsyms)), "lorahip_encode_packets_cfgs")
+        return syms, nsyms
+
+    def work(self, messages, index):
+        """list of bytes-like and the encoder of each -> list of uint16 symbol arrays (None where the block has no defined result), as
+        LoRaEncoder.work; raises where a message has no encoder (-3) or is longer than this build encodes (-2)"""
+        import torch
+        P = len(messages)
+        if len(index) != P:
+            raise ValueError("LoRaEncoderSet.work(): one index per message")
+        if P == 0:
+            return []
+        host, n = _pack_rows(messages)
+        idx = np.asarray(index, np.int64)
+        dev = torch.device("cuda", self._ctx.device)
+        syms, nsyms = self.encode_batch(torch.from_numpy(host).to(dev), torch.from_numpy(n).to(dev),
+                                        torch.from_numpy(np.clip(idx, -1, 2 ** 31 - 1).astype(np.int32)).to(dev))
+        syms, nsyms = syms.cpu().numpy().view(np.uint16), nsyms.cpu().numpy()
+        for i in range(P):
+            if nsyms[i] == -3:
+                raise ValueError("LoRaEncoderSet.work(): message %d names encoder %d of %d" % (i, int(idx[i]), len(self._cfgs)))
+            if nsyms[i] == -2:
+                raise ValueError("LoRaEncoderSet.work(): message %d is longer than this build encodes (lorahip_encode_max_bytes())" % i)
+        return [syms[i, :nsyms[i]].copy() if nsyms[i] >= 0 else None for i in range(P)]
+
+
+def _to_dev(x, dtype, dev):
+    """a device tensor of `dtype` from a device tensor, an array or a list"""
+    import torch
+    if _is_torch(x):
+        return x.to(device=dev, dtype=dtype)
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype=np.dtype(str(dtype).replace("torch.", "")))).to(dev)
+
+
+def transmit_mixed(payloads, encoders, index, row, start, n_rows, row_len, table=None, sync=0x12, ampl=1.0, sigma=0.0, seed=0, nbytes=None,
+                   out=None, ctx=None, device=0):
+    """bytes -> symbols -> IQ -> (noise) on the device for frames of DIFFERENT SF and coding rate placed in channel rows: ONE
+    LoRaEncoderSet.encode_batch -> ONE Context.mod_frames_sched -> Context.add_awgn, all queued on the torch stream with no host
+    synchronisation in between -- a downlink scheduler, or the load in front of a synthesiser or a mixed-SF receiver.
+
+    payloads: a list of bytes-like, or a (P, stride) uint8 device tensor with nbytes a (P,) int32 device tensor.
+    encoders: 1..64 LoRaEncoder objects, or a LoRaEncoderSet. Frame p is encoded by encoders[i], i = index[p] or table[index[p]], and
+    modulated at THAT encoder's SF (gathered on the device) into out[row[p], start[p]:start[p] + body] (lorahip_mod_body_len). index, row
+    (int32), start (int64) and table: device tensors, arrays or lists. Frames must not overlap; the rest of the rows is silence.
+    out: a contiguous (n_rows, row_len) complex64 device tensor to write into (it is zeroed first), or None to make one.
+    ctx: any Context to reuse (device and stream only; one is made and closed otherwise).
+    Returns (iq (n_rows, row_len) complex64, nsyms (P,) int32, status (P,) int32): status as Context.mod_frames_sched -- a message without
+    an encoder (nsyms -3) or refused by it (-1, -2) has status -1 and its slot stays silent."""
+    import torch
+    own = ctx is None
+    if own:
+        ctx = Context(7, device=device)
+    try:
+        dev = torch.device("cuda", ctx.device)
+        if not _is_torch(payloads):
+            host, n = _pack_rows(payloads)
+            payloads, nbytes = torch.from_numpy(host).to(dev), torch.from_numpy(n).to(dev)
+        elif nbytes is None:
+            raise ValueError("device payload rows need nbytes, a (P,) int32 device tensor")
+        encs = encoders._on(ctx) if isinstance(encoders, LoRaEncoderSet) else LoRaEncoderSet(encoders, ctx=ctx)
+        index, row, start = _to_dev(index, torch.int32, dev), _to_dev(row, torch.int32, dev), _to_dev(start, torch.int64, dev)
+        table = None if table is None else _to_dev(table, torch.int32, dev)
+        if out is None:
+            out = torch.zeros((int(n_rows), int(row_len)), dtype=torch.complex64, device=dev)
+        else:
+            if tuple(out.shape) != (int(n_rows), int(row_len)) or out.dtype != torch.complex64 or not out.is_contiguous():
+                raise ValueError("out must be a contiguous (n_rows, row_len) complex64 device tensor")
+            out.zero_()
+        stride = min(int(payloads.shape[1]), ctx._lib.lorahip_encode_max_bytes())
+        syms, nsyms = encs.encode_batch(payloads, nbytes, index, table=table, sym_stride=encs.max_symbols(stride))
+        # the SF of every frame: that of its encoder, 0 (no such SF) where it has none -- gathered on the device
+        sf_of = torch.tensor(encs.spread_factors, dtype=torch.int32, device=dev)
+        i = index.to(torch.int64)
+        if table is not None:
+            ok = (i >= 0) & (i < table.numel())
+            i = torch.where(ok, table.to(torch.int64)[i.clamp(0, table.numel() - 1)], torch.full_like(i, -1))
+        ok = (i >= 0) & (i < sf_of.numel())
+        sf = torch.where(ok, sf_of[i.clamp(0, sf_of.numel() - 1)], torch.zeros((), dtype=torch.int32, device=dev)).contiguous()
+        status = ctx.mod_frames_sched(syms, nsyms, sf, row, start, out, ampl=ampl, sync=sync)
+        if sigma:
+            ctx.add_awgn(out, sigma, seed)
+        if own:
+            ctx.synchronize()                  # the context must outlive the queued work
+        return out, nsyms, status
     finally:
         if own:
             ctx.close()

@@ -704,6 +704,112 @@ int lorahip_mod_frames_var(lorahip_ctx *ctx, float *iq_dev, const size_t frame_s
 }
 
 /***********************************************************************
+ * the transmit side with the settings per packet: the encoder over a table (lorahip_codec.hip: encodeGroupCfgs) and the scheduled
+ * modulator (lorahip_txsched.hip)
+ **********************************************************************/
+//! the argument checks of the encoder's table launch that need no device, in the order lorahip_decode_packets_cfgs makes its own
+static int encodeCfgsOk(const lorahip_encoder_cfg *cfgs, const size_t n_cfgs, const bool haveTable, const size_t n_table, const size_t byte_stride,
+                        const size_t sym_stride)
+{
+    if (cfgs == nullptr || n_cfgs == 0 || n_cfgs > size_t(LORAHIP_ENC_MAX_CFGS)) return LORAHIP_E_INVALID;
+    for (size_t i = 0; i < n_cfgs; i++)
+        if (!encoderCfgOk(cfgs + i)) return LORAHIP_E_INVALID;
+    if ((haveTable && n_table == 0) || n_table > 0x7fffffffu) return LORAHIP_E_INVALID;
+    if (byte_stride > size_t(lorahip_encode_max_bytes()) || sym_stride == 0 || sym_stride > size_t(decodeMaxSymbols())) return LORAHIP_E_INVALID;
+    return LORAHIP_OK;
+}
+
+int lorahip_encode_packets_cfgs(lorahip_ctx *ctx, const lorahip_encoder_cfg *cfgs, const size_t n_cfgs, const int32_t *index_dev,
+                                const int32_t *table_dev, const size_t n_table, const uint8_t *bytes_dev, const size_t byte_stride,
+                                const int32_t *nbytes_dev, const size_t n_packets, uint16_t *syms_dev, const size_t sym_stride,
+                                int32_t *nsyms_dev)
+{
+    if (ctx == nullptr) return LORAHIP_E_INVALID;
+    { const int rc = encodeCfgsOk(cfgs, n_cfgs, table_dev != nullptr, n_table, byte_stride, sym_stride); if (rc != LORAHIP_OK) return rc; }
+    if (n_packets == 0) return LORAHIP_OK;
+    if (!index_dev || (byte_stride && !bytes_dev) || !nbytes_dev || !syms_dev || !nsyms_dev || n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
+    EncodeCfg tab[LORAHIP_ENC_MAX_CFGS];
+    for (size_t i = 0; i < n_cfgs; i++)
+    {
+        const lorahip_encoder_cfg &c = cfgs[i];
+        const EncodeCfg e = { c.sf, c.ppm, c.rdd, c.explicit_hdr ? 1 : 0, c.crc ? 1 : 0, c.whitening ? 1 : 0, 0, 0 };
+        tab[i] = e;
+    }
+    const DeviceGuard guard(ctx->device);
+    EncodeArgs a = {};
+    a.bytes = bytes_dev; a.nbytes = nbytes_dev; a.syms = syms_dev; a.nsyms = nsyms_dev;
+    a.nPackets = unsigned(n_packets); a.byteStride = int(byte_stride); a.symStride = int(sym_stride);
+    LORAHIP_TRY(launchEncodeCfgs(a, tab, n_cfgs, index_dev, table_dev, int(n_table), ctx->stream));
+    return LORAHIP_OK;
+}
+
+int lorahip_encode_packets_cfgs_host(lorahip_ctx *ctx, const lorahip_encoder_cfg *cfgs, const size_t n_cfgs, const int32_t *index,
+                                     const int32_t *table, const size_t n_table, const uint8_t *bytes, const size_t byte_stride,
+                                     const int32_t *nbytes, const size_t n_packets, uint16_t *syms, const size_t sym_stride, int32_t *nsyms)
+{
+    if (ctx == nullptr) return LORAHIP_E_INVALID;
+    { const int rc = encodeCfgsOk(cfgs, n_cfgs, table != nullptr, n_table, byte_stride, sym_stride); if (rc != LORAHIP_OK) return rc; }
+    if (n_packets == 0) return LORAHIP_OK;
+    if (!index || (byte_stride && !bytes) || !nbytes || !syms || !nsyms || n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
+    const DeviceGuard guard(ctx->device);
+    struct Piece { size_t off, bytes; };
+    size_t cur = 0;
+    auto carve = [&cur](const size_t bytes) { Piece p = { cur, bytes }; cur += (bytes + 255) & ~size_t(255); return p; };
+    const Piece pByte = carve(n_packets * byte_stride);
+    const Piece pN = carve(n_packets * sizeof(int32_t));
+    const Piece pIdx = carve(n_packets * sizeof(int32_t));
+    const Piece pTab = carve(table ? n_table * sizeof(int32_t) : 0);
+    const size_t inBytes = cur;
+    const Piece pSym = carve(n_packets * sym_stride * sizeof(uint16_t));
+    const Piece pLen = carve(n_packets * sizeof(int32_t));
+    { const int rc = growStage(ctx, cur, cur); if (rc != LORAHIP_OK) return rc; }
+    char *d = ctx->dStage.get(), *h = ctx->hStage.get();
+    if (pByte.bytes) std::memcpy(h + pByte.off, bytes, pByte.bytes);
+    std::memcpy(h + pN.off, nbytes, pN.bytes);
+    std::memcpy(h + pIdx.off, index, pIdx.bytes);
+    if (table) std::memcpy(h + pTab.off, table, pTab.bytes);
+    LORAHIP_TRY(hipMemcpyAsync(d, h, inBytes, hipMemcpyHostToDevice, ctx->stream));
+    const int rc = lorahip_encode_packets_cfgs(ctx, cfgs, n_cfgs, reinterpret_cast<const int32_t *>(d + pIdx.off),
+                                               table ? reinterpret_cast<const int32_t *>(d + pTab.off) : nullptr, n_table,
+                                               reinterpret_cast<const uint8_t *>(d + pByte.off), byte_stride, reinterpret_cast<const int32_t *>(d + pN.off),
+                                               n_packets, reinterpret_cast<uint16_t *>(d + pSym.off), sym_stride, reinterpret_cast<int32_t *>(d + pLen.off));
+    if (rc != LORAHIP_OK) return rc;
+    LORAHIP_TRY(hipMemcpyAsync(h + inBytes, d + inBytes, cur - inBytes, hipMemcpyDeviceToHost, ctx->stream));
+    LORAHIP_TRY(hipStreamSynchronize(ctx->stream));
+    std::memcpy(syms, h + pSym.off, pSym.bytes);
+    std::memcpy(nsyms, h + pLen.off, pLen.bytes);
+    return LORAHIP_OK;
+}
+
+size_t lorahip_mod_body_len(const int sf, const size_t nsyms)
+{
+    if (sf < LORAHIP_SF_MIN || sf > LORAHIP_SF_MAX) return 0;
+    const size_t N = size_t(1) << sf;
+    return N * (10 + 2 + 2 + nsyms) + N / 4;
+}
+
+int lorahip_mod_frames_sched(lorahip_ctx *ctx, float *iq_dev, const size_t n_rows, const size_t row_stride, const size_t row_len,
+                             const uint16_t *syms_dev, const size_t sym_stride, const int32_t *nsyms_dev, const int32_t *sf_dev,
+                             const int32_t *row_dev, const int64_t *start_dev, const float *ampl_dev, const size_t n_frames,
+                             const unsigned char sync, const float ampl, const int lanes, int32_t *status_dev)
+{
+    if (ctx == nullptr || (lanes != 0 && lanes != 4 && lanes != 16 && lanes != 64)) return LORAHIP_E_INVALID;
+    if (row_len > row_stride || sym_stride == 0 || sym_stride > size_t(decodeMaxSymbols())) return LORAHIP_E_INVALID;
+    // (rows and samples are addressed with 64 bits on the device; the counts themselves are ints there)
+    if (n_rows > 0x7fffffffu || n_frames > 0x7fffffffu || row_stride > (size_t(1) << 62)) return LORAHIP_E_INVALID;
+    if (n_frames == 0) return LORAHIP_OK;
+    if (!iq_dev || !syms_dev || !nsyms_dev || !sf_dev || !row_dev || !start_dev) return LORAHIP_E_INVALID;
+    const DeviceGuard guard(ctx->device);
+    ModSchedArgs a;
+    a.iq = reinterpret_cast<float2 *>(iq_dev); a.rowStride = (long long)row_stride; a.rowLen = (long long)row_len; a.nRows = int(n_rows);
+    a.syms = syms_dev; a.symStride = int(sym_stride); a.nsyms = nsyms_dev; a.sf = sf_dev; a.row = row_dev;
+    a.start = reinterpret_cast<const long long *>(start_dev); a.amplOf = ampl_dev;
+    a.nFrames = unsigned(n_frames); a.sync = int(sync); a.ampl = ampl; a.status = status_dev;
+    LORAHIP_TRY(launchModFramesSched(a, lanes, ctx->stream));
+    return LORAHIP_OK;
+}
+
+/***********************************************************************
  * LoRaDetector<float> shim
  **********************************************************************/
 } // extern "C"

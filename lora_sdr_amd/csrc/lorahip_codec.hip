@@ -177,8 +177,9 @@ struct DecodeCfgTable
     DecodeCfg e[LORAHIP_DEC_MAX_CFGS];
 };
 
-//! packet p's entry of the table, -1 where there is none
-__device__ __forceinline__ int cfgIndexOf(const DecodeCfgTable &tab, const unsigned p)
+//! packet p's entry of the table (DecodeCfgTable, or the encoder's EncodeCfgTable below), -1 where there is none
+template <class Table>
+__device__ __forceinline__ int cfgIndexOf(const Table &tab, const unsigned p)
 {
     int i = tab.index[p];
     if (tab.table != nullptr)
@@ -746,12 +747,14 @@ struct EncodeCaps { int byteCap, cwCap; };
  * whitening from the sequence table (the encoder's Sx1272ComputeWhitening and the decoder's two registers give the same bytes: position
  * = codeword index behind the header codewords, in both blocks). Pass 3: a lane per output symbol -- bit m = bit k of codeword
  * (m + k) % PPM of its interleaver block, Gray -> binary, shift; lanes store consecutive symbols of the row, zeros behind the packet.
- * Pad nibbles (codewords behind the last byte, up to a whole block) are 0: the reference reads them past the end of its vector. */
+ * Pad nibbles (codewords behind the last byte, up to a whole block) are 0: the reference reads them past the end of its vector.
+ * encodeGroup hands in its kernel arguments (every setting a launch-uniform scalar); encodeGroupCfgs hands in the packet's own entry of its
+ * table with that entry's caps, and `slice`, the launch's distance between two groups' LDS. No barrier stands under a condition.
+ * known = false (no such entry): the row is zeroed and reported as -3, nothing of the packet is read. */
 template <int G>
-__global__ void __launch_bounds__(256) encodeGroup(const EncodeArgs a, const EncodeCaps caps, const int perBlock)
+__device__ __forceinline__ void encodeGroupBody(const EncodeArgs a, const EncodeCaps caps, const int slice, const int perBlock, const bool known)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smemEnc[];
-    const int slice = (caps.byteCap + caps.cwCap + 15) & ~15;
     const int g = threadIdx.x / G, t = threadIdx.x % G;
     unsigned char *sByte = smemEnc + (size_t)g * slice;
     unsigned char *sCw = sByte + caps.byteCap;
@@ -766,8 +769,8 @@ __global__ void __launch_bounds__(256) encodeGroup(const EncodeArgs a, const Enc
     const int PPM = a.ppm == 0 ? sf : a.ppm;                                                 // LoRaEncoder.cpp:165
     const int bs = 4 + a.rdd;
     const int hdrCw = a.explicitHdr ? LORAHIP_N_HDR_CODEWORDS : 0;
-    int outcome = -1;                                                                        // nothing defined (see lorahip.h)
-    bool go = have && len >= 0;
+    int outcome = known ? -1 : -3;                                                           // nothing defined / no such entry (see lorahip.h)
+    bool go = have && known && len >= 0;
     if (go && len > a.byteStride) { outcome = -2; go = false; }
     const int nb = go ? len + (a.crc ? 2 : 0) : 0;                                           // :171
     const int numCodewords = ((2 * nb + hdrCw + PPM - 1) / PPM) * PPM;                       // :175
@@ -858,6 +861,12 @@ __global__ void __launch_bounds__(256) encodeGroup(const EncodeArgs a, const Enc
         }
         if (t == 0) a.nsyms[p] = go ? numSymbols : outcome;
     }
+}
+
+template <int G>
+__global__ void __launch_bounds__(256) encodeGroup(const EncodeArgs a, const EncodeCaps caps, const int perBlock)
+{
+    encodeGroupBody<G>(a, caps, (caps.byteCap + caps.cwCap + 15) & ~15, perBlock, true);
 }
 
 //! symbols of a packet of n payload bytes (LoRaEncoder.cpp:171-176); -1 where the reference's own expression wraps
@@ -985,6 +994,85 @@ hipError_t launchRemapChannels(int *chan, const int *globalOf, const size_t n, c
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(remapChannels, dim3(unsigned((n + 255) / 256)), dim3(256), 0, stream, chan, globalOf, unsigned(n), int(nLocal));
     return hipGetLastError();
+}
+
+/***********************************************************************
+ * the encoder with the settings per packet (lorahip_encode_packets_cfgs): encodeGroupBody over a table, as decodeGroupCfgs runs
+ * decodeGroupBody. Behind the uniform kernels on purpose: those stay the functions they were, in the order they were.
+ **********************************************************************/
+/*! The settings of a table launch, by value in the kernel arguments: packet p runs under e[i], i = index[p] or table[index[p]] (cfgIndexOf);
+ * without such an entry the outcome is -3 and the row is zeroed. The caps are the slice entry i needs over the rows of the launch. */
+struct EncodeCfgTable
+{
+    const int *index, *table;
+    int nTable, nCfgs;
+    EncodeCfg e[LORAHIP_ENC_MAX_CFGS];
+};
+
+//! the rows of the launch with entry e as their settings: what encodeGroupBody reads as `a`
+__device__ __forceinline__ EncodeArgs withCfg(const EncodeArgs &rows, const EncodeCfg &e)
+{
+    EncodeArgs a = rows;
+    a.sf = e.sf; a.ppm = e.ppm; a.rdd = e.rdd; a.explicitHdr = e.explicitHdr; a.crc = e.crc; a.whitening = e.whitening;
+    return a;
+}
+
+template <int G>
+__global__ void __launch_bounds__(256) encodeGroupCfgs(const EncodeArgs rows, const EncodeCfgTable tab, const int slice, const int perBlock)
+{
+    const int g = threadIdx.x / G;
+    const unsigned p = blockIdx.x * perBlock + g;
+    const int i = (g < perBlock && p < rows.nPackets) ? cfgIndexOf(tab, p) : 0;     // (an idle group: any entry, it does nothing)
+    const EncodeCfg &e = tab.e[i < 0 ? 0 : i];
+    const EncodeCaps caps = { e.byteCap, e.cwCap };
+    encodeGroupBody<G>(withCfg(rows, e), caps, slice, perBlock, i >= 0);
+}
+
+template <int G>
+static hipError_t launchEncodeGroupCfgs(const EncodeArgs &rows, const EncodeCfgTable &tab, const size_t slice, hipStream_t stream)
+{
+    const size_t ldsMax = 160 * 1024;
+    unsigned perBlock = 256 / G;
+    if (slice > ldsMax) return hipErrorInvalidValue;                // (lorahip_encode_packets_cfgs bounds byte_stride: cannot happen)
+    if (slice * perBlock > ldsMax) perBlock = unsigned(ldsMax / slice);
+    static unsigned long long attrDone = 0;
+    {
+        const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(encodeGroupCfgs<G>), ldsMax, attrDone);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((encodeGroupCfgs<G>), dim3((rows.nPackets + perBlock - 1) / perBlock), dim3(256), slice * perBlock, stream, rows, tab, int(slice),
+                       int(perBlock));
+    return hipGetLastError();
+}
+
+/* Every entry gets the caps of ITS settings over the rows of the launch (encodeCaps: its group lays out its slice with them); the launch has
+ * ONE lane count and ONE slice, those of the entry that needs most -- the lane count by launchEncode's rule on that entry's row symbols. */
+hipError_t launchEncodeCfgs(const EncodeArgs &rows, const EncodeCfg *cfgs, const size_t nCfgs, const int *index, const int *table, const int nTable,
+                            hipStream_t stream)
+{
+    if (rows.nPackets == 0) return hipSuccess;
+    if (nCfgs == 0 || nCfgs > size_t(LORAHIP_ENC_MAX_CFGS)) return hipErrorInvalidValue;
+    EncodeCfgTable tab;
+    tab.index = index; tab.table = table; tab.nTable = nTable; tab.nCfgs = int(nCfgs);
+    long rowSyms = 0;
+    size_t slice = 0;
+    for (size_t i = 0; i < size_t(LORAHIP_ENC_MAX_CFGS); i++)       // (no entry of the argument block is left unset)
+    {
+        EncodeCfg &e = tab.e[i];
+        e = cfgs[i < nCfgs ? i : 0];
+        EncodeArgs a = rows;
+        a.sf = e.sf; a.ppm = e.ppm; a.rdd = e.rdd; a.explicitHdr = e.explicitHdr; a.crc = e.crc; a.whitening = e.whitening;
+        const EncodeCaps caps = encodeCaps(a);
+        e.byteCap = caps.byteCap; e.cwCap = caps.cwCap;
+        const long bySyms = caps.cwCap == 0 ? 0 : LORAHIP_N_HDR_SYMBOLS + (caps.cwCap / (e.ppm == 0 ? e.sf : e.ppm) - 1) * (4 + e.rdd);
+        rowSyms = bySyms > rowSyms ? bySyms : rowSyms;
+        const size_t s = size_t((caps.byteCap + caps.cwCap + 15) & ~15);
+        slice = s > slice ? s : slice;
+    }
+    if (rowSyms <= 48) return launchEncodeGroupCfgs<8>(rows, tab, slice, stream);
+    if (rowSyms <= 96) return launchEncodeGroupCfgs<16>(rows, tab, slice, stream);
+    if (rowSyms <= 200) return launchEncodeGroupCfgs<32>(rows, tab, slice, stream);
+    return launchEncodeGroupCfgs<64>(rows, tab, slice, stream);
 }
 
 // rows: the de-whitening takes its length as a uint16_t in the reference (LoRaCodes.hpp: Sx1272ComputeWhiteningLfsr), i.e. messages of

@@ -278,6 +278,12 @@ struct EncodeArgs
 };
 hipError_t launchEncode(const EncodeArgs &a, hipStream_t stream);
 long encodeNumSymbols(int sf, int ppm, int rdd, int explicitHdr, int crc, size_t nBytes);
+//! one entry of an encoder table launch: the six settings of EncodeArgs, then the LDS caps launchEncodeCfgs works out for them
+struct EncodeCfg { int sf, ppm, rdd, explicitHdr, crc, whitening, byteCap, cwCap; };
+constexpr int LORAHIP_ENC_MAX_CFGS = 64;        // entries of a table: they travel by value in the kernel arguments (64 * 32 bytes)
+//! the rows of `rows` (its six settings are not read), packet p under cfgs[index[p]] or cfgs[table[index[p]]]; outcome -3 without such an entry
+hipError_t launchEncodeCfgs(const EncodeArgs &rows, const EncodeCfg *cfgs, size_t nCfgs, const int *index, const int *table, int nTable,
+                            hipStream_t stream);
 
 //! launchers (lorahip_kernels.hip / lorahip_fast.hip)
 hipError_t launchDetect(int sf, int variant, const DetectArgs &a, const FastTables &ft, hipStream_t stream);
@@ -319,6 +325,25 @@ hipError_t launchModFrames(float2 *iq, long long frameStride, const unsigned sho
 //! per-frame symbol counts read on the device (lorahip_tx.hip); every frame is walked to the length of maxNsyms symbols
 hipError_t launchModFramesVar(float2 *iq, long long frameStride, const unsigned short *syms, long long symStride, const int *nsyms,
                               size_t nFrames, int maxNsyms, int sync, float ampl, int padding, int sf, hipStream_t stream);
+//! argument block of the scheduled modulator (lorahip_txsched.hip); device pointers, one entry per frame
+struct ModSchedArgs
+{
+    float2 *iq;                     // [nRows][rowStride], written only inside the frames' bodies
+    long long rowStride, rowLen;
+    int nRows;
+    const unsigned short *syms;     // [nFrames][symStride]
+    int symStride;
+    const int *nsyms, *sf, *row;    // [nFrames]
+    const long long *start;         // [nFrames]
+    const float *amplOf;            // [nFrames] or nullptr: `ampl` for every frame
+    unsigned nFrames;
+    int sync;
+    float ampl;
+    int *status;                    // [nFrames] or nullptr
+};
+//! lanes per frame: 4, 16 or 64, or 0 for modSchedLanes(nFrames)
+hipError_t launchModFramesSched(const ModSchedArgs &a, int lanes, hipStream_t stream);
+int modSchedLanes(size_t nFrames);
 hipError_t launchAwgn(float2 *iq, size_t n, float sigma, unsigned long long seed, hipStream_t stream);
 hipError_t launchMembw(const float2 *iq, size_t nBytes, int pattern, int blocks, float *scratch, hipStream_t stream);
 
