@@ -612,7 +612,7 @@ typedef struct lorahip_decoder_cfg {
     size_t struct_size;     /* = sizeof(lorahip_decoder_cfg) */
     int32_t sf;             /* setSpreadFactor      default 10 */
     int32_t ppm;            /* setSymbolSize        default 0 = sf */
-    int32_t rdd;            /* setCodingRate        default 4 ("4/8") */
+    int32_t rdd;            /* setCodingRate        default 4 ("4/8"); LORAHIP_RDD_FROM_HEADER (-1): each packet's header names it (below) */
     int32_t crcc;           /* enableCrcc           default 0 */
     int32_t interleaving;   /* enableInterleaving   default 1 */
     int32_t error_check;    /* enableErrorCheck     default 0 */
@@ -650,6 +650,57 @@ int lorahip_decode_packets_cfgs(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfg
 int lorahip_decode_packets_cfgs_host(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfgs, size_t n_cfgs, const int32_t *index,
                                      const int32_t *table, size_t n_table, const uint16_t *syms, size_t sym_stride, const int32_t *nsyms,
                                      size_t n_packets, uint8_t *out, size_t out_stride, int32_t *out_len, int32_t *dropped);
+/* The CODING RATE FROM THE HEADER: rdd = LORAHIP_RDD_FROM_HEADER in a lorahip_decoder_cfg (one entry per SF is then enough for a gateway).
+ * The reference de-interleaves and de-whitens a message at the rate of its SETTER and reads the header's rate field only for the Hamming
+ * step (LoRaDecoder.cpp:228-255, :296): a packet sent at another rate comes out as garbage. Under an entry with rdd = -1, packet p gives
+ * exactly what lorahip_decode_packets gives it under the same entry with rdd = r -- every byte of the output row, out_len (-1 and -2
+ * included, by the row rule and the plan of rate r), dropped, and the bytes left untouched behind out_len -- where
+ *       r = ((decodeHamming84sx(cw2) & 0xf) >> 1) & 7,
+ * cw2 = codeword 2 of the first interleaver block: de-interleaved at 4/8 from the first 8 Gray-coded symbols, not whitened -- the same
+ * bits at every configured rate, which is why the header block is sent that way. r > 4: out_len = -1, dropped = 1, nothing written (what
+ * every setting gives such a header, :293 / :297). Fewer than 8 symbols, PPM > sf: as before. Accepted only with explicit_hdr = 1 and
+ * interleaving = 1; anything else with rdd = -1, and rdd < -1, is LORAHIP_E_INVALID in every entry point below and above, nothing
+ * launched. A table may hold such entries beside any others. lorahip_decode_plan: sym_cap, cw_cap and lds_slice_bytes of a header-rate
+ * entry are each the largest of the same entry's at rdd = 0..4.
+ * (The lane-per-packet checker -- lorahip_set_variant 1 -- keeps its own, stricter row rule: -2 for every packet longer than its row or
+ * than 520 symbols, at every rate, so also for a rate field of 5..7. One corner stays the definition's and not "the uniform launch's": a
+ * packet of 517..519 symbols with a field of 5..7 is -1 / dropped, where the checker's uniform launch rounds it past 520 symbols -- -2 --
+ * at 4/6 (519 symbols: and at 4/7) only.) */
+#define LORAHIP_RDD_FROM_HEADER (-1)
+/* The HEADER REPORT of a packet: what the decoder learns from the header and the checksum and the outputs above do not show (a packet
+ * forwarder's codr / size / stat). It never changes out, out_len or dropped. Written by lorahip_decode_packets_info for EVERY packet:
+ *   "header not reached" -- out_len = -3, fewer than 8 symbols, PPM > sf, interleaving off, and (checker kernel only) its own -2 --:
+ *       length = rdd = hdr_residue = need_syms = -1, crc = fec_error = 0.
+ *   explicit header: length, rdd and hdr_residue are the decoded header's as soon as it is read (:283-291), also where the packet is then
+ *       dropped by the error check (:293), for a rate field > 4 (:297) or for a row shorter than the length (:313).
+ *   need_syms is set once the decode has passed :313 (the message holds the announced bytes by count) -- so for every out_len >= 0, for
+ *       -2, and for packets dropped later --, else -1.
+ *   crc is set where the reference computes the checksum (:367-388): with a header whenever the header's crc flag is set (crcc only
+ *       decides whether a mismatch drops), without a header only with crcc = 1; a decode that ended before leaves 0.
+ *   fec_error is the reference's `error` flag at the statement where this packet's decode ended: header codewords only for a packet
+ *       that ended in the header stage, header + first block + the codewords of the announced bytes otherwise. */
+typedef struct lorahip_packet_info {   /* 32 bytes */
+    int32_t length;       /* announced payload bytes: header byte 0 (explicit), data_length (implicit); -1: the header was not reached */
+    int32_t rdd;          /* the header's rate field 0..7, also where it is > 4 and the packet is dropped; the entry's rdd without a header; -1 not reached */
+    int32_t crc;          /* 1 checksum carried and equal, -1 carried and different, 0 none evaluated (none carried / not enabled / decode ended before) */
+    int32_t hdr_residue;  /* header byte 2 after LoRaDecoder.cpp:291 (0 = the header's checksum agrees), -1 without an explicit header or not reached */
+    int32_t fec_error;    /* the reference's `error` flag where the decode of this packet ended (0 / 1) */
+    int32_t need_syms;    /* symbols the announced length needs (whole interleaver blocks, the kernel's needSyms); also set when out_len = -2; -1 not known */
+    int32_t reserved[2];  /* 0 */
+} lorahip_packet_info;
+/* lorahip_decode_packets_cfgs with the report: info_dev[n_packets], or NULL for none (then exactly lorahip_decode_packets_cfgs).
+ * index_dev may be NULL only with n_cfgs == 1 and table_dev == NULL: every packet runs under entry 0 -- the uniform launch of
+ * lorahip_decode_packets; with more entries a NULL index_dev is LORAHIP_E_INVALID. Everything else as lorahip_decode_packets_cfgs. The
+ * other decoder entry points forward to this one. */
+int lorahip_decode_packets_info(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfgs, size_t n_cfgs, const int32_t *index_dev,
+                                const int32_t *table_dev, size_t n_table, const uint16_t *syms_dev, size_t sym_stride,
+                                const int32_t *nsyms_dev, size_t n_packets, uint8_t *out_dev, size_t out_stride, int32_t *out_len_dev,
+                                int32_t *dropped_dev, lorahip_packet_info *info_dev);
+/* ... with every buffer in HOST memory, as lorahip_decode_packets_cfgs_host; synchronous */
+int lorahip_decode_packets_info_host(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfgs, size_t n_cfgs, const int32_t *index,
+                                     const int32_t *table, size_t n_table, const uint16_t *syms, size_t sym_stride, const int32_t *nsyms,
+                                     size_t n_packets, uint8_t *out, size_t out_stride, int32_t *out_len, int32_t *dropped,
+                                     lorahip_packet_info *info);
 /* What a launch over rows of sym_stride symbols under these configurations runs on (host only, no device touched; the launches call the
  * same function): a packet's symbols, codewords and nibbles live in an LDS slice of its lane group, sized by what the configuration can
  * need -- (sym_cap * 2 + 2 * cw_cap + 15) & ~15 bytes; lanes_per_packet is 8 / 16 / 32 / 64 for the largest sym_cap <= 48 / <= 96 / <= 200 /

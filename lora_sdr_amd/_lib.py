@@ -40,6 +40,14 @@ class DecoderCfg(C.Structure):
                                                                           "explicit_hdr", "hdr", "data_length")]
 
 
+RDD_FROM_HEADER = -1      # LORAHIP_RDD_FROM_HEADER: DecoderCfg.rdd, the coding rate each packet's explicit header names
+
+
+class PacketInfo(C.Structure):
+    """struct lorahip_packet_info (32 bytes): the header report of one packet"""
+    _fields_ = [(n, C.c_int32) for n in ("length", "rdd", "crc", "hdr_residue", "fec_error", "need_syms")] + [("reserved", C.c_int32 * 2)]
+
+
 class EncoderCfg(C.Structure):
     """struct lorahip_encoder_cfg"""
     _fields_ = [("struct_size", C.c_size_t)] + [(n, C.c_int32) for n in ("sf", "ppm", "rdd", "explicit_hdr", "crc", "whitening")]
@@ -172,6 +180,10 @@ SIGNATURES = {
                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "lorahip_decode_packets_cfgs_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                                   C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "lorahip_decode_packets_info": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                             C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lorahip_decode_packets_info_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                  C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lorahip_decode_plan": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
     "lorahip_decode_max_symbols": (C.c_int, []),
     "lorahip_decode_max_data_length": (C.c_int, []),

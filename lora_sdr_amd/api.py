@@ -1509,7 +1509,7 @@ class LoRaDecoder:
     work(packets): list of int16/uint16 symbol arrays (what LoRaDemod posts) -> list of bytes arrays (None where the
     block posts nothing); decode_batch(): the same on device tensors."""
 
-    _CR = {"4/4": 0, "4/5": 1, "4/6": 2, "4/7": 3, "4/8": 4}
+    _CR = {"4/4": 0, "4/5": 1, "4/6": 2, "4/7": 3, "4/8": 4}      # the block's five strings (shared with LoRaEncoder)
 
     def __init__(self, device=0):
         self._ctx = Context(7, device=device)             # device + stream only; the decoder has its own sf
@@ -1525,6 +1525,11 @@ class LoRaDecoder:
     def setSymbolSize(self, ppm): self._cfg.ppm = int(ppm)
 
     def setCodingRate(self, cr):
+        """one of the block's five strings, or "header" (the decoder only, not the block's): each packet at the rate its own explicit
+        header names (LORAHIP_RDD_FROM_HEADER)"""
+        if cr == "header":
+            self._cfg.rdd = _lib.RDD_FROM_HEADER
+            return
         if cr not in self._CR:
             raise ValueError("LoRaDecoder::setCodingRate(%s): unknown coding rate" % cr)   # InvalidArgumentException :150
         self._cfg.rdd = self._CR[cr]
@@ -1539,9 +1544,10 @@ class LoRaDecoder:
     def getDropped(self): return self._dropped
     def activate(self): self._dropped = 0
 
-    def decode_batch(self, syms, nsyms):
+    def decode_batch(self, syms, nsyms, info=False):
         """syms: (P, stride) int16/uint16 device tensor, nsyms: (P,) int32 device tensor ->
-        (out uint8 (P, out_stride), out_len int32 (P,), dropped int32 (P,)) device tensors"""
+        (out uint8 (P, out_stride), out_len int32 (P,), dropped int32 (P,)) device tensors; info=True: a fourth, (P, 8) int32 -- the
+        header report, a row per packet with the fields of struct lorahip_packet_info in include/lorahip.h"""
         import torch
         if syms.dim() != 2 or syms.dtype not in (torch.int16, torch.uint16) or nsyms.dtype != torch.int32:
             raise ValueError("syms must be (P, stride) 16-bit, nsyms (P,) int32 device tensors")
@@ -1552,6 +1558,12 @@ class LoRaDecoder:
         out_len = torch.empty(P, dtype=torch.int32, device=syms.device)
         dropped = torch.empty(P, dtype=torch.int32, device=syms.device)
         self._ctx.use_torch_stream()
+        if info:
+            rep = torch.empty((P, 8), dtype=torch.int32, device=syms.device)
+            check(self._ctx._lib.lorahip_decode_packets_info(self._ctx._h, C.byref(self._cfg), 1, None, None, 0, _dptr(syms), stride, _dptr(nsyms), P,
+                                                             _dptr(out), out_stride, _dptr(out_len), _dptr(dropped), _dptr(rep)),
+                  "lorahip_decode_packets_info")
+            return out, out_len, dropped, rep
         check(self._ctx._lib.lorahip_decode_packets(self._ctx._h, C.byref(self._cfg), _dptr(syms), stride, _dptr(nsyms), P,
                                                     _dptr(out), out_stride, _dptr(out_len), _dptr(dropped)), "lorahip_decode_packets")
         return out, out_len, dropped
@@ -1619,9 +1631,10 @@ class LoRaDecoderSet:
     def getDropped(self): return self._dropped
     def activate(self): self._dropped = 0
 
-    def decode_batch(self, syms, nsyms, index, table=None):
+    def decode_batch(self, syms, nsyms, index, table=None, info=False):
         """syms: (P, stride) int16/uint16, nsyms: (P,) int32, index: (P,) int32, table: (T,) int32 or None -- device tensors ->
-        (out uint8 (P, out_stride), out_len int32 (P,), dropped int32 (P,)) device tensors, as LoRaDecoder.decode_batch"""
+        (out uint8 (P, out_stride), out_len int32 (P,), dropped int32 (P,)) device tensors, as LoRaDecoder.decode_batch (info=True: and the
+        (P, 8) int32 header report)"""
         import torch
         if syms.dim() != 2 or syms.dtype not in (torch.int16, torch.uint16) or nsyms.dtype != torch.int32:
             raise ValueError("syms must be (P, stride) 16-bit, nsyms (P,) int32 device tensors")
@@ -1635,6 +1648,13 @@ class LoRaDecoderSet:
         out_len = torch.empty(P, dtype=torch.int32, device=syms.device)
         dropped = torch.empty(P, dtype=torch.int32, device=syms.device)
         self._ctx.use_torch_stream()
+        if info:
+            rep = torch.empty((P, 8), dtype=torch.int32, device=syms.device)
+            check(self._ctx._lib.lorahip_decode_packets_info(self._ctx._h, self._cfgs, len(self._cfgs), _dptr(index),
+                                                             None if table is None else _dptr(table), 0 if table is None else int(table.numel()),
+                                                             _dptr(syms), stride, _dptr(nsyms), P, _dptr(out), out_stride, _dptr(out_len), _dptr(dropped),
+                                                             _dptr(rep)), "lorahip_decode_packets_info")
+            return out, out_len, dropped, rep
         check(self._ctx._lib.lorahip_decode_packets_cfgs(self._ctx._h, self._cfgs, len(self._cfgs), _dptr(index),
                                                          None if table is None else _dptr(table), 0 if table is None else int(table.numel()),
                                                          _dptr(syms), stride, _dptr(nsyms), P, _dptr(out), out_stride, _dptr(out_len), _dptr(dropped)),

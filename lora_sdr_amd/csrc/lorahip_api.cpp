@@ -439,7 +439,13 @@ int lorahip_add_awgn(lorahip_ctx *ctx, float *iq_dev, const size_t n_samples, co
 static int decoderCfgOk(const lorahip_decoder_cfg *cfg)
 {
     if (cfg->struct_size != sizeof(lorahip_decoder_cfg)) return LORAHIP_E_INVALID;
-    if (cfg->sf < 1 || cfg->sf > LORAHIP_SF_MAX || cfg->ppm < 0 || cfg->ppm > cfg->sf || cfg->rdd < 0 || cfg->rdd > 4 || cfg->data_length < 0) return LORAHIP_E_INVALID;
+    if (cfg->sf < 1 || cfg->sf > LORAHIP_SF_MAX || cfg->ppm < 0 || cfg->ppm > cfg->sf || cfg->rdd < LORAHIP_RDD_FROM_HEADER || cfg->rdd > 4 || cfg->data_length < 0) return LORAHIP_E_INVALID;
+    // the rate from the header: there has to be one, and the de-interleaver that reaches it
+    if (cfg->rdd == LORAHIP_RDD_FROM_HEADER && !(cfg->explicit_hdr && cfg->interleaving))
+    {
+        setLastError("rdd = LORAHIP_RDD_FROM_HEADER needs explicit_hdr = 1 and interleaving = 1");
+        return LORAHIP_E_INVALID;
+    }
     // An explicit header occupies the first 5 codewords of the first (PPM-codeword) block: with fewer than 5 bits per symbol the
     // reference whitens `PPM - 5` (an unsigned short: ~65535) codewords past its buffer (LoRaDecoder.cpp:235, undefined behaviour).
     // There is nothing to be identical to; refuse the configuration instead of corrupting device memory.
@@ -478,14 +484,8 @@ int lorahip_decode_packets(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfg, con
     if (!syms_dev || !nsyms_dev || !out_dev || !out_len_dev || !dropped_dev || n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
     { const int rc = decoderCfgOk(cfg); if (rc != LORAHIP_OK) return rc; }
     if (!decodeRowsOk(sym_stride, out_stride)) return LORAHIP_E_INVALID;
-    const DeviceGuard guard(ctx->device);
-    DecodeArgs a;
-    a.syms = syms_dev; a.nsyms = nsyms_dev; a.out = out_dev; a.outLen = out_len_dev; a.dropped = dropped_dev;
-    a.nPackets = unsigned(n_packets); a.symStride = int(sym_stride); a.outStride = int(out_stride);
-    a.sf = cfg->sf; a.ppm = cfg->ppm; a.rdd = cfg->rdd; a.crcc = cfg->crcc; a.interleaving = cfg->interleaving;
-    a.errorCheck = cfg->error_check; a.explicitHdr = cfg->explicit_hdr; a.hdr = cfg->hdr; a.dataLength = cfg->data_length;
-    LORAHIP_TRY(launchDecode(a, ctx->variant, ctx->stream));
-    return LORAHIP_OK;
+    return lorahip_decode_packets_info(ctx, cfg, 1, nullptr, nullptr, 0, syms_dev, sym_stride, nsyms_dev, n_packets, out_dev, out_stride, out_len_dev,
+                                       dropped_dev, nullptr);
 }
 
 /* The same for a caller in HOST memory (a Pothos block: lora_sdr_amd/pothos/LoRaDecoderBatch.cpp): the rows are staged through the
@@ -543,12 +543,39 @@ int lorahip_decode_packets_cfgs(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfg
     if ((table_dev != nullptr && n_table == 0) || n_table > 0x7fffffffu || !decodeRowsOk(sym_stride, out_stride)) return LORAHIP_E_INVALID;
     if (n_packets == 0) return LORAHIP_OK;
     if (!index_dev || !syms_dev || !nsyms_dev || !out_dev || !out_len_dev || !dropped_dev || n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
-    DecodeCfg tab[LORAHIP_DEC_MAX_CFGS];
-    for (size_t i = 0; i < n_cfgs; i++) tab[i] = decodeCfgOf(cfgs[i]);
+    return lorahip_decode_packets_info(ctx, cfgs, n_cfgs, index_dev, table_dev, n_table, syms_dev, sym_stride, nsyms_dev, n_packets, out_dev, out_stride,
+                                       out_len_dev, dropped_dev, nullptr);
+}
+
+/* The one launch behind every decoder entry point: a table of configurations (index_dev NULL: the uniform launch under its only entry) and,
+ * where asked for, the header report of every packet. */
+int lorahip_decode_packets_info(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfgs, const size_t n_cfgs, const int32_t *index_dev,
+                                const int32_t *table_dev, const size_t n_table, const uint16_t *syms_dev, const size_t sym_stride,
+                                const int32_t *nsyms_dev, const size_t n_packets, uint8_t *out_dev, const size_t out_stride,
+                                int32_t *out_len_dev, int32_t *dropped_dev, lorahip_packet_info *info_dev)
+{
+    static_assert(sizeof(lorahip_packet_info) == 32, "the kernels write eight int32 per packet");
+    if (ctx == nullptr) return LORAHIP_E_INVALID;
+    { const int rc = decodeCfgsOk(cfgs, n_cfgs); if (rc != LORAHIP_OK) return rc; }
+    if (index_dev == nullptr && (n_cfgs != 1 || table_dev != nullptr)) return LORAHIP_E_INVALID;
+    if ((table_dev != nullptr && n_table == 0) || n_table > 0x7fffffffu || !decodeRowsOk(sym_stride, out_stride)) return LORAHIP_E_INVALID;
+    if (n_packets == 0) return LORAHIP_OK;
+    if (!syms_dev || !nsyms_dev || !out_dev || !out_len_dev || !dropped_dev || n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
     const DeviceGuard guard(ctx->device);
     DecodeArgs a = {};
     a.syms = syms_dev; a.nsyms = nsyms_dev; a.out = out_dev; a.outLen = out_len_dev; a.dropped = dropped_dev;
     a.nPackets = unsigned(n_packets); a.symStride = int(sym_stride); a.outStride = int(out_stride);
+    a.info = reinterpret_cast<int *>(info_dev);
+    if (index_dev == nullptr)
+    {
+        const lorahip_decoder_cfg *cfg = cfgs;
+        a.sf = cfg->sf; a.ppm = cfg->ppm; a.rdd = cfg->rdd; a.crcc = cfg->crcc; a.interleaving = cfg->interleaving;
+        a.errorCheck = cfg->error_check; a.explicitHdr = cfg->explicit_hdr; a.hdr = cfg->hdr; a.dataLength = cfg->data_length;
+        LORAHIP_TRY(launchDecode(a, ctx->variant, ctx->stream));
+        return LORAHIP_OK;
+    }
+    DecodeCfg tab[LORAHIP_DEC_MAX_CFGS];
+    for (size_t i = 0; i < n_cfgs; i++) tab[i] = decodeCfgOf(cfgs[i]);
     LORAHIP_TRY(launchDecodeCfgs(a, tab, n_cfgs, index_dev, table_dev, int(n_table), ctx->variant, ctx->stream));
     return LORAHIP_OK;
 }
@@ -562,39 +589,57 @@ int lorahip_decode_packets_cfgs_host(lorahip_ctx *ctx, const lorahip_decoder_cfg
     { const int rc = decodeCfgsOk(cfgs, n_cfgs); if (rc != LORAHIP_OK) return rc; }
     if ((table != nullptr && n_table == 0) || n_table > 0x7fffffffu || !decodeRowsOk(sym_stride, out_stride)) return LORAHIP_E_INVALID;
     if (n_packets == 0) return LORAHIP_OK;
-    if (!index || !syms || !nsyms || !out || !out_len || !dropped || n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
+    if (!index) return LORAHIP_E_INVALID;
+    return lorahip_decode_packets_info_host(ctx, cfgs, n_cfgs, index, table, n_table, syms, sym_stride, nsyms, n_packets, out, out_stride, out_len, dropped,
+                                            nullptr);
+}
+
+int lorahip_decode_packets_info_host(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfgs, const size_t n_cfgs, const int32_t *index,
+                                     const int32_t *table, const size_t n_table, const uint16_t *syms, const size_t sym_stride,
+                                     const int32_t *nsyms, const size_t n_packets, uint8_t *out, const size_t out_stride, int32_t *out_len,
+                                     int32_t *dropped, lorahip_packet_info *info)
+{
+    if (ctx == nullptr) return LORAHIP_E_INVALID;
+    { const int rc = decodeCfgsOk(cfgs, n_cfgs); if (rc != LORAHIP_OK) return rc; }
+    if (index == nullptr && (n_cfgs != 1 || table != nullptr)) return LORAHIP_E_INVALID;
+    if ((table != nullptr && n_table == 0) || n_table > 0x7fffffffu || !decodeRowsOk(sym_stride, out_stride)) return LORAHIP_E_INVALID;
+    if (n_packets == 0) return LORAHIP_OK;
+    if (!syms || !nsyms || !out || !out_len || !dropped || n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
     const DeviceGuard guard(ctx->device);
     struct Piece { size_t off, bytes; };
     size_t cur = 0;
     auto carve = [&cur](const size_t bytes) { Piece p = { cur, bytes }; cur += (bytes + 255) & ~size_t(255); return p; };
     const Piece pSym = carve(n_packets * sym_stride * sizeof(uint16_t));
     const Piece pN = carve(n_packets * sizeof(int32_t));
-    const Piece pIdx = carve(n_packets * sizeof(int32_t));
+    const Piece pIdx = carve(index ? n_packets * sizeof(int32_t) : 0);
     const Piece pTab = carve(table ? n_table * sizeof(int32_t) : 0);
     const size_t inBytes = cur;
     const Piece pOut = carve(n_packets * out_stride);
     const Piece pLen = carve(n_packets * sizeof(int32_t));
     const Piece pDrop = carve(n_packets * sizeof(int32_t));
+    const Piece pInfo = carve(info ? n_packets * sizeof(lorahip_packet_info) : 0);
     { const int rc = growStage(ctx, cur, cur); if (rc != LORAHIP_OK) return rc; }
     char *d = ctx->dStage.get(), *h = ctx->hStage.get();
     std::memcpy(h + pSym.off, syms, pSym.bytes);
     std::memcpy(h + pN.off, nsyms, pN.bytes);
-    std::memcpy(h + pIdx.off, index, pIdx.bytes);
+    if (index) std::memcpy(h + pIdx.off, index, pIdx.bytes);
     if (table) std::memcpy(h + pTab.off, table, pTab.bytes);
     // the output rows travel both ways: a packet without an entry (-3) leaves its row as the caller had it
     std::memcpy(h + pOut.off, out, pOut.bytes);
     LORAHIP_TRY(hipMemcpyAsync(d, h, pOut.off + pOut.bytes, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = lorahip_decode_packets_cfgs(ctx, cfgs, n_cfgs, reinterpret_cast<const int32_t *>(d + pIdx.off),
+    const int rc = lorahip_decode_packets_info(ctx, cfgs, n_cfgs, index ? reinterpret_cast<const int32_t *>(d + pIdx.off) : nullptr,
                                                table ? reinterpret_cast<const int32_t *>(d + pTab.off) : nullptr, n_table,
                                                reinterpret_cast<const uint16_t *>(d + pSym.off), sym_stride, reinterpret_cast<const int32_t *>(d + pN.off),
                                                n_packets, reinterpret_cast<uint8_t *>(d + pOut.off), out_stride, reinterpret_cast<int32_t *>(d + pLen.off),
-                                               reinterpret_cast<int32_t *>(d + pDrop.off));
+                                               reinterpret_cast<int32_t *>(d + pDrop.off),
+                                               info ? reinterpret_cast<lorahip_packet_info *>(d + pInfo.off) : nullptr);
     if (rc != LORAHIP_OK) return rc;
     LORAHIP_TRY(hipMemcpyAsync(h + inBytes, d + inBytes, cur - inBytes, hipMemcpyDeviceToHost, ctx->stream));
     LORAHIP_TRY(hipStreamSynchronize(ctx->stream));
     std::memcpy(out, h + pOut.off, pOut.bytes);
     std::memcpy(out_len, h + pLen.off, pLen.bytes);
     std::memcpy(dropped, h + pDrop.off, pDrop.bytes);
+    if (info) std::memcpy(info, h + pInfo.off, pInfo.bytes);
     return LORAHIP_OK;
 }
 

@@ -199,6 +199,14 @@ __device__ __forceinline__ DecodeArgs withCfg(const DecodeArgs &rows, const Deco
     return a;
 }
 
+//! the header report of packet p (struct lorahip_packet_info: length, rdd, crc, hdr_residue, fec_error, need_syms, two reserved words)
+__device__ __forceinline__ void writePacketInfo(int *info, const unsigned p, const int length, const int rdd, const int crc, const int residue,
+                                                const int fecError, const int needSyms)
+{
+    int *w = info + (size_t)p * 8;
+    w[0] = length; w[1] = rdd; w[2] = crc; w[3] = residue; w[4] = fecError; w[5] = needSyms; w[6] = 0; w[7] = 0;
+}
+
 //! packet p under the settings in `a`: launch-uniform scalars in decodePackets, the packet's own in decodePacketsCfgs
 __device__ __forceinline__ void decodeOnePacket(const DecodeArgs a, const unsigned p)
 {
@@ -206,6 +214,8 @@ __device__ __forceinline__ void decodeOnePacket(const DecodeArgs a, const unsign
     const unsigned short *in = a.syms + (size_t)p * a.symStride;
     unsigned char *out = a.out + (size_t)p * a.outStride;
     int outLen = -1, dropped = 0;
+    int iLen = -1, iRdd = -1, iCrc = 0, iRes = -1, iNeed = -1;                               // the report: "header not reached"
+    bool error = false, bad = false;                                                         // :273-274
 
     unsigned short symbols[LORAHIP_DEC_MAX_SYMBOLS];
     unsigned char codewords[LORAHIP_DEC_MAX_CODEWORDS];
@@ -216,10 +226,42 @@ __device__ __forceinline__ void decodeOnePacket(const DecodeArgs a, const unsign
     do
     {
         if (PPM > sf || nsyms < LORAHIP_N_HDR_SYMBOLS) break;                                // :202 (throws), :208
-        const int numSymbols = ((nsyms + (4 + a.rdd) - 1) / (4 + a.rdd)) * (4 + a.rdd);      // :210
-        const int numCodewords = (numSymbols / (4 + a.rdd)) * PPM;                           // :211
+        int cfgRdd = a.rdd;                                                                  // the rate the setter would have been given
+        if (cfgRdd < 0)
+        {
+            // LORAHIP_RDD_FROM_HEADER: the header block by itself -- the first 8 symbols, Gray-coded, de-interleaved at 4/8, not whitened
+            // (:228-255 do exactly this to them at every configured rate) -- names the rate the rest of the message is read at
+            unsigned short hs[LORAHIP_N_HDR_SYMBOLS];
+            unsigned char hc[LORAHIP_SF_MAX + 4];
+            for (int i = 0; i < LORAHIP_N_HDR_SYMBOLS; i++)
+            {
+                unsigned short sym = i < a.symStride ? in[i] : 0;
+                sym = (unsigned short)(sym + (1 << (sf - PPM)) / 2);
+                sym = (unsigned short)(sym >> (sf - PPM));
+                hs[i] = (unsigned short)(sym ^ (sym >> 1));
+            }
+            for (int i = 0; i < PPM; i++) hc[i] = 0;
+            diagonalDeinterleave(hs, LORAHIP_N_HDR_SYMBOLS, hc, PPM, LORAHIP_HDR_RDD);
+            bool hErr = false, hBad = false;
+            unsigned char hb[3];
+            hb[0] = (unsigned char)((decodeHamming84(hc[1], hErr, hBad) & 0xf) | (decodeHamming84(hc[0], hErr, hBad) << 4));
+            hb[1] = decodeHamming84(hc[2], hErr, hBad) & 0xf;
+            hb[2] = (unsigned char)((decodeHamming84(hc[4], hErr, hBad) & 0xf) | (decodeHamming84(hc[3], hErr, hBad) << 4));
+            hb[2] ^= headerChecksum(hb);
+            cfgRdd = (hb[1] >> 1) & 0x7;
+            if (cfgRdd > 4)                                                                  // every rate setting drops it (:293 or :297)
+            {
+                // ... unless this kernel's own row rule comes first: a packet longer than its row, or than this build, is -2 at EVERY rate
+                if (nsyms > a.symStride || nsyms > LORAHIP_DEC_MAX_SYMBOLS) { outLen = -2; break; }
+                dropped = 1;
+                iLen = hb[0]; iRdd = cfgRdd; iRes = hb[2]; error = hErr;
+                break;
+            }
+        }
+        const int numSymbols = ((nsyms + (4 + cfgRdd) - 1) / (4 + cfgRdd)) * (4 + cfgRdd);   // :210
+        const int numCodewords = (numSymbols / (4 + cfgRdd)) * PPM;                          // :211
         if (numSymbols > LORAHIP_DEC_MAX_SYMBOLS || nsyms > a.symStride || numCodewords + 4 > LORAHIP_DEC_MAX_CODEWORDS) { outLen = -2; break; }   // larger than this build / this row supports
-        int rdd = a.rdd;                                                                     // :215
+        int rdd = cfgRdd;                                                                    // :215
         for (int i = 0; i < numSymbols; i++)                                                 // :218-222
         {
             unsigned short sym = i < nsyms ? in[i] : 0;
@@ -259,7 +301,6 @@ __device__ __forceinline__ void decodeOnePacket(const DecodeArgs a, const unsign
             }
         }
 
-        bool error = false, bad = false;                                                     // :273-274
         const int nbytes = (numCodewords + 1) / 2;
         for (int i = 0; i < nbytes + 8; i++) bytes[i] = 0;
         int dOfs = 0, cOfs = 0;
@@ -273,6 +314,7 @@ __device__ __forceinline__ void decodeOnePacket(const DecodeArgs a, const unsign
             bytes[2] = decodeHamming84(codewords[4], error, bad) & 0xf;
             bytes[2] |= (unsigned char)(decodeHamming84(codewords[3], error, bad) << 4);     // checksum
             bytes[2] ^= headerChecksum(bytes);
+            iLen = bytes[0]; iRdd = (bytes[1] >> 1) & 0x7; iRes = bytes[2];
             if (error && a.errorCheck) { dropped = 1; break; }
             if (0 == (bytes[1] & 1)) checkCrc = false;
             rdd = (bytes[1] >> 1) & 0x7;
@@ -286,8 +328,18 @@ __device__ __forceinline__ void decodeOnePacket(const DecodeArgs a, const unsign
         {
             packetLength = a.dataLength;
             dataLength = a.crcc ? packetLength + 2 : packetLength;
+            iLen = a.dataLength; iRdd = cfgRdd;
         }
         if (dataLength > nbytes) { dropped = 1; break; }                                     // :313
+        {
+            // the report's need_syms: the whole interleaver blocks that hold the codewords :315-361 decode for this length
+            const int shift = a.explicitHdr ? 1 : 0;
+            long long cEnd = 2 * dataLength - shift;
+            const int fill = PPM + (((PPM + shift) & 1) ? 1 : 0);
+            if (cEnd < fill) cEnd = fill;
+            const long long nBlocks = (cEnd + PPM - 1) / PPM;
+            iNeed = (int)(cfgRdd != LORAHIP_HDR_RDD ? LORAHIP_N_HDR_SYMBOLS + (nBlocks - 1) * (4 + cfgRdd) : nBlocks * (4 + cfgRdd));
+        }
         for (; cOfs < PPM; cOfs++, dOfs++)                                                   // :315-320
         {
             if (dOfs & 1) bytes[dOfs >> 1] |= (unsigned char)(decodeHamming84(codewords[cOfs], error, bad) << 4);
@@ -314,6 +366,7 @@ __device__ __forceinline__ void decodeOnePacket(const DecodeArgs a, const unsign
             {
                 const unsigned short crc = dataChecksum(bytes + 3, (int)packetLength);
                 const unsigned short packetCrc = (unsigned short)(bytes[3 + packetLength] | (bytes[4 + packetLength] << 8));
+                iCrc = crc == packetCrc ? 1 : -1;
                 if (crc != packetCrc && checkCrc) { dropped = 1; break; }
                 bytes[3 + packetLength] ^= (unsigned char)crc;
                 bytes[4 + packetLength] ^= (unsigned char)(crc >> 8);
@@ -324,6 +377,7 @@ __device__ __forceinline__ void decodeOnePacket(const DecodeArgs a, const unsign
         {
             const unsigned short crc = dataChecksum(bytes, a.dataLength);
             const unsigned short packetCrc = (unsigned short)(bytes[a.dataLength] | (bytes[a.dataLength + 1] << 8));
+            iCrc = crc == packetCrc ? 1 : -1;
             if (crc != packetCrc) { dropped = 1; break; }
             bytes[a.dataLength + 0] ^= (unsigned char)crc;
             bytes[a.dataLength + 1] ^= (unsigned char)(crc >> 8);
@@ -336,6 +390,7 @@ __device__ __forceinline__ void decodeOnePacket(const DecodeArgs a, const unsign
     } while (false);
     a.outLen[p] = outLen;
     a.dropped[p] = dropped;
+    if (a.info != nullptr) writePacketInfo(a.info, p, iLen, iRdd, iCrc, iRes, error ? 1 : 0, iNeed);
 }
 
 __global__ void __launch_bounds__(64) decodePackets(const DecodeArgs a)
@@ -428,21 +483,58 @@ template <int G> __device__ __forceinline__ bool groupAny(const bool p)
  * any length the demodulator can produce decodes like the reference decodes it. */
 struct DecodeCaps { int symCap, cwCap; };
 
+//! the slice a configuration at a FIXED rate needs (see DecodeCaps): the symbols / codewords that can reach the output, or the whole row if
+//! that is less. On the host for the plan; on the device for a header-rate packet, whose decisions are those of the rate its header names.
+__host__ __device__ __forceinline__ DecodeCaps decodeCapsAt(const int sf, const int ppm, const int rdd, const int explicitHdr, const int dataLength,
+                                                            const int symStride)
+{
+    const int PPM = ppm == 0 ? sf : ppm, bs = 4 + rdd;
+    long long nBlocks;
+    if (explicitHdr)                                                 // (a length of one byte: 32-bit arithmetic -- the device takes this branch)
+    {
+        const int cEnd = 2 * (255 + 5) < PPM + 1 ? PPM + 1 : 2 * (255 + 5);
+        nBlocks = (cEnd + PPM - 1) / PPM + 1;
+    }
+    else
+    {
+        long long cEnd = 2 * ((long long)dataLength + 2);
+        if (cEnd < PPM + 1) cEnd = PPM + 1;
+        nBlocks = (cEnd + PPM - 1) / PPM + 1;
+    }
+    const long long symNeed = LORAHIP_N_HDR_SYMBOLS + nBlocks * bs;
+    const int rowBlocks = (symStride + 7 + 8) / bs + 1;
+    const long long symRow = (long long)rowBlocks * bs + LORAHIP_N_HDR_SYMBOLS;                   // the row, rounded up to whole blocks
+    DecodeCaps c;
+    c.symCap = int(symNeed < symRow ? symNeed : symRow);
+    // codewords of those symbols (+ the 4 zero entries behind numCodewords the nibble loop may read, + nibble offsets): symCap / bs blocks
+    // + 2 -- symCap is 8 + a whole number of blocks of 4..8 symbols in BOTH branches (symNeed = 8 + nBlocks * bs, symRow = 8 + rowBlocks *
+    // bs), so symCap / bs = (8 + B * bs) / bs = B + 8 / bs exactly, and 8 / bs is 2 for bs = 4 and 1 for bs = 5..8: no division needed
+    const long long capBlocks = (symNeed < symRow ? nBlocks : (long long)rowBlocks) + (bs == 4 ? 2 : 1);
+    c.cwCap = int((capBlocks + 2) * PPM + 16);
+    return c;
+}
+
+__host__ __device__ __forceinline__ int decodeSliceOf(const DecodeCaps c) { return (c.symCap * 2 + 2 * c.cwCap + 15) & ~15; }
+
 /*! One packet per group of G lanes under the settings in `a` and the caps of THOSE settings; `slice` is the launch's distance between two
  * groups' LDS (>= what the caps need). decodeGroup hands in its kernel arguments, so every setting is a launch-uniform scalar there;
  * decodeGroupCfgs hands in the packet's own entry of the table, the same for every lane of a group (the lanes of a group share p): whatever
  * is group-uniform below stays so, and no barrier stands under a condition (the `go` flag), so the 256 threads meet at every one of them
- * whatever their packets' settings are. known = false (no such entry): the packet is reported as -3 and nothing of it is read or written. */
+ * whatever their packets' settings are. known = false (no such entry): the packet is reported as -3 and nothing of it is read or written.
+ * a.rdd < 0 (LORAHIP_RDD_FROM_HEADER): `caps` are the largest of the entry's five rates; the packet's rate, and with it its own caps and
+ * layout, are resolved behind the first barrier, and from there on it is a packet of the uniform launch at that rate. a.info, where set,
+ * gets the packet's header report (struct lorahip_packet_info); it changes nothing else. */
 template <int G>
 __device__ __forceinline__ void decodeGroupBody(const DecodeArgs a, const DecodeCaps caps, const int slice, const int perBlock, const bool known)
 {
     // per packet: symCap Gray-coded symbols (u16), then the codewords (u8), then the nibbles (u8), 16-byte aligned slices
     extern __shared__ __attribute__((aligned(16))) unsigned char smemDec[];
-    const int symCap = caps.symCap, cwCap = caps.cwCap;
+    int symCap = caps.symCap, cwCap = caps.cwCap;
     const int g = threadIdx.x / G, t = threadIdx.x % G;
     unsigned short *sSym = reinterpret_cast<unsigned short *>(smemDec + (size_t)g * slice);
     unsigned char *sCw = smemDec + (size_t)g * slice + symCap * 2;
     unsigned char *sNib = sCw + cwCap;
+    int iLen = -1, iRdd = -1, iCrc = 0, iRes = -1, iNeed = -1;     // the report (lorahip_packet_info): "header not reached"
     const unsigned p = blockIdx.x * perBlock + g;
     const bool have = g < perBlock && p < a.nPackets;               // (long slices: fewer packets per workgroup than groups, the rest idle)
     const unsigned pc = have ? p : 0;
@@ -453,20 +545,25 @@ __device__ __forceinline__ void decodeGroupBody(const DecodeArgs a, const Decode
 
     const int sf = a.sf;
     const int PPM = a.ppm == 0 ? sf : a.ppm;                                                 // LoRaDecoder.cpp:201
-    const int bs = 4 + a.rdd;                                                                // symbols per interleaver block
-    const int numSymbols = ((nsyms + bs - 1) / bs) * bs;                                     // :210
-    const int numCodewords = (numSymbols / bs) * PPM;                                        // :211
+    // the coding rate of the setter. A header-rate entry (a.rdd < 0) has none: the packet's header names it, behind the first barrier, and
+    // everything from `rate` to `cwLoad` is worked out again there; until then only the Gray-code load runs, which does not depend on it
+    int rate = a.rdd < 0 ? LORAHIP_HDR_RDD : a.rdd;
+    int bs = 4 + rate;                                                                       // symbols per interleaver block
+    int numSymbols = ((nsyms + bs - 1) / bs) * bs;                                           // :210
+    int numCodewords = (numSymbols / bs) * PPM;                                              // :211
     // the row holds the first symStride symbols of a longer packet: whether that is enough is known once the length is (below)
     const int rowSyms = nsyms < a.symStride ? nsyms : a.symStride;
-    const int symLoad = numSymbols < symCap ? numSymbols : symCap;                           // what of it this slice holds
-    const int cwLoad = numCodewords + 4 < cwCap ? numCodewords + 4 : cwCap;
+    int symLoad = numSymbols < symCap ? numSymbols : symCap;                                 // what of it this slice holds
+    int cwLoad = numCodewords + 4 < cwCap ? numCodewords + 4 : cwCap;
     // group-uniform early outs (:202 throws, :208 too short)
     bool go = have && known && !(PPM > sf || nsyms < LORAHIP_N_HDR_SYMBOLS);
 
     // ---- Gray code with rounding to the symbol size (:218-222) --------------------------------------------------------
     if (go && !a.interleaving && nsyms > a.symStride) { outLen = -2; go = false; }           // every symbol is output: the row must hold them all
+    // header rate: numSymbols is nsyms rounded up to a block of 4..8, so nsyms + 7 covers every rate (zeros behind the row, as always)
+    const int grayLoad = !a.interleaving ? numSymbols : a.rdd < 0 ? (nsyms + 7 < symCap ? nsyms + 7 : symCap) : symLoad;
     if (go)
-        for (int i = t; i < (a.interleaving ? symLoad : numSymbols); i += G)
+        for (int i = t; i < grayLoad; i += G)
         {
             unsigned short sym = i < rowSyms ? in[i] : 0;
             sym = (unsigned short)(sym + (1 << (sf - PPM)) / 2);
@@ -479,9 +576,43 @@ __device__ __forceinline__ void decodeGroupBody(const DecodeArgs a, const Decode
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __syncthreads();
 
+    // ---- header rate (LORAHIP_RDD_FROM_HEADER): every lane of the group reads the rate field out of the first eight symbols, alike ----
+    // Codeword 2 of the first block holds it: de-interleaved at 4/8 over symbols 0..7 and never whitened at ANY configured rate (:228-255:
+    // both branches give the first PPM codewords from exactly these symbols, and the explicit header's five are skipped by the whitening),
+    // so the field does not depend on the rate the body below runs at. From here on the packet is a packet of the uniform launch at that
+    // rate: its block size, its counts, and the caps and the slice layout of THAT rate's plan (they fit: the entry's slice is the
+    // largest of the five; Gray-coded symbols behind symCap lie where its codewords go and are overwritten before anything reads them).
+    // A field of 5..7 runs at 4/8 into the header stage, which drops it (the error check or :297) -- as it would under every setting.
+    if (a.rdd < 0)                                                                           // (group-uniform; no barrier inside)
+    {
+        if (go)
+        {
+            unsigned cw2 = 0;
+            for (int k = 0; k < LORAHIP_N_HDR_SYMBOLS; k++)
+            {
+                int m = 2 - (k < PPM ? k : k - PPM);                                        // 2 - k % PPM (5 <= PPM: a header-rate entry has a header)
+                if (m < 0) m += PPM;
+                cw2 |= ((sSym[k] >> m) & 1u) << k;
+            }
+            bool e2 = false, b2 = false;
+            const int field = ((decodeHamming84((unsigned char)cw2, e2, b2) & 0xf) >> 1) & 0x7;
+            rate = field > 4 ? LORAHIP_HDR_RDD : field;
+        }
+        const DecodeCaps cr = decodeCapsAt(sf, a.ppm, rate, 1, a.dataLength, a.symStride);       // (a header-rate entry has a header)
+        symCap = cr.symCap; cwCap = cr.cwCap;
+        sCw = smemDec + (size_t)g * slice + symCap * 2;
+        sNib = sCw + cwCap;
+        bs = 4 + rate;
+        const int nBlocks = (nsyms + bs - 1) / bs;
+        numSymbols = nBlocks * bs;                                                           // :210
+        numCodewords = nBlocks * PPM;                                                        // :211
+        symLoad = numSymbols < symCap ? numSymbols : symCap;
+        cwLoad = numCodewords + 4 < cwCap ? numCodewords + 4 : cwCap;
+    }
+
     // ---- diagonal de-interleave (:366-381) + de-whitening (:225-255), one codeword per lane and round ------------------
     // the first block is always 4/8 over 8 symbols unless the whole packet is (then every block is)
-    const bool hdrBlock = a.rdd != LORAHIP_HDR_RDD;
+    const bool hdrBlock = rate != LORAHIP_HDR_RDD;
     if (go)
         for (int c = t; c < cwLoad; c += G)
         {
@@ -490,8 +621,8 @@ __device__ __forceinline__ void decodeGroupBody(const DecodeArgs a, const Decode
             {
                 int x, i, symOff, R;
                 if (hdrBlock && c < PPM) { x = 0; i = c; symOff = 0; R = LORAHIP_HDR_RDD; }
-                else if (hdrBlock) { x = (c - PPM) / PPM; i = (c - PPM) - x * PPM; symOff = LORAHIP_N_HDR_SYMBOLS + x * bs; R = a.rdd; }
-                else { x = c / PPM; i = c - x * PPM; symOff = x * bs; R = a.rdd; }
+                else if (hdrBlock) { x = (c - PPM) / PPM; i = (c - PPM) - x * PPM; symOff = LORAHIP_N_HDR_SYMBOLS + x * bs; R = rate; }
+                else { x = c / PPM; i = c - x * PPM; symOff = x * bs; R = rate; }
                 // with a header block the payload's symbols may end inside a block of `bs`: the reference de-interleaves
                 // (numSymbols - 8) / bs whole blocks and leaves the rest of the codewords zero
                 // (... and a block whose symbols lie behind the slice is behind what any length can need: left zero, never read)
@@ -509,7 +640,7 @@ __device__ __forceinline__ void decodeGroupBody(const DecodeArgs a, const Decode
                 // (the tables end behind the last codeword any length can need: LORAHIP_DEC_MAX_DATA_LENGTH)
                 if (pos >= 0 && (pos >> 1) < LORAHIP_WHITEN_LEN && !(hdrBlock && c >= PPM && numSymbols <= LORAHIP_N_HDR_SYMBOLS))
                 {
-                    const int Rw = (hdrBlock && c < PPM) ? LORAHIP_HDR_RDD : a.rdd;
+                    const int Rw = (hdrBlock && c < PPM) ? LORAHIP_HDR_RDD : rate;
                     const unsigned keep = 0xffu >> (4 - Rw);
                     cw ^= kCodec.white[Rw == 1 ? 1 : 0][pos & 1][pos >> 1] & keep;
                 }
@@ -524,7 +655,7 @@ __device__ __forceinline__ void decodeGroupBody(const DecodeArgs a, const Decode
     const int nbytes = (numCodewords + 1) / 2;
     long long packetLength = 0, dataLength = 0;
     bool checkCrc = a.crcc != 0;
-    int rdd = a.rdd;
+    int rdd = rate;
     unsigned char h0 = 0, h1 = 0, h2 = 0;
     if (go)
     {
@@ -535,6 +666,7 @@ __device__ __forceinline__ void decodeGroupBody(const DecodeArgs a, const Decode
             h2 = (unsigned char)((decodeHamming84(sCw[4], error, bad) & 0xf) | (decodeHamming84(sCw[3], error, bad) << 4));   // checksum
             const unsigned char hb[2] = { h0, h1 };
             h2 ^= headerChecksum(hb);
+            iLen = h0; iRdd = (h1 >> 1) & 0x7; iRes = h2;
             if (error && a.errorCheck) { dropped = 1; go = false; }
             if (go)
             {
@@ -549,6 +681,7 @@ __device__ __forceinline__ void decodeGroupBody(const DecodeArgs a, const Decode
         {
             packetLength = a.dataLength;
             dataLength = a.crcc ? packetLength + 2 : packetLength;
+            iLen = a.dataLength; iRdd = rate;
         }
         if (go && dataLength > nbytes) { dropped = 1; go = false; }                          // :313
     }
@@ -567,6 +700,7 @@ __device__ __forceinline__ void decodeGroupBody(const DecodeArgs a, const Decode
         // they lie inside the row; if not, the caller's rows are too short for this packet (-2: reported, never guessed)
         const long long nBlocks = (cEnd + PPM - 1) / PPM;
         const long long needSyms = hdrBlock ? LORAHIP_N_HDR_SYMBOLS + (nBlocks - 1) * bs : nBlocks * bs;
+        iNeed = (int)needSyms;
         if ((nsyms > a.symStride && needSyms > a.symStride) || needSyms > symCap || cEnd + 4 > cwCap) { outLen = -2; go = false; }
     }
     if (go)
@@ -605,6 +739,7 @@ __device__ __forceinline__ void decodeGroupBody(const DecodeArgs a, const Decode
         crc &= 0xffff;
         const unsigned packetCrc = (sNib[2 * (base + len)] | (sNib[2 * (base + len) + 1] << 4)) |
                                    ((sNib[2 * (base + len) + 2] | (sNib[2 * (base + len) + 3] << 4)) << 8);
+        iCrc = crc == packetCrc ? 1 : -1;
         if (a.explicitHdr)
         {
             if (crc != packetCrc && checkCrc) { dropped = 1; go = false; }
@@ -633,29 +768,32 @@ __device__ __forceinline__ void decodeGroupBody(const DecodeArgs a, const Decode
     {
         a.outLen[p] = known ? outLen : -3;
         a.dropped[p] = dropped;
+        // (error: every lane's own after the header, the group's after the nibbles -- where the decode ended, it is the reference's flag)
+        if (a.info != nullptr) writePacketInfo(a.info, p, iLen, iRdd, iCrc, iRes, error ? 1 : 0, iNeed);
     }
 }
 
 template <int G>
-__global__ void __launch_bounds__(256) decodeGroup(const DecodeArgs a, const DecodeCaps caps, const int perBlock)
+__global__ void __launch_bounds__(256) decodeGroup(const DecodeArgs a, const DecodeCaps caps, const int slice, const int perBlock)
 {
-    decodeGroupBody<G>(a, caps, ((caps.symCap * 2 + 2 * caps.cwCap + 15) & ~15), perBlock, true);
+    decodeGroupBody<G>(a, caps, slice, perBlock, true);
 }
 
 //! the slice a configuration needs (see DecodeCaps): the symbols / codewords that can reach the output, or the whole row if that is less
-static DecodeCaps decodeCaps(const DecodeCfg &a, const int symStride)
+//! A header-rate entry (rdd < 0) runs each packet on the caps of the rate its header names: it gets the largest of the five in each component,
+//! and the largest of their slices (which holds any of the five layouts, and the Gray-code load of min(nsyms + 7, symCap) symbols).
+static DecodeCaps decodeCaps(const DecodeCfg &a, const int symStride, int &slice)
 {
-    const int PPM = a.ppm == 0 ? a.sf : a.ppm, bs = 4 + a.rdd;
-    const long long bytesMax = a.explicitHdr ? 255 + 5 : (long long)a.dataLength + 2;
-    long long cEnd = 2 * bytesMax;
-    if (cEnd < PPM + 1) cEnd = PPM + 1;
-    const long long nBlocks = (cEnd + PPM - 1) / PPM + 1;
-    const long long symNeed = LORAHIP_N_HDR_SYMBOLS + nBlocks * bs;
-    const long long symRow = ((symStride + 7 + 8) / bs + 1) * bs + LORAHIP_N_HDR_SYMBOLS;         // the row, rounded up to whole blocks
-    DecodeCaps c;
-    c.symCap = int(symNeed < symRow ? symNeed : symRow);
-    // codewords of those symbols (+ the 4 zero entries behind numCodewords the nibble loop may read, + nibble offsets)
-    c.cwCap = int((c.symCap / bs + 2) * PPM + 16);
+    DecodeCaps c = { 0, 0 };
+    slice = 0;
+    for (int r = a.rdd < 0 ? 0 : a.rdd; r <= (a.rdd < 0 ? 4 : a.rdd); r++)
+    {
+        const DecodeCaps cr = decodeCapsAt(a.sf, a.ppm, r, a.explicitHdr, a.dataLength, symStride);
+        const int sr = decodeSliceOf(cr);
+        c.symCap = cr.symCap > c.symCap ? cr.symCap : c.symCap;
+        c.cwCap = cr.cwCap > c.cwCap ? cr.cwCap : c.cwCap;
+        slice = sr > slice ? sr : slice;
+    }
     return c;
 }
 
@@ -669,9 +807,9 @@ DecodeTiling decodePlan(DecodeCfg *cfgs, const size_t nCfgs, const int symStride
     DecodeTiling t = { 0, 0, 0, 0, 0 };
     for (size_t i = 0; i < nCfgs; i++)
     {
-        const DecodeCaps c = decodeCaps(cfgs[i], symStride);
+        int slice = 0;
+        const DecodeCaps c = decodeCaps(cfgs[i], symStride, slice);
         cfgs[i].symCap = c.symCap; cfgs[i].cwCap = c.cwCap;
-        const int slice = (c.symCap * 2 + 2 * c.cwCap + 15) & ~15;
         t.symCap = c.symCap > t.symCap ? c.symCap : t.symCap;
         t.cwCap = c.cwCap > t.cwCap ? c.cwCap : t.cwCap;
         t.slice = slice > t.slice ? slice : t.slice;
@@ -698,7 +836,7 @@ static hipError_t launchDecodeGroup(const DecodeArgs &a, const DecodeTiling &t, 
         const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(decodeGroup<G>), 160 * 1024, attrDone);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((decodeGroup<G>), dim3((a.nPackets + t.perBlock - 1) / t.perBlock), dim3(256), size_t(t.slice) * t.perBlock, stream, a, caps, t.perBlock);
+    hipLaunchKernelGGL((decodeGroup<G>), dim3((a.nPackets + t.perBlock - 1) / t.perBlock), dim3(256), size_t(t.slice) * t.perBlock, stream, a, caps, t.slice, t.perBlock);
     return hipGetLastError();
 }
 
@@ -930,7 +1068,12 @@ __global__ void __launch_bounds__(64) decodePacketsCfgs(const DecodeArgs rows, c
     const unsigned p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= rows.nPackets) return;
     const int i = cfgIndexOf(tab, p);
-    if (i < 0) { rows.outLen[p] = -3; rows.dropped[p] = 0; return; }
+    if (i < 0)
+    {
+        rows.outLen[p] = -3; rows.dropped[p] = 0;
+        if (rows.info != nullptr) writePacketInfo(rows.info, p, -1, -1, 0, -1, 0, -1);
+        return;
+    }
     decodeOnePacket(withCfg(rows, tab.e[i]), p);
 }
 

@@ -248,7 +248,8 @@ struct DecodeArgs
     int *dropped;                   // [nPackets] the block called drop()
     unsigned nPackets;
     int symStride, outStride;
-    int sf, ppm, rdd, crcc, interleaving, errorCheck, explicitHdr, hdr, dataLength;
+    int sf, ppm, rdd, crcc, interleaving, errorCheck, explicitHdr, hdr, dataLength;   // rdd -1: each packet's own header names it
+    int *info;                      // [nPackets][8] struct lorahip_packet_info, or null: no report
 };
 hipError_t launchDecode(const DecodeArgs &a, int variant, hipStream_t stream);   // variant 1: the lane-per-packet checker
 //! one entry of a table launch: the nine settings of DecodeArgs, then the LDS caps decodePlan() works out for them
