@@ -426,6 +426,27 @@ int lorahip_demod_rewind(lorahip_demod *d);
  * launch stream was told to follow before the call, lorahip_demod_stream_follow), has read them before they are overwritten -- one
  * set of rows is enough. lorahip_demod_receive_flush also resumes a channel whose record capacity the
  * last step filled (that step's remaining packets follow the others in the rows). */
+/* WHEN a packet arrived, in samples of its channel's stream (all int64 from the kernel's registers to the row; never narrowed).
+ * With consumed[i] what call i of LoRaDemod::work() consumes and P(i) = consumed[0] + .. + consumed[i-1], for a packet posted by call k
+ * whose frame's DOWNCHIRP1 call is j and whose first DATASYMBOLS call is m:
+ *   end_pos    P(k + 1): just after the posting call -- the "RX finished" instant (Semtech's tmst)
+ *   data_pos   P(m): first sample of the first data symbol            = end_pos - len * N
+ *   sync_pos   P(j): start of the call that emits the frame's signals  = data_pos - (N/4 + freq_error/2) - N   (int division)
+ *   freq_error the "error" that call j emits (LoRaDemod.cpp:265-267)
+ * The kernels record end_pos and freq_error at the post; the identities hold because every DATASYMBOLS call consumes N, QUARTERCHIRP
+ * N/4 + freqError/2, DOWNCHIRP1 N, and freqError does not change from DOWNCHIRP1 to the post. A signal's position (below) is P(j), so
+ * (channel, sync_pos) == (channel, pos) joins a packet with its signal exactly.
+ * Origin: that of lorahip_demod_consumed -- one-shot runs (lorahip_demod_run*, the segment runs) count from the first sample the run
+ * was given for the channel (a caller of the segment runs adds its first_sample[c]; a packet begun in an earlier one-shot run has
+ * data_pos / sync_pos below 0), append runs and receiver steps count absolute positions in the channel's row since the last
+ * lorahip_demod_rewind. To answer an uplink: lorahip_mod_frames_sched(start = end_pos + delay). */
+typedef struct lorahip_rx_info { int64_t end_pos, data_pos, sync_pos, freq_error; } lorahip_rx_info;
+
+/* Versioned by struct_size: the size up to and including `reserved` (before info_dev existed) is accepted and means "no info_dev".
+ * info_dev (nullable): [cap_packets] lorahip_rx_info per packet row, device memory, filled in the same stream order as the other rows
+ * by ordinary (async 0 / 1) and pipelined (async 2) steps; rows too small lose nothing, the info arrives with the re-delivery. A
+ * RESIDENT step (async 3) does not deliver it: a call whose rows carry info_dev, or whose registered signal rows carry pos, is refused
+ * with LORAHIP_E_INVALID before anything is rung (lorahip_last_error() says so); the object stays usable for ordinary steps. */
 typedef struct lorahip_packet_rows {
     size_t struct_size;     /* = sizeof(lorahip_packet_rows) */
     uint16_t *syms_dev; size_t sym_stride;      /* [cap_packets][sym_stride], zero padded */
@@ -437,7 +458,9 @@ typedef struct lorahip_packet_rows {
                                receiver may run ahead of the last report. Call k then reports step k - depth (the rows of call k - depth),
                                the flush everything left, and the caller cycles depth + 1 sets of rows. A step ends with its slowest
                                workgroup; with more steps in flight the fast ones work ahead instead of waiting for it. Otherwise 0. */
+    lorahip_rx_info *info_dev;                   /* [cap_packets], nullable (see above); absent in the previous struct_size */
 } lorahip_packet_rows;
+#define LORAHIP_PACKET_ROWS_SIZE_V4 (offsetof(lorahip_packet_rows, info_dev))
 int lorahip_demod_receive(lorahip_demod *d, const float *iq_dev, size_t row_stride, size_t n_valid, const lorahip_packet_rows *rows,
                           size_t *n_packets, int64_t *work_calls);
 /* The block's signals in a running receiver (the reference emits "error" / "power" / "snr" once per packet at DOWNCHIRP1, LoRaDemod.cpp:
@@ -461,7 +484,11 @@ typedef struct lorahip_signal_rows {
     float *power;           /* [cap]  "power"                                         :268 */
     float *snr;             /* [cap]  "snr"                                           :269 */
     size_t cap;
+    int64_t *pos;           /* [cap]  nullable: where the emitting call began (= lorahip_rx_info::sync_pos of the frame's packet); device or
+                               pinned host memory like its siblings. Absent in the previous struct_size (the size up to `cap`), which is
+                               still accepted. */
 } lorahip_signal_rows;
+#define LORAHIP_SIGNAL_ROWS_SIZE_V4 (offsetof(lorahip_signal_rows, pos))
 int lorahip_demod_receive_signal_rows(lorahip_demod *d, const lorahip_signal_rows *rows /* nullable */);
 size_t lorahip_demod_receive_num_signals(const lorahip_demod *d);
 int lorahip_demod_receive_flush(lorahip_demod *d, const lorahip_packet_rows *rows /* nullable: the last step's packets are dropped */,
@@ -503,6 +530,15 @@ int lorahip_demod_get_packets(const lorahip_demod *d, int32_t *channels, int64_t
  * *n_packets = the total over the parts; the rows are complete when the call returns. Over several devices: LORAHIP_E_INVALID. */
 int lorahip_demod_packets_to_device(lorahip_demod *d, uint16_t *syms_dev, size_t sym_stride, int32_t *nsyms_dev, int32_t *channel_dev,
                                     size_t cap_packets, size_t *n_packets);
+/* The same with info_dev[p] = packet p's lorahip_rx_info (device memory, [cap_packets], nullable: then exactly the entry above, which
+ * forwards here with NULL). Both sources fill it: the packing on the device from the kernel's records and the upload from the host queue. On a
+ * mixed handle whose parts share a device the rows come in the same order; positions are per channel and are not remapped. */
+int lorahip_demod_packets_to_device_info(lorahip_demod *d, uint16_t *syms_dev, size_t sym_stride, int32_t *nsyms_dev, int32_t *channel_dev,
+                                         lorahip_rx_info *info_dev, size_t cap_packets, size_t *n_packets);
+/* out[i] = lorahip_rx_info of queued packet i, in lorahip_demod_get_packets' order (streaming and host-driven modes give the same values);
+ * pos[i] = position of queued signal i, in lorahip_demod_get_signals' order. cap below the queue's length: LORAHIP_E_INVALID. */
+int lorahip_demod_get_packets_info(const lorahip_demod *d, lorahip_rx_info *out, size_t cap);
+int lorahip_demod_get_signals_pos(const lorahip_demod *d, int64_t *pos, size_t cap);
 void lorahip_demod_clear_packets(lorahip_demod *d);
 /* samples of `channel`'s stream the last lorahip_demod_run[_device] consumed (the sum of its consume() calls, :320): a
  * streaming caller presents the unconsumed remainder again in front of the next chunk, as the framework's port buffer does */

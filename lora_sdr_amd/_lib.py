@@ -77,9 +77,34 @@ class PacketRows(C.Structure):
                 ("channel_dev", C.c_void_p), ("cap_packets", C.c_size_t), ("async_", C.c_int32), ("reserved", C.c_int32)]
 
 
+class PacketRowsInfo(PacketRows):
+    """struct lorahip_packet_rows with its last member, info_dev (PacketRows is the previous struct_size, which the library still takes: no info)"""
+    _fields_ = [("info_dev", C.c_void_p)]
+
+
 class SignalRows(C.Structure):
     """struct lorahip_signal_rows"""
     _fields_ = [("struct_size", C.c_size_t), ("channel", C.c_void_p), ("error", C.c_void_p), ("power", C.c_void_p), ("snr", C.c_void_p), ("cap", C.c_size_t)]
+
+
+class SignalRowsPos(SignalRows):
+    """struct lorahip_signal_rows with its last member, pos (SignalRows is the previous struct_size: no positions)"""
+    _fields_ = [("pos", C.c_void_p)]
+
+
+class RxInfo(C.Structure):
+    """struct lorahip_rx_info (32 bytes): when a packet arrived, in samples of its channel's stream. P of them are a (P, 4) int64
+    array, which is how the Python layer hands them out; RxInfo.COLUMNS names the columns and RxInfo.view(a) gives a numpy array of
+    that shape the fields by name (a["end_pos"], ...)."""
+    _fields_ = [(n, C.c_int64) for n in ("end_pos", "data_pos", "sync_pos", "freq_error")]
+    COLUMNS = ("end_pos", "data_pos", "sync_pos", "freq_error")
+    END_POS, DATA_POS, SYNC_POS, FREQ_ERROR = range(4)
+
+    @staticmethod
+    def view(a):
+        import numpy as np
+        a = np.ascontiguousarray(a, np.int64).reshape(-1, 4)
+        return a.view(np.dtype([(n, np.int64) for n in RxInfo.COLUMNS])).reshape(-1)
 
 
 class WorkResult(C.Structure):
@@ -250,6 +275,9 @@ SIGNATURES = {
     "lorahip_demod_set_mode": (C.c_int, [C.c_void_p, C.c_int]),
     "lorahip_demod_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "lorahip_demod_packets_to_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "lorahip_demod_packets_to_device_info": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "lorahip_demod_get_packets_info": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "lorahip_demod_get_signals_pos": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "lorahip_demod_run": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),
     "lorahip_demod_run_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int64)]),
     "lorahip_demod_run_device_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]),

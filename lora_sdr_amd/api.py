@@ -1163,13 +1163,19 @@ class LoRaDemod(_Handle):
         """keep the block's error / power / snr signals (LoRaDemod.cpp:267-269) without a per-call trace"""
         check(self._lib.lorahip_demod_set_signals(self._h, int(bool(on))), "lorahip_demod_set_signals")
 
-    def signals(self):
-        """the queued signal emissions as arrays: channel, round, error, power, snr (cleared with the packets)"""
+    def signals(self, pos=False):
+        """the queued signal emissions as arrays: channel, round, error, power, snr (cleared with the packets); pos=True adds the int64
+        sample position at which the emitting call began -- the sync_pos of the frame's packet (lorahip_rx_info), the key match_signals joins on"""
         n = int(self._lib.lorahip_demod_num_signals(self._h))
         ch, rd, er = np.empty(n, np.int32), np.empty(n, np.int64), np.empty(n, np.int32)
         pw, sn = np.empty(n, np.float32), np.empty(n, np.float32)
         check(self._lib.lorahip_demod_get_signals(self._h, ch.ctypes.data, rd.ctypes.data, er.ctypes.data, pw.ctypes.data, sn.ctypes.data, n),
               "lorahip_demod_get_signals")
+        if pos:
+            ps = np.empty(n, np.int64)
+            if n:
+                check(self._lib.lorahip_demod_get_signals_pos(self._h, ps.ctypes.data, n), "lorahip_demod_get_signals_pos")
+            return ch, rd, er, pw, sn, ps
         return ch, rd, er, pw, sn
 
     def rewind(self):
@@ -1189,24 +1195,28 @@ class LoRaDemod(_Handle):
             self._lib.lorahip_demod_reset_stream(self._h)
         return rounds.value
 
-    def receiver_rows(self, cap_packets, stride=None):
-        """device tensors for receive(): (cap_packets, stride) int16 symbols, (cap_packets,) int32 lengths and channels"""
+    def receiver_rows(self, cap_packets, stride=None, info=False):
+        """device tensors for receive(): (cap_packets, stride) int16 symbols, (cap_packets,) int32 lengths and channels; info=True adds a
+        fourth, (cap_packets, 4) int64: end_pos, data_pos, sync_pos, freq_error per packet (lorahip_rx_info; RxInfo names the columns),
+        which receive() / receive_flush() pass on (not with async_=3: refused)"""
         import torch
         dev = torch.device("cuda", int(self._device))
         if stride is None:
             stride = max(8, min(self._mtu, int(self._lib.lorahip_decode_max_symbols())))      # no packet is longer than the MTU (LoRaDemod.cpp:291)
-        return (torch.empty((int(cap_packets), int(stride)), dtype=torch.int16, device=dev), torch.empty(int(cap_packets), dtype=torch.int32, device=dev),
+        rows = (torch.empty((int(cap_packets), int(stride)), dtype=torch.int16, device=dev), torch.empty(int(cap_packets), dtype=torch.int32, device=dev),
                 torch.empty(int(cap_packets), dtype=torch.int32, device=dev))
+        return rows + (torch.empty((int(cap_packets), 4), dtype=torch.int64, device=dev),) if info else rows
 
-    def receiver_signal_rows(self, cap, pinned_host=False):
+    def receiver_signal_rows(self, cap, pinned_host=False, pos=False):
         """lorahip_demod_receive_signal_rows: with set_signals(True), every receive() / receive_flush() delivers the block's signals
         (error / power / snr once per packet at DOWNCHIRP1, LoRaDemod.cpp:267-269) of the step whose packets it delivers into these
         rows, last_signals() of them. Returns the tensors (channel int32, error int32, power float32, snr float32): device memory, or --
         pinned_host -- numpy arrays over pinned host memory the device writes directly (read them after the stream has passed).
-        cap = 0 unregisters (receiver steps drop the signals again)."""
+        cap = 0 unregisters (receiver steps drop the signals again). pos=True adds a fifth member, int64: the sample position at which
+        the emitting call began (absolute in the channel's row; equals the sync_pos of the frame's packet)."""
         import torch
-        r = _lib.SignalRows()
-        r.struct_size = C.sizeof(_lib.SignalRows)
+        r = _lib.SignalRowsPos() if pos else _lib.SignalRows()
+        r.struct_size = C.sizeof(r)
         cap = int(cap)
         if cap == 0:
             self._sig_rows = None
@@ -1214,12 +1224,18 @@ class LoRaDemod(_Handle):
             return None
         if pinned_host:
             rows = (pinned_empty((cap,), np.int32), pinned_empty((cap,), np.int32), pinned_empty((cap,), np.float32), pinned_empty((cap,), np.float32))
-            r.channel, r.error, r.power, r.snr = (a.ctypes.data for a in rows)
+            if pos:
+                rows += (pinned_empty((cap,), np.int64),)
+                r.pos = rows[4].ctypes.data
+            r.channel, r.error, r.power, r.snr = (a.ctypes.data for a in rows[:4])
         else:
             dev = torch.device("cuda", int(self._device))
             rows = (torch.empty(cap, dtype=torch.int32, device=dev), torch.empty(cap, dtype=torch.int32, device=dev),
                     torch.empty(cap, dtype=torch.float32, device=dev), torch.empty(cap, dtype=torch.float32, device=dev))
-            r.channel, r.error, r.power, r.snr = (a.data_ptr() for a in rows)
+            if pos:
+                rows += (torch.empty(cap, dtype=torch.int64, device=dev),)
+                r.pos = rows[4].data_ptr()
+            r.channel, r.error, r.power, r.snr = (a.data_ptr() for a in rows[:4])
         r.cap = cap
         check(self._lib.lorahip_demod_receive_signal_rows(self._h, C.byref(r)), "lorahip_demod_receive_signal_rows")
         self._sig_rows = rows                                # (kept alive while registered)
@@ -1228,12 +1244,12 @@ class LoRaDemod(_Handle):
     def register_signal_rows(self, rows):
         """register a set made by receiver_signal_rows() again: a caller that alternates two sets of packet rows (pipelined consumers, the
         resident receiver) alternates two sets of signal rows the same way, one registration before each receive()"""
-        r = _lib.SignalRows()
-        r.struct_size = C.sizeof(_lib.SignalRows)
-        if isinstance(rows[0], np.ndarray):
-            r.channel, r.error, r.power, r.snr = (a.ctypes.data for a in rows)
-        else:
-            r.channel, r.error, r.power, r.snr = (a.data_ptr() for a in rows)
+        r = _lib.SignalRowsPos() if len(rows) > 4 else _lib.SignalRows()       # (a fifth member: the positions)
+        r.struct_size = C.sizeof(r)
+        ptr = (lambda a: a.ctypes.data) if isinstance(rows[0], np.ndarray) else (lambda a: a.data_ptr())
+        r.channel, r.error, r.power, r.snr = (ptr(a) for a in rows[:4])
+        if len(rows) > 4:
+            r.pos = ptr(rows[4])
         r.cap = int(rows[0].shape[0])
         check(self._lib.lorahip_demod_receive_signal_rows(self._h, C.byref(r)), "lorahip_demod_receive_signal_rows")
         self._sig_rows = rows
@@ -1254,9 +1270,11 @@ class LoRaDemod(_Handle):
         return int(self._lib.lorahip_demod_receive_num_signals(self._h))
 
     def _rows_struct(self, rows, async_, depth=0):
-        syms, nsyms, chan = rows
-        r = _lib.PacketRows()
-        r.struct_size = C.sizeof(_lib.PacketRows)
+        syms, nsyms, chan = rows[:3]
+        r = _lib.PacketRowsInfo() if len(rows) > 3 else _lib.PacketRows()      # (a fourth tensor: receiver_rows(info=True))
+        r.struct_size = C.sizeof(r)
+        if len(rows) > 3:
+            r.info_dev = rows[3].data_ptr()
         r.syms_dev, r.sym_stride, r.nsyms_dev, r.channel_dev = syms.data_ptr(), int(syms.shape[1]), nsyms.data_ptr(), chan.data_ptr()
         r.cap_packets, r.async_, r.reserved = int(syms.shape[0]), int(async_), int(depth)
         return r
@@ -1361,18 +1379,22 @@ class LoRaDemod(_Handle):
         check(self._lib.lorahip_demod_run(self._h, ptrs, lens, C.byref(rounds)), "lorahip_demod_run")
         return rounds.value
 
-    def packets_arrays(self, clear=True):
+    def packets_arrays(self, clear=True, info=False):
         """The queued packets as four flat arrays -- channel (int32), round (int64), length (int64), and all symbols back to
-        back (int16) -- in posting order: what lorahip_demod_get_packets delivers, without per-packet Python objects"""
+        back (int16) -- in posting order: what lorahip_demod_get_packets delivers, without per-packet Python objects. info=True adds a
+        fifth, (P, 4) int64: end_pos, data_pos, sync_pos, freq_error per packet (lorahip_rx_info; RxInfo names the columns)"""
         n = self._lib.lorahip_demod_num_packets(self._h)
         ns = self._lib.lorahip_demod_num_packet_symbols(self._h)
         ch, rd, ln = np.empty(n, np.int32), np.empty(n, np.int64), np.empty(n, np.int64)
         syms = np.empty(ns, np.int16)
         check(self._lib.lorahip_demod_get_packets(self._h, ch.ctypes.data, rd.ctypes.data, ln.ctypes.data, n, syms.ctypes.data, ns),
               "lorahip_demod_get_packets")
+        inf = np.empty((n, 4), np.int64)
+        if info and n:
+            check(self._lib.lorahip_demod_get_packets_info(self._h, inf.ctypes.data, n), "lorahip_demod_get_packets_info")
         if clear:
             self._lib.lorahip_demod_clear_packets(self._h)
-        return ch, rd, ln, syms
+        return (ch, rd, ln, syms, inf) if info else (ch, rd, ln, syms)
 
     def clear_packets(self):
         """drop the queued packets (what packets*(clear=True) do after reading them)"""
@@ -1384,13 +1406,14 @@ class LoRaDemod(_Handle):
         parts = np.split(syms, np.cumsum(ln)[:-1]) if ch.size else []       # views into one array: no per-packet copy
         return list(zip(ch.tolist(), rd.tolist(), parts))
 
-    def packets_device(self, stride=None, clear=True):
+    def packets_device(self, stride=None, clear=True, info=False):
         """The queued packets as device tensors in the decoder's input layout -- (P, stride) int16 symbols (zero padded), (P,) int32
         lengths, (P,) int32 channels -- ready for LoRaDecoder.decode_batch(); no per-packet Python work. Straight after a
         work() of the streaming mode the packets never visit the host (rows ordered by channel, then time); otherwise the
         rows follow packets()'s order. stride defaults to the MTU. On a mixed object whose parts share one device: the parts' rows
         one after the other in packets()'s order, each part's as above, with global channel numbers -- the input of
-        LoRaDecoderSet.decode_batch(syms, nsyms, index=channels, table=decoder of channel); over several devices: refused."""
+        LoRaDecoderSet.decode_batch(syms, nsyms, index=channels, table=decoder of channel); over several devices: refused.
+        info=True adds a fourth tensor, (P, 4) int64: end_pos, data_pos, sync_pos, freq_error per row (lorahip_rx_info)."""
         import torch
         n = int(self._lib.lorahip_demod_num_packets(self._h))
         dev = torch.device("cuda", int(self._device))
@@ -1399,14 +1422,20 @@ class LoRaDemod(_Handle):
         syms = torch.empty((n, int(stride)), dtype=torch.int16, device=dev)      # every element is written (rows are zero padded)
         nsyms = torch.empty(n, dtype=torch.int32, device=dev)
         chan = torch.empty(n, dtype=torch.int32, device=dev)
+        inf = torch.empty((n, 4), dtype=torch.int64, device=dev) if info else None
         got = C.c_size_t()
         if n:
             torch.cuda.current_stream(dev).synchronize()            # the blocks may have pending work of their previous owner
-            check(self._lib.lorahip_demod_packets_to_device(self._h, C.c_void_p(syms.data_ptr()), int(stride), C.c_void_p(nsyms.data_ptr()),
-                                                            C.c_void_p(chan.data_ptr()), n, C.byref(got)), "lorahip_demod_packets_to_device")
+            if info:
+                check(self._lib.lorahip_demod_packets_to_device_info(self._h, C.c_void_p(syms.data_ptr()), int(stride), C.c_void_p(nsyms.data_ptr()),
+                                                                     C.c_void_p(chan.data_ptr()), C.c_void_p(inf.data_ptr()), n, C.byref(got)),
+                      "lorahip_demod_packets_to_device_info")
+            else:
+                check(self._lib.lorahip_demod_packets_to_device(self._h, C.c_void_p(syms.data_ptr()), int(stride), C.c_void_p(nsyms.data_ptr()),
+                                                                C.c_void_p(chan.data_ptr()), n, C.byref(got)), "lorahip_demod_packets_to_device")
         if clear:
             self._lib.lorahip_demod_clear_packets(self._h)
-        return syms, nsyms, chan
+        return (syms, nsyms, chan, inf) if info else (syms, nsyms, chan)
 
     def consumed(self, channel):
         """samples of the channel's stream consumed by the last work()"""
@@ -1951,3 +1980,35 @@ def transmit_mixed(payloads, encoders, index, row, start, n_rows, row_len, table
     finally:
         if own:
             ctx.close()
+
+
+def match_signals(info, chan, sig_chan, sig_pos):
+    """Which signal belongs to which packet: per packet the index of its signal in (sig_chan, sig_pos), or -1 where there is none, by
+    the exact key (channel, sync_pos) == (signal channel, signal position) -- a frame's signals are emitted by its DOWNCHIRP1 call,
+    whose start is the packet's sync_pos (lorahip_rx_info). info: (P, 4) int64 as packets_arrays / packets_device / receiver_rows
+    (info=True) give it; chan: (P,); sig_chan, sig_pos: (S,) as signals(pos=True) / receiver_signal_rows(pos=True) give them -- all
+    numpy arrays, or all device tensors: then the (P,) int64 result is a device tensor and nothing is synchronised with the host (every
+    shape follows from the arguments' shapes). Compared in blocks of at most 2^22 pairs."""
+    if not _is_torch(info):
+        info, sig_pos = np.asarray(info, np.int64).reshape(-1, 4), np.asarray(sig_pos, np.int64)
+    P, S = int(info.shape[0]), int(sig_pos.shape[0])
+    if _is_torch(info):
+        import torch
+        out = torch.full((P,), -1, dtype=torch.int64, device=info.device)
+        if P == 0 or S == 0:
+            return out
+        sync, ch, sch, sps = info[:, 2], chan.to(torch.int64), sig_chan.to(torch.int64), sig_pos.to(torch.int64)
+        step = max(1, (1 << 22) // S)
+        for p0 in range(0, P, step):
+            hit = (ch[p0:p0 + step, None] == sch[None, :]) & (sync[p0:p0 + step, None] == sps[None, :])
+            out[p0:p0 + step] = torch.where(hit.any(1), hit.to(torch.int8).argmax(1), out[p0:p0 + step])
+        return out
+    ch, sch, sps = np.asarray(chan, np.int64), np.asarray(sig_chan, np.int64), sig_pos
+    out = np.full(P, -1, np.int64)
+    if P == 0 or S == 0:
+        return out
+    step = max(1, (1 << 22) // S)
+    for p0 in range(0, P, step):
+        hit = (ch[p0:p0 + step, None] == sch[None, :]) & (info[p0:p0 + step, 2, None] == sps[None, :])
+        out[p0:p0 + step] = np.where(hit.any(1), hit.argmax(1), -1)
+    return out

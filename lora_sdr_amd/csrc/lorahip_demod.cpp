@@ -508,11 +508,24 @@ int lorahip_demod_get_packets(const lorahip_demod *dm, int32_t *channels, int64_
     return LORAHIP_OK;
 }
 
+int lorahip_demod_get_packets_info(const lorahip_demod *dm, lorahip_rx_info *out, const size_t cap)
+{
+    { const int rc = drained(dm); if (rc != LORAHIP_OK) return rc; }
+    if (dm->comp) return dm->comp->getPacketsInfo(out, cap);
+    if (dm == nullptr || out == nullptr || cap < dm->packets.size()) return LORAHIP_E_INVALID;
+    for (size_t i = 0; i < dm->packets.size(); i++)
+    {
+        const Packet &p = dm->packets[i];
+        out[i] = rxInfo(p.endPos, (long long)p.len, p.freqError, (long long)dm->N);
+    }
+    return LORAHIP_OK;
+}
+
 static int packetsToDevice(lorahip_demod *dm, uint16_t *syms_dev, const size_t sym_stride, int32_t *nsyms_dev, int32_t *channel_dev,
-                           const size_t cap_packets, size_t *n_packets, const bool sync)
+                           lorahip_rx_info *info_dev, const size_t cap_packets, size_t *n_packets, const bool sync)
 {
     if (dm == nullptr) return LORAHIP_E_INVALID;
-    if (dm->comp) return dm->comp->packetsToDevice(syms_dev, sym_stride, nsyms_dev, channel_dev, cap_packets, n_packets);   // (always complete on return)
+    if (dm->comp) return dm->comp->packetsToDevice(syms_dev, sym_stride, nsyms_dev, channel_dev, info_dev, cap_packets, n_packets);   // (always complete on return)
     {
         // The records of the last streaming launch are still on the device and nothing else is queued: pack them there
         // (rows: channels ascending, time ascending inside a channel). A channel that entered the launch inside a packet found
@@ -530,7 +543,7 @@ static int packetsToDevice(lorahip_demod *dm, uint16_t *syms_dev, const size_t s
             hipStream_t st = dm->ctx->stream;
             // the rows are numbered on the device (scanDescribe: exclusive prefix sum of the per-channel packet counts): nothing is
             // uploaded, and nothing on the host is reused, so the caller decides whether to wait
-            LORAHIP_TRY(packPackets(dm, Q.lay, dm->sDev.get(), n, syms_dev, sym_stride, nsyms_dev, channel_dev, st));
+            LORAHIP_TRY(packPackets(dm, Q.lay, dm->sDev.get(), n, syms_dev, sym_stride, nsyms_dev, channel_dev, info_dev, st));
             if (sync) LORAHIP_TRY(hipStreamSynchronize(st));
             return LORAHIP_OK;
         }
@@ -542,7 +555,9 @@ static int packetsToDevice(lorahip_demod *dm, uint16_t *syms_dev, const size_t s
     if (syms_dev == nullptr || nsyms_dev == nullptr || sym_stride == 0 || cap_packets < P) return LORAHIP_E_INVALID;
     const DeviceGuard guard(dm->ctx->device);
     const size_t nbSym = align256(P * sym_stride * sizeof(uint16_t)), nbInt = align256(P * sizeof(int32_t));
-    { const int grc = growDense(dm, nbSym + 2 * nbInt); if (grc != LORAHIP_OK) return grc; }
+    const size_t nbInfo = info_dev ? align256(P * sizeof(lorahip_rx_info)) : 0;
+    { const int grc = growDense(dm, nbSym + 2 * nbInt + nbInfo); if (grc != LORAHIP_OK) return grc; }
+    lorahip_rx_info *hi = reinterpret_cast<lorahip_rx_info *>(dm->hDense.get() + nbSym + 2 * nbInt);
     uint16_t *hs = reinterpret_cast<uint16_t *>(dm->hDense.get());
     int32_t *hn = reinterpret_cast<int32_t *>(dm->hDense.get() + nbSym), *hc = reinterpret_cast<int32_t *>(dm->hDense.get() + nbSym + nbInt);
     std::memset(hs, 0, P * sym_stride * sizeof(uint16_t));
@@ -552,11 +567,13 @@ static int packetsToDevice(lorahip_demod *dm, uint16_t *syms_dev, const size_t s
         std::memcpy(hs + i * sym_stride, dm->pktSyms.data() + p.off, (p.len < sym_stride ? p.len : sym_stride) * sizeof(uint16_t));
         hn[i] = int32_t(p.len > 0x7fffffffu ? 0x7fffffff : p.len);     // the true length: a packet longer than the stride is flagged by the decoder
         hc[i] = p.channel;
+        if (info_dev) hi[i] = rxInfo(p.endPos, (long long)p.len, p.freqError, (long long)dm->N);
     }
     hipStream_t st = dm->ctx->stream;
     LORAHIP_TRY(hipMemcpyAsync(syms_dev, hs, P * sym_stride * sizeof(uint16_t), hipMemcpyHostToDevice, st));
     LORAHIP_TRY(hipMemcpyAsync(nsyms_dev, hn, P * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if (channel_dev) LORAHIP_TRY(hipMemcpyAsync(channel_dev, hc, P * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (info_dev) LORAHIP_TRY(hipMemcpyAsync(info_dev, hi, P * sizeof(lorahip_rx_info), hipMemcpyHostToDevice, st));
     LORAHIP_TRY(hipStreamSynchronize(st));                              // the pinned scratch is reused by the next run
     return LORAHIP_OK;
 }
@@ -564,18 +581,24 @@ static int packetsToDevice(lorahip_demod *dm, uint16_t *syms_dev, const size_t s
 int lorahip_demod_packets_to_device(lorahip_demod *dm, uint16_t *syms_dev, const size_t sym_stride, int32_t *nsyms_dev, int32_t *channel_dev,
                                     const size_t cap_packets, size_t *n_packets)
 {
-    return packetsToDevice(dm, syms_dev, sym_stride, nsyms_dev, channel_dev, cap_packets, n_packets, true);
+    return packetsToDevice(dm, syms_dev, sym_stride, nsyms_dev, channel_dev, nullptr, cap_packets, n_packets, true);
+}
+
+int lorahip_demod_packets_to_device_info(lorahip_demod *dm, uint16_t *syms_dev, const size_t sym_stride, int32_t *nsyms_dev, int32_t *channel_dev,
+                                         lorahip_rx_info *info_dev, const size_t cap_packets, size_t *n_packets)
+{
+    return packetsToDevice(dm, syms_dev, sym_stride, nsyms_dev, channel_dev, info_dev, cap_packets, n_packets, true);
 }
 
 } // extern "C"
 
 namespace lorahip {
-int demodPacketsToDeviceQueued(lorahip_demod *dm, uint16_t *symsDev, const size_t symStride, int32_t *nsymsDev, int32_t *channelDev, const size_t capPackets,
-                               size_t *nPackets, const int32_t *globalOf, const size_t nLocal)
+int demodPacketsToDeviceQueued(lorahip_demod *dm, uint16_t *symsDev, const size_t symStride, int32_t *nsymsDev, int32_t *channelDev, lorahip_rx_info *infoDev,
+                               const size_t capPackets, size_t *nPackets, const int32_t *globalOf, const size_t nLocal)
 {
     if (dm == nullptr || dm->comp) return LORAHIP_E_INVALID;
     size_t n = 0;
-    const int rc = packetsToDevice(dm, symsDev, symStride, nsymsDev, channelDev, capPackets, &n, false);
+    const int rc = packetsToDevice(dm, symsDev, symStride, nsymsDev, channelDev, infoDev, capPackets, &n, false);
     if (nPackets) *nPackets = n;
     if (rc != LORAHIP_OK || n == 0 || channelDev == nullptr || globalOf == nullptr) return rc;
     const DeviceGuard guard(dm->ctx->device);
@@ -621,14 +644,17 @@ static int signalsToRows(lorahip_demod *dm, const size_t first, size_t *n, const
     if (S == 0) return LORAHIP_OK;
     if (first + S > R.cap) { setLastError("lorahip_demod_receive: the signal rows cannot hold the signals that are due"); return LORAHIP_E_INVALID; }
     const size_t nb = align256(S * sizeof(int32_t));
-    { const int grc = growDense(dm, 4 * nb); if (grc != LORAHIP_OK) return grc; }
+    const size_t nbPos = R.pos ? align256(S * sizeof(int64_t)) : 0;
+    { const int grc = growDense(dm, 4 * nb + nbPos); if (grc != LORAHIP_OK) return grc; }
+    int64_t *hq = reinterpret_cast<int64_t *>(dm->hDense.get() + 4 * nb);
     int32_t *hc = reinterpret_cast<int32_t *>(dm->hDense.get()), *he = reinterpret_cast<int32_t *>(dm->hDense.get() + nb);
     float *hp = reinterpret_cast<float *>(dm->hDense.get() + 2 * nb), *hs = reinterpret_cast<float *>(dm->hDense.get() + 3 * nb);
-    for (size_t i = 0; i < S; i++) { const Signal &g = dm->signals[i]; hc[i] = g.channel; he[i] = g.error; hp[i] = g.power; hs[i] = g.snr; }
+    for (size_t i = 0; i < S; i++) { const Signal &g = dm->signals[i]; hc[i] = g.channel; he[i] = g.error; hp[i] = g.power; hs[i] = g.snr; if (R.pos) hq[i] = g.pos; }
     if (R.channel) LORAHIP_TRY(hipMemcpyAsync(R.channel + first, hc, S * sizeof(int32_t), hipMemcpyDefault, st));
     if (R.error) LORAHIP_TRY(hipMemcpyAsync(R.error + first, he, S * sizeof(int32_t), hipMemcpyDefault, st));
     if (R.power) LORAHIP_TRY(hipMemcpyAsync(R.power + first, hp, S * sizeof(float), hipMemcpyDefault, st));
     if (R.snr) LORAHIP_TRY(hipMemcpyAsync(R.snr + first, hs, S * sizeof(float), hipMemcpyDefault, st));
+    if (R.pos) LORAHIP_TRY(hipMemcpyAsync(R.pos + first, hq, S * sizeof(int64_t), hipMemcpyDefault, st));
     LORAHIP_TRY(hipStreamSynchronize(st));                              // the pinned scratch is reused by the next run
     return LORAHIP_OK;
 }
@@ -638,9 +664,12 @@ int lorahip_demod_receive_signal_rows(lorahip_demod *dm, const lorahip_signal_ro
     if (dm == nullptr) return LORAHIP_E_INVALID;
     if (dm->comp) { setLastError("receiver steps are per part: lorahip_demod_part_handle"); return LORAHIP_E_INVALID; }
     if (rows == nullptr) { std::memset(&dm->sigRows, 0, sizeof(dm->sigRows)); dm->sigRowsOn = false; return LORAHIP_OK; }
-    if (rows->struct_size != sizeof(lorahip_signal_rows) || rows->cap > 0x7fffffffu) return LORAHIP_E_INVALID;
-    dm->sigRows = *rows;
-    dm->sigRowsOn = rows->cap != 0 && (rows->channel || rows->error || rows->power || rows->snr);
+    // versioned by struct_size: the size before `pos` existed is still taken, and means "no positions"
+    if ((rows->struct_size != sizeof(lorahip_signal_rows) && rows->struct_size != LORAHIP_SIGNAL_ROWS_SIZE_V4) || rows->cap > 0x7fffffffu) return LORAHIP_E_INVALID;
+    std::memset(&dm->sigRows, 0, sizeof(dm->sigRows));
+    std::memcpy(&dm->sigRows, rows, rows->struct_size);
+    dm->sigRows.struct_size = sizeof(lorahip_signal_rows);
+    dm->sigRowsOn = rows->cap != 0 && (dm->sigRows.channel || dm->sigRows.error || dm->sigRows.power || dm->sigRows.snr || dm->sigRows.pos);
     return LORAHIP_OK;
 }
 
@@ -663,10 +692,23 @@ int lorahip_demod_resident_active(const lorahip_demod *dm)
     return dm && !dm->comp && dm->res.active ? 1 : 0;
 }
 
-int lorahip_demod_receive(lorahip_demod *dm, const float *iq_dev, const size_t row_stride, const size_t n_valid, const lorahip_packet_rows *rows,
+//! the caller's rows in today's layout: versioned by struct_size, the size before `info_dev` existed is still taken and means "absent"
+//! (nothing behind the caller's struct_size is read)
+static bool takeRows(const lorahip_packet_rows *rows, lorahip_packet_rows &full)
+{
+    if (rows->struct_size != sizeof(lorahip_packet_rows) && rows->struct_size != LORAHIP_PACKET_ROWS_SIZE_V4) return false;
+    std::memset(&full, 0, sizeof(full));
+    std::memcpy(&full, rows, rows->struct_size);
+    full.struct_size = sizeof(full);
+    return true;
+}
+
+int lorahip_demod_receive(lorahip_demod *dm, const float *iq_dev, const size_t row_stride, const size_t n_valid, const lorahip_packet_rows *rows_in,
                           size_t *n_packets, int64_t *work_calls)
 {
-    if (dm == nullptr || rows == nullptr || rows->struct_size != sizeof(lorahip_packet_rows)) return LORAHIP_E_INVALID;
+    lorahip_packet_rows full;
+    if (dm == nullptr || rows_in == nullptr || !takeRows(rows_in, full)) return LORAHIP_E_INVALID;
+    const lorahip_packet_rows *rows = &full;
     if (n_packets) *n_packets = 0;
     if (work_calls) *work_calls = 0;
     if (dm->comp) { setLastError("append runs are per part: lorahip_demod_part_handle"); return LORAHIP_E_INVALID; }
@@ -677,6 +719,12 @@ int lorahip_demod_receive(lorahip_demod *dm, const float *iq_dev, const size_t r
         if (rows->async == 3)
         {
             if (dm->pipe.active) { setLastError("a pipelined step is in flight: lorahip_demod_receive_flush first"); return LORAHIP_E_INVALID; }
+            // the step message (and its check word) has no place for them: refused before anything is rung
+            if (rows->info_dev != nullptr || (dm->sigRowsOn && dm->sigRows.pos != nullptr))
+            {
+                setLastError("lorahip_demod_receive (resident, async = 3): info_dev / signal positions are not delivered by resident steps -- use async 0, 1 or 2, or pass rows without them");
+                return LORAHIP_E_INVALID;
+            }
             const int prc = residentStep(dm, iq_dev, row_stride, n_valid, rows, n_packets, work_calls, handled);
             if (handled || prc != LORAHIP_OK) return prc;
         }
@@ -695,7 +743,7 @@ int lorahip_demod_receive(lorahip_demod *dm, const float *iq_dev, const size_t r
     if (work_calls) *work_calls = dm->workCalls - calls0;
     size_t n = 0;
     dm->lastSignals = 0;
-    rc = packetsToDevice(dm, rows->syms_dev, rows->sym_stride, rows->nsyms_dev, rows->channel_dev, rows->cap_packets, &n, rows->async == 0);
+    rc = packetsToDevice(dm, rows->syms_dev, rows->sym_stride, rows->nsyms_dev, rows->channel_dev, rows->info_dev, rows->cap_packets, &n, rows->async == 0);
     if (n_packets) *n_packets = n;
     if (rc != LORAHIP_OK) return rc;                                    // (the packets stay queued: a caller with too few rows can fetch them)
     rc = signalsToRows(dm, 0, &dm->lastSignals, rows->async == 0);      // the block's signals of this step, beside its packets
@@ -720,7 +768,7 @@ static int flushResume(lorahip_demod *dm, const lorahip_packet_rows *rows, const
     if (rows == nullptr) { lorahip_demod_clear_packets(dm); return LORAHIP_OK; }
     size_t n2 = 0;
     rc = packetsToDevice(dm, rows->syms_dev ? rows->syms_dev + row * rows->sym_stride : nullptr, rows->sym_stride, rows->nsyms_dev ? rows->nsyms_dev + row : nullptr,
-                         rows->channel_dev ? rows->channel_dev + row : nullptr, rows->cap_packets - row, &n2, true);
+                         rows->channel_dev ? rows->channel_dev + row : nullptr, rows->info_dev ? rows->info_dev + row : nullptr, rows->cap_packets - row, &n2, true);
     if (nPackets) *nPackets = n0 + n2;
     if (rc != LORAHIP_OK) return rc;
     const size_t s1 = dm->lastSignals;
@@ -732,9 +780,11 @@ static int flushResume(lorahip_demod *dm, const lorahip_packet_rows *rows, const
     return LORAHIP_OK;
 }
 
-int lorahip_demod_receive_flush(lorahip_demod *dm, const lorahip_packet_rows *rows, size_t *n_packets, int64_t *work_calls)
+int lorahip_demod_receive_flush(lorahip_demod *dm, const lorahip_packet_rows *rows_in, size_t *n_packets, int64_t *work_calls)
 {
-    if (dm == nullptr || (rows != nullptr && rows->struct_size != sizeof(lorahip_packet_rows))) return LORAHIP_E_INVALID;
+    lorahip_packet_rows full;
+    if (dm == nullptr || (rows_in != nullptr && !takeRows(rows_in, full))) return LORAHIP_E_INVALID;
+    const lorahip_packet_rows *rows = rows_in ? &full : nullptr;
     if (n_packets) *n_packets = 0;
     if (work_calls) *work_calls = 0;
     if (dm->comp) return LORAHIP_OK;
@@ -792,6 +842,15 @@ int lorahip_demod_get_signals(const lorahip_demod *dm, int32_t *channels, int64_
         if (powers) powers[i] = g.power;
         if (snrs) snrs[i] = g.snr;
     }
+    return LORAHIP_OK;
+}
+
+int lorahip_demod_get_signals_pos(const lorahip_demod *dm, int64_t *pos, const size_t cap)
+{
+    { const int rc = drained(dm); if (rc != LORAHIP_OK) return rc; }
+    if (dm->comp) return dm->comp->getSignalsPos(pos, cap);
+    if (dm == nullptr || pos == nullptr || cap < dm->signals.size()) return LORAHIP_E_INVALID;
+    for (size_t i = 0; i < dm->signals.size(); i++) pos[i] = dm->signals[i].pos;
     return LORAHIP_OK;
 }
 

@@ -39,12 +39,12 @@ void leaveStateOnDevice(lorahip_demod *dm)
 //! the n packets of a record set of layout L at `rec` into rows (stream-ordered on `st`, no wait; the rows are numbered on the device,
 //! channels ascending). The scratch (growDense) has been sized by the caller.
 hipError_t packPackets(const lorahip_demod *dm, const StreamLayout &L, const char *rec, const size_t n, uint16_t *syms, const size_t symStride,
-                              int32_t *nsyms, int32_t *chan, hipStream_t st)
+                              int32_t *nsyms, int32_t *chan, lorahip_rx_info *info, hipStream_t st)
 {
     const size_t nbRow = align256(L.B * sizeof(int));
     return launchPackPackets(reinterpret_cast<const StreamPacket *>(rec + L.oPkt), reinterpret_cast<const int *>(rec + L.oNPkt),
                              reinterpret_cast<const short *>(rec + L.oSym), reinterpret_cast<int *>(dm->dDense.get()), L.B, int(L.symStride), int(L.capPkt), n,
-                             reinterpret_cast<long long *>(dm->dDense.get() + nbRow), syms, int(symStride), nsyms, chan, st);
+                             reinterpret_cast<long long *>(dm->dDense.get() + nbRow), syms, int(symStride), nsyms, chan, info, int(dm->N), st);
 }
 
 //! the signals of a record set of layout L at `rec` into the registered signal rows from row `first` on (stream-ordered on `st`, no wait)
@@ -52,7 +52,7 @@ hipError_t packSignals(const lorahip_demod *dm, const StreamLayout &L, const cha
 {
     const lorahip_signal_rows &R = dm->sigRows;
     return launchPackSignals(reinterpret_cast<const StreamSignal *>(rec + L.oSig), reinterpret_cast<const int *>(rec + L.oNSig), L.B, int(L.capPkt),
-                             R.channel, R.error, R.power, R.snr, first, R.cap, st);
+                             R.channel, R.error, R.power, R.snr, reinterpret_cast<long long *>(R.pos), first, R.cap, st);
 }
 
 //! summary of record set `set` into the object's books (waits for that step's kernel); its packets stay in the set until packed
@@ -100,7 +100,7 @@ static int pipePack(lorahip_demod *dm, const int set, const lorahip_packet_rows 
     if (beside) LORAHIP_TRY(hipStreamWaitEvent(P.side.get(), P.entry.get(), 0));
     if (n)
         LORAHIP_TRY(packPackets(dm, L, P.dev[set].get(), n, rows->syms_dev + firstRow * rows->sym_stride, rows->sym_stride, rows->nsyms_dev + firstRow,
-                                rows->channel_dev ? rows->channel_dev + firstRow : nullptr, packStream));
+                                rows->channel_dev ? rows->channel_dev + firstRow : nullptr, rows->info_dev ? rows->info_dev + firstRow : nullptr, packStream));
     if (ns) LORAHIP_TRY(packSignals(dm, L, P.dev[set].get(), firstSig, packStream));
     if (beside)
     {

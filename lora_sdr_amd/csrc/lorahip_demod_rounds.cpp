@@ -215,6 +215,7 @@ int runRounds(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
                 {
                     Signal g;
                     g.channel = int32_t(c); g.round = k.callCount; g.error = r.sig_error; g.power = r.sig_power; g.snr = r.sig_snr;
+                    g.pos = int64_t(k.pos);                                                      // the call has not consumed yet (below)
                     dm->signals.push_back(g);
                 }
             }
@@ -230,6 +231,7 @@ int runRounds(lorahip_demod *dm, const float *iqDev, int64_t *roundsOut)
                 p.round = k.callCount;                                                           // = the lock-step round where every stream began with the run
                 p.off = dm->pktSyms.size();
                 p.len = k.symCount;
+                p.endPos = int64_t(k.pos) + r.consumed; p.freqError = k.freqError;               // as frameStep records them (st.pos is the mirror's here)
                 dm->pktSyms.insert(dm->pktSyms.end(), k.outSymbols.begin(), k.outSymbols.begin() + long(k.symCount));
                 dm->packets.push_back(p);
             }

@@ -54,6 +54,8 @@ struct Packet
     int32_t channel;
     int64_t round;
     size_t off, len;
+    int64_t endPos;         // lorahip_rx_info::end_pos and ::freq_error (the other two positions follow from these and len: rxInfo)
+    int32_t freqError;
 };
 
 //! one emission of the block's "error" / "power" / "snr" signals (LoRaDemod.cpp:267-269)
@@ -63,6 +65,7 @@ struct Signal
     int64_t round;
     int32_t error;
     float power, snr;
+    int64_t pos;            // where the emitting call began (= the sync_pos of the frame's packet)
 };
 
 inline size_t align256(const size_t x) { return (x + 255) & ~size_t(255); }
@@ -249,7 +252,7 @@ bool stateOnDevice(const lorahip_demod *dm);
 void noteSteadyStep(lorahip_demod *dm, size_t rowStride, size_t nValid);
 void leaveStateOnDevice(lorahip_demod *dm);
 hipError_t packPackets(const lorahip_demod *dm, const StreamLayout &L, const char *rec, size_t n, uint16_t *syms, size_t symStride, int32_t *nsyms, int32_t *chan,
-                       hipStream_t st);
+                       lorahip_rx_info *info, hipStream_t st);
 hipError_t packSignals(const lorahip_demod *dm, const StreamLayout &L, const char *rec, size_t first, hipStream_t st);
 bool rowsHold(const lorahip_packet_rows *rows, size_t n);
 int pipeFlush(lorahip_demod *dm, const lorahip_packet_rows *rows, size_t *nPackets, int64_t *calls);

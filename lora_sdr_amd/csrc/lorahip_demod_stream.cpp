@@ -123,7 +123,7 @@ static int drainLaunch(lorahip_demod *dm, const StreamLayout &L)
         {
             const StreamSignal &q = hSig[c * maxSig + size_t(j)];
             Signal g;
-            g.channel = int32_t(c); g.round = q.callIndex; g.error = q.error; g.power = q.power; g.snr = q.snr;
+            g.channel = int32_t(c); g.round = q.callIndex; g.error = q.error; g.power = q.power; g.snr = q.snr; g.pos = q.pos;
             dm->signals.push_back(g);
         }
         // symbols of this launch continue the packet the previous launches left open (k.outSymbols[0..carry[c]))
@@ -137,6 +137,7 @@ static int drainLaunch(lorahip_demod *dm, const StreamLayout &L)
             pk.round = q.callIndex;
             pk.off = dm->pktSyms.size();
             pk.len = size_t(q.len);
+            pk.endPos = q.endPos; pk.freqError = q.freqError;
             dm->pktSyms.insert(dm->pktSyms.end(), k.outSymbols.begin(), k.outSymbols.begin() + long(carry[c]));
             const size_t fresh = size_t(q.len) - carry[c];
             dm->pktSyms.insert(dm->pktSyms.end(), sy + p, sy + p + fresh);

@@ -70,11 +70,12 @@ __host__ __device__ __forceinline__ void frameStep(StreamState &st, const Stream
     const int downTable = sync3 ? 1 : (isD1 ? 0 : st.downTable);                                        // :212, :257
 
     if (writer && isDA) o.symOut[o.nSym] = (short)value;                                                 // out[_symCount++] = value  :290
-    if (writer && post) { StreamPacket q; q.callIndex = st.callCount; q.len = symCount; o.pktOut[o.nPkt] = q; }   // postMessage  :295-298
+    // postMessage  :295-298; with it where the call ends in the stream (consume(total), :320) and the frame's frequency error
+    if (writer && post) { StreamPacket q; q.callIndex = st.callCount; q.len = symCount; q.endPos = st.pos + total; q.freqError = st.freqError; q.pad = 0; o.pktOut[o.nPkt] = q; }
     if (o.sigOut)                                                                                        // uniform over the launch
     {
         // emitSignal("error" / "power" / "snr") as a record of its own (:267-269): the caller evaluated the logarithms for this call
-        if (writer && isD1) { StreamSignal g; g.callIndex = st.callCount; g.error = freqError; g.power = power; g.snr = snr; o.sigOut[o.nSig] = g; }
+        if (writer && isD1) { StreamSignal g; g.callIndex = st.callCount; g.error = freqError; g.power = power; g.snr = snr; g.pos = st.pos; o.sigOut[o.nSig] = g; }
         o.nSig += isD1 ? 1 : 0;
     }
     if (writer && o.out)

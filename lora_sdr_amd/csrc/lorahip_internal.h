@@ -101,10 +101,24 @@ __host__ __device__ inline bool nearStep(const float d)
 
 //! one posted packet: the call (round) it was posted in and its length; its symbols are the next `len` entries
 //! of the channel's symbol stream (after what earlier launches carried over)
-struct StreamPacket { int callIndex; int len; };
+//! endPos = StreamState::pos just after the posting call (the "RX finished" instant, in samples of the channel's stream: origin as
+//! lorahip_demod_consumed), freqError = _freqError at the post -- the "error" the frame's DOWNCHIRP1 call emitted, which nothing changes
+//! in between. From these two and len the other positions of lorahip_rx_info follow (include/lorahip.h). New members behind the old.
+struct StreamPacket { int callIndex; int len; long long endPos; int freqError; int pad; };
+//! a packet's lorahip_rx_info from what the post recorded (include/lorahip.h has the identities); 64-bit throughout
+__host__ __device__ inline lorahip_rx_info rxInfo(const long long endPos, const long long len, const int freqError, const long long N)
+{
+    lorahip_rx_info r;
+    r.end_pos = endPos;
+    r.data_pos = endPos - len * N;
+    r.sync_pos = r.data_pos - (N / 4 + (long long)(freqError / 2)) - N;      // QUARTERCHIRP's N/4 + freqError/2 (int division, :278), DOWNCHIRP1's N
+    r.freq_error = freqError;
+    return r;
+}
 //! what the block emits on its "error" / "power" / "snr" signals at DOWNCHIRP1 (LoRaDemod.cpp:267-269), one record per emission:
-//! kept only when the caller asked for signals (lorahip_demod_set_signals) -- a receiver without a per-call trace still gets them
-struct StreamSignal { int callIndex; int error; float power; float snr; };
+//! kept only when the caller asked for signals (lorahip_demod_set_signals) -- a receiver without a per-call trace still gets them;
+//! pos = StreamState::pos when the emitting call began (= lorahip_rx_info::sync_pos of the frame's packet: the join key)
+struct StreamSignal { int callIndex; int error; float power; float snr; long long pos; };
 
 /*! The RESIDENT receiver (lorahip_demod_receive with async = 3; lorahip_streamkernel.h, RES): one launch stays on the device across the
  * receiver's steps. The host describes a step in a ResidentMsg, written with plain stores into a ring in PINNED HOST memory (the
@@ -313,9 +327,10 @@ bool streamPairsAvailable(int sf, int log2WindowLanes);
 hipError_t launchStreamPairs(int sf, int log2WindowLanes, const StreamArgs &s, hipStream_t stream);
 hipError_t launchCompactRows(void *dst, const void *src, size_t rows, size_t srcPitchBytes, size_t rowBytes, hipStream_t stream);
 hipError_t launchPackSignals(const StreamSignal *sigOut, const int *nSig, size_t nChannels, int capPkt, int *channel, int *error, float *power, float *snr,
-                             size_t firstRow, size_t capRows, hipStream_t stream);
+                             long long *pos, size_t firstRow, size_t capRows, hipStream_t stream);
 hipError_t launchPackPackets(const StreamPacket *pktOut, const int *nPkt, const short *symOut, int *rowStart, size_t nChannels, int cap, int capPkt,
-                             size_t nPackets, long long *srcOff, unsigned short *symsOut, int stride, int *nsymsOut, int *channelOut, hipStream_t stream);
+                             size_t nPackets, long long *srcOff, unsigned short *symsOut, int stride, int *nsymsOut, int *channelOut, lorahip_rx_info *infoOut, int N,
+                             hipStream_t stream);
 hipError_t launchCopySegments(float2 *dst, const float2 *src, const long long *srcOff, const long long *dstOff, const int *len, size_t nSeg,
                               hipStream_t stream);
 hipError_t launchSynth(int sf, float2 *iq, const unsigned short *sym, size_t nWindows,
@@ -417,7 +432,8 @@ public:
     int getPacket(size_t i, int32_t *channel, int64_t *round, size_t *len, int16_t *out, size_t cap) const;
     int getPackets(int32_t *channels, int64_t *rounds, int64_t *lens, size_t capPackets, int16_t *syms, size_t capSyms) const;
     int getSignals(int32_t *channels, int64_t *rounds, int32_t *errors, float *powers, float *snrs, size_t cap) const;
-    int packetsToDevice(uint16_t *symsDev, size_t symStride, int32_t *nsymsDev, int32_t *channelDev, size_t capPackets, size_t *nPackets);
+    int getPacketsInfo(lorahip_rx_info *out, size_t cap) const; int getSignalsPos(int64_t *pos, size_t cap) const;
+    int packetsToDevice(uint16_t *symsDev, size_t symStride, int32_t *nsymsDev, int32_t *channelDev, lorahip_rx_info *infoDev, size_t capPackets, size_t *nPackets);
     void clearPackets();
     int64_t consumed(size_t c) const; int consumedAll(int64_t *out) const;
     int64_t workCalls() const; double kernelMs() const; int lastLaunches() const; int nearThreshold(int64_t *sq, int64_t *st) const;
@@ -435,8 +451,8 @@ private:
 //! a part's share of a mixed handle's packet hand-off (lorahip_demod.cpp): lorahip_demod_packets_to_device of the plain object `dm`, then
 //! channel_dev[j] = globalOf[channel_dev[j]] (globalOf: nLocal entries on the device) behind it on the object's stream. The device path
 //! returns with both queued, not waited for: demodStreamSync() ends it.
-int demodPacketsToDeviceQueued(lorahip_demod *dm, uint16_t *symsDev, size_t symStride, int32_t *nsymsDev, int32_t *channelDev, size_t capPackets,
-                               size_t *nPackets, const int32_t *globalOf, size_t nLocal);
+int demodPacketsToDeviceQueued(lorahip_demod *dm, uint16_t *symsDev, size_t symStride, int32_t *nsymsDev, int32_t *channelDev, lorahip_rx_info *infoDev,
+                               size_t capPackets, size_t *nPackets, const int32_t *globalOf, size_t nLocal);
 int demodStreamSync(lorahip_demod *dm);
 
 //! n host pieces -> device memory back to back from dDst, asynchronous on ctx->stream (pinned pieces by DMA straight away, the

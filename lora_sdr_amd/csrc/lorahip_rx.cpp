@@ -327,12 +327,42 @@ int Composite::getSignals(int32_t *channels, int64_t *rounds, int32_t *errors, f
     catch (const std::bad_alloc &) { setLastError("out of host memory"); return LORAHIP_E_NOMEM; }        // nothing may cross the C ABI
 }
 
+//! the parts' packet info / signal positions one after the other, in getPackets' / getSignals' order (positions are per channel: nothing to remap)
+int Composite::getPacketsInfo(lorahip_rx_info *out, const size_t cap) const
+{
+    if (out == nullptr || cap < numPackets()) return LORAHIP_E_INVALID;
+    size_t at = 0;
+    for (const auto &q : p->parts)
+    {
+        const size_t n = lorahip_demod_num_packets(q.d);
+        const int rc = n ? lorahip_demod_get_packets_info(q.d, out + at, n) : LORAHIP_OK;
+        if (rc != LORAHIP_OK) return rc;
+        at += n;
+    }
+    return LORAHIP_OK;
+}
+
+int Composite::getSignalsPos(int64_t *pos, const size_t cap) const
+{
+    if (pos == nullptr || cap < numSignals()) return LORAHIP_E_INVALID;
+    size_t at = 0;
+    for (const auto &q : p->parts)
+    {
+        const size_t n = lorahip_demod_num_signals(q.d);
+        const int rc = n ? lorahip_demod_get_signals_pos(q.d, pos + at, n) : LORAHIP_OK;
+        if (rc != LORAHIP_OK) return rc;
+        at += n;
+    }
+    return LORAHIP_OK;
+}
+
 /* The queued packets of every part as the rows of ONE decoder launch (lorahip_decode_packets_cfgs, table = configuration of channel): the
  * parts one after the other in the queue's order, each through the plain object's hand-off into its share of the rows -- packed on the
  * device, on the part's own stream, where its records are still the only copy; from its host queue otherwise -- and renumbered there from
  * local to global channels (the channels of one SF are not contiguous globally: a table per part, uploaded once). Nothing is waited for
  * until every part's work is queued; the rows are complete on return. */
-int Composite::packetsToDevice(uint16_t *symsDev, const size_t symStride, int32_t *nsymsDev, int32_t *channelDev, const size_t capPackets, size_t *nPackets)
+int Composite::packetsToDevice(uint16_t *symsDev, const size_t symStride, int32_t *nsymsDev, int32_t *channelDev, lorahip_rx_info *infoDev, const size_t capPackets,
+                               size_t *nPackets)
 {
     Impl &I = *p;
     for (const Impl::Part &q : I.parts)
@@ -366,7 +396,7 @@ int Composite::packetsToDevice(uint16_t *symsDev, const size_t symStride, int32_
         const size_t n = lorahip_demod_num_packets(q.d);
         if (n == 0) continue;
         size_t got = 0;
-        rc = demodPacketsToDeviceQueued(q.d, symsDev + at * symStride, symStride, nsymsDev + at, channelDev ? channelDev + at : nullptr, n, &got,
+        rc = demodPacketsToDeviceQueued(q.d, symsDev + at * symStride, symStride, nsymsDev + at, channelDev ? channelDev + at : nullptr, infoDev ? infoDev + at : nullptr, n, &got,
                                         q.dGlobalOf.get(), q.chan.size());
         if (rc != LORAHIP_OK) break;
         queued.push_back(&q);

@@ -91,7 +91,8 @@ __global__ void packCopy(const short *__restrict__ symOut, const long long *__re
 //! and one launch, s29_ / s36_. With ONE workgroup the descriptions in the same launch were slower by far -- 65536 packets walked by
 //! 1024 lanes, profiles/r04 -- and all three steps in one workgroup for launches of <= 2048 packets are slower too: s43_*.)
 __global__ void __launch_bounds__(1024) scanDescribe(const StreamPacket *__restrict__ pktOut, const int *__restrict__ nPkt, const unsigned nChannels, const int cap,
-                                                     const int capPkt, long long *__restrict__ srcOff, int *__restrict__ nsyms, int *__restrict__ channel)
+                                                     const int capPkt, long long *__restrict__ srcOff, int *__restrict__ nsyms, int *__restrict__ channel,
+                                                     lorahip_rx_info *__restrict__ info, const int N)
 {
     __shared__ int sWave[16];
     const unsigned first = blockIdx.x * 1024u, c = first + threadIdx.x;
@@ -117,22 +118,24 @@ __global__ void __launch_bounds__(1024) scanDescribe(const StreamPacket *__restr
     long long off = (long long)c * cap;
     for (int j = 0; j < mine; j++)
     {
-        const int len = pktOut[(size_t)c * capPkt + j].len;
+        const StreamPacket q = pktOut[(size_t)c * capPkt + j];
+        const int len = q.len;
         srcOff[row0 + j] = off;
         nsyms[row0 + j] = len;
         if (channel) channel[row0 + j] = (int)c;
+        if (info) info[row0 + j] = rxInfo(q.endPos, len, q.freqError, N);     // uniform over the launch: null unless asked for
         off += len;
     }
 }
 
 hipError_t launchPackPackets(const StreamPacket *pktOut, const int *nPkt, const short *symOut, int *rowStart, const size_t nChannels,
                              const int cap, const int capPkt, const size_t nPackets, long long *srcOff, unsigned short *symsOut, const int stride,
-                             int *nsymsOut, int *channelOut, hipStream_t stream)
+                             int *nsymsOut, int *channelOut, lorahip_rx_info *infoOut, const int N, hipStream_t stream)
 {
     if (nPackets == 0) return hipSuccess;
     (void)rowStart;                                     // (the row numbers stay in registers since the two steps are one launch)
     hipLaunchKernelGGL(scanDescribe, dim3(unsigned((nChannels + 1023) / 1024)), dim3(1024), 0, stream, pktOut, nPkt, unsigned(nChannels), cap, capPkt, srcOff,
-                       nsymsOut, channelOut);
+                       nsymsOut, channelOut, infoOut, N);
     hipLaunchKernelGGL(packCopy, dim3(unsigned(nPackets)), dim3(64), 0, stream, symOut, srcOff, nsymsOut, symsOut, stride);
     return hipGetLastError();
 }
@@ -145,7 +148,7 @@ hipError_t launchPackPackets(const StreamPacket *pktOut, const int *nPkt, const 
  **********************************************************************/
 __global__ void __launch_bounds__(1024) packSignals(const StreamSignal *__restrict__ sigOut, const int *__restrict__ nSig, const unsigned nChannels, const int capPkt,
                                                     int *__restrict__ channel, int *__restrict__ error, float *__restrict__ power, float *__restrict__ snr,
-                                                    const unsigned firstRow, const unsigned capRows)
+                                                    long long *__restrict__ pos, const unsigned firstRow, const unsigned capRows)
 {
     __shared__ int sWave[16];
     const unsigned first = blockIdx.x * 1024u, c = first + threadIdx.x;
@@ -174,15 +177,16 @@ __global__ void __launch_bounds__(1024) packSignals(const StreamSignal *__restri
         if (error) error[r] = q.error;
         if (power) power[r] = q.power;
         if (snr) snr[r] = q.snr;
+        if (pos) pos[r] = q.pos;
     }
 }
 
 hipError_t launchPackSignals(const StreamSignal *sigOut, const int *nSig, const size_t nChannels, const int capPkt, int *channel, int *error, float *power,
-                             float *snr, const size_t firstRow, const size_t capRows, hipStream_t stream)
+                             float *snr, long long *pos, const size_t firstRow, const size_t capRows, hipStream_t stream)
 {
     if (nChannels == 0) return hipSuccess;
     hipLaunchKernelGGL(packSignals, dim3(unsigned((nChannels + 1023) / 1024)), dim3(1024), 0, stream, sigOut, nSig, unsigned(nChannels), capPkt, channel, error, power,
-                       snr, unsigned(firstRow), unsigned(capRows));
+                       snr, pos, unsigned(firstRow), unsigned(capRows));
     return hipGetLastError();
 }
 

@@ -491,7 +491,7 @@ demodStream(const StreamArgs s)
                         const int symCount = st.symCount + 1;
                         const bool post = (unsigned)symCount >= s.mtu || squelchedB;                         // :291
                         if (tc == 0) o.symOut[o.nSym] = (short)valueB;                                       // out[_symCount++] = value  :290
-                        if (tc == 0 && post) { StreamPacket q; q.callIndex = st.callCount; q.len = symCount; o.pktOut[o.nPkt] = q; }   // :295-298
+                        if (tc == 0 && post) { StreamPacket q; q.callIndex = st.callCount; q.len = symCount; q.endPos = st.pos + N; q.freqError = st.freqError; q.pad = 0; o.pktOut[o.nPkt] = q; }   // :295-298
                         o.nSym++; o.nPkt += post ? 1 : 0; o.calls++;
                         st.finefreqError = post ? 0.0f : st.finefreqError;                                   // :299
                         st.state = post ? ST_FRAMESYNC : ST_DATASYMBOLS;                                     // :300
