@@ -660,7 +660,8 @@ int lorahip_decode_packets(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfg, con
                            const int32_t *nsyms_dev, size_t n_packets, uint8_t *out_dev, size_t out_stride,
                            int32_t *out_len_dev, int32_t *dropped_dev);
 /* The same with every buffer in HOST memory (staged through the context's pinned buffer; synchronous): what a host-side block calls
- * -- lora_sdr_amd/pothos/LoRaDecoderBatch.cpp collects the messages waiting on its inputs into rows and posts the bytes. */
+ * -- lora_sdr_amd/pothos/LoRaDecoderBatch.cpp collects the messages waiting on its inputs into rows and posts the bytes. The bytes of
+ * an output row behind out_len (the whole row where out_len < 0) are unspecified: the rows are copied out, never in. */
 int lorahip_decode_packets_host(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfg, const uint16_t *syms, size_t sym_stride,
                                 const int32_t *nsyms, size_t n_packets, uint8_t *out, size_t out_stride, int32_t *out_len,
                                 int32_t *dropped);

@@ -1532,6 +1532,76 @@ class LoRaDemod(_Handle):
         return [dict((f, getattr(r, f)) for f, _ in WorkResult._fields_) for r in arr]
 
 
+def _table_args(table):
+    """(pointer, entries) of an optional (T,) int32 device table"""
+    return _dptr(table), 0 if table is None else int(table.numel())
+
+
+def _index_ok(index, table, P, rows_ok=True):
+    import torch
+    if index.dtype != torch.int32 or index.numel() != P or not rows_ok or (table is not None and table.dtype != torch.int32):
+        raise ValueError("index must be (P,) int32, table (T,) int32 device tensors")
+
+
+def _decode_rows(ctx, cfgs, n_cfgs, syms, nsyms, index, table, info):
+    """the one decoder call of LoRaDecoder (index None) and LoRaDecoderSet: checks, outputs, lorahip_decode_packets_info on the torch
+    stream -> (out, out_len, dropped), and the (P, 8) header report with info"""
+    import torch
+    if syms.dim() != 2 or syms.dtype not in (torch.int16, torch.uint16) or nsyms.dtype != torch.int32:
+        raise ValueError("syms must be (P, stride) 16-bit, nsyms (P,) int32 device tensors")
+    P, stride = int(syms.shape[0]), int(syms.shape[1])
+    if index is not None:
+        _index_ok(index, table, P, nsyms.numel() == P)
+        index, table = index.contiguous(), None if table is None else table.contiguous()
+    syms, nsyms = syms.contiguous(), nsyms.contiguous()
+    out_stride = 2 * (stride + 8)
+    out = torch.zeros((P, out_stride), dtype=torch.uint8, device=syms.device)
+    out_len = torch.empty(P, dtype=torch.int32, device=syms.device)
+    dropped = torch.empty(P, dtype=torch.int32, device=syms.device)
+    rep = torch.empty((P, 8), dtype=torch.int32, device=syms.device) if info else None
+    ctx.use_torch_stream()
+    check(ctx._lib.lorahip_decode_packets_info(ctx._h, cfgs, n_cfgs, _dptr(index), *_table_args(table), _dptr(syms), stride, _dptr(nsyms), P,
+                                               _dptr(out), out_stride, _dptr(out_len), _dptr(dropped), _dptr(rep)), "lorahip_decode_packets_info")
+    return (out, out_len, dropped, rep) if info else (out, out_len, dropped)
+
+
+def _encode_rows(ctx, cfgs, n_cfgs, data, nbytes, index, table, sym_stride):
+    """the one encoder call of LoRaEncoder (index None: lorahip_encode_packets) and LoRaEncoderSet (lorahip_encode_packets_cfgs): checks,
+    outputs, the call on the torch stream -> (syms, nsyms)"""
+    import torch
+    if data.dim() != 2 or data.dtype != torch.uint8 or nbytes.dtype != torch.int32 or nbytes.numel() != data.shape[0]:
+        raise ValueError("data must be a (P, stride) uint8, nbytes a (P,) int32 device tensor")
+    P, stride = int(data.shape[0]), int(data.shape[1])
+    if index is not None:
+        _index_ok(index, table, P)
+        index, table = index.contiguous(), None if table is None else table.contiguous()
+    data, nbytes = data.contiguous(), nbytes.contiguous()
+    syms = torch.empty((P, int(sym_stride)), dtype=torch.int16, device=data.device)
+    nsyms = torch.empty(P, dtype=torch.int32, device=data.device)
+    ctx.use_torch_stream()
+    rows = (C.c_void_p(data.data_ptr()), stride, _dptr(nbytes), P, _dptr(syms), int(sym_stride), _dptr(nsyms))
+    if index is None:
+        check(ctx._lib.lorahip_encode_packets(ctx._h, cfgs, *rows), "lorahip_encode_packets")
+    else:
+        check(ctx._lib.lorahip_encode_packets_cfgs(ctx._h, cfgs, n_cfgs, _dptr(index), *_table_args(table), *rows), "lorahip_encode_packets_cfgs")
+    return syms, nsyms
+
+
+def _pack_symbols(packets):
+    """list of symbol arrays -> ((P, stride) uint16 rows, stride at least 8, and (P,) int32 counts)"""
+    host = np.zeros((len(packets), max(8, max(len(p) for p in packets))), np.uint16)
+    for i, p in enumerate(packets):
+        host[i, :len(p)] = np.asarray(p).astype(np.uint16)
+    return host, np.array([len(p) for p in packets], np.int32)
+
+
+def _decoded(out, out_len, interleaving):
+    """the result list of a decoder's work(): a row's bytes (16-bit words without the de-interleaver: interleaving[i] false), None where
+    the block posts nothing"""
+    return [None if out_len[i] < 0 else out[i, :out_len[i]].copy() if interleaving[i] else out[i, :2 * out_len[i]].view(np.uint16).copy()
+            for i in range(len(out_len))]
+
+
 class LoRaDecoder:
     """The `/lora/lora_decoder` block (LoRaDecoder.cpp), same setters and defaults, for batches of symbol packets.
 
@@ -1577,25 +1647,7 @@ class LoRaDecoder:
         """syms: (P, stride) int16/uint16 device tensor, nsyms: (P,) int32 device tensor ->
         (out uint8 (P, out_stride), out_len int32 (P,), dropped int32 (P,)) device tensors; info=True: a fourth, (P, 8) int32 -- the
         header report, a row per packet with the fields of struct lorahip_packet_info in include/lorahip.h"""
-        import torch
-        if syms.dim() != 2 or syms.dtype not in (torch.int16, torch.uint16) or nsyms.dtype != torch.int32:
-            raise ValueError("syms must be (P, stride) 16-bit, nsyms (P,) int32 device tensors")
-        syms, nsyms = syms.contiguous(), nsyms.contiguous()
-        P, stride = int(syms.shape[0]), int(syms.shape[1])
-        out_stride = 2 * (stride + 8)
-        out = torch.zeros((P, out_stride), dtype=torch.uint8, device=syms.device)
-        out_len = torch.empty(P, dtype=torch.int32, device=syms.device)
-        dropped = torch.empty(P, dtype=torch.int32, device=syms.device)
-        self._ctx.use_torch_stream()
-        if info:
-            rep = torch.empty((P, 8), dtype=torch.int32, device=syms.device)
-            check(self._ctx._lib.lorahip_decode_packets_info(self._ctx._h, C.byref(self._cfg), 1, None, None, 0, _dptr(syms), stride, _dptr(nsyms), P,
-                                                             _dptr(out), out_stride, _dptr(out_len), _dptr(dropped), _dptr(rep)),
-                  "lorahip_decode_packets_info")
-            return out, out_len, dropped, rep
-        check(self._ctx._lib.lorahip_decode_packets(self._ctx._h, C.byref(self._cfg), _dptr(syms), stride, _dptr(nsyms), P,
-                                                    _dptr(out), out_stride, _dptr(out_len), _dptr(dropped)), "lorahip_decode_packets")
-        return out, out_len, dropped
+        return _decode_rows(self._ctx, C.byref(self._cfg), 1, syms, nsyms, None, None, info)
 
     def work(self, packets):
         import torch
@@ -1604,24 +1656,12 @@ class LoRaDecoder:
         P = len(packets)
         if P == 0:
             return []
-        stride = max(8, max(len(p) for p in packets))
-        host = np.zeros((P, stride), np.uint16)
-        for i, p in enumerate(packets):
-            host[i, :len(p)] = np.asarray(p).astype(np.uint16)
-        n = np.array([len(p) for p in packets], np.int32)
+        host, n = _pack_symbols(packets)
         dev = torch.device("cuda", self._ctx.device)
         out, out_len, dropped = self.decode_batch(torch.from_numpy(host.view(np.int16)).to(dev), torch.from_numpy(n).to(dev))
         out, out_len, dropped = out.cpu().numpy(), out_len.cpu().numpy(), dropped.cpu().numpy()
         self._dropped += int(dropped.sum())
-        res = []
-        for i in range(P):
-            if out_len[i] < 0:
-                res.append(None)
-            elif self._cfg.interleaving:
-                res.append(out[i, :out_len[i]].copy())
-            else:
-                res.append(out[i, :2 * out_len[i]].view(np.uint16).copy())
-        return res
+        return _decoded(out, out_len, [self._cfg.interleaving] * P)
 
 
 class LoRaDecoderSet:
@@ -1664,31 +1704,7 @@ class LoRaDecoderSet:
         """syms: (P, stride) int16/uint16, nsyms: (P,) int32, index: (P,) int32, table: (T,) int32 or None -- device tensors ->
         (out uint8 (P, out_stride), out_len int32 (P,), dropped int32 (P,)) device tensors, as LoRaDecoder.decode_batch (info=True: and the
         (P, 8) int32 header report)"""
-        import torch
-        if syms.dim() != 2 or syms.dtype not in (torch.int16, torch.uint16) or nsyms.dtype != torch.int32:
-            raise ValueError("syms must be (P, stride) 16-bit, nsyms (P,) int32 device tensors")
-        P, stride = int(syms.shape[0]), int(syms.shape[1])
-        if index.dtype != torch.int32 or index.numel() != P or nsyms.numel() != P or (table is not None and table.dtype != torch.int32):
-            raise ValueError("index must be (P,) int32, table (T,) int32 device tensors")
-        syms, nsyms, index = syms.contiguous(), nsyms.contiguous(), index.contiguous()
-        table = None if table is None else table.contiguous()
-        out_stride = 2 * (stride + 8)
-        out = torch.zeros((P, out_stride), dtype=torch.uint8, device=syms.device)
-        out_len = torch.empty(P, dtype=torch.int32, device=syms.device)
-        dropped = torch.empty(P, dtype=torch.int32, device=syms.device)
-        self._ctx.use_torch_stream()
-        if info:
-            rep = torch.empty((P, 8), dtype=torch.int32, device=syms.device)
-            check(self._ctx._lib.lorahip_decode_packets_info(self._ctx._h, self._cfgs, len(self._cfgs), _dptr(index),
-                                                             None if table is None else _dptr(table), 0 if table is None else int(table.numel()),
-                                                             _dptr(syms), stride, _dptr(nsyms), P, _dptr(out), out_stride, _dptr(out_len), _dptr(dropped),
-                                                             _dptr(rep)), "lorahip_decode_packets_info")
-            return out, out_len, dropped, rep
-        check(self._ctx._lib.lorahip_decode_packets_cfgs(self._ctx._h, self._cfgs, len(self._cfgs), _dptr(index),
-                                                         None if table is None else _dptr(table), 0 if table is None else int(table.numel()),
-                                                         _dptr(syms), stride, _dptr(nsyms), P, _dptr(out), out_stride, _dptr(out_len), _dptr(dropped)),
-              "lorahip_decode_packets_cfgs")
-        return out, out_len, dropped
+        return _decode_rows(self._ctx, self._cfgs, len(self._cfgs), syms, nsyms, index, table, info)
 
     def work(self, packets, index):
         """list of symbol arrays and the decoder of each -> list of bytes arrays (None where the block posts nothing), as
@@ -1699,30 +1715,19 @@ class LoRaDecoderSet:
             raise ValueError("LoRaDecoderSet.work(): one index per packet")
         if P == 0:
             return []
-        stride = max(8, max(len(p) for p in packets))
-        host = np.zeros((P, stride), np.uint16)
-        for i, p in enumerate(packets):
-            host[i, :len(p)] = np.asarray(p).astype(np.uint16)
-        n = np.array([len(p) for p in packets], np.int32)
+        host, n = _pack_symbols(packets)
         idx = np.asarray(index, np.int64)
         dev = torch.device("cuda", self._ctx.device)
         out, out_len, dropped = self.decode_batch(torch.from_numpy(host.view(np.int16)).to(dev), torch.from_numpy(n).to(dev),
                                                   torch.from_numpy(np.clip(idx, -1, 2 ** 31 - 1).astype(np.int32)).to(dev))
         out, out_len, dropped = out.cpu().numpy(), out_len.cpu().numpy(), dropped.cpu().numpy()
         self._dropped += int(dropped.sum())
-        res = []
         for i in range(P):
             if out_len[i] == -3:
                 raise ValueError("LoRaDecoderSet.work(): packet %d names decoder %d of %d" % (i, int(idx[i]), len(self._cfgs)))
             if out_len[i] == -2:
                 raise ValueError("LoRaDecoderSet.work(): packet %d does not fit its row" % i)
-            if out_len[i] < 0:
-                res.append(None)
-            elif self._cfgs[int(idx[i])].interleaving:
-                res.append(out[i, :out_len[i]].copy())
-            else:
-                res.append(out[i, :2 * out_len[i]].view(np.uint16).copy())
-        return res
+        return _decoded(out, out_len, [self._cfgs[int(j)].interleaving for j in idx])
 
 
 class LoRaEncoder:
@@ -1760,19 +1765,9 @@ class LoRaEncoder:
     def encode_batch(self, data, nbytes, sym_stride=None):
         """data: (P, stride) uint8 device tensor, nbytes: (P,) int32 device tensor -> (syms uint16-as-int16 (P, sym_stride), nsyms int32
         (P,)) device tensors, queued on the torch stream. sym_stride defaults to what a message of `stride` bytes needs."""
-        import torch
-        if data.dim() != 2 or data.dtype != torch.uint8 or nbytes.dtype != torch.int32 or nbytes.numel() != data.shape[0]:
-            raise ValueError("data must be a (P, stride) uint8, nbytes a (P,) int32 device tensor")
-        data, nbytes = data.contiguous(), nbytes.contiguous()
-        P, stride = int(data.shape[0]), int(data.shape[1])
-        if sym_stride is None:
-            sym_stride = max(8, self.num_symbols(min(stride, self._ctx._lib.lorahip_encode_max_bytes())))
-        syms = torch.empty((P, int(sym_stride)), dtype=torch.int16, device=data.device)
-        nsyms = torch.empty(P, dtype=torch.int32, device=data.device)
-        self._ctx.use_torch_stream()
-        check(self._ctx._lib.lorahip_encode_packets(self._ctx._h, C.byref(self._cfg), C.c_void_p(data.data_ptr()), stride, _dptr(nbytes), P,
-                                                    _dptr(syms), int(sym_stride), _dptr(nsyms)), "lorahip_encode_packets")
-        return syms, nsyms
+        if sym_stride is None and data.dim() == 2:
+            sym_stride = max(8, self.num_symbols(min(int(data.shape[1]), self._ctx._lib.lorahip_encode_max_bytes())))
+        return _encode_rows(self._ctx, C.byref(self._cfg), 1, data, nbytes, None, None, sym_stride)
 
     def work(self, messages):
         import torch
@@ -1877,24 +1872,9 @@ class LoRaEncoderSet:
         """data: (P, stride) uint8, nbytes: (P,) int32, index: (P,) int32, table: (T,) int32 or None -- device tensors -> (syms
         uint16-as-int16 (P, sym_stride), nsyms int32 (P,)) device tensors, queued on the torch stream. sym_stride defaults to what a
         message of `stride` bytes needs under the member that makes most of it."""
-        import torch
-        if data.dim() != 2 or data.dtype != torch.uint8 or nbytes.dtype != torch.int32 or nbytes.numel() != data.shape[0]:
-            raise ValueError("data must be a (P, stride) uint8, nbytes a (P,) int32 device tensor")
-        P, stride = int(data.shape[0]), int(data.shape[1])
-        if index.dtype != torch.int32 or index.numel() != P or (table is not None and table.dtype != torch.int32):
-            raise ValueError("index must be (P,) int32, table (T,) int32 device tensors")
-        data, nbytes, index = data.contiguous(), nbytes.contiguous(), index.contiguous()
-        table = None if table is None else table.contiguous()
-        if sym_stride is None:
-            sym_stride = self.max_symbols(min(stride, self._ctx._lib.lorahip_encode_max_bytes()))
-        syms = torch.empty((P, int(sym_stride)), dtype=torch.int16, device=data.device)
-        nsyms = torch.empty(P, dtype=torch.int32, device=data.device)
-        self._ctx.use_torch_stream()
-        check(self._ctx._lib.lorahip_encode_packets_cfgs(self._ctx._h, self._cfgs, len(self._cfgs), _dptr(index),
-                                                         None if table is None else _dptr(table), 0 if table is None else int(table.numel()),
-                                                         C.c_void_p(data.data_ptr()), stride, _dptr(nbytes), P, _dptr(syms), int(sym_stride),
-                                                         _dptr(nsyms)), "lorahip_encode_packets_cfgs")
-        return syms, nsyms
+        if sym_stride is None and data.dim() == 2:
+            sym_stride = self.max_symbols(min(int(data.shape[1]), self._ctx._lib.lorahip_encode_max_bytes()))
+        return _encode_rows(self._ctx, self._cfgs, len(self._cfgs), data, nbytes, index, table, sym_stride)
 
     def work(self, messages, index):
         """list of bytes-like and the encoder of each -> list of uint16 symbol arrays (None where the block has no defined result), as

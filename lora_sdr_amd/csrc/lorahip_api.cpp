@@ -66,8 +66,8 @@ static bool isGfx950(const int device)
     return std::strncmp(prop.gcnArchName, "gfx950", 6) == 0;
 }
 
-//! device and pinned-host staging of the host-pointer entry point (the IQ itself goes through gatherUpload: device side only)
-static int growStage(lorahip_ctx *ctx, const size_t devBytes, const size_t hostBytes)
+//! device and pinned-host staging of the host-pointer entry points (the IQ itself goes through gatherUpload: device side only)
+int growStage(lorahip_ctx *ctx, const size_t devBytes, const size_t hostBytes)
 {
     if (devBytes <= ctx->dStage.bytes() && hostBytes <= ctx->hStage.bytes()) return LORAHIP_OK;
     LORAHIP_TRY(regrowPair(ctx->dStage, devBytes + devBytes / 4, ctx->hStage, hostBytes + hostBytes / 4 + 256, hipHostMallocDefault));
@@ -435,306 +435,8 @@ int lorahip_add_awgn(lorahip_ctx *ctx, float *iq_dev, const size_t n_samples, co
     return LORAHIP_OK;
 }
 
-//! what lorahip_decode_packets refuses of a configuration (host arithmetic only): shared with the table launch and lorahip_decode_plan
-static int decoderCfgOk(const lorahip_decoder_cfg *cfg)
-{
-    if (cfg->struct_size != sizeof(lorahip_decoder_cfg)) return LORAHIP_E_INVALID;
-    if (cfg->sf < 1 || cfg->sf > LORAHIP_SF_MAX || cfg->ppm < 0 || cfg->ppm > cfg->sf || cfg->rdd < LORAHIP_RDD_FROM_HEADER || cfg->rdd > 4 || cfg->data_length < 0) return LORAHIP_E_INVALID;
-    // the rate from the header: there has to be one, and the de-interleaver that reaches it
-    if (cfg->rdd == LORAHIP_RDD_FROM_HEADER && !(cfg->explicit_hdr && cfg->interleaving))
-    {
-        setLastError("rdd = LORAHIP_RDD_FROM_HEADER needs explicit_hdr = 1 and interleaving = 1");
-        return LORAHIP_E_INVALID;
-    }
-    // An explicit header occupies the first 5 codewords of the first (PPM-codeword) block: with fewer than 5 bits per symbol the
-    // reference whitens `PPM - 5` (an unsigned short: ~65535) codewords past its buffer (LoRaDecoder.cpp:235, undefined behaviour).
-    // There is nothing to be identical to; refuse the configuration instead of corrupting device memory.
-    if (cfg->explicit_hdr && cfg->interleaving && (cfg->ppm ? cfg->ppm : cfg->sf) < 5)
-    {
-        setLastError("explicit header needs a symbol size (PPM) of at least 5 bits");
-        return LORAHIP_E_INVALID;
-    }
-    // without a header the length of every packet is the setter's: what the decoder's tables reach bounds it (the reference has no bound;
-    // a LoRa length field is one byte). Refused loudly -- never a packet silently not decoded.
-    if (!cfg->explicit_hdr && cfg->interleaving && cfg->data_length > decodeMaxDataLength())
-    {
-        setLastError("data_length beyond what this build decodes (lorahip_decode_max_data_length())");
-        return LORAHIP_E_INVALID;
-    }
-    return LORAHIP_OK;
-}
-
-static bool decodeRowsOk(const size_t sym_stride, const size_t out_stride)
-{
-    return !(sym_stride == 0 || sym_stride > size_t(decodeMaxSymbols()) || (out_stride & 1) || out_stride < 2 * (sym_stride + 8));
-}
-
-static DecodeCfg decodeCfgOf(const lorahip_decoder_cfg &c)
-{
-    const DecodeCfg d = { c.sf, c.ppm, c.rdd, c.crcc, c.interleaving, c.error_check, c.explicit_hdr, c.hdr, c.data_length, 0, 0 };
-    return d;
-}
-
-int lorahip_decode_packets(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfg, const uint16_t *syms_dev, const size_t sym_stride,
-                           const int32_t *nsyms_dev, const size_t n_packets, uint8_t *out_dev, const size_t out_stride,
-                           int32_t *out_len_dev, int32_t *dropped_dev)
-{
-    if (ctx == nullptr || cfg == nullptr || cfg->struct_size != sizeof(lorahip_decoder_cfg)) return LORAHIP_E_INVALID;
-    if (n_packets == 0) return LORAHIP_OK;
-    if (!syms_dev || !nsyms_dev || !out_dev || !out_len_dev || !dropped_dev || n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
-    { const int rc = decoderCfgOk(cfg); if (rc != LORAHIP_OK) return rc; }
-    if (!decodeRowsOk(sym_stride, out_stride)) return LORAHIP_E_INVALID;
-    return lorahip_decode_packets_info(ctx, cfg, 1, nullptr, nullptr, 0, syms_dev, sym_stride, nsyms_dev, n_packets, out_dev, out_stride, out_len_dev,
-                                       dropped_dev, nullptr);
-}
-
-/* The same for a caller in HOST memory (a Pothos block: lora_sdr_amd/pothos/LoRaDecoderBatch.cpp): the rows are staged through the
- * context's pinned buffer, decoded, and the three outputs copied back; synchronous. */
-int lorahip_decode_packets_host(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfg, const uint16_t *syms, const size_t sym_stride,
-                                const int32_t *nsyms, const size_t n_packets, uint8_t *out, const size_t out_stride, int32_t *out_len,
-                                int32_t *dropped)
-{
-    if (ctx == nullptr || cfg == nullptr) return LORAHIP_E_INVALID;
-    if (n_packets == 0) return LORAHIP_OK;
-    if (!syms || !nsyms || !out || !out_len || !dropped || n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
-    if (sym_stride == 0 || sym_stride > size_t(decodeMaxSymbols()) || (out_stride & 1) || out_stride < 2 * (sym_stride + 8)) return LORAHIP_E_INVALID;
-    const DeviceGuard guard(ctx->device);
-    struct Piece { size_t off, bytes; };
-    size_t cur = 0;
-    auto carve = [&cur](const size_t bytes) { Piece p = { cur, bytes }; cur += (bytes + 255) & ~size_t(255); return p; };
-    const Piece pSym = carve(n_packets * sym_stride * sizeof(uint16_t));
-    const Piece pN = carve(n_packets * sizeof(int32_t));
-    const size_t inBytes = cur;
-    const Piece pOut = carve(n_packets * out_stride);
-    const Piece pLen = carve(n_packets * sizeof(int32_t));
-    const Piece pDrop = carve(n_packets * sizeof(int32_t));
-    { const int rc = growStage(ctx, cur, cur); if (rc != LORAHIP_OK) return rc; }
-    char *d = ctx->dStage.get(), *h = ctx->hStage.get();
-    std::memcpy(h + pSym.off, syms, pSym.bytes);
-    std::memcpy(h + pN.off, nsyms, pN.bytes);
-    LORAHIP_TRY(hipMemcpyAsync(d, h, inBytes, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = lorahip_decode_packets(ctx, cfg, reinterpret_cast<const uint16_t *>(d + pSym.off), sym_stride, reinterpret_cast<const int32_t *>(d + pN.off),
-                                          n_packets, reinterpret_cast<uint8_t *>(d + pOut.off), out_stride, reinterpret_cast<int32_t *>(d + pLen.off),
-                                          reinterpret_cast<int32_t *>(d + pDrop.off));
-    if (rc != LORAHIP_OK) return rc;
-    LORAHIP_TRY(hipMemcpyAsync(h + inBytes, d + inBytes, cur - inBytes, hipMemcpyDeviceToHost, ctx->stream));
-    LORAHIP_TRY(hipStreamSynchronize(ctx->stream));
-    std::memcpy(out, h + pOut.off, pOut.bytes);
-    std::memcpy(out_len, h + pLen.off, pLen.bytes);
-    std::memcpy(dropped, h + pDrop.off, pDrop.bytes);
-    return LORAHIP_OK;
-}
-
-//! the argument checks of the table launch and of the plan query that need no device
-static int decodeCfgsOk(const lorahip_decoder_cfg *cfgs, const size_t n_cfgs)
-{
-    if (cfgs == nullptr || n_cfgs == 0 || n_cfgs > size_t(LORAHIP_DEC_MAX_CFGS)) return LORAHIP_E_INVALID;
-    for (size_t i = 0; i < n_cfgs; i++) { const int rc = decoderCfgOk(cfgs + i); if (rc != LORAHIP_OK) return rc; }
-    return LORAHIP_OK;
-}
-
-int lorahip_decode_packets_cfgs(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfgs, const size_t n_cfgs, const int32_t *index_dev,
-                                const int32_t *table_dev, const size_t n_table, const uint16_t *syms_dev, const size_t sym_stride,
-                                const int32_t *nsyms_dev, const size_t n_packets, uint8_t *out_dev, const size_t out_stride,
-                                int32_t *out_len_dev, int32_t *dropped_dev)
-{
-    if (ctx == nullptr) return LORAHIP_E_INVALID;
-    { const int rc = decodeCfgsOk(cfgs, n_cfgs); if (rc != LORAHIP_OK) return rc; }
-    if ((table_dev != nullptr && n_table == 0) || n_table > 0x7fffffffu || !decodeRowsOk(sym_stride, out_stride)) return LORAHIP_E_INVALID;
-    if (n_packets == 0) return LORAHIP_OK;
-    if (!index_dev || !syms_dev || !nsyms_dev || !out_dev || !out_len_dev || !dropped_dev || n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
-    return lorahip_decode_packets_info(ctx, cfgs, n_cfgs, index_dev, table_dev, n_table, syms_dev, sym_stride, nsyms_dev, n_packets, out_dev, out_stride,
-                                       out_len_dev, dropped_dev, nullptr);
-}
-
-/* The one launch behind every decoder entry point: a table of configurations (index_dev NULL: the uniform launch under its only entry) and,
- * where asked for, the header report of every packet. */
-int lorahip_decode_packets_info(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfgs, const size_t n_cfgs, const int32_t *index_dev,
-                                const int32_t *table_dev, const size_t n_table, const uint16_t *syms_dev, const size_t sym_stride,
-                                const int32_t *nsyms_dev, const size_t n_packets, uint8_t *out_dev, const size_t out_stride,
-                                int32_t *out_len_dev, int32_t *dropped_dev, lorahip_packet_info *info_dev)
-{
-    static_assert(sizeof(lorahip_packet_info) == 32, "the kernels write eight int32 per packet");
-    if (ctx == nullptr) return LORAHIP_E_INVALID;
-    { const int rc = decodeCfgsOk(cfgs, n_cfgs); if (rc != LORAHIP_OK) return rc; }
-    if (index_dev == nullptr && (n_cfgs != 1 || table_dev != nullptr)) return LORAHIP_E_INVALID;
-    if ((table_dev != nullptr && n_table == 0) || n_table > 0x7fffffffu || !decodeRowsOk(sym_stride, out_stride)) return LORAHIP_E_INVALID;
-    if (n_packets == 0) return LORAHIP_OK;
-    if (!syms_dev || !nsyms_dev || !out_dev || !out_len_dev || !dropped_dev || n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
-    const DeviceGuard guard(ctx->device);
-    DecodeArgs a = {};
-    a.syms = syms_dev; a.nsyms = nsyms_dev; a.out = out_dev; a.outLen = out_len_dev; a.dropped = dropped_dev;
-    a.nPackets = unsigned(n_packets); a.symStride = int(sym_stride); a.outStride = int(out_stride);
-    a.info = reinterpret_cast<int *>(info_dev);
-    if (index_dev == nullptr)
-    {
-        const lorahip_decoder_cfg *cfg = cfgs;
-        a.sf = cfg->sf; a.ppm = cfg->ppm; a.rdd = cfg->rdd; a.crcc = cfg->crcc; a.interleaving = cfg->interleaving;
-        a.errorCheck = cfg->error_check; a.explicitHdr = cfg->explicit_hdr; a.hdr = cfg->hdr; a.dataLength = cfg->data_length;
-        LORAHIP_TRY(launchDecode(a, ctx->variant, ctx->stream));
-        return LORAHIP_OK;
-    }
-    DecodeCfg tab[LORAHIP_DEC_MAX_CFGS];
-    for (size_t i = 0; i < n_cfgs; i++) tab[i] = decodeCfgOf(cfgs[i]);
-    LORAHIP_TRY(launchDecodeCfgs(a, tab, n_cfgs, index_dev, table_dev, int(n_table), ctx->variant, ctx->stream));
-    return LORAHIP_OK;
-}
-
-int lorahip_decode_packets_cfgs_host(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfgs, const size_t n_cfgs, const int32_t *index,
-                                     const int32_t *table, const size_t n_table, const uint16_t *syms, const size_t sym_stride,
-                                     const int32_t *nsyms, const size_t n_packets, uint8_t *out, const size_t out_stride, int32_t *out_len,
-                                     int32_t *dropped)
-{
-    if (ctx == nullptr) return LORAHIP_E_INVALID;
-    { const int rc = decodeCfgsOk(cfgs, n_cfgs); if (rc != LORAHIP_OK) return rc; }
-    if ((table != nullptr && n_table == 0) || n_table > 0x7fffffffu || !decodeRowsOk(sym_stride, out_stride)) return LORAHIP_E_INVALID;
-    if (n_packets == 0) return LORAHIP_OK;
-    if (!index) return LORAHIP_E_INVALID;
-    return lorahip_decode_packets_info_host(ctx, cfgs, n_cfgs, index, table, n_table, syms, sym_stride, nsyms, n_packets, out, out_stride, out_len, dropped,
-                                            nullptr);
-}
-
-int lorahip_decode_packets_info_host(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfgs, const size_t n_cfgs, const int32_t *index,
-                                     const int32_t *table, const size_t n_table, const uint16_t *syms, const size_t sym_stride,
-                                     const int32_t *nsyms, const size_t n_packets, uint8_t *out, const size_t out_stride, int32_t *out_len,
-                                     int32_t *dropped, lorahip_packet_info *info)
-{
-    if (ctx == nullptr) return LORAHIP_E_INVALID;
-    { const int rc = decodeCfgsOk(cfgs, n_cfgs); if (rc != LORAHIP_OK) return rc; }
-    if (index == nullptr && (n_cfgs != 1 || table != nullptr)) return LORAHIP_E_INVALID;
-    if ((table != nullptr && n_table == 0) || n_table > 0x7fffffffu || !decodeRowsOk(sym_stride, out_stride)) return LORAHIP_E_INVALID;
-    if (n_packets == 0) return LORAHIP_OK;
-    if (!syms || !nsyms || !out || !out_len || !dropped || n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
-    const DeviceGuard guard(ctx->device);
-    struct Piece { size_t off, bytes; };
-    size_t cur = 0;
-    auto carve = [&cur](const size_t bytes) { Piece p = { cur, bytes }; cur += (bytes + 255) & ~size_t(255); return p; };
-    const Piece pSym = carve(n_packets * sym_stride * sizeof(uint16_t));
-    const Piece pN = carve(n_packets * sizeof(int32_t));
-    const Piece pIdx = carve(index ? n_packets * sizeof(int32_t) : 0);
-    const Piece pTab = carve(table ? n_table * sizeof(int32_t) : 0);
-    const size_t inBytes = cur;
-    const Piece pOut = carve(n_packets * out_stride);
-    const Piece pLen = carve(n_packets * sizeof(int32_t));
-    const Piece pDrop = carve(n_packets * sizeof(int32_t));
-    const Piece pInfo = carve(info ? n_packets * sizeof(lorahip_packet_info) : 0);
-    { const int rc = growStage(ctx, cur, cur); if (rc != LORAHIP_OK) return rc; }
-    char *d = ctx->dStage.get(), *h = ctx->hStage.get();
-    std::memcpy(h + pSym.off, syms, pSym.bytes);
-    std::memcpy(h + pN.off, nsyms, pN.bytes);
-    if (index) std::memcpy(h + pIdx.off, index, pIdx.bytes);
-    if (table) std::memcpy(h + pTab.off, table, pTab.bytes);
-    // the output rows travel both ways: a packet without an entry (-3) leaves its row as the caller had it
-    std::memcpy(h + pOut.off, out, pOut.bytes);
-    LORAHIP_TRY(hipMemcpyAsync(d, h, pOut.off + pOut.bytes, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = lorahip_decode_packets_info(ctx, cfgs, n_cfgs, index ? reinterpret_cast<const int32_t *>(d + pIdx.off) : nullptr,
-                                               table ? reinterpret_cast<const int32_t *>(d + pTab.off) : nullptr, n_table,
-                                               reinterpret_cast<const uint16_t *>(d + pSym.off), sym_stride, reinterpret_cast<const int32_t *>(d + pN.off),
-                                               n_packets, reinterpret_cast<uint8_t *>(d + pOut.off), out_stride, reinterpret_cast<int32_t *>(d + pLen.off),
-                                               reinterpret_cast<int32_t *>(d + pDrop.off),
-                                               info ? reinterpret_cast<lorahip_packet_info *>(d + pInfo.off) : nullptr);
-    if (rc != LORAHIP_OK) return rc;
-    LORAHIP_TRY(hipMemcpyAsync(h + inBytes, d + inBytes, cur - inBytes, hipMemcpyDeviceToHost, ctx->stream));
-    LORAHIP_TRY(hipStreamSynchronize(ctx->stream));
-    std::memcpy(out, h + pOut.off, pOut.bytes);
-    std::memcpy(out_len, h + pLen.off, pLen.bytes);
-    std::memcpy(dropped, h + pDrop.off, pDrop.bytes);
-    if (info) std::memcpy(info, h + pInfo.off, pInfo.bytes);
-    return LORAHIP_OK;
-}
-
-int lorahip_decode_plan(const lorahip_decoder_cfg *cfgs, const size_t n_cfgs, const size_t sym_stride, lorahip_decode_tiling *plan)
-{
-    if (plan == nullptr || plan->struct_size != sizeof(lorahip_decode_tiling)) return LORAHIP_E_INVALID;
-    *plan = lorahip_decode_tiling();
-    plan->struct_size = sizeof(lorahip_decode_tiling);
-    { const int rc = decodeCfgsOk(cfgs, n_cfgs); if (rc != LORAHIP_OK) return rc; }
-    if (sym_stride == 0 || sym_stride > size_t(decodeMaxSymbols())) return LORAHIP_E_INVALID;
-    DecodeCfg tab[LORAHIP_DEC_MAX_CFGS];
-    for (size_t i = 0; i < n_cfgs; i++) tab[i] = decodeCfgOf(cfgs[i]);
-    const DecodeTiling t = decodePlan(tab, n_cfgs, int(sym_stride));
-    plan->lanes_per_packet = t.lanes; plan->sym_cap = t.symCap; plan->cw_cap = t.cwCap; plan->lds_slice_bytes = t.slice; plan->packets_per_workgroup = t.perBlock;
-    return LORAHIP_OK;
-}
-
-int lorahip_decode_max_symbols(void) { return decodeMaxSymbols(); }
-int lorahip_decode_max_data_length(void) { return decodeMaxDataLength(); }
-
-/***********************************************************************
- * batched encoder (lorahip_codec.hip: encodeGroup) and the modulator with per-frame symbol counts (lorahip_tx.hip)
- **********************************************************************/
-//! what LoRaEncoder::work() cannot do either: PPM > SF throws (LoRaEncoder.cpp:166); an explicit header with PPM < 5 makes `PPM - cOfs`
-//! wrap (:200). sf as the decoder configuration accepts it.
-static bool encoderCfgOk(const lorahip_encoder_cfg *cfg)
-{
-    if (cfg == nullptr || cfg->struct_size != sizeof(lorahip_encoder_cfg)) return false;
-    if (cfg->sf < 1 || cfg->sf > LORAHIP_SF_MAX || cfg->ppm < 0 || cfg->ppm > cfg->sf || cfg->rdd < 0 || cfg->rdd > 4) return false;
-    if (cfg->explicit_hdr && (cfg->ppm ? cfg->ppm : cfg->sf) < 5)
-    {
-        setLastError("explicit header needs a symbol size (PPM) of at least 5 bits");
-        return false;
-    }
-    return true;
-}
-
-long lorahip_encode_num_symbols(const lorahip_encoder_cfg *cfg, const size_t n_bytes)
-{
-    if (!encoderCfgOk(cfg) || n_bytes > size_t(decodeMaxDataLength())) return -1;
-    return encodeNumSymbols(cfg->sf, cfg->ppm, cfg->rdd, cfg->explicit_hdr, cfg->crc, n_bytes);
-}
-
-int lorahip_encode_max_bytes(void) { return decodeMaxDataLength(); }
-
-int lorahip_encode_packets(lorahip_ctx *ctx, const lorahip_encoder_cfg *cfg, const uint8_t *bytes_dev, const size_t byte_stride,
-                           const int32_t *nbytes_dev, const size_t n_packets, uint16_t *syms_dev, const size_t sym_stride,
-                           int32_t *nsyms_dev)
-{
-    if (ctx == nullptr || !encoderCfgOk(cfg)) return LORAHIP_E_INVALID;
-    if (byte_stride > size_t(lorahip_encode_max_bytes()) || sym_stride == 0 || sym_stride > size_t(decodeMaxSymbols())) return LORAHIP_E_INVALID;
-    if (n_packets == 0) return LORAHIP_OK;
-    if ((byte_stride && !bytes_dev) || !nbytes_dev || !syms_dev || !nsyms_dev || n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
-    const DeviceGuard guard(ctx->device);
-    EncodeArgs a;
-    a.bytes = bytes_dev; a.nbytes = nbytes_dev; a.syms = syms_dev; a.nsyms = nsyms_dev;
-    a.nPackets = unsigned(n_packets); a.byteStride = int(byte_stride); a.symStride = int(sym_stride);
-    a.sf = cfg->sf; a.ppm = cfg->ppm; a.rdd = cfg->rdd; a.explicitHdr = cfg->explicit_hdr ? 1 : 0; a.crc = cfg->crc ? 1 : 0;
-    a.whitening = cfg->whitening ? 1 : 0;
-    LORAHIP_TRY(launchEncode(a, ctx->stream));
-    return LORAHIP_OK;
-}
-
-/* The same for a caller in HOST memory: staged through the context's pinned buffer like lorahip_decode_packets_host; synchronous. */
-int lorahip_encode_packets_host(lorahip_ctx *ctx, const lorahip_encoder_cfg *cfg, const uint8_t *bytes, const size_t byte_stride,
-                                const int32_t *nbytes, const size_t n_packets, uint16_t *syms, const size_t sym_stride, int32_t *nsyms)
-{
-    if (ctx == nullptr || !encoderCfgOk(cfg)) return LORAHIP_E_INVALID;
-    if (byte_stride > size_t(lorahip_encode_max_bytes()) || sym_stride == 0 || sym_stride > size_t(decodeMaxSymbols())) return LORAHIP_E_INVALID;
-    if (n_packets == 0) return LORAHIP_OK;
-    if ((byte_stride && !bytes) || !nbytes || !syms || !nsyms || n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
-    const DeviceGuard guard(ctx->device);
-    struct Piece { size_t off, bytes; };
-    size_t cur = 0;
-    auto carve = [&cur](const size_t bytes) { Piece p = { cur, bytes }; cur += (bytes + 255) & ~size_t(255); return p; };
-    const Piece pByte = carve(n_packets * byte_stride);
-    const Piece pN = carve(n_packets * sizeof(int32_t));
-    const size_t inBytes = cur;
-    const Piece pSym = carve(n_packets * sym_stride * sizeof(uint16_t));
-    const Piece pLen = carve(n_packets * sizeof(int32_t));
-    { const int rc = growStage(ctx, cur, cur); if (rc != LORAHIP_OK) return rc; }
-    char *d = ctx->dStage.get(), *h = ctx->hStage.get();
-    if (pByte.bytes) std::memcpy(h + pByte.off, bytes, pByte.bytes);
-    std::memcpy(h + pN.off, nbytes, pN.bytes);
-    LORAHIP_TRY(hipMemcpyAsync(d, h, inBytes, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = lorahip_encode_packets(ctx, cfg, reinterpret_cast<const uint8_t *>(d + pByte.off), byte_stride, reinterpret_cast<const int32_t *>(d + pN.off),
-                                          n_packets, reinterpret_cast<uint16_t *>(d + pSym.off), sym_stride, reinterpret_cast<int32_t *>(d + pLen.off));
-    if (rc != LORAHIP_OK) return rc;
-    LORAHIP_TRY(hipMemcpyAsync(h + inBytes, d + inBytes, cur - inBytes, hipMemcpyDeviceToHost, ctx->stream));
-    LORAHIP_TRY(hipStreamSynchronize(ctx->stream));
-    std::memcpy(syms, h + pSym.off, pSym.bytes);
-    std::memcpy(nsyms, h + pLen.off, pLen.bytes);
-    return LORAHIP_OK;
-}
-
+/* (the batched decoder and encoder: lorahip_codec_api.cpp) */
+//! the modulator with per-frame symbol counts (lorahip_tx.hip)
 int lorahip_mod_frames_var(lorahip_ctx *ctx, float *iq_dev, const size_t frame_stride, const uint16_t *syms_dev, const size_t sym_stride,
                            const int32_t *nsyms_dev, const size_t n_frames, const size_t max_nsyms, const unsigned char sync,
                            const float ampl, const size_t padding)
@@ -748,84 +450,7 @@ int lorahip_mod_frames_var(lorahip_ctx *ctx, float *iq_dev, const size_t frame_s
     return LORAHIP_OK;
 }
 
-/***********************************************************************
- * the transmit side with the settings per packet: the encoder over a table (lorahip_codec.hip: encodeGroupCfgs) and the scheduled
- * modulator (lorahip_txsched.hip)
- **********************************************************************/
-//! the argument checks of the encoder's table launch that need no device, in the order lorahip_decode_packets_cfgs makes its own
-static int encodeCfgsOk(const lorahip_encoder_cfg *cfgs, const size_t n_cfgs, const bool haveTable, const size_t n_table, const size_t byte_stride,
-                        const size_t sym_stride)
-{
-    if (cfgs == nullptr || n_cfgs == 0 || n_cfgs > size_t(LORAHIP_ENC_MAX_CFGS)) return LORAHIP_E_INVALID;
-    for (size_t i = 0; i < n_cfgs; i++)
-        if (!encoderCfgOk(cfgs + i)) return LORAHIP_E_INVALID;
-    if ((haveTable && n_table == 0) || n_table > 0x7fffffffu) return LORAHIP_E_INVALID;
-    if (byte_stride > size_t(lorahip_encode_max_bytes()) || sym_stride == 0 || sym_stride > size_t(decodeMaxSymbols())) return LORAHIP_E_INVALID;
-    return LORAHIP_OK;
-}
-
-int lorahip_encode_packets_cfgs(lorahip_ctx *ctx, const lorahip_encoder_cfg *cfgs, const size_t n_cfgs, const int32_t *index_dev,
-                                const int32_t *table_dev, const size_t n_table, const uint8_t *bytes_dev, const size_t byte_stride,
-                                const int32_t *nbytes_dev, const size_t n_packets, uint16_t *syms_dev, const size_t sym_stride,
-                                int32_t *nsyms_dev)
-{
-    if (ctx == nullptr) return LORAHIP_E_INVALID;
-    { const int rc = encodeCfgsOk(cfgs, n_cfgs, table_dev != nullptr, n_table, byte_stride, sym_stride); if (rc != LORAHIP_OK) return rc; }
-    if (n_packets == 0) return LORAHIP_OK;
-    if (!index_dev || (byte_stride && !bytes_dev) || !nbytes_dev || !syms_dev || !nsyms_dev || n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
-    EncodeCfg tab[LORAHIP_ENC_MAX_CFGS];
-    for (size_t i = 0; i < n_cfgs; i++)
-    {
-        const lorahip_encoder_cfg &c = cfgs[i];
-        const EncodeCfg e = { c.sf, c.ppm, c.rdd, c.explicit_hdr ? 1 : 0, c.crc ? 1 : 0, c.whitening ? 1 : 0, 0, 0 };
-        tab[i] = e;
-    }
-    const DeviceGuard guard(ctx->device);
-    EncodeArgs a = {};
-    a.bytes = bytes_dev; a.nbytes = nbytes_dev; a.syms = syms_dev; a.nsyms = nsyms_dev;
-    a.nPackets = unsigned(n_packets); a.byteStride = int(byte_stride); a.symStride = int(sym_stride);
-    LORAHIP_TRY(launchEncodeCfgs(a, tab, n_cfgs, index_dev, table_dev, int(n_table), ctx->stream));
-    return LORAHIP_OK;
-}
-
-int lorahip_encode_packets_cfgs_host(lorahip_ctx *ctx, const lorahip_encoder_cfg *cfgs, const size_t n_cfgs, const int32_t *index,
-                                     const int32_t *table, const size_t n_table, const uint8_t *bytes, const size_t byte_stride,
-                                     const int32_t *nbytes, const size_t n_packets, uint16_t *syms, const size_t sym_stride, int32_t *nsyms)
-{
-    if (ctx == nullptr) return LORAHIP_E_INVALID;
-    { const int rc = encodeCfgsOk(cfgs, n_cfgs, table != nullptr, n_table, byte_stride, sym_stride); if (rc != LORAHIP_OK) return rc; }
-    if (n_packets == 0) return LORAHIP_OK;
-    if (!index || (byte_stride && !bytes) || !nbytes || !syms || !nsyms || n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
-    const DeviceGuard guard(ctx->device);
-    struct Piece { size_t off, bytes; };
-    size_t cur = 0;
-    auto carve = [&cur](const size_t bytes) { Piece p = { cur, bytes }; cur += (bytes + 255) & ~size_t(255); return p; };
-    const Piece pByte = carve(n_packets * byte_stride);
-    const Piece pN = carve(n_packets * sizeof(int32_t));
-    const Piece pIdx = carve(n_packets * sizeof(int32_t));
-    const Piece pTab = carve(table ? n_table * sizeof(int32_t) : 0);
-    const size_t inBytes = cur;
-    const Piece pSym = carve(n_packets * sym_stride * sizeof(uint16_t));
-    const Piece pLen = carve(n_packets * sizeof(int32_t));
-    { const int rc = growStage(ctx, cur, cur); if (rc != LORAHIP_OK) return rc; }
-    char *d = ctx->dStage.get(), *h = ctx->hStage.get();
-    if (pByte.bytes) std::memcpy(h + pByte.off, bytes, pByte.bytes);
-    std::memcpy(h + pN.off, nbytes, pN.bytes);
-    std::memcpy(h + pIdx.off, index, pIdx.bytes);
-    if (table) std::memcpy(h + pTab.off, table, pTab.bytes);
-    LORAHIP_TRY(hipMemcpyAsync(d, h, inBytes, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = lorahip_encode_packets_cfgs(ctx, cfgs, n_cfgs, reinterpret_cast<const int32_t *>(d + pIdx.off),
-                                               table ? reinterpret_cast<const int32_t *>(d + pTab.off) : nullptr, n_table,
-                                               reinterpret_cast<const uint8_t *>(d + pByte.off), byte_stride, reinterpret_cast<const int32_t *>(d + pN.off),
-                                               n_packets, reinterpret_cast<uint16_t *>(d + pSym.off), sym_stride, reinterpret_cast<int32_t *>(d + pLen.off));
-    if (rc != LORAHIP_OK) return rc;
-    LORAHIP_TRY(hipMemcpyAsync(h + inBytes, d + inBytes, cur - inBytes, hipMemcpyDeviceToHost, ctx->stream));
-    LORAHIP_TRY(hipStreamSynchronize(ctx->stream));
-    std::memcpy(syms, h + pSym.off, pSym.bytes);
-    std::memcpy(nsyms, h + pLen.off, pLen.bytes);
-    return LORAHIP_OK;
-}
-
+//! the scheduled modulator of the transmit side with the settings per packet (lorahip_txsched.hip)
 size_t lorahip_mod_body_len(const int sf, const size_t nsyms)
 {
     if (sf < LORAHIP_SF_MIN || sf > LORAHIP_SF_MAX) return 0;

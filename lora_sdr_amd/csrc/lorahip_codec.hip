@@ -16,6 +16,7 @@
 // decodePackets (context variant 1): one lane walks one packet statement by statement in the reference's order, working arrays
 // in per-lane scratch -- the round-1 kernel, kept as the A/B checker.
 #include "lorahip_internal.h"
+#include <type_traits>
 
 namespace lorahip {
 
@@ -191,7 +192,7 @@ __device__ __forceinline__ int cfgIndexOf(const Table &tab, const unsigned p)
 }
 
 //! the rows of the launch with entry e as their settings: what the decoder bodies below read as `a`
-__device__ __forceinline__ DecodeArgs withCfg(const DecodeArgs &rows, const DecodeCfg &e)
+__host__ __device__ __forceinline__ DecodeArgs withCfg(const DecodeArgs &rows, const DecodeCfg &e)
 {
     DecodeArgs a = rows;
     a.sf = e.sf; a.ppm = e.ppm; a.rdd = e.rdd; a.crcc = e.crcc; a.interleaving = e.interleaving;
@@ -779,6 +780,35 @@ __global__ void __launch_bounds__(256) decodeGroup(const DecodeArgs a, const Dec
     decodeGroupBody<G>(a, caps, slice, perBlock, true);
 }
 
+//! What the four group kernels share on the host. The LDS a workgroup of theirs may ask for: the device's 160 KiB (the plans fit under it).
+constexpr int kGroupLdsMax = 160 * 1024;
+
+//! lanes per packet by the symbols of the longest row a launch can meet (a lane per symbol in the widest pass, about as many codewords)
+static int lanesFor(const long rowSyms) { return rowSyms <= 48 ? 8 : rowSyms <= 96 ? 16 : rowSyms <= 200 ? 32 : 64; }
+
+//! f(std::integral_constant<int, G>()) for the kernel instance of G = `lanes` lanes per packet
+template <class F>
+static hipError_t withLanes(const int lanes, F &&f)
+{
+    if (lanes == 8) return f(std::integral_constant<int, 8>());
+    if (lanes == 16) return f(std::integral_constant<int, 16>());
+    if (lanes == 32) return f(std::integral_constant<int, 32>());
+    return f(std::integral_constant<int, 64>());
+}
+
+//! group kernel K over nPackets packets, perBlock of them per workgroup on `slice` bytes of LDS each; the attribute once per instance and device
+template <auto K, class... Args>
+static hipError_t launchGroup(const unsigned nPackets, const int perBlock, const int slice, hipStream_t stream, const Args &...args)
+{
+    static unsigned long long attrDone = 0;
+    {
+        const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(K), kGroupLdsMax, attrDone);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(K, dim3((nPackets + perBlock - 1) / perBlock), dim3(256), size_t(slice) * perBlock, stream, args...);
+    return hipGetLastError();
+}
+
 //! the slice a configuration needs (see DecodeCaps): the symbols / codewords that can reach the output, or the whole row if that is less
 //! A header-rate entry (rdd < 0) runs each packet on the caps of the rate its header names: it gets the largest of the five in each component,
 //! and the largest of their slices (which holds any of the five layouts, and the Gray-code load of min(nsyms + 7, symCap) symbols).
@@ -814,47 +844,26 @@ DecodeTiling decodePlan(DecodeCfg *cfgs, const size_t nCfgs, const int symStride
         t.cwCap = c.cwCap > t.cwCap ? c.cwCap : t.cwCap;
         t.slice = slice > t.slice ? slice : t.slice;
     }
-    t.lanes = t.symCap <= 48 ? 8 : t.symCap <= 96 ? 16 : t.symCap <= 200 ? 32 : 64;
-    const int ldsMax = 160 * 1024;
+    t.lanes = lanesFor(t.symCap);
     t.perBlock = 256 / t.lanes;
-    if (t.slice * t.perBlock > ldsMax) t.perBlock = ldsMax / t.slice;
+    if (t.slice * t.perBlock > kGroupLdsMax) t.perBlock = kGroupLdsMax / t.slice;
     return t;
 }
 
-static DecodeCfg cfgOf(const DecodeArgs &a)
+hipError_t launchDecode(const DecodeArgs &rows, const DecodeCfg &cfg, const int variant, hipStream_t stream)
 {
-    const DecodeCfg c = { a.sf, a.ppm, a.rdd, a.crcc, a.interleaving, a.errorCheck, a.explicitHdr, a.hdr, a.dataLength, 0, 0 };
-    return c;
-}
-
-template <int G>
-static hipError_t launchDecodeGroup(const DecodeArgs &a, const DecodeTiling &t, hipStream_t stream)
-{
-    const DecodeCaps caps = { t.symCap, t.cwCap };
-    static unsigned long long attrDone = 0;
-    {
-        const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(decodeGroup<G>), 160 * 1024, attrDone);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((decodeGroup<G>), dim3((a.nPackets + t.perBlock - 1) / t.perBlock), dim3(256), size_t(t.slice) * t.perBlock, stream, a, caps, t.slice, t.perBlock);
-    return hipGetLastError();
-}
-
-hipError_t launchDecode(const DecodeArgs &a, const int variant, hipStream_t stream)
-{
-    if (a.nPackets == 0) return hipSuccess;
+    if (rows.nPackets == 0) return hipSuccess;
+    const DecodeArgs a = withCfg(rows, cfg);
     if (variant == 1)
     {
         hipLaunchKernelGGL(decodePackets, dim3((a.nPackets + 63) / 64), dim3(64), 0, stream, a);
         return hipGetLastError();
     }
-    DecodeCfg c = cfgOf(a);
+    DecodeCfg c = cfg;
     const DecodeTiling t = decodePlan(&c, 1, a.symStride);
     if (t.perBlock < 1) return hipErrorInvalidValue;                // (lorahip_decode_packets bounds data_length: cannot happen)
-    if (t.lanes == 8) return launchDecodeGroup<8>(a, t, stream);
-    if (t.lanes == 16) return launchDecodeGroup<16>(a, t, stream);
-    if (t.lanes == 32) return launchDecodeGroup<32>(a, t, stream);
-    return launchDecodeGroup<64>(a, t, stream);
+    const DecodeCaps caps = { t.symCap, t.cwCap };
+    return withLanes(t.lanes, [&](auto g) { return launchGroup<decodeGroup<decltype(g)::value>>(a.nPackets, t.perBlock, t.slice, stream, a, caps, t.slice, t.perBlock); });
 }
 
 /***********************************************************************
@@ -1017,46 +1026,59 @@ long encodeNumSymbols(const int sf, const int ppm, const int rdd, const int expl
     return LORAHIP_N_HDR_SYMBOLS + (numCodewords / PPM - 1) * (4 + rdd);
 }
 
-static EncodeCaps encodeCaps(const EncodeArgs &a)
+//! the slice an entry needs over rows of byteStride bytes and symStride symbols (see EncodeCaps)
+static EncodeCaps encodeCaps(const EncodeCfg &e, const int byteStride, const int symStride)
 {
-    const long PPM = a.ppm == 0 ? a.sf : a.ppm, bs = 4 + a.rdd;
-    const long nbMax = long(a.byteStride) + (a.crc ? 2 : 0);
-    const long cwByBytes = ((2 * nbMax + (a.explicitHdr ? LORAHIP_N_HDR_CODEWORDS : 0) + PPM - 1) / PPM) * PPM;
-    const long cwBySyms = a.symStride < LORAHIP_N_HDR_SYMBOLS ? 0 : ((a.symStride - LORAHIP_N_HDR_SYMBOLS) / bs + 1) * PPM;
+    const long PPM = e.ppm == 0 ? e.sf : e.ppm, bs = 4 + e.rdd;
+    const long nbMax = long(byteStride) + (e.crc ? 2 : 0);
+    const long cwByBytes = ((2 * nbMax + (e.explicitHdr ? LORAHIP_N_HDR_CODEWORDS : 0) + PPM - 1) / PPM) * PPM;
+    const long cwBySyms = symStride < LORAHIP_N_HDR_SYMBOLS ? 0 : ((symStride - LORAHIP_N_HDR_SYMBOLS) / bs + 1) * PPM;
     EncodeCaps c;
     c.cwCap = int(cwByBytes < cwBySyms ? cwByBytes : cwBySyms);
     c.byteCap = (c.cwCap / 2 + 2 + 3) & ~3;
     return c;
 }
 
-template <int G>
-static hipError_t launchEncodeGroup(const EncodeArgs &a, const EncodeCaps &caps, hipStream_t stream)
+/* What a launch over rows of byteStride bytes and symStride symbols under these settings runs on -- the one place that decides it, for the
+ * uniform launch (one entry) and the table launch, as decodePlan is for the decoder. Every entry gets the caps of ITS settings (its group lays
+ * out its slice with them); the launch has ONE lane count and ONE slice: the lanes by the symbols a row can hold under the entry that makes
+ * most of it, the slice the largest entry's, and as many packets per workgroup as fit the LDS (0: not even one -- the entry points bound
+ * byte_stride, so this cannot happen). */
+EncodeTiling encodePlan(EncodeCfg *cfgs, const size_t nCfgs, const int byteStride, const int symStride)
 {
-    const size_t slice = size_t((caps.byteCap + caps.cwCap + 15) & ~15);
-    const size_t ldsMax = 160 * 1024;
-    unsigned perBlock = 256 / G;
-    if (slice > ldsMax) return hipErrorInvalidValue;                // (lorahip_encode_packets bounds byte_stride: cannot happen)
-    if (slice * perBlock > ldsMax) perBlock = unsigned(ldsMax / slice);
-    static unsigned long long attrDone = 0;
+    EncodeTiling t = { 0, 0, 0, 0, 0 };
+    long rowSyms = 0;
+    for (size_t i = 0; i < nCfgs; i++)
     {
-        const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(encodeGroup<G>), ldsMax, attrDone);
-        if (e != hipSuccess) return e;
+        EncodeCfg &e = cfgs[i];
+        const EncodeCaps c = encodeCaps(e, byteStride, symStride);
+        e.byteCap = c.byteCap; e.cwCap = c.cwCap;
+        t.byteCap = c.byteCap > t.byteCap ? c.byteCap : t.byteCap;
+        t.cwCap = c.cwCap > t.cwCap ? c.cwCap : t.cwCap;
+        const long bySyms = c.cwCap == 0 ? 0 : LORAHIP_N_HDR_SYMBOLS + (c.cwCap / (e.ppm == 0 ? e.sf : e.ppm) - 1) * (4 + e.rdd);
+        rowSyms = bySyms > rowSyms ? bySyms : rowSyms;
+        const int slice = (c.byteCap + c.cwCap + 15) & ~15;
+        t.slice = slice > t.slice ? slice : t.slice;
     }
-    hipLaunchKernelGGL((encodeGroup<G>), dim3((a.nPackets + perBlock - 1) / perBlock), dim3(256), slice * perBlock, stream, a, caps, int(perBlock));
-    return hipGetLastError();
+    t.lanes = lanesFor(rowSyms);
+    t.perBlock = 256 / t.lanes;
+    if (t.slice * t.perBlock > kGroupLdsMax) t.perBlock = kGroupLdsMax / t.slice;
+    return t;
 }
 
-hipError_t launchEncode(const EncodeArgs &a, hipStream_t stream)
+//! (defined with the table kernels below)
+__host__ __device__ __forceinline__ EncodeArgs withCfg(const EncodeArgs &rows, const EncodeCfg &e);
+
+hipError_t launchEncode(const EncodeArgs &rows, const EncodeCfg &cfg, hipStream_t stream)
 {
-    if (a.nPackets == 0) return hipSuccess;
-    const EncodeCaps caps = encodeCaps(a);
-    // lanes per packet by the symbols a row of this launch can hold (a lane per symbol in the last pass, about as many codewords)
-    const long bySyms = LORAHIP_N_HDR_SYMBOLS + (caps.cwCap / (a.ppm == 0 ? a.sf : a.ppm) - 1) * (4 + a.rdd);
-    const long rowSyms = caps.cwCap == 0 ? 0 : bySyms;
-    if (rowSyms <= 48) return launchEncodeGroup<8>(a, caps, stream);
-    if (rowSyms <= 96) return launchEncodeGroup<16>(a, caps, stream);
-    if (rowSyms <= 200) return launchEncodeGroup<32>(a, caps, stream);
-    return launchEncodeGroup<64>(a, caps, stream);
+    if (rows.nPackets == 0) return hipSuccess;
+    EncodeCfg c = cfg;
+    const EncodeTiling t = encodePlan(&c, 1, rows.byteStride, rows.symStride);
+    if (t.perBlock < 1) return hipErrorInvalidValue;                // (lorahip_encode_packets bounds byte_stride: cannot happen)
+    const EncodeArgs a = withCfg(rows, c);
+    const EncodeCaps caps = { t.byteCap, t.cwCap };
+    // (encodeGroup works its slice out of the caps: the one entry's is the launch's)
+    return withLanes(t.lanes, [&](auto g) { return launchGroup<encodeGroup<decltype(g)::value>>(a.nPackets, t.perBlock, t.slice, stream, a, caps, t.perBlock); });
 }
 
 /***********************************************************************
@@ -1089,19 +1111,6 @@ __global__ void __launch_bounds__(256) decodeGroupCfgs(const DecodeArgs rows, co
     decodeGroupBody<G>(withCfg(rows, e), caps, slice, perBlock, i >= 0);
 }
 
-template <int G>
-static hipError_t launchDecodeGroupCfgs(const DecodeArgs &rows, const DecodeCfgTable &tab, const DecodeTiling &t, hipStream_t stream)
-{
-    static unsigned long long attrDone = 0;
-    {
-        const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(decodeGroupCfgs<G>), 160 * 1024, attrDone);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((decodeGroupCfgs<G>), dim3((rows.nPackets + t.perBlock - 1) / t.perBlock), dim3(256), size_t(t.slice) * t.perBlock, stream, rows, tab,
-                       t.slice, t.perBlock);
-    return hipGetLastError();
-}
-
 hipError_t launchDecodeCfgs(const DecodeArgs &rows, const DecodeCfg *cfgs, const size_t nCfgs, const int *index, const int *table, const int nTable,
                             const int variant, hipStream_t stream)
 {
@@ -1117,10 +1126,7 @@ hipError_t launchDecodeCfgs(const DecodeArgs &rows, const DecodeCfg *cfgs, const
         return hipGetLastError();
     }
     if (t.perBlock < 1) return hipErrorInvalidValue;                // (lorahip_decode_packets_cfgs bounds data_length: cannot happen)
-    if (t.lanes == 8) return launchDecodeGroupCfgs<8>(rows, tab, t, stream);
-    if (t.lanes == 16) return launchDecodeGroupCfgs<16>(rows, tab, t, stream);
-    if (t.lanes == 32) return launchDecodeGroupCfgs<32>(rows, tab, t, stream);
-    return launchDecodeGroupCfgs<64>(rows, tab, t, stream);
+    return withLanes(t.lanes, [&](auto g) { return launchGroup<decodeGroupCfgs<decltype(g)::value>>(rows.nPackets, t.perBlock, t.slice, stream, rows, tab, t.slice, t.perBlock); });
 }
 
 //! channel_dev[j] = globalOf[channel_dev[j]] for the n rows one part of a mixed handle packed (lorahip_rx.cpp: the hand-off speaks global channels)
@@ -1153,7 +1159,7 @@ struct EncodeCfgTable
 };
 
 //! the rows of the launch with entry e as their settings: what encodeGroupBody reads as `a`
-__device__ __forceinline__ EncodeArgs withCfg(const EncodeArgs &rows, const EncodeCfg &e)
+__host__ __device__ __forceinline__ EncodeArgs withCfg(const EncodeArgs &rows, const EncodeCfg &e)
 {
     EncodeArgs a = rows;
     a.sf = e.sf; a.ppm = e.ppm; a.rdd = e.rdd; a.explicitHdr = e.explicitHdr; a.crc = e.crc; a.whitening = e.whitening;
@@ -1171,25 +1177,6 @@ __global__ void __launch_bounds__(256) encodeGroupCfgs(const EncodeArgs rows, co
     encodeGroupBody<G>(withCfg(rows, e), caps, slice, perBlock, i >= 0);
 }
 
-template <int G>
-static hipError_t launchEncodeGroupCfgs(const EncodeArgs &rows, const EncodeCfgTable &tab, const size_t slice, hipStream_t stream)
-{
-    const size_t ldsMax = 160 * 1024;
-    unsigned perBlock = 256 / G;
-    if (slice > ldsMax) return hipErrorInvalidValue;                // (lorahip_encode_packets_cfgs bounds byte_stride: cannot happen)
-    if (slice * perBlock > ldsMax) perBlock = unsigned(ldsMax / slice);
-    static unsigned long long attrDone = 0;
-    {
-        const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(encodeGroupCfgs<G>), ldsMax, attrDone);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((encodeGroupCfgs<G>), dim3((rows.nPackets + perBlock - 1) / perBlock), dim3(256), slice * perBlock, stream, rows, tab, int(slice),
-                       int(perBlock));
-    return hipGetLastError();
-}
-
-/* Every entry gets the caps of ITS settings over the rows of the launch (encodeCaps: its group lays out its slice with them); the launch has
- * ONE lane count and ONE slice, those of the entry that needs most -- the lane count by launchEncode's rule on that entry's row symbols. */
 hipError_t launchEncodeCfgs(const EncodeArgs &rows, const EncodeCfg *cfgs, const size_t nCfgs, const int *index, const int *table, const int nTable,
                             hipStream_t stream)
 {
@@ -1197,25 +1184,11 @@ hipError_t launchEncodeCfgs(const EncodeArgs &rows, const EncodeCfg *cfgs, const
     if (nCfgs == 0 || nCfgs > size_t(LORAHIP_ENC_MAX_CFGS)) return hipErrorInvalidValue;
     EncodeCfgTable tab;
     tab.index = index; tab.table = table; tab.nTable = nTable; tab.nCfgs = int(nCfgs);
-    long rowSyms = 0;
-    size_t slice = 0;
-    for (size_t i = 0; i < size_t(LORAHIP_ENC_MAX_CFGS); i++)       // (no entry of the argument block is left unset)
-    {
-        EncodeCfg &e = tab.e[i];
-        e = cfgs[i < nCfgs ? i : 0];
-        EncodeArgs a = rows;
-        a.sf = e.sf; a.ppm = e.ppm; a.rdd = e.rdd; a.explicitHdr = e.explicitHdr; a.crc = e.crc; a.whitening = e.whitening;
-        const EncodeCaps caps = encodeCaps(a);
-        e.byteCap = caps.byteCap; e.cwCap = caps.cwCap;
-        const long bySyms = caps.cwCap == 0 ? 0 : LORAHIP_N_HDR_SYMBOLS + (caps.cwCap / (e.ppm == 0 ? e.sf : e.ppm) - 1) * (4 + e.rdd);
-        rowSyms = bySyms > rowSyms ? bySyms : rowSyms;
-        const size_t s = size_t((caps.byteCap + caps.cwCap + 15) & ~15);
-        slice = s > slice ? s : slice;
-    }
-    if (rowSyms <= 48) return launchEncodeGroupCfgs<8>(rows, tab, slice, stream);
-    if (rowSyms <= 96) return launchEncodeGroupCfgs<16>(rows, tab, slice, stream);
-    if (rowSyms <= 200) return launchEncodeGroupCfgs<32>(rows, tab, slice, stream);
-    return launchEncodeGroupCfgs<64>(rows, tab, slice, stream);
+    for (size_t i = 0; i < nCfgs; i++) tab.e[i] = cfgs[i];
+    const EncodeTiling t = encodePlan(tab.e, nCfgs, rows.byteStride, rows.symStride);
+    for (size_t i = nCfgs; i < size_t(LORAHIP_ENC_MAX_CFGS); i++) tab.e[i] = tab.e[0];                  // (no entry of the argument block is left unset)
+    if (t.perBlock < 1) return hipErrorInvalidValue;                // (lorahip_encode_packets_cfgs bounds byte_stride: cannot happen)
+    return withLanes(t.lanes, [&](auto g) { return launchGroup<encodeGroupCfgs<decltype(g)::value>>(rows.nPackets, t.perBlock, t.slice, stream, rows, tab, t.slice, t.perBlock); });
 }
 
 // rows: the de-whitening takes its length as a uint16_t in the reference (LoRaCodes.hpp: Sx1272ComputeWhiteningLfsr), i.e. messages of

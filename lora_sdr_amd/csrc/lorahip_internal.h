@@ -265,9 +265,10 @@ struct DecodeArgs
     int sf, ppm, rdd, crcc, interleaving, errorCheck, explicitHdr, hdr, dataLength;   // rdd -1: each packet's own header names it
     int *info;                      // [nPackets][8] struct lorahip_packet_info, or null: no report
 };
-hipError_t launchDecode(const DecodeArgs &a, int variant, hipStream_t stream);   // variant 1: the lane-per-packet checker
 //! one entry of a table launch: the nine settings of DecodeArgs, then the LDS caps decodePlan() works out for them
 struct DecodeCfg { int sf, ppm, rdd, crcc, interleaving, errorCheck, explicitHdr, hdr, dataLength, symCap, cwCap; };
+//! the rows of `rows` (its nine settings are not read) under the one configuration cfg
+hipError_t launchDecode(const DecodeArgs &rows, const DecodeCfg &cfg, int variant, hipStream_t stream);   // variant 1: the lane-per-packet checker
 constexpr int LORAHIP_DEC_MAX_CFGS = 64;        // entries of a table: they travel by value in the kernel arguments (64 * 44 bytes)
 //! what a decoder launch runs on (lorahip_decode_plan): lanes per packet, the largest caps, the LDS slice of a group, packets per workgroup
 struct DecodeTiling { int lanes, symCap, cwCap, slice, perBlock; };
@@ -291,11 +292,15 @@ struct EncodeArgs
     int byteStride, symStride;
     int sf, ppm, rdd, explicitHdr, crc, whitening;
 };
-hipError_t launchEncode(const EncodeArgs &a, hipStream_t stream);
 long encodeNumSymbols(int sf, int ppm, int rdd, int explicitHdr, int crc, size_t nBytes);
-//! one entry of an encoder table launch: the six settings of EncodeArgs, then the LDS caps launchEncodeCfgs works out for them
+//! one entry of an encoder table launch: the six settings of EncodeArgs, then the LDS caps encodePlan() works out for them
 struct EncodeCfg { int sf, ppm, rdd, explicitHdr, crc, whitening, byteCap, cwCap; };
 constexpr int LORAHIP_ENC_MAX_CFGS = 64;        // entries of a table: they travel by value in the kernel arguments (64 * 32 bytes)
+//! what an encoder launch runs on, the mirror of DecodeTiling: lanes per packet, the largest caps, the LDS slice of a group, packets per workgroup
+struct EncodeTiling { int lanes, byteCap, cwCap, slice, perBlock; };
+EncodeTiling encodePlan(EncodeCfg *cfgs, size_t nCfgs, int byteStride, int symStride);     // fills every entry's caps; host only
+//! the rows of `rows` (its six settings are not read) under the one configuration cfg
+hipError_t launchEncode(const EncodeArgs &rows, const EncodeCfg &cfg, hipStream_t stream);
 //! the rows of `rows` (its six settings are not read), packet p under cfgs[index[p]] or cfgs[table[index[p]]]; outcome -3 without such an entry
 hipError_t launchEncodeCfgs(const EncodeArgs &rows, const EncodeCfg *cfgs, size_t nCfgs, const int *index, const int *table, int nTable,
                             hipStream_t stream);
@@ -406,6 +411,8 @@ struct DeviceGuard
 
 void setLastError(const std::string &s);
 int hipFail(hipError_t e, const char *what);
+//! room in the context's staging pair (dStage / pinned hStage) for a host-pointer entry point (lorahip_api.cpp; the codec's: lorahip_codec_api.cpp)
+int growStage(lorahip_ctx *ctx, size_t devBytes, size_t hostBytes);
 
 #define LORAHIP_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return ::lorahip::hipFail(_e, #expr); } while (0)
 
