@@ -5,6 +5,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <complex>
+#include <memory>
 #include <string>
 #include <vector>
 #include "../../include/lorahip.h"
@@ -452,7 +453,7 @@ public:
 private:
     Composite();
     struct Impl;
-    Impl *p;
+    std::unique_ptr<Impl> p;
 };
 
 //! a part's share of a mixed handle's packet hand-off (lorahip_demod.cpp): lorahip_demod_packets_to_device of the plain object `dm`, then

@@ -10,26 +10,13 @@
 // device's events have passed (lorahip_mixed_synchronize). No data-path collective: channels are independent units.
 #include "lorahip_own.h"
 #include <algorithm>
-#include <condition_variable>
 #include <cstring>
-#include <mutex>
-#include <new>
-#include <thread>
 
 using namespace lorahip;
 
 namespace {
-//! one device's launch thread: sleeps until a step is posted, issues the shard's launches, reports the code
-struct Worker
-{
-    std::thread th;
-    std::mutex mu;
-    std::condition_variable cv;
-    bool have = false, done = true, quit = false;
-    const float *iq = nullptr; uint16_t *sym = nullptr; float *power = nullptr, *pavg = nullptr, *fidx = nullptr;
-    int rc = LORAHIP_OK;
-    std::string err;
-};
+struct MixedDestroy { void operator()(lorahip_mixed *m) const { lorahip_mixed_destroy(m); } };
+using MixedPtr = std::unique_ptr<lorahip_mixed, MixedDestroy>;
 } // namespace
 
 struct lorahip_mixed
@@ -50,43 +37,13 @@ struct lorahip_mixed
     std::vector<Bucket> buckets;
     bool planned;
     // several devices: the object is a container of single-device schedulers (buckets stays empty)
-    std::vector<lorahip_mixed *> shards;     // one per entry of `devices`, nullptr where a shard got no channel
+    std::vector<MixedPtr> shards;            // one per entry of `devices`, null where a shard got no channel
     std::vector<int> devices;
     std::vector<int32_t> shardOf;            // per channel
     std::vector<std::vector<uint32_t>> shardChannels;   // per shard: its channels ordered by SF, then channel number
     std::vector<uint32_t> localOf;           // per channel: its index among its shard's channels
-    std::vector<Worker *> workers;
+    std::vector<std::unique_ptr<ParkedThread>> threads;   // per shard that has channels: the host thread that issues its launches
 };
-
-static void stopWorkers(lorahip_mixed *m)
-{
-    for (Worker *w : m->workers)
-    {
-        if (w == nullptr) continue;
-        { std::lock_guard<std::mutex> g(w->mu); w->quit = true; }
-        w->cv.notify_all();
-        if (w->th.joinable()) w->th.join();
-        delete w;
-    }
-    m->workers.clear();
-}
-
-static void workerLoop(lorahip_mixed *shard, Worker *w)
-{
-    std::unique_lock<std::mutex> lk(w->mu);
-    while (true)
-    {
-        w->cv.wait(lk, [w] { return w->have || w->quit; });
-        if (w->quit) return;
-        w->have = false;
-        lk.unlock();
-        const int rc = lorahip_mixed_detect(shard, w->iq, w->sym, w->power, w->pavg, w->fidx);
-        const std::string err = rc == LORAHIP_OK ? std::string() : std::string(lorahip_last_error());   // last_error is per thread
-        lk.lock();
-        w->rc = rc; w->err = err; w->done = true;
-        w->cv.notify_all();
-    }
-}
 
 extern "C" {
 
@@ -130,8 +87,7 @@ int lorahip_shard_plan(const int32_t *channel_sf, const size_t n_channels, const
 void lorahip_mixed_destroy(lorahip_mixed *m)
 {
     if (m == nullptr) return;
-    stopWorkers(m);
-    for (lorahip_mixed *sh : m->shards) lorahip_mixed_destroy(sh);
+    m->threads.clear();                      // the threads end first, then the shards they launch on
     m->shards.clear();
     while (!m->buckets.empty())
     {
@@ -148,7 +104,7 @@ int lorahip_mixed_create(lorahip_mixed **out, const int device, const int32_t *c
     *out = nullptr;
     for (size_t c = 0; c < n_channels; c++)
         if (channel_sf[c] < LORAHIP_SF_MIN || channel_sf[c] > LORAHIP_SF_MAX) return LORAHIP_E_INVALID;
-    lorahip_mixed *m = new (std::nothrow) lorahip_mixed();
+    MixedPtr m(new (std::nothrow) lorahip_mixed());
     if (m == nullptr) return LORAHIP_E_NOMEM;
     m->device = device; m->nChannels = n_channels; m->S = 0; m->planned = false;
     m->sf.assign(channel_sf, channel_sf + n_channels);
@@ -161,12 +117,12 @@ int lorahip_mixed_create(lorahip_mixed **out, const int device, const int32_t *c
         for (size_t c = 0; c < n_channels; c++) if (channel_sf[c] == sf) { m->row[c] = int64_t(rows++); b.channels.push_back(uint32_t(c)); }
         if (b.channels.empty()) continue;
         const int rc = lorahip_create(&b.ctx, device, sf);          // private non-blocking stream: the buckets overlap
-        if (rc != LORAHIP_OK) { lorahip_mixed_destroy(m); return rc; }
+        if (rc != LORAHIP_OK) return rc;
         m->buckets.push_back(std::move(b));
         const DeviceGuard guard(device);
-        if (m->buckets.back().done.ensure(hipEventDisableTiming) != hipSuccess) { lorahip_mixed_destroy(m); return LORAHIP_E_HIP; }
+        if (m->buckets.back().done.ensure(hipEventDisableTiming) != hipSuccess) return LORAHIP_E_HIP;
     }
-    *out = m;
+    *out = m.release();
     return LORAHIP_OK;
 }
 
@@ -177,7 +133,7 @@ int lorahip_mixed_create_multi(lorahip_mixed **out, const int *devices, const si
     *out = nullptr;
     for (size_t c = 0; c < n_channels; c++)
         if (channel_sf[c] < LORAHIP_SF_MIN || channel_sf[c] > LORAHIP_SF_MAX) return LORAHIP_E_INVALID;
-    lorahip_mixed *m = new (std::nothrow) lorahip_mixed();
+    MixedPtr m(new (std::nothrow) lorahip_mixed());
     if (m == nullptr) return LORAHIP_E_NOMEM;
     int rc = LORAHIP_OK;
     try
@@ -193,23 +149,25 @@ int lorahip_mixed_create_multi(lorahip_mixed **out, const int *devices, const si
         for (int sf = LORAHIP_SF_MIN; rc == LORAHIP_OK && sf <= LORAHIP_SF_MAX; sf++)
             for (size_t c = 0; c < n_channels; c++)
                 if (channel_sf[c] == sf) { auto &v = m->shardChannels[size_t(m->shardOf[c])]; m->localOf[c] = uint32_t(v.size()); v.push_back(uint32_t(c)); }
-        m->shards.assign(n_devices, nullptr);
-        m->workers.assign(n_devices, nullptr);
+        m->shards.resize(n_devices);
+        m->threads.resize(n_devices);
         for (size_t s = 0; rc == LORAHIP_OK && s < n_devices; s++)
         {
             const auto &ch = m->shardChannels[s];
             if (ch.empty()) continue;
             std::vector<int32_t> sfs(ch.size());
             for (size_t i = 0; i < ch.size(); i++) sfs[i] = channel_sf[ch[i]];
-            rc = lorahip_mixed_create(&m->shards[s], devices[s], sfs.data(), sfs.size());
+            lorahip_mixed *shard = nullptr;
+            rc = lorahip_mixed_create(&shard, devices[s], sfs.data(), sfs.size());
             if (rc != LORAHIP_OK) break;
-            m->workers[s] = new Worker();
-            m->workers[s]->th = std::thread(workerLoop, m->shards[s], m->workers[s]);
+            m->shards[s].reset(shard);
+            m->threads[s] = std::make_unique<ParkedThread>();
+            if (!m->threads[s]->start()) { setLastError("lorahip_mixed_create_multi: a launch thread could not be started"); rc = LORAHIP_E_NOMEM; }
         }
     }
     catch (const std::exception &e) { setLastError(std::string("lorahip_mixed_create_multi: ") + e.what()); rc = LORAHIP_E_NOMEM; }
-    if (rc != LORAHIP_OK) { lorahip_mixed_destroy(m); return rc; }
-    *out = m;
+    if (rc != LORAHIP_OK) return rc;
+    *out = m.release();
     return LORAHIP_OK;
 }
 
@@ -226,7 +184,7 @@ int lorahip_mixed_device(const lorahip_mixed *m, const size_t shard, int32_t *de
 lorahip_mixed *lorahip_mixed_shard(const lorahip_mixed *m, const size_t shard)
 {
     if (m == nullptr || m->shards.empty()) return shard == 0 ? const_cast<lorahip_mixed *>(m) : nullptr;
-    return shard < m->shards.size() ? m->shards[shard] : nullptr;
+    return shard < m->shards.size() ? m->shards[shard].get() : nullptr;
 }
 
 int lorahip_mixed_shard_of(const lorahip_mixed *m, int32_t *shard_of_channel)
@@ -244,25 +202,8 @@ int lorahip_mixed_detect_multi(lorahip_mixed *m, const float *const *iq_dev, uin
     if (m->shards.empty()) return lorahip_mixed_detect(m, iq_dev[0], sym_dev[0], power_dev[0], power_avg_dev[0], f_index_dev[0]);
     // every device's launches are issued by that device's own host thread, all at once; this call returns when all are ISSUED
     // (asynchronous like lorahip_mixed_detect; lorahip_mixed_synchronize is the join on the devices' events)
-    for (size_t s = 0; s < m->shards.size(); s++)
-    {
-        Worker *w = m->workers[s];
-        if (w == nullptr) continue;
-        { std::lock_guard<std::mutex> g(w->mu);
-          w->iq = iq_dev[s]; w->sym = sym_dev[s]; w->power = power_dev[s]; w->pavg = power_avg_dev[s]; w->fidx = f_index_dev[s];
-          w->have = true; w->done = false; }
-        w->cv.notify_all();
-    }
-    int rc = LORAHIP_OK;
-    for (size_t s = 0; s < m->shards.size(); s++)
-    {
-        Worker *w = m->workers[s];
-        if (w == nullptr) continue;
-        std::unique_lock<std::mutex> lk(w->mu);
-        w->cv.wait(lk, [w] { return w->done; });
-        if (w->rc != LORAHIP_OK && rc == LORAHIP_OK) { rc = w->rc; setLastError(w->err); }
-    }
-    return rc;
+    return runOnThreads(m->shards.size(), [m](const size_t s) { return m->threads[s].get(); }, [&](const size_t s) {
+        return lorahip_mixed_detect(m->shards[s].get(), iq_dev[s], sym_dev[s], power_dev[s], power_avg_dev[s], f_index_dev[s]); });
 }
 
 size_t lorahip_mixed_num_buckets(const lorahip_mixed *m) { return m ? m->buckets.size() : 0; }
@@ -307,7 +248,7 @@ int lorahip_mixed_plan(lorahip_mixed *m, const int64_t *channel_offset, const si
             const auto &ch = m->shardChannels[s];
             local.resize(ch.size());
             for (size_t i = 0; i < ch.size(); i++) local[i] = channel_offset[ch[i]];
-            const int rc = lorahip_mixed_plan(m->shards[s], local.data(), windows_per_channel);
+            const int rc = lorahip_mixed_plan(m->shards[s].get(), local.data(), windows_per_channel);
             if (rc != LORAHIP_OK) return rc;
         }
         m->S = windows_per_channel;
@@ -365,7 +306,7 @@ int lorahip_mixed_synchronize(lorahip_mixed *m)
     if (m == nullptr) return LORAHIP_E_INVALID;
     if (!m->shards.empty())
     {
-        for (lorahip_mixed *sh : m->shards) if (sh) { const int rc = lorahip_mixed_synchronize(sh); if (rc != LORAHIP_OK) return rc; }
+        for (const MixedPtr &sh : m->shards) if (sh) { const int rc = lorahip_mixed_synchronize(sh.get()); if (rc != LORAHIP_OK) return rc; }
         return LORAHIP_OK;
     }
     const DeviceGuard guard(m->device);

@@ -4,6 +4,9 @@
 // owner's DeviceGuard makes the right one current around every allocation and release.
 #pragma once
 #include "lorahip_internal.h"
+#include "lorahip_worker.h"
+#include <memory>
+#include <new>
 
 namespace lorahip {
 
@@ -109,6 +112,9 @@ private:
     hipStream_t s = nullptr;
 };
 
+struct CopyPool;                                     // the parked helpers of the staging fills: lorahip_upload.cpp
+struct CopyPoolDelete { void operator()(CopyPool *p) const; };
+
 //! two pinned staging buffers of the host -> device gather (lorahip_upload.cpp)
 struct Uploader
 {
@@ -116,10 +122,28 @@ struct Uploader
     Event ev[2];
     bool busy[2] = {false, false};
     bool ready = false;
-    void *pool = nullptr;           // CopyPool: lorahip_upload.cpp
+    std::unique_ptr<CopyPool, CopyPoolDelete> pool;
     void release();                 // back to "not initialised": buffers, events and the pool's threads
     ~Uploader() { release(); }
 };
+
+//! fn(i) on threadOf(i) for every i < n at once (runOnAll), as the containers of several devices or parts need it: the first failure's
+//! code, and its text -- lorahip_last_error is per thread, so it is read on the worker -- as the calling thread's last error
+template <class ThreadOf, class Fn> int runOnThreads(const size_t n, const ThreadOf &threadOf, const Fn &fn)
+{
+    try
+    {
+        std::vector<std::string> err(n);
+        size_t failed = 0;
+        const int rc = runOnAll(n, threadOf, [&](const size_t i) {
+            const int r = fn(i);
+            try { if (r != LORAHIP_OK) err[i] = lorahip_last_error(); } catch (const std::bad_alloc &) {}   // (the code without its text)
+            return r; }, &failed);
+        if (rc != LORAHIP_OK) setLastError(err[failed]);
+        return rc;
+    }
+    catch (const std::bad_alloc &) { setLastError("out of host memory"); return LORAHIP_E_NOMEM; }        // nothing may cross the C ABI
+}
 
 } // namespace lorahip
 

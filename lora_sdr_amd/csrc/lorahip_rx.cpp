@@ -9,54 +9,24 @@
 // single-SF object's would, and every accessor maps global channel numbers to (part, local channel).
 #include "lorahip_own.h"
 #include <algorithm>
-#include <condition_variable>
 #include <cstring>
 #include <functional>
-#include <mutex>
-#include <new>
-#include <thread>
 
 namespace lorahip {
 
 namespace {
-//! a part's host thread: sleeps until a task is posted, runs it, keeps its code and error text (lorahip_last_error is per thread)
-struct PartWorker
-{
-    std::thread th;
-    std::mutex mu;
-    std::condition_variable cv;
-    bool have = false, done = true, quit = false;
-    std::function<int()> task;
-    int rc = LORAHIP_OK;
-    std::string err;
-    void loop()
-    {
-        std::unique_lock<std::mutex> lk(mu);
-        while (true)
-        {
-            cv.wait(lk, [this] { return have || quit; });
-            if (quit) return;
-            have = false;
-            lk.unlock();
-            const int r = task();
-            const std::string e = r == LORAHIP_OK ? std::string() : std::string(lorahip_last_error());
-            lk.lock();
-            rc = r; err = e; done = true;
-            cv.notify_all();
-        }
-    }
-};
+struct DemodDestroy { void operator()(lorahip_demod *d) const { lorahip_demod_destroy(d); } };
 } // namespace
 
 struct Composite::Impl
 {
     struct Part
     {
-        lorahip_demod *d = nullptr;
+        std::unique_ptr<lorahip_demod, DemodDestroy> d;
         int device = 0, deviceSlot = 0, sf = 0;
         std::vector<uint32_t> chan;             // global channel numbers, ascending
         DevBuf<int32_t> dGlobalOf;              // the same on the part's device, made by the first packet hand-off (packetsToDevice)
-        PartWorker *w = nullptr;
+        std::unique_ptr<ParkedThread> w;        // the host thread that issues its runs; none in a handle of one part
     };
     std::vector<Part> parts;
     std::vector<int> devices;
@@ -69,62 +39,43 @@ struct Composite::Impl
     {
         for (Part &p : parts)
         {
-            if (p.w)
-            {
-                { std::lock_guard<std::mutex> g(p.w->mu); p.w->quit = true; }
-                p.w->cv.notify_all();
-                if (p.w->th.joinable()) p.w->th.join();
-                delete p.w;
-            }
+            p.w.reset();                        // the thread ends first: it runs the part
             // (only where a hand-off made the table: a part whose creation failed may name a device that does not exist, and a failed
             // hipSetDevice would stay behind as this thread's last HIP error for the next launch to find)
             if (p.dGlobalOf.get() != nullptr) { const DeviceGuard guard(p.device); p.dGlobalOf.reset(); }
-            if (p.d) lorahip_demod_destroy(p.d);
+            p.d.reset();
         }
     }
 
     //! fn(part index) on every part, each on its own host thread; the first failure's code, its text as this thread's last error
-    int onAll(const std::function<int(size_t)> &fn)
+    template <class Fn> int onAll(const Fn &fn)
     {
         if (parts.size() == 1) return fn(0);
-        for (size_t i = 0; i < parts.size(); i++)
-        {
-            PartWorker *w = parts[i].w;
-            { std::lock_guard<std::mutex> g(w->mu); w->task = [&fn, i] { return fn(i); }; w->have = true; w->done = false; }
-            w->cv.notify_all();
-        }
-        int rc = LORAHIP_OK;
-        for (size_t i = 0; i < parts.size(); i++)
-        {
-            PartWorker *w = parts[i].w;
-            std::unique_lock<std::mutex> lk(w->mu);
-            w->cv.wait(lk, [w] { return w->done; });
-            if (w->rc != LORAHIP_OK && rc == LORAHIP_OK) { rc = w->rc; setLastError(w->err); }
-        }
-        return rc;
+        return runOnThreads(parts.size(), [this](const size_t i) { return parts[i].w.get(); }, fn);
     }
 
     //! the same on the calling thread, part after part (setters, accessors)
     int each(const std::function<int(lorahip_demod *)> &fn)
     {
-        for (Part &p : parts) { const int rc = fn(p.d); if (rc != LORAHIP_OK) return rc; }
+        for (Part &p : parts) { const int rc = fn(p.d.get()); if (rc != LORAHIP_OK) return rc; }
         return LORAHIP_OK;
     }
 };
 
-Composite::Composite() : p(nullptr) {}
-Composite::~Composite() { delete p; }
+Composite::Composite() {}
+Composite::~Composite() {}
 
 int Composite::create(Composite **out, const int *devices, const size_t nDev, const int32_t *channelSf, const size_t n)
 {
     if (out == nullptr || devices == nullptr || nDev == 0 || nDev > 4096 || channelSf == nullptr || n == 0 || n > 0x7fffffffu) return LORAHIP_E_INVALID;
     *out = nullptr;
     for (size_t c = 0; c < n; c++) if (channelSf[c] < LORAHIP_SF_MIN || channelSf[c] > LORAHIP_SF_MAX) return LORAHIP_E_INVALID;
-    Composite *k = nullptr;
     try
     {
-        k = new Composite();
-        k->p = new Impl();
+        std::unique_ptr<Composite> k(new Composite());
+        k->p = std::make_unique<Impl>();
+        // (what is torn down on the way out may leave its own last error: the failure's text is put back behind it)
+        const auto fail = [&k](const int rc) { const std::string e = lorahip_last_error(); k.reset(); setLastError(e); return rc; };
         Impl &I = *k->p;
         I.B = n;
         I.devices.assign(devices, devices + nDev);
@@ -132,7 +83,7 @@ int Composite::create(Composite **out, const int *devices, const size_t nDev, co
         for (size_t c = 1; c < n; c++) I.uniformSf = I.uniformSf && channelSf[c] == channelSf[0];
         std::vector<int32_t> shard(n, 0);
         const int prc = lorahip_shard_plan(channelSf, n, nDev, shard.data());
-        if (prc != LORAHIP_OK) { delete k; return prc; }
+        if (prc != LORAHIP_OK) return prc;
         I.partOf.assign(n, 0); I.localOf.assign(n, 0);
         for (size_t s = 0; s < nDev; s++)
             for (int sf = LORAHIP_SF_MIN; sf <= LORAHIP_SF_MAX; sf++)
@@ -145,8 +96,10 @@ int Composite::create(Composite **out, const int *devices, const size_t nDev, co
                 // whatever throws afterwards
                 I.parts.push_back(std::move(part));
                 Impl::Part &slot = I.parts.back();
-                const int rc = lorahip_demod_create(&slot.d, slot.device, sf, slot.chan.size());
-                if (rc != LORAHIP_OK) { const std::string e = lorahip_last_error(); delete k; setLastError(e); return rc; }
+                lorahip_demod *d = nullptr;
+                const int rc = lorahip_demod_create(&d, slot.device, sf, slot.chan.size());
+                if (rc != LORAHIP_OK) return fail(rc);
+                slot.d.reset(d);
                 for (size_t j = 0; j < slot.chan.size(); j++) { I.partOf[slot.chan[j]] = uint32_t(I.parts.size() - 1); I.localOf[slot.chan[j]] = uint32_t(j); }
             }
         // The parts of one device run side by side (runSegments: a stream and a host thread each), so a part's launch does not have the
@@ -158,19 +111,18 @@ int Composite::create(Composite **out, const int *devices, const size_t nDev, co
             unsigned long long others = 0;
             for (const Impl::Part &q : I.parts)
                 if (&q != &part && q.device == part.device) others += ((unsigned long long)q.chan.size() << (q.sf - 4)) / 64u + 1u;
-            demodSetCoResidentWaves(part.d, others > 0xffffffffull ? 0xffffffffu : unsigned(others));
+            demodSetCoResidentWaves(part.d.get(), others > 0xffffffffull ? 0xffffffffu : unsigned(others));
         }
         if (I.parts.size() > 1)
             for (Impl::Part &part : I.parts)
             {
-                part.w = new PartWorker();
-                part.w->th = std::thread(&PartWorker::loop, part.w);
+                part.w = std::make_unique<ParkedThread>();
+                if (!part.w->start()) { setLastError("lorahip_demod_create_mixed: a part's host thread could not be started"); return fail(LORAHIP_E_HIP); }
             }
+        *out = k.release();
+        return LORAHIP_OK;
     }
-    catch (const std::bad_alloc &) { delete k; return LORAHIP_E_NOMEM; }
-    catch (const std::exception &e) { delete k; setLastError(e.what()); return LORAHIP_E_HIP; }   // a thread could not be started
-    *out = k;
-    return LORAHIP_OK;
+    catch (const std::bad_alloc &) { return LORAHIP_E_NOMEM; }
 }
 
 size_t Composite::numChannels() const { return p->B; }
@@ -190,7 +142,7 @@ int Composite::partOf(int32_t *part, int32_t *local) const
     for (size_t c = 0; c < p->B; c++) { if (part) part[c] = int32_t(p->partOf[c]); if (local) local[c] = int32_t(p->localOf[c]); }
     return LORAHIP_OK;
 }
-lorahip_demod *Composite::part(const size_t i) const { return i < p->parts.size() ? p->parts[i].d : nullptr; }
+lorahip_demod *Composite::part(const size_t i) const { return i < p->parts.size() ? p->parts[i].d.get() : nullptr; }
 
 int Composite::setSync(const unsigned char v) { return p->each([v](lorahip_demod *d) { return lorahip_demod_set_sync(d, v); }); }
 int Composite::setThreshold(const double v) { return p->each([v](lorahip_demod *d) { return lorahip_demod_set_threshold(d, v); }); }
@@ -233,7 +185,7 @@ int Composite::run(const float *const *streams, const size_t *nSamples, int64_t 
             ptr[i].resize(ch.size()); len[i].resize(ch.size());
             for (size_t j = 0; j < ch.size(); j++) { ptr[i][j] = streams[ch[j]]; len[i][j] = nSamples[ch[j]]; }
         }
-        const int rc = I.onAll([&](const size_t i) { return lorahip_demod_run(I.parts[i].d, ptr[i].data(), len[i].data(), &rd[i]); });
+        const int rc = I.onAll([&](const size_t i) { return lorahip_demod_run(I.parts[i].d.get(), ptr[i].data(), len[i].data(), &rd[i]); });
         if (rounds) *rounds = *std::max_element(rd.begin(), rd.end());
         return rc;
     }
@@ -256,26 +208,26 @@ int Composite::runSegments(const float *const *iqPerDevice, const size_t nDev, c
             for (size_t j = 0; j < ch.size(); j++) { fs[i][j] = first[ch[j]]; len[i][j] = nSamples[ch[j]]; }
         }
         const int rc = I.onAll([&](const size_t i) {
-            return lorahip_demod_run_device_segments(I.parts[i].d, iqPerDevice[I.parts[i].deviceSlot], fs[i].data(), len[i].data(), &rd[i]); });
+            return lorahip_demod_run_device_segments(I.parts[i].d.get(), iqPerDevice[I.parts[i].deviceSlot], fs[i].data(), len[i].data(), &rd[i]); });
         if (rounds) *rounds = *std::max_element(rd.begin(), rd.end());
         return rc;
     }
     catch (const std::bad_alloc &) { setLastError("out of host memory"); return LORAHIP_E_NOMEM; }        // nothing may cross the C ABI
 }
 
-size_t Composite::numPackets() const { size_t n = 0; for (const auto &q : p->parts) n += lorahip_demod_num_packets(q.d); return n; }
-size_t Composite::numPacketSymbols() const { size_t n = 0; for (const auto &q : p->parts) n += lorahip_demod_num_packet_symbols(q.d); return n; }
-size_t Composite::numSignals() const { size_t n = 0; for (const auto &q : p->parts) n += lorahip_demod_num_signals(q.d); return n; }
+size_t Composite::numPackets() const { size_t n = 0; for (const auto &q : p->parts) n += lorahip_demod_num_packets(q.d.get()); return n; }
+size_t Composite::numPacketSymbols() const { size_t n = 0; for (const auto &q : p->parts) n += lorahip_demod_num_packet_symbols(q.d.get()); return n; }
+size_t Composite::numSignals() const { size_t n = 0; for (const auto &q : p->parts) n += lorahip_demod_num_signals(q.d.get()); return n; }
 
 int Composite::getPacket(size_t i, int32_t *channel, int64_t *round, size_t *len, int16_t *out, const size_t cap) const
 {
     for (const auto &q : p->parts)
     {
-        const size_t n = lorahip_demod_num_packets(q.d);
+        const size_t n = lorahip_demod_num_packets(q.d.get());
         if (i < n)
         {
             int32_t ch = 0;
-            const int rc = lorahip_demod_get_packet(q.d, i, &ch, round, len, out, cap);
+            const int rc = lorahip_demod_get_packet(q.d.get(), i, &ch, round, len, out, cap);
             if (rc == LORAHIP_OK && channel) *channel = int32_t(q.chan[size_t(ch)]);
             return rc;
         }
@@ -293,9 +245,9 @@ int Composite::getPackets(int32_t *channels, int64_t *rounds, int64_t *lens, con
         std::vector<int32_t> ch;
         for (const auto &q : p->parts)
         {
-            const size_t n = lorahip_demod_num_packets(q.d), ns = lorahip_demod_num_packet_symbols(q.d);
+            const size_t n = lorahip_demod_num_packets(q.d.get()), ns = lorahip_demod_num_packet_symbols(q.d.get());
             ch.resize(n);
-            const int rc = lorahip_demod_get_packets(q.d, ch.data(), rounds ? rounds + at : nullptr, lens ? lens + at : nullptr, n, syms ? syms + sat : nullptr, ns);
+            const int rc = lorahip_demod_get_packets(q.d.get(), ch.data(), rounds ? rounds + at : nullptr, lens ? lens + at : nullptr, n, syms ? syms + sat : nullptr, ns);
             if (rc != LORAHIP_OK) return rc;
             if (channels) for (size_t j = 0; j < n; j++) channels[at + j] = int32_t(q.chan[size_t(ch[j])]);
             at += n; sat += ns;
@@ -314,9 +266,9 @@ int Composite::getSignals(int32_t *channels, int64_t *rounds, int32_t *errors, f
         std::vector<int32_t> ch;
         for (const auto &q : p->parts)
         {
-            const size_t n = lorahip_demod_num_signals(q.d);
+            const size_t n = lorahip_demod_num_signals(q.d.get());
             ch.resize(n);
-            const int rc = lorahip_demod_get_signals(q.d, ch.data(), rounds ? rounds + at : nullptr, errors ? errors + at : nullptr, powers ? powers + at : nullptr,
+            const int rc = lorahip_demod_get_signals(q.d.get(), ch.data(), rounds ? rounds + at : nullptr, errors ? errors + at : nullptr, powers ? powers + at : nullptr,
                                                      snrs ? snrs + at : nullptr, n);
             if (rc != LORAHIP_OK) return rc;
             if (channels) for (size_t j = 0; j < n; j++) channels[at + j] = int32_t(q.chan[size_t(ch[j])]);
@@ -334,8 +286,8 @@ int Composite::getPacketsInfo(lorahip_rx_info *out, const size_t cap) const
     size_t at = 0;
     for (const auto &q : p->parts)
     {
-        const size_t n = lorahip_demod_num_packets(q.d);
-        const int rc = n ? lorahip_demod_get_packets_info(q.d, out + at, n) : LORAHIP_OK;
+        const size_t n = lorahip_demod_num_packets(q.d.get());
+        const int rc = n ? lorahip_demod_get_packets_info(q.d.get(), out + at, n) : LORAHIP_OK;
         if (rc != LORAHIP_OK) return rc;
         at += n;
     }
@@ -348,8 +300,8 @@ int Composite::getSignalsPos(int64_t *pos, const size_t cap) const
     size_t at = 0;
     for (const auto &q : p->parts)
     {
-        const size_t n = lorahip_demod_num_signals(q.d);
-        const int rc = n ? lorahip_demod_get_signals_pos(q.d, pos + at, n) : LORAHIP_OK;
+        const size_t n = lorahip_demod_num_signals(q.d.get());
+        const int rc = n ? lorahip_demod_get_signals_pos(q.d.get(), pos + at, n) : LORAHIP_OK;
         if (rc != LORAHIP_OK) return rc;
         at += n;
     }
@@ -393,27 +345,27 @@ int Composite::packetsToDevice(uint16_t *symsDev, const size_t symStride, int32_
     queued.reserve(I.parts.size());                     // (no allocation once work is in flight)
     for (Impl::Part &q : I.parts)
     {
-        const size_t n = lorahip_demod_num_packets(q.d);
+        const size_t n = lorahip_demod_num_packets(q.d.get());
         if (n == 0) continue;
         size_t got = 0;
-        rc = demodPacketsToDeviceQueued(q.d, symsDev + at * symStride, symStride, nsymsDev + at, channelDev ? channelDev + at : nullptr, infoDev ? infoDev + at : nullptr, n, &got,
+        rc = demodPacketsToDeviceQueued(q.d.get(), symsDev + at * symStride, symStride, nsymsDev + at, channelDev ? channelDev + at : nullptr, infoDev ? infoDev + at : nullptr, n, &got,
                                         q.dGlobalOf.get(), q.chan.size());
         if (rc != LORAHIP_OK) break;
         queued.push_back(&q);
         at += n;
     }
-    for (Impl::Part *q : queued) { const int src = demodStreamSync(q->d); if (rc == LORAHIP_OK) rc = src; }
+    for (Impl::Part *q : queued) { const int src = demodStreamSync(q->d.get()); if (rc == LORAHIP_OK) rc = src; }
     return rc;
     }
     catch (const std::bad_alloc &) { setLastError("out of host memory"); return LORAHIP_E_NOMEM; }        // nothing may cross the C ABI
 }
 
-void Composite::clearPackets() { for (auto &q : p->parts) lorahip_demod_clear_packets(q.d); }
+void Composite::clearPackets() { for (auto &q : p->parts) lorahip_demod_clear_packets(q.d.get()); }
 
 int64_t Composite::consumed(const size_t c) const
 {
     if (c >= p->B) return LORAHIP_E_INVALID;
-    return lorahip_demod_consumed(p->parts[p->partOf[c]].d, p->localOf[c]);
+    return lorahip_demod_consumed(p->parts[p->partOf[c]].d.get(), p->localOf[c]);
 }
 
 int Composite::consumedAll(int64_t *out) const
@@ -424,7 +376,7 @@ int Composite::consumedAll(int64_t *out) const
         for (const auto &q : p->parts)
         {
             tmp.resize(q.chan.size());
-            const int rc = lorahip_demod_consumed_all(q.d, tmp.data());
+            const int rc = lorahip_demod_consumed_all(q.d.get(), tmp.data());
             if (rc != LORAHIP_OK) return rc;
             for (size_t j = 0; j < q.chan.size(); j++) out[q.chan[j]] = tmp[j];
         }
@@ -433,16 +385,16 @@ int Composite::consumedAll(int64_t *out) const
     catch (const std::bad_alloc &) { setLastError("out of host memory"); return LORAHIP_E_NOMEM; }        // nothing may cross the C ABI
 }
 
-int64_t Composite::workCalls() const { int64_t n = 0; for (const auto &q : p->parts) n += lorahip_demod_work_calls(q.d); return n; }
-double Composite::kernelMs() const { double m = 0; for (const auto &q : p->parts) m = std::max(m, lorahip_demod_kernel_ms(q.d)); return m; }
-int Composite::lastLaunches() const { int m = 0; for (const auto &q : p->parts) m = std::max(m, lorahip_demod_last_launches(q.d)); return m; }
+int64_t Composite::workCalls() const { int64_t n = 0; for (const auto &q : p->parts) n += lorahip_demod_work_calls(q.d.get()); return n; }
+double Composite::kernelMs() const { double m = 0; for (const auto &q : p->parts) m = std::max(m, lorahip_demod_kernel_ms(q.d.get())); return m; }
+int Composite::lastLaunches() const { int m = 0; for (const auto &q : p->parts) m = std::max(m, lorahip_demod_last_launches(q.d.get())); return m; }
 int Composite::nearThreshold(int64_t *sq, int64_t *st) const
 {
     int64_t a = 0, b = 0;
     for (const auto &q : p->parts)
     {
         int64_t x = 0, y = 0;
-        const int rc = lorahip_demod_near_threshold(q.d, &x, &y);
+        const int rc = lorahip_demod_near_threshold(q.d.get(), &x, &y);
         if (rc != LORAHIP_OK) return rc;
         a += x; b += y;
     }
@@ -471,17 +423,17 @@ int Composite::setPorts(const lorahip_demod_ports *ports)
         if (sub.fft_dev) sub.fft_dev += 2 * first * sub.fft_cap_frames * N;
         if (sub.dec_dev) sub.dec_dev += 2 * first * sub.dec_cap_samples;
         if (sub.raw_dev) sub.raw_dev += 2 * first * sub.raw_cap_samples;
-        const int rc = lorahip_demod_set_ports(q.d, &sub);
+        const int rc = lorahip_demod_set_ports(q.d.get(), &sub);
         if (rc != LORAHIP_OK) return rc;
     }
     return LORAHIP_OK;
 }
 
-#define LORAHIP_RX_CHANNEL(c) if ((c) >= p->B) return LORAHIP_E_INVALID; lorahip_demod *d_ = p->parts[p->partOf[c]].d; const size_t l_ = p->localOf[c]
+#define LORAHIP_RX_CHANNEL(c) if ((c) >= p->B) return LORAHIP_E_INVALID; lorahip_demod *d_ = p->parts[p->partOf[c]].d.get(); const size_t l_ = p->localOf[c]
 int Composite::portCounts(const size_t c, size_t *f, size_t *d, size_t *r) const { LORAHIP_RX_CHANNEL(c); return lorahip_demod_port_counts(d_, l_, f, d, r); }
 int Composite::getLabels(const size_t c, char *buf, const size_t cap, size_t *n, size_t *bytes) const { LORAHIP_RX_CHANNEL(c); return lorahip_demod_get_labels(d_, l_, buf, cap, n, bytes); }
 int Composite::getTrace(const size_t c, lorahip_work_result *out, const size_t cap) const { LORAHIP_RX_CHANNEL(c); return lorahip_demod_get_trace(d_, l_, out, cap); }
-size_t Composite::traceLen(const size_t c) const { if (c >= p->B) return 0; return lorahip_demod_trace_len(p->parts[p->partOf[c]].d, p->localOf[c]); }
+size_t Composite::traceLen(const size_t c) const { if (c >= p->B) return 0; return lorahip_demod_trace_len(p->parts[p->partOf[c]].d.get(), p->localOf[c]); }
 #undef LORAHIP_RX_CHANNEL
 
 } // namespace lorahip

@@ -5,10 +5,8 @@
 // pieces that already live in pinned memory (lorahip_host_alloc, or anything hipHostMalloc'ed / hipHostRegister'ed) skip the
 // staging copy and go straight to the DMA engine.
 #include "lorahip_own.h"
-#include <condition_variable>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <thread>
 
 namespace lorahip {
@@ -79,72 +77,56 @@ static void copyShare(const std::vector<Seg> &segs, const size_t share, const in
  * bounds an upload from ordinary memory, ran at 37 GB/s where the DMA engine takes 55.) */
 struct CopyPool
 {
-    std::vector<std::thread> th;
-    std::mutex m;
-    std::condition_variable go, done;
-    const std::vector<Seg> *segs = nullptr;
-    size_t share = 0;
-    unsigned gen = 0;
-    int running = 0;
-    bool quit = false;
-
-    void worker(const int k)
+    //! helper k: a parked thread and the share it was last posted (the task a ParkedThread borrows)
+    struct Helper
     {
-        unsigned seen = 0;
-        for (;;)
+        const std::vector<Seg> *segs = nullptr;
+        size_t share = 0;
+        int k = 0;
+        ParkedThread th;                                  // (last: it goes first, before what its task reads)
+        int operator()() const { copyShare(*segs, share, k); return 0; }
+    };
+    std::vector<std::unique_ptr<Helper>> helper;          // helper[k - 1] copies share k; null where it could not be started
+
+    //! helpers for the shares 1 .. T-1 where there are none yet: a failed start is tried again by the next fill
+    void start(const int T)
+    {
+        try
         {
-            const std::vector<Seg> *mine; size_t sh;
+            if (helper.size() < size_t(T - 1)) helper.resize(size_t(T - 1));
+            for (int k = 1; k < T; k++)
             {
-                std::unique_lock<std::mutex> lk(m);
-                go.wait(lk, [&] { return quit || gen != seen; });
-                if (quit) return;
-                seen = gen; mine = segs; sh = share;
-            }
-            copyShare(*mine, sh, k);
-            {
-                std::lock_guard<std::mutex> lk(m);
-                if (--running == 0) done.notify_one();
+                if (helper[size_t(k - 1)]) continue;
+                auto h = std::make_unique<Helper>();
+                if (h->th.start()) helper[size_t(k - 1)] = std::move(h);
             }
         }
-    }
-    //! helpers 1 .. n-1 (as many as could be started); the caller is thread 0
-    int start(const int n)
-    {
-        try { for (int k = int(th.size()) + 1; k < n; k++) th.emplace_back(&CopyPool::worker, this, k); }
-        catch (...) {}                                    // (no exception may cross the C ABI: fewer helpers, the caller copies their shares)
-        return int(th.size()) + 1;
+        catch (const std::bad_alloc &) {}                 // (no exception may cross the C ABI: fewer helpers, the caller copies their shares)
     }
     void run(const std::vector<Seg> &s, const size_t total, const int T)
     {
-        const int have = start(T);
+        start(T);
         const size_t sh = (total + size_t(T) - 1) / size_t(T);
-        {
-            std::lock_guard<std::mutex> lk(m);
-            segs = &s; share = sh; running = have - 1; gen++;
-        }
-        go.notify_all();
+        // (helpers beyond T, from an earlier larger T, are posted nothing)
+        const auto helperOf = [&](const int k) { return size_t(k - 1) < helper.size() ? helper[size_t(k - 1)].get() : nullptr; };
+        for (int k = 1; k < T; k++)
+            if (Helper *h = helperOf(k)) { h->segs = &s; h->share = sh; h->k = k; h->th.post(*h); }
         copyShare(s, sh, 0);
-        for (int k = have; k < T; k++) copyShare(s, sh, k);   // shares of helpers that could not be started
-        // (helpers beyond T, from an earlier larger T, find their share empty)
-        std::unique_lock<std::mutex> lk(m);
-        done.wait(lk, [&] { return running == 0; });
-    }
-    ~CopyPool(void)
-    {
-        { std::lock_guard<std::mutex> lk(m); quit = true; }
-        go.notify_all();
-        for (auto &t : th) t.join();
+        for (int k = 1; k < T; k++) if (helperOf(k) == nullptr) copyShare(s, sh, k);   // shares of helpers that could not be started
+        for (int k = 1; k < T; k++) if (Helper *h = helperOf(k)) (void)h->th.wait();
     }
 };
+
+void CopyPoolDelete::operator()(CopyPool *p) const { delete p; }
 
 //! the segments of one staging fill, copied by the calling thread and up to T-1 parked helpers
 static void copySegments(Uploader &u, const std::vector<Seg> &segs, const size_t total)
 {
     const int T = total >= (size_t(4) << 20) ? uploadThreads() : 1;
     if (T <= 1) { for (const Seg &s : segs) std::memcpy(s.dst, s.src, s.bytes); return; }
-    if (u.pool == nullptr) u.pool = new (std::nothrow) CopyPool();
+    if (u.pool == nullptr) u.pool.reset(new (std::nothrow) CopyPool());
     if (u.pool == nullptr) { for (const Seg &s : segs) std::memcpy(s.dst, s.src, s.bytes); return; }
-    static_cast<CopyPool *>(u.pool)->run(segs, total, T);
+    u.pool->run(segs, total, T);
 }
 
 int gatherUpload(lorahip_ctx *ctx, void *dDstV, const void *const *src, const size_t *bytes, const size_t n)
@@ -236,8 +218,7 @@ void Uploader::release()
 {
     for (int k = 0; k < 2; k++) { buf[k].reset(); ev[k].reset(); busy[k] = false; }
     ready = false;
-    delete static_cast<CopyPool *>(pool);                 // (parks no thread beyond the context's life)
-    pool = nullptr;
+    pool.reset();                                         // (parks no thread beyond the context's life)
 }
 
 } // namespace lorahip

@@ -82,6 +82,42 @@ def test_demod_takes_one_2d_host_array(gpu, oracle):
     a.close(); b.close()
 
 
+def test_many_ordinary_pieces_through_the_parked_helpers_equal_one_device_buffer(gpu):
+    """The staging fill that takes the helper threads (lorahip_upload.cpp, CopyPool: fills of 4 MiB and more): 24 separately allocated
+    ordinary arrays of unequal lengths, each below 1 MiB (so none is asked whether it is pinned, and no run of equal pieces is merged
+    into one copy), 17 MiB together, so that the helpers' share boundaries fall inside pieces. The reference is the same streams laid
+    back to back in ONE device tensor (work_segments: nothing is uploaded through the pool): the packets (channel, symbols; a channel's
+    in time order) and the consumption are equal."""
+    import lora_sdr_amd as L
+    rng = np.random.default_rng(2121)
+    sf, B = 7, 24
+    lens = 60000 + 2731 * np.arange(B)
+    assert lens.max() * 8 < (1 << 20) and np.unique(lens).size == B and lens.sum() * 8 >= (4 << 20)
+    sent = [rng.integers(0, 256, 8).astype(np.uint8) for _ in range(6)]
+    tx, nsyms = L.transmit(sent, sf=sf, cr="4/8")
+    tx = tx.cpu().numpy()
+    streams = []
+    for c in range(B):
+        st = (0.05 * (rng.standard_normal(lens[c]) + 1j * rng.standard_normal(lens[c]))).astype(np.complex64)
+        if c % 4 == 1:
+            at = 300 + 1111 * c
+            st[at:at + tx.shape[1]] += tx[c // 4]
+        streams.append(st)
+    assert not any(np.shares_memory(a, b) for a in streams for b in streams if a is not b)
+    a = L.LoRaDemod(sf, n_channels=B); a.setMTU(int(nsyms.max()))
+    a.work(streams)
+    got, got_consumed = sorted(a.packets(), key=lambda p: p[0]), a.consumed_all()
+    first = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    b = L.LoRaDemod(sf, n_channels=B); b.setMTU(int(nsyms.max()))
+    b.work_segments(gpu.from_numpy(np.concatenate(streams)).cuda(), first, lens.astype(np.uint64))
+    want, want_consumed = sorted(b.packets(), key=lambda p: p[0]), b.consumed_all()
+    assert sum(1 for c, _r, _s in want if c % 4 == 1) >= 6
+    assert len(got) == len(want)
+    assert all(x[0] == y[0] and np.array_equal(x[2], y[2]) for x, y in zip(got, want))
+    assert np.array_equal(got_consumed, want_consumed)
+    a.close(); b.close()
+
+
 def test_pinned_allocation_round_trip(gpu):
     import lora_sdr_amd as L
     a = L.pinned_empty((3, 5), np.float32)
