@@ -758,6 +758,62 @@ int lorahip_decode_max_symbols(void);
 int lorahip_decode_max_data_length(void);
 
 /* -------------------------------------------------------------------------------------
+ * Soft-decision receive: a second pass over packets the demodulator has already found. lorahip_soft_symbols turns the symbol windows of
+ * each packet into one log-likelihood ratio per bit the decoder reads; lorahip_decode_packets_soft decodes rows of such values with a
+ * maximum-likelihood FEC step. No other entry point, kernel or result depends on either.
+ *
+ * SOFT SYMBOLS. n_packets RUNS of consecutive windows at the SF of the context. Window s of run p is the window lorahip_detect_batch
+ * evaluates with offsets = first_sample[p] + s*N, chirp_sel_all = LORAHIP_CHIRP_UP, fine_err = fine_err[p] and, as fine_idx0, the
+ * fine_idx_out of window s - 1 (fine_idx0[p] for s = 0); its bins X[k] are that call's fft_out bit for bit (default build of the
+ * kernels), sym_dev[p][s] is that call's sym. With
+ *       P[k] = re*re + im*im                                                         (float, no contraction)
+ *       g(k) = binaryToGray16(uint16((k + ((1 << (sf-ppm)) / 2)) >> (sf-ppm))) & ((1 << ppm) - 1)      (LoRaDecoder.cpp:218-222)
+ *       llr[p][s][m] = max{P[k] : bit m of g(k) = 1} - max{P[k] : bit m of g(k) = 0},   m = 0..ppm-1
+ * -- the max-log metric on |X|^2, positive = bit 1; one float subtraction of two exact maxima, so independent of any reduction order.
+ * Row p of llr_dev is sym_stride * ppm floats, window s at s * ppm; windows s >= min(nsyms[p], sym_stride) are not evaluated and their
+ * entries (and sym_dev's) are left as they were; nsyms[p] < 1: nothing is read or written for the run. ppm = 0 means sf.
+ * fine_idx0 / fine_err of a packet are the demodulator's _fineTuneIndex / _finefreqError when its first DATASYMBOLS call begins (both
+ * constant from there to the post, LoRaDemod.cpp:299, :308): in a trace (lorahip_demod_set_trace) the fine_idx_before / fine_err_before
+ * of the call that starts at lorahip_rx_info::data_pos. A fine_idx0 outside [0, 128*N) is masked into the table: an unspecified row,
+ * never a fault. LORAHIP_E_INVALID, nothing launched: a null required pointer with n_packets > 0, ppm outside 0..sf, sym_stride 0 or
+ * above lorahip_decode_max_symbols(), n_packets > 0x7fffffff. n_packets = 0 is no work. Asynchronous on the context's stream. */
+int lorahip_soft_symbols(lorahip_ctx *ctx, const float *iq_dev,
+                         const int64_t *first_sample_dev,   /* [n_packets] sample index in iq_dev of the run's first window */
+                         const int32_t *nsyms_dev,          /* [n_packets] windows in the run */
+                         const int32_t *fine_idx0_dev,      /* [n_packets] nullable -> 0 */
+                         const float *fine_err_dev,         /* [n_packets] nullable -> 0 */
+                         size_t n_packets, int ppm, float *llr_dev, size_t sym_stride,
+                         uint16_t *sym_dev /* nullable, [n_packets][sym_stride] */);
+/* THE SOFT DECODER: lorahip_decode_packets_info with rows of LLRs in place of rows of symbols. Packet p under entry e reads symbol s, bit m,
+ * at llr_dev[p * llr_stride + s * PPM_e + m] (PPM_e = the entry's ppm, or its sf), s < min(nsyms[p], sym_stride); every other symbol of
+ * its blocks is all-zero LLRs, as the hard decoder's are zero symbols. sym_stride * PPM_e <= llr_stride <= 8 * 12 * sym_stride for every
+ * entry (LORAHIP_E_INVALID otherwise). The hard bit of
+ * an LLR is 1 iff llr > 0.
+ *   - De-interleave and whitening move LLRs: bit k of codeword i of a block is the LLR at (symbol symOff + k, bit m), i = (m + k) % PPM; a
+ *     whitening bit of 1 negates it; bits a block does not carry (k >= 4 + its rate) are 0. Header block and whitening offsets as
+ *     LoRaDecoder.cpp:225-255.
+ *   - Where the reference calls decodeHamming84sx / 74sx / checkParity64 / 54 or passes a 4/4 nibble through, the nibble is the x in 0..15
+ *     that maximises M(x) = sum over k = 0..n-1 ascending of (bit k of enc(x) ? +L[k] : -L[k]), accumulated in float from 0.0f in that
+ *     order; the smallest x wins ties; enc = the encoder's codeword at the rate that call decodes (n = 4 + rdd; the first block: n = 8).
+ *   - The reference's `error` flag (error_check, fec_error) is still the hard decoders' over the hard bits: the hard codeword is the hard
+ *     bits of the LLRs as read, de-interleaved, XOR the whitening bits -- so drops and the report mean what they mean in the hard decoder.
+ *   - Header checksum and length, the CRC and its drop, hdr, the outcomes -1 / -2 / -3 (the row rule on the caps of lorahip_decode_plan),
+ *     need_syms and LORAHIP_RDD_FROM_HEADER (the rate field of the soft-decoded codeword 2) are the hard decoder's.
+ * On LLRs of +1 / -1 made from an encoder's row of symbols the result is lorahip_decode_packets_info's on that row (every codeword it
+ * decodes is a codeword, and a codeword beats every other candidate). interleaving = 0 in any entry is LORAHIP_E_INVALID (its output is symbols); lorahip_set_variant does not apply. The LLRs
+ * are read from device memory per codeword: a packet's LDS slice is 16 + cw_cap bytes at the lane count of lorahip_decode_plan, so every
+ * configuration the hard decoder accepts fits, data_length up to lorahip_decode_max_data_length() included. */
+int lorahip_decode_packets_soft(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfgs, size_t n_cfgs, const int32_t *index_dev,
+                                const int32_t *table_dev, size_t n_table, const float *llr_dev, size_t llr_stride, size_t sym_stride,
+                                const int32_t *nsyms_dev, size_t n_packets, uint8_t *out_dev, size_t out_stride, int32_t *out_len_dev,
+                                int32_t *dropped_dev, lorahip_packet_info *info_dev);
+/* ... with every buffer in HOST memory, as lorahip_decode_packets_info_host; synchronous */
+int lorahip_decode_packets_soft_host(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfgs, size_t n_cfgs, const int32_t *index,
+                                     const int32_t *table, size_t n_table, const float *llr, size_t llr_stride, size_t sym_stride,
+                                     const int32_t *nsyms, size_t n_packets, uint8_t *out, size_t out_stride, int32_t *out_len,
+                                     int32_t *dropped, lorahip_packet_info *info);
+
+/* -------------------------------------------------------------------------------------
  * Batched encoder (the first block of the chain): what the LoRaEncoder block does with one message of bytes
  * (LoRaEncoder.cpp:161-233 on LoRaCodes.hpp), for n_packets messages of different lengths at once. Parameters and defaults are
  * the block's (LoRaEncoder.cpp:78-85, setters :101-133): coding rate "4/4".."4/8" = rdd 0..4.

@@ -253,6 +253,32 @@ class Context(_Handle):
                                               float(noise_sigma), int(seed) & (2 ** 64 - 1)), "lorahip_synth_symbols")
         return iq
 
+    def soft_symbols(self, iq, first_sample, nsyms, fine_idx0=None, fine_err=None, ppm=0, sym_stride=None, hard=False, out=None):
+        """Per-bit log-likelihood ratios of P runs of consecutive symbol windows (lorahip_soft_symbols: the definition is in
+        include/lorahip.h). iq: complex64 device tensor (flat stream); first_sample (P,) int64, nsyms (P,) int32, fine_idx0 (P,) int32 or
+        None, fine_err (P,) float32 or None -- device tensors. -> llr (P, sym_stride, ppm) float32, zero behind a run's windows; with
+        hard=True also sym (P, sym_stride) int16 (uint16 payload), the hard symbol of each window. sym_stride must be given (a default
+        would have to read nsyms back): nothing here waits for the device. out: the caller's llr (or (llr, sym) with hard=True) to
+        write into instead of new zeroed tensors; entries behind a run's windows are left as they are."""
+        import torch
+        if sym_stride is None:
+            raise ValueError("soft_symbols: sym_stride (windows per row) must be given")
+        iq = iq.reshape(-1)
+        P, S, W = int(nsyms.numel()), int(sym_stride), int(ppm) or self.sf
+        if first_sample.numel() != P or any(x is not None and x.numel() != P for x in (fine_idx0, fine_err)):
+            raise ValueError("soft_symbols: one entry per run in first_sample, nsyms, fine_idx0, fine_err")
+        if out is not None:                               # the caller's rows: entries behind a run's windows stay as they are
+            llr, sym = out if hard else (out, None)
+            if tuple(llr.shape) != (P, S, W) or (hard and tuple(sym.shape) != (P, S)) or (hard and sym.dtype not in (torch.int16, torch.uint16)):
+                raise ValueError("soft_symbols: out must be llr (P, sym_stride, ppm) float32 [, sym (P, sym_stride) 16-bit]")
+        else:
+            llr = torch.zeros((P, S, W), dtype=torch.float32, device=iq.device)
+            sym = torch.zeros((P, S), dtype=torch.int16, device=iq.device) if hard else None
+        self.use_torch_stream()
+        check(self._lib.lorahip_soft_symbols(self._h, _dptr(iq, torch.complex64), _dptr(first_sample, torch.int64), _dptr(nsyms, torch.int32),
+                                             _dptr(fine_idx0, torch.int32), _dptr(fine_err, torch.float32), P, int(ppm), _dptr(llr, torch.float32), S,
+                                             _dptr(sym)), "lorahip_soft_symbols")
+        return (llr, sym) if hard else llr
 
     # ------------------------------------------------------------------
     def mod_frame_len(self, nsyms, padding=1):
@@ -1543,25 +1569,34 @@ def _index_ok(index, table, P, rows_ok=True):
         raise ValueError("index must be (P,) int32, table (T,) int32 device tensors")
 
 
-def _decode_rows(ctx, cfgs, n_cfgs, syms, nsyms, index, table, info):
-    """the one decoder call of LoRaDecoder (index None) and LoRaDecoderSet: checks, outputs, lorahip_decode_packets_info on the torch
-    stream -> (out, out_len, dropped), and the (P, 8) header report with info"""
+def _decode_rows(ctx, cfgs, n_cfgs, rows, nsyms, index, table, info, soft=False, width=None):
+    """the one decoder call of LoRaDecoder (index None) and LoRaDecoderSet: checks, outputs, the entry point on the torch stream ->
+    (out, out_len, dropped), and the (P, 8) header report with info. rows: (P, stride) 16-bit symbols (lorahip_decode_packets_info), or
+    with soft (P, stride, W) float32 LLRs as Context.soft_symbols returns them (lorahip_decode_packets_soft, rows of stride * W floats); width: the
+    W a single decoder reads -- a wider or narrower tensor is refused, not read as packed rows."""
     import torch
-    if syms.dim() != 2 or syms.dtype not in (torch.int16, torch.uint16) or nsyms.dtype != torch.int32:
+    if soft:
+        if rows.dim() != 3 or rows.dtype != torch.float32 or nsyms.dtype != torch.int32:
+            raise ValueError("llr must be (P, sym_stride, ppm) float32, nsyms (P,) int32 device tensors")
+        if width is not None and int(rows.shape[2]) != width:
+            raise ValueError("llr holds %d values per symbol, this decoder reads %d" % (int(rows.shape[2]), width))
+    elif rows.dim() != 2 or rows.dtype not in (torch.int16, torch.uint16) or nsyms.dtype != torch.int32:
         raise ValueError("syms must be (P, stride) 16-bit, nsyms (P,) int32 device tensors")
-    P, stride = int(syms.shape[0]), int(syms.shape[1])
+    P, stride = int(rows.shape[0]), int(rows.shape[1])
     if index is not None:
         _index_ok(index, table, P, nsyms.numel() == P)
         index, table = index.contiguous(), None if table is None else table.contiguous()
-    syms, nsyms = syms.contiguous(), nsyms.contiguous()
+    rows, nsyms = rows.contiguous(), nsyms.contiguous()
     out_stride = 2 * (stride + 8)
-    out = torch.zeros((P, out_stride), dtype=torch.uint8, device=syms.device)
-    out_len = torch.empty(P, dtype=torch.int32, device=syms.device)
-    dropped = torch.empty(P, dtype=torch.int32, device=syms.device)
-    rep = torch.empty((P, 8), dtype=torch.int32, device=syms.device) if info else None
+    out = torch.zeros((P, out_stride), dtype=torch.uint8, device=rows.device)
+    out_len = torch.empty(P, dtype=torch.int32, device=rows.device)
+    dropped = torch.empty(P, dtype=torch.int32, device=rows.device)
+    rep = torch.empty((P, 8), dtype=torch.int32, device=rows.device) if info else None
     ctx.use_torch_stream()
-    check(ctx._lib.lorahip_decode_packets_info(ctx._h, cfgs, n_cfgs, _dptr(index), *_table_args(table), _dptr(syms), stride, _dptr(nsyms), P,
-                                               _dptr(out), out_stride, _dptr(out_len), _dptr(dropped), _dptr(rep)), "lorahip_decode_packets_info")
+    name = "lorahip_decode_packets_soft" if soft else "lorahip_decode_packets_info"
+    row_args = (_dptr(rows), stride * int(rows.shape[2]), stride) if soft else (_dptr(rows), stride)
+    check(getattr(ctx._lib, name)(ctx._h, cfgs, n_cfgs, _dptr(index), *_table_args(table), *row_args, _dptr(nsyms), P,
+                                  _dptr(out), out_stride, _dptr(out_len), _dptr(dropped), _dptr(rep)), name)
     return (out, out_len, dropped, rep) if info else (out, out_len, dropped)
 
 
@@ -1649,6 +1684,12 @@ class LoRaDecoder:
         header report, a row per packet with the fields of struct lorahip_packet_info in include/lorahip.h"""
         return _decode_rows(self._ctx, C.byref(self._cfg), 1, syms, nsyms, None, None, info)
 
+    def decode_soft(self, llr, nsyms, info=False):
+        """decode_batch on rows of per-bit LLRs (Context.soft_symbols): llr (P, sym_stride, ppm) float32 with ppm this decoder's symbol
+        size, nsyms (P,) int32 -> what decode_batch returns. Maximum-likelihood FEC nibbles; drops and the report as the hard decoder's
+        (lorahip_decode_packets_soft in include/lorahip.h). Needs the de-interleaver on."""
+        return _decode_rows(self._ctx, C.byref(self._cfg), 1, llr, nsyms, None, None, info, soft=True, width=self._cfg.ppm or self._cfg.sf)
+
     def work(self, packets):
         import torch
         if self._cfg.ppm > self._cfg.sf:
@@ -1705,6 +1746,11 @@ class LoRaDecoderSet:
         (out uint8 (P, out_stride), out_len int32 (P,), dropped int32 (P,)) device tensors, as LoRaDecoder.decode_batch (info=True: and the
         (P, 8) int32 header report)"""
         return _decode_rows(self._ctx, self._cfgs, len(self._cfgs), syms, nsyms, index, table, info)
+
+    def decode_soft(self, llr, nsyms, index, table=None, info=False):
+        """decode_batch on rows of per-bit LLRs, as LoRaDecoder.decode_soft: llr (P, sym_stride, W) float32; a packet whose decoder reads
+        ppm < W bits per symbol has its symbol s at s * ppm of its row (lorahip_decode_packets_soft)"""
+        return _decode_rows(self._ctx, self._cfgs, len(self._cfgs), llr, nsyms, index, table, info, soft=True)
 
     def work(self, packets, index):
         """list of symbol arrays and the decoder of each -> list of bytes arrays (None where the block posts nothing), as

@@ -372,6 +372,32 @@ int lorahip_detect_batch_host(lorahip_ctx *ctx, const lorahip_batch *b)
     return LORAHIP_OK;
 }
 
+//! per-bit LLRs of runs of consecutive symbol windows (lorahip_soft.hip)
+int lorahip_soft_symbols(lorahip_ctx *ctx, const float *iq_dev, const int64_t *first_sample_dev, const int32_t *nsyms_dev,
+                         const int32_t *fine_idx0_dev, const float *fine_err_dev, const size_t n_packets, const int ppm,
+                         float *llr_dev, const size_t sym_stride, uint16_t *sym_dev)
+{
+    if (ctx == nullptr || ppm < 0 || ppm > ctx->sf) return LORAHIP_E_INVALID;
+    if (sym_stride == 0 || sym_stride > size_t(decodeMaxSymbols()) || n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
+    if (n_packets == 0) return LORAHIP_OK;
+    if (!iq_dev || !first_sample_dev || !nsyms_dev || !llr_dev) return LORAHIP_E_INVALID;
+    const DeviceGuard guard(ctx->device);
+    SoftArgs a;
+    a.iq = reinterpret_cast<const float2 *>(iq_dev);
+    a.first = reinterpret_cast<const long long *>(first_sample_dev);
+    a.nsyms = nsyms_dev; a.fineIdx0 = fine_idx0_dev; a.fineErr = fine_err_dev;
+    a.llr = llr_dev; a.sym = sym_dev;
+    a.down = ctx->dDown.get(); a.fine = ctx->dFine.get();
+    a.fineA = ctx->fineGather ? nullptr : ctx->dFineA.get();
+    a.fineB = ctx->fineGather ? nullptr : ctx->dFineB.get();
+    a.nRuns = unsigned(n_packets); a.symStride = int(sym_stride); a.ppm = ppm == 0 ? ctx->sf : ppm;
+    FastTables ft;
+    ft.twStage = ctx->dTwStage.get();
+    ft.nBlocksHint = ctx->cuCount;
+    LORAHIP_TRY(launchSoftSymbols(ctx->sf, a, ft, ctx->stream));
+    return LORAHIP_OK;
+}
+
 int lorahip_timer_start(lorahip_ctx *ctx)
 {
     if (ctx == nullptr) return LORAHIP_E_INVALID;

@@ -1191,6 +1191,278 @@ hipError_t launchEncodeCfgs(const EncodeArgs &rows, const EncodeCfg *cfgs, const
     return withLanes(t.lanes, [&](auto g) { return launchGroup<encodeGroupCfgs<decltype(g)::value>>(rows.nPackets, t.perBlock, t.slice, stream, rows, tab, t.slice, t.perBlock); });
 }
 
+/***********************************************************************
+ * the soft-decision decoder (lorahip_decode_packets_soft): a symbol is its PPM log-likelihood ratios (positive: bit 1 of the Gray-coded,
+ * rounded symbol value), and every FEC nibble is the x in 0..15 whose codeword correlates best with the codeword's LLRs. Behind the hard
+ * kernels on purpose: those stay the functions they were. What decodeSoftBody shares with decodeGroupBody is the order of the reference's
+ * decisions, the row rule and everything from the checksum on, statement for statement; the `error` flag is still the hard decoders' over
+ * the hard bits (llr > 0). The LLRs stay in global memory: a lane gathers the (at most eight) values of its codeword from the symbols of
+ * its interleaver block -- the same diagonal the hard kernel walks in LDS -- so a packet's LDS slice holds its nibbles and nothing else,
+ * and no configuration outgrows it.
+ **********************************************************************/
+namespace {
+
+/*! Codeword c of packet row `llr` (PPM floats per symbol, rowSyms symbols present): its hard bits, de-whitened, and in L[0..7] its LLRs with a
+ * whitening bit of 1 negating the value. Bits the block does not carry, symbols behind the row, a block that is not whole and codewords
+ * behind numCodewords are hard 0 / LLR 0, as decodeGroupBody's zero symbols and zero codewords are. */
+__device__ __forceinline__ unsigned softCodeword(const float *llr, const int rowSyms, const int c, const int PPM, const int rate, const bool hdrBlock,
+                                                 const int numSymbols, const int numCodewords, const int explicitHdr, float (&L)[8])
+{
+#pragma unroll
+    for (int k = 0; k < 8; k++) L[k] = 0.0f;
+    if (c >= numCodewords) return 0u;
+    const int bs = 4 + rate;
+    int x, i, symOff, R;
+    if (hdrBlock && c < PPM) { x = 0; i = c; symOff = 0; R = LORAHIP_HDR_RDD; }
+    else if (hdrBlock) { x = (c - PPM) / PPM; i = (c - PPM) - x * PPM; symOff = LORAHIP_N_HDR_SYMBOLS + x * bs; R = rate; }
+    else { x = c / PPM; i = c - x * PPM; symOff = x * bs; R = rate; }
+    unsigned cw = 0;
+    if (!hdrBlock || c < PPM || symOff + (4 + R) <= numSymbols)
+    {
+#pragma unroll
+        for (int k = 0; k < 8; k++)
+        {
+            int m = i - (k % PPM);
+            if (m < 0) m += PPM;
+            if (k < 4 + R && symOff + k < rowSyms) L[k] = llr[(size_t)(symOff + k) * PPM + m];
+            cw |= (L[k] > 0.0f ? 1u : 0u) << k;
+        }
+    }
+    const int pos = explicitHdr ? c - LORAHIP_N_HDR_CODEWORDS : c;
+    if (pos >= 0 && (pos >> 1) < LORAHIP_WHITEN_LEN && !(hdrBlock && c >= PPM && numSymbols <= LORAHIP_N_HDR_SYMBOLS))
+    {
+        const int Rw = (hdrBlock && c < PPM) ? LORAHIP_HDR_RDD : rate;
+        const unsigned w = kCodec.white[Rw == 1 ? 1 : 0][pos & 1][pos >> 1] & (0xffu >> (4 - Rw));
+        cw ^= w;
+#pragma unroll
+        for (int k = 0; k < 8; k++) L[k] = ((w >> k) & 1u) ? -L[k] : L[k];
+    }
+    return cw;
+}
+
+//! the nibble x that maximises M(x) = sum over k = 0..3+rdd ascending of (bit k of the rate's codeword of x ? +L[k] : -L[k]), in float;
+//! the smallest x among equals
+__device__ __forceinline__ unsigned softNibble(const float (&L)[8], const int rdd)
+{
+    unsigned best = 0;
+    float bestM = 0.0f;
+    for (unsigned x = 0; x < 16; x++)
+    {
+        const unsigned code = encodeNibble(x, rdd);
+        float M = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 8; k++)
+            if (k < 4 + rdd) M = M + (((code >> k) & 1u) ? L[k] : -L[k]);
+        if (x == 0 || M > bestM) { bestM = M; best = x; }
+    }
+    return best;
+}
+
+} // namespace
+
+template <int G>
+__device__ __forceinline__ void decodeSoftBody(const DecodeArgs a, const float *llrRows, const long long llrStride, const DecodeCaps caps, const int slice,
+                                               const int perBlock, const bool known)
+{
+    // per packet: 16 bytes for the header block's five codewords (hard bits, then soft nibbles), then the nibbles
+    extern __shared__ __attribute__((aligned(16))) unsigned char smemDec[];
+    int symCap = caps.symCap, cwCap = caps.cwCap;
+    const int g = threadIdx.x / G, t = threadIdx.x % G;
+    unsigned char *sHdr = smemDec + (size_t)g * slice;
+    unsigned char *sNib = sHdr + 16;
+    int iLen = -1, iRdd = -1, iCrc = 0, iRes = -1, iNeed = -1;     // the report (lorahip_packet_info): "header not reached"
+    const unsigned p = blockIdx.x * perBlock + g;
+    const bool have = g < perBlock && p < a.nPackets;
+    const unsigned pc = have ? p : 0;
+    const int nsyms = have ? a.nsyms[pc] : 0;
+    unsigned char *out = a.out + (size_t)pc * a.outStride;
+    int outLen = -1, dropped = 0;
+
+    const int sf = a.sf;
+    const int PPM = a.ppm == 0 ? sf : a.ppm;                                                 // LoRaDecoder.cpp:201
+    const float *llr = llrRows + (size_t)pc * llrStride;
+    int rate = a.rdd < 0 ? LORAHIP_HDR_RDD : a.rdd;
+    int bs = 4 + rate;
+    int numSymbols = ((nsyms + bs - 1) / bs) * bs;                                           // :210
+    int numCodewords = (numSymbols / bs) * PPM;                                              // :211
+    const int rowSyms = nsyms < a.symStride ? nsyms : a.symStride;
+    bool go = have && known && !(PPM > sf || nsyms < LORAHIP_N_HDR_SYMBOLS);                 // :202, :208
+
+    // ---- the five header codewords: always the first block at 4/8 over symbols 0..7, never whitened ------------------------
+    if (go && a.explicitHdr)
+        for (int c = t; c < LORAHIP_N_HDR_CODEWORDS; c += G)
+        {
+            float L[8];
+            sHdr[c] = (unsigned char)softCodeword(llr, rowSyms, c, PPM, LORAHIP_HDR_RDD, false, LORAHIP_N_HDR_SYMBOLS, PPM, 1, L);
+            sHdr[8 + c] = (unsigned char)softNibble(L, LORAHIP_HDR_RDD);
+        }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __syncthreads();
+
+    // ---- header rate (LORAHIP_RDD_FROM_HEADER): the soft-decoded codeword 2 names it; from here on a packet of that rate -----------
+    if (a.rdd < 0)                                                                           // (group-uniform; no barrier inside)
+    {
+        if (go)
+        {
+            const int field = (sHdr[8 + 2] >> 1) & 0x7;
+            rate = field > 4 ? LORAHIP_HDR_RDD : field;
+        }
+        const DecodeCaps cr = decodeCapsAt(sf, a.ppm, rate, 1, a.dataLength, a.symStride);
+        symCap = cr.symCap; cwCap = cr.cwCap;
+        bs = 4 + rate;
+        const int nBlocks = (nsyms + bs - 1) / bs;
+        numSymbols = nBlocks * bs;
+        numCodewords = nBlocks * PPM;
+    }
+    const bool hdrBlock = rate != LORAHIP_HDR_RDD;
+
+    // ---- header (:283-311), evaluated by every lane of the group alike: the nibbles soft, the error flag from the hard bits ----------
+    bool error = false, bad = false;
+    const int nbytes = (numCodewords + 1) / 2;
+    long long packetLength = 0, dataLength = 0;
+    bool checkCrc = a.crcc != 0;
+    int rdd = rate;
+    unsigned char h0 = 0, h1 = 0, h2 = 0;
+    if (go)
+    {
+        if (a.explicitHdr)
+        {
+            for (int c = 0; c < LORAHIP_N_HDR_CODEWORDS; c++) (void)decodeHamming84(sHdr[c], error, bad);
+            h0 = (unsigned char)(sHdr[8 + 1] | (sHdr[8 + 0] << 4));                          // length
+            h1 = sHdr[8 + 2];                                                                // coding rate and crc enable
+            h2 = (unsigned char)(sHdr[8 + 4] | (sHdr[8 + 3] << 4));                          // checksum
+            const unsigned char hb[2] = { h0, h1 };
+            h2 ^= headerChecksum(hb);
+            iLen = h0; iRdd = (h1 >> 1) & 0x7; iRes = h2;
+            if (error && a.errorCheck) { dropped = 1; go = false; }
+            if (go)
+            {
+                if (0 == (h1 & 1)) checkCrc = false;
+                rdd = (h1 >> 1) & 0x7;
+                if (rdd > 4) { dropped = 1; go = false; }
+                packetLength = h0;
+                dataLength = packetLength + ((h1 & 1) ? 5 : 3);
+            }
+        }
+        else
+        {
+            packetLength = a.dataLength;
+            dataLength = a.crcc ? packetLength + 2 : packetLength;
+            iLen = a.dataLength; iRdd = rate;
+        }
+        if (go && dataLength > nbytes) { dropped = 1; go = false; }                          // :313
+    }
+
+    // ---- nibbles (:315-361), a codeword per lane and round, its LLRs gathered from the row ------------------------------------------
+    const int c0 = a.explicitHdr ? LORAHIP_N_HDR_CODEWORDS : 0, shift = a.explicitHdr ? 1 : 0;
+    long long cEnd = 0;
+    if (go)
+    {
+        cEnd = 2 * dataLength - shift;
+        const int fill = PPM + (((PPM + shift) & 1) ? 1 : 0);
+        if (cEnd < fill) cEnd = fill;
+        const long long nBlocks = (cEnd + PPM - 1) / PPM;
+        const long long needSyms = hdrBlock ? LORAHIP_N_HDR_SYMBOLS + (nBlocks - 1) * bs : nBlocks * bs;
+        iNeed = (int)needSyms;
+        // the row rule of decodeGroupBody, on the caps of the hard plan: the same packets are -2 in both decoders
+        if ((nsyms > a.symStride && needSyms > a.symStride) || needSyms > symCap || cEnd + 4 > cwCap) { outLen = -2; go = false; }
+    }
+    if (go)
+    {
+        if (a.explicitHdr) { sNib[0] = h0 & 0xf; sNib[1] = h0 >> 4; sNib[2] = h1 & 0xf; sNib[3] = 0; sNib[4] = h2 & 0xf; sNib[5] = h2 >> 4; }
+        for (int c = c0 + t; c < cEnd; c += G)
+        {
+            float L[8];
+            const unsigned char cw = (unsigned char)softCodeword(llr, rowSyms, c, PPM, rate, hdrBlock, numSymbols, numCodewords, a.explicitHdr, L);
+            if (c < PPM) (void)decodeHamming84(cw, error, bad);
+            else (void)decodeNibble(cw, rdd, error, bad);
+            sNib[c + shift] = (unsigned char)softNibble(L, c < PPM ? LORAHIP_HDR_RDD : rdd);
+        }
+        for (long long v = cEnd + shift + t; v < 2 * (dataLength + 1); v += G) sNib[v] = 0;
+    }
+    error = groupAny<G>(error);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __syncthreads();
+    if (go && error && a.errorCheck) { dropped = 1; go = false; }                            // :342, :363
+
+    // ---- checksum (:367-388) and output: decodeGroupBody's, statement for statement ----------------------------------------------------
+    int dOfs = 0;
+    if (go && (a.explicitHdr ? (h1 & 1) != 0 : checkCrc))
+    {
+        const int base = a.explicitHdr ? 3 : 0;
+        const int len = a.explicitHdr ? (int)packetLength : a.dataLength;
+        unsigned acc = 0;
+        for (int i = t; i < len; i += G)
+        {
+            const unsigned byte = sNib[2 * (base + i)] | (sNib[2 * (base + i) + 1] << 4);
+            acc ^= crcShift(byte, kCodec.xpow[len - 1 - i]);
+        }
+        unsigned crc = groupXor<G>(acc);
+        crc ^= kCodec.lfsr8[len];
+        crc ^= (unsigned)kCodec.lfsr8[len + 1] << 8;
+        crc &= 0xffff;
+        const unsigned packetCrc = (sNib[2 * (base + len)] | (sNib[2 * (base + len) + 1] << 4)) |
+                                   ((sNib[2 * (base + len) + 2] | (sNib[2 * (base + len) + 3] << 4)) << 8);
+        iCrc = crc == packetCrc ? 1 : -1;
+        if (a.explicitHdr)
+        {
+            if (crc != packetCrc && checkCrc) { dropped = 1; go = false; }
+        }
+        else if (crc != packetCrc) { dropped = 1; go = false; }
+        if (go && t == 0)
+        {
+            const unsigned lo = (sNib[2 * (base + len)] | (sNib[2 * (base + len) + 1] << 4)) ^ (crc & 0xff);
+            const unsigned hi = (sNib[2 * (base + len) + 2] | (sNib[2 * (base + len) + 3] << 4)) ^ (crc >> 8);
+            sNib[2 * (base + len)] = lo & 0xf; sNib[2 * (base + len) + 1] = (lo >> 4) & 0xf;
+            sNib[2 * (base + len) + 2] = hi & 0xf; sNib[2 * (base + len) + 3] = (hi >> 4) & 0xf;
+        }
+    }
+    if (go && a.explicitHdr && !a.hdr) { dOfs = 3; dataLength -= 5; }                        // :379
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __syncthreads();
+    if (go && dataLength >= 0)
+    {
+        for (long long i = t; i < dataLength; i += G) out[i] = (unsigned char)(sNib[2 * (dOfs + i)] | (sNib[2 * (dOfs + i) + 1] << 4));   // :391-395
+        outLen = (int)dataLength;
+    }
+    if (have && t == 0)
+    {
+        a.outLen[p] = known ? outLen : -3;
+        a.dropped[p] = dropped;
+        if (a.info != nullptr) writePacketInfo(a.info, p, iLen, iRdd, iCrc, iRes, error ? 1 : 0, iNeed);
+    }
+}
+
+template <int G>
+__global__ void __launch_bounds__(256) decodeSoftCfgs(const DecodeArgs rows, const float *llr, const long long llrStride, const DecodeCfgTable tab,
+                                                      const int slice, const int perBlock)
+{
+    const int g = threadIdx.x / G;
+    const unsigned p = blockIdx.x * perBlock + g;
+    // index null: the uniform launch under the table's only entry
+    const int i = (g < perBlock && p < rows.nPackets && tab.index != nullptr) ? cfgIndexOf(tab, p) : 0;
+    const DecodeCfg &e = tab.e[i < 0 ? 0 : i];
+    const DecodeCaps caps = { e.symCap, e.cwCap };
+    decodeSoftBody<G>(withCfg(rows, e), llr, llrStride, caps, slice, perBlock, i >= 0);
+}
+
+hipError_t launchDecodeSoft(const DecodeArgs &rows, const float *llr, const long long llrStride, const DecodeCfg *cfgs, const size_t nCfgs,
+                            const int *index, const int *table, const int nTable, hipStream_t stream)
+{
+    if (rows.nPackets == 0) return hipSuccess;
+    if (nCfgs == 0 || nCfgs > size_t(LORAHIP_DEC_MAX_CFGS)) return hipErrorInvalidValue;
+    DecodeCfgTable tab;
+    tab.index = index; tab.table = table; tab.nTable = nTable; tab.nCfgs = int(nCfgs);
+    for (size_t i = 0; i < size_t(LORAHIP_DEC_MAX_CFGS); i++) tab.e[i] = cfgs[i < nCfgs ? i : 0];
+    // lanes and caps of the hard plan (the caps enter the row rule); the slice is the nibbles' alone
+    const DecodeTiling t = decodePlan(tab.e, nCfgs, rows.symStride);
+    const int slice = (16 + t.cwCap + 15) & ~15;
+    int perBlock = 256 / t.lanes;
+    if (slice * perBlock > kGroupLdsMax) perBlock = kGroupLdsMax / slice;
+    if (perBlock < 1) return hipErrorInvalidValue;                  // (the entry points bound data_length: cannot happen)
+    return withLanes(t.lanes, [&](auto g) { return launchGroup<decodeSoftCfgs<decltype(g)::value>>(rows.nPackets, perBlock, slice, stream, rows, llr, llrStride, tab, slice, perBlock); });
+}
+
 // rows: the de-whitening takes its length as a uint16_t in the reference (LoRaCodes.hpp: Sx1272ComputeWhiteningLfsr), i.e. messages of
 // up to 65535 codewords are what the reference itself decodes as written; 16384 symbols stay below that at every setting
 int decodeMaxSymbols() { return 16384; }

@@ -133,6 +133,7 @@ struct DecodeCall
     uint8_t *out; size_t out_stride;
     int32_t *out_len, *dropped;
     lorahip_packet_info *info;
+    const float *llr = nullptr; size_t llr_stride = 0;     // the soft forms: rows of LLRs in place of syms
 };
 
 //! The forms that take ONE configuration let a call without packets succeed before they look at the configuration: the device form
@@ -153,8 +154,20 @@ int decodeCallOk(const lorahip_ctx *ctx, const DecodeCall &c, const Single singl
     { const int rc = decodeCfgsOk(c.cfgs, c.n_cfgs); if (rc != LORAHIP_OK) return rc; }
     if (!needIndex && c.index == nullptr && (c.n_cfgs != 1 || c.table != nullptr)) return LORAHIP_E_INVALID;
     if ((c.table != nullptr && c.n_table == 0) || c.n_table > 0x7fffffffu || !decodeRowsOk(c.sym_stride, c.out_stride)) return LORAHIP_E_INVALID;
+    if (c.llr != nullptr || c.llr_stride != 0)
+    {
+        // the soft forms: no output of symbols, and every entry's symbols inside a row
+        for (size_t i = 0; i < c.n_cfgs; i++)
+        {
+            if (!c.cfgs[i].interleaving) { setLastError("the soft decoder needs interleaving = 1"); return LORAHIP_E_INVALID; }
+            if (c.llr_stride / size_t(c.cfgs[i].ppm ? c.cfgs[i].ppm : c.cfgs[i].sf) < c.sym_stride) return LORAHIP_E_INVALID;
+        }
+        // a row is at most sym_stride symbols of LORAHIP_SF_MAX values; padding up to eight times that is taken, more is a garbage stride
+        // (and n_packets * llr_stride * sizeof(float), which the host form stages, stays far below 2^64: 2^31 * 2^21 * 4)
+        if (c.llr_stride > c.sym_stride * size_t(LORAHIP_SF_MAX) * 8) return LORAHIP_E_INVALID;
+    }
     if (c.n_packets == 0) return LORAHIP_OK;
-    if ((needIndex && !c.index) || !c.syms || !c.nsyms || !c.out || !c.out_len || !c.dropped || c.n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
+    if ((needIndex && !c.index) || (!c.syms && !c.llr) || !c.nsyms || !c.out || !c.out_len || !c.dropped || c.n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
     return LORAHIP_OK;
 }
 
@@ -170,7 +183,8 @@ int decodeRun(lorahip_ctx *ctx, const DecodeCall &c)
     a.info = reinterpret_cast<int *>(c.info);
     DecodeCfg tab[LORAHIP_DEC_MAX_CFGS];
     for (size_t i = 0; i < c.n_cfgs; i++) tab[i] = decodeCfgOf(c.cfgs[i]);
-    if (c.index == nullptr) LORAHIP_TRY(launchDecode(a, tab[0], ctx->variant, ctx->stream));
+    if (c.llr != nullptr) LORAHIP_TRY(launchDecodeSoft(a, c.llr, (long long)c.llr_stride, tab, c.n_cfgs, c.index, c.table, int(c.n_table), ctx->stream));
+    else if (c.index == nullptr) LORAHIP_TRY(launchDecode(a, tab[0], ctx->variant, ctx->stream));
     else LORAHIP_TRY(launchDecodeCfgs(a, tab, c.n_cfgs, c.index, c.table, int(c.n_table), ctx->variant, ctx->stream));
     return LORAHIP_OK;
 }
@@ -182,15 +196,15 @@ int decodeStaged(lorahip_ctx *ctx, const DecodeCall &c, const bool rowsBothWays)
 {
     const DeviceGuard guard(ctx->device);
     Staged st(ctx);
-    const Staged::Piece pSym = st.in(c.syms, c.n_packets * c.sym_stride * sizeof(uint16_t)), pN = st.in(c.nsyms, c.n_packets * sizeof(int32_t));
+    const Staged::Piece pSym = c.llr ? st.in(c.llr, c.n_packets * c.llr_stride * sizeof(float)) : st.in(c.syms, c.n_packets * c.sym_stride * sizeof(uint16_t)), pN = st.in(c.nsyms, c.n_packets * sizeof(int32_t));
     const Staged::Piece pIdx = st.in(c.index, c.n_packets * sizeof(int32_t)), pTab = st.in(c.table, c.n_table * sizeof(int32_t));
     const Staged::Piece pOut = rowsBothWays ? st.inout(c.out, c.n_packets * c.out_stride) : st.out(c.out, c.n_packets * c.out_stride);
     const Staged::Piece pLen = st.out(c.out_len, c.n_packets * sizeof(int32_t)), pDrop = st.out(c.dropped, c.n_packets * sizeof(int32_t));
     const Staged::Piece pInfo = st.out(c.info, c.n_packets * sizeof(lorahip_packet_info));
     { const int rc = st.upload(); if (rc != LORAHIP_OK) return rc; }
-    const DecodeCall d = { c.cfgs, c.n_cfgs, st.dev<const int32_t>(pIdx), st.dev<const int32_t>(pTab), c.n_table, st.dev<const uint16_t>(pSym), c.sym_stride,
+    const DecodeCall d = { c.cfgs, c.n_cfgs, st.dev<const int32_t>(pIdx), st.dev<const int32_t>(pTab), c.n_table, c.llr ? nullptr : st.dev<const uint16_t>(pSym), c.sym_stride,
                            st.dev<const int32_t>(pN), c.n_packets, st.dev<uint8_t>(pOut), c.out_stride, st.dev<int32_t>(pLen), st.dev<int32_t>(pDrop),
-                           st.dev<lorahip_packet_info>(pInfo) };
+                           st.dev<lorahip_packet_info>(pInfo), c.llr ? st.dev<const float>(pSym) : nullptr, c.llr_stride };
     { const int rc = decodeRun(ctx, d); if (rc != LORAHIP_OK) return rc; }
     return st.download();
 }
@@ -341,6 +355,27 @@ int lorahip_decode_packets_info_host(lorahip_ctx *ctx, const lorahip_decoder_cfg
                                      int32_t *dropped, lorahip_packet_info *info)
 {
     const DecodeCall c = { cfgs, n_cfgs, index, table, n_table, syms, sym_stride, nsyms, n_packets, out, out_stride, out_len, dropped, info };
+    return decodeEntry(ctx, c, Single::No, false, Where::HostRowsBothWays);
+}
+
+int lorahip_decode_packets_soft(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfgs, const size_t n_cfgs, const int32_t *index_dev,
+                                const int32_t *table_dev, const size_t n_table, const float *llr_dev, const size_t llr_stride, const size_t sym_stride,
+                                const int32_t *nsyms_dev, const size_t n_packets, uint8_t *out_dev, const size_t out_stride,
+                                int32_t *out_len_dev, int32_t *dropped_dev, lorahip_packet_info *info_dev)
+{
+    if (llr_stride == 0) return LORAHIP_E_INVALID;
+    const DecodeCall c = { cfgs, n_cfgs, index_dev, table_dev, n_table, nullptr, sym_stride, nsyms_dev, n_packets, out_dev, out_stride, out_len_dev, dropped_dev, info_dev,
+                           llr_dev, llr_stride };
+    return decodeEntry(ctx, c, Single::No, false, Where::Device);
+}
+
+int lorahip_decode_packets_soft_host(lorahip_ctx *ctx, const lorahip_decoder_cfg *cfgs, const size_t n_cfgs, const int32_t *index,
+                                     const int32_t *table, const size_t n_table, const float *llr, const size_t llr_stride, const size_t sym_stride,
+                                     const int32_t *nsyms, const size_t n_packets, uint8_t *out, const size_t out_stride, int32_t *out_len,
+                                     int32_t *dropped, lorahip_packet_info *info)
+{
+    if (llr_stride == 0) return LORAHIP_E_INVALID;
+    const DecodeCall c = { cfgs, n_cfgs, index, table, n_table, nullptr, sym_stride, nsyms, n_packets, out, out_stride, out_len, dropped, info, llr, llr_stride };
     return decodeEntry(ctx, c, Single::No, false, Where::HostRowsBothWays);
 }
 

@@ -61,6 +61,25 @@ struct FastTables
 //! host: stage-major twiddle table from kissfft's table (lorahip_fast.hip)
 std::vector<cf32> buildStageTwiddles(int sf, const std::vector<cf32> &tw);
 
+//! argument block of the soft symbol kernels (lorahip_soft.hip); device pointers, one entry per run of consecutive windows
+struct SoftArgs
+{
+    const float2 *iq;
+    const long long *first;     // [nRuns] sample index of the run's first window
+    const int *nsyms;           // [nRuns] windows in the run
+    const int *fineIdx0;        // [nRuns], nullable
+    const float *fineErr;       // [nRuns], nullable
+    float *llr;                 // [nRuns][symStride][ppm]
+    unsigned short *sym;        // [nRuns][symStride], nullable
+    const float2 *down;
+    const float2 *fine;
+    const double2 *fineA;       // split of the fine-tune table (lorahip_fine.h); nullptr: gather from `fine`
+    const double2 *fineB;
+    unsigned nRuns;
+    int symStride, ppm;         // ppm: 1..sf
+};
+hipError_t launchSoftSymbols(int sf, const SoftArgs &a, const FastTables &ft, hipStream_t stream);
+
 //! per-channel state of the LoRaDemod block as the streaming kernel keeps it (LoRaDemod.cpp:385-392)
 struct StreamState
 {
@@ -277,6 +296,10 @@ DecodeTiling decodePlan(DecodeCfg *cfgs, size_t nCfgs, int symStride);          
 //! the rows of `rows` (its nine settings are not read), packet p under cfgs[index[p]] or cfgs[table[index[p]]]; outcome -3 without such an entry
 hipError_t launchDecodeCfgs(const DecodeArgs &rows, const DecodeCfg *cfgs, size_t nCfgs, const int *index, const int *table, int nTable,
                             int variant, hipStream_t stream);
+//! the soft-decision decoder: rows.syms is not read; packet p's symbol s is the PPM floats at llr + p * llrStride + s * PPM (PPM of p's entry).
+//! index null: every packet under cfgs[0]
+hipError_t launchDecodeSoft(const DecodeArgs &rows, const float *llr, long long llrStride, const DecodeCfg *cfgs, size_t nCfgs, const int *index,
+                            const int *table, int nTable, hipStream_t stream);
 //! chan[j] = globalOf[chan[j]], j < n (the packet hand-off of a mixed handle)
 hipError_t launchRemapChannels(int *chan, const int *globalOf, size_t n, size_t nLocal, hipStream_t stream);
 int decodeMaxSymbols();
