@@ -5,6 +5,9 @@
 // whitening with the two interleaved LFSRs, Hamming / parity decode, parse and check the explicit header, check the
 // payload CRC. Integer and bit work on a few hundred bytes per packet.
 //
+// Three kernel families, each as a uniform launch and over a table of per-packet settings (decodeGroupCfgs, decodePacketsCfgs; the soft
+// decoder has the table form only), and the encoder (encodeGroup, encodeGroupCfgs) behind them.
+//
 // decodeGroup (the default): a GROUP of G = 8 / 16 / 32 / 64 lanes of a wavefront owns a packet (G by the row length of the
 // launch), the packet's symbols, codewords and nibbles live in the group's slice of LDS, and every stage is data-parallel over
 // the lanes of the group: a lane Gray-codes its symbols, builds its codewords bit by bit from the (at most eight) symbols of
@@ -13,8 +16,15 @@
 // with lane shuffles. No per-lane arrays, no scratch. The order of the reference's decisions (what is decoded before which
 // check, which coding rate applies where) is kept exactly; only the loops became lanes.
 //
+// decodeSoftCfgs (lorahip_decode_packets_soft): the same lane groups over rows of per-bit LLRs, which stay in global memory: a lane gathers
+// its codeword's (at most eight) values and takes the maximum-likelihood nibble; LDS holds the nibbles alone.
+//
+// What the two group decoders share -- which packet a group owns, the counts at a rate, where a codeword lies, the header, the lengths,
+// the row rule, the checksum, the output and the report -- is ONE set of stage functions (packetOf .. writePacket, in front of
+// decodeGroupBody); the bodies are their own front ends and the workgroup barriers, with the stages between them.
+//
 // decodePackets (context variant 1): one lane walks one packet statement by statement in the reference's order, working arrays
-// in per-lane scratch -- the round-1 kernel, kept as the A/B checker.
+// in per-lane scratch -- the round-1 kernel, kept as the A/B checker; it shares nothing with the group kernels.
 #include "lorahip_internal.h"
 #include <type_traits>
 
@@ -517,6 +527,220 @@ __host__ __device__ __forceinline__ DecodeCaps decodeCapsAt(const int sf, const 
 
 __host__ __device__ __forceinline__ int decodeSliceOf(const DecodeCaps c) { return (c.symCap * 2 + 2 * c.cwCap + 15) & ~15; }
 
+/***********************************************************************
+ * The stages of the reference block that the two lane-group decoders share: decodeGroupBody (hard, below) and decodeSoftBody (soft, behind
+ * the encoder) are their own front ends -- how a codeword's bits or LLRs are fetched and how a nibble is decided -- with these between
+ * their barriers. Every rule of the reference about which packets exist, how long they are and what is reported is written here, once.
+ * No stage holds a workgroup barrier: those stand in the two bodies, at top level, so the 256 threads of a table launch meet at every one
+ * whatever their packets' settings are; a packet that is done only clears `go`. Everything here is the same for every lane of a group.
+ **********************************************************************/
+namespace {
+
+//! one packet's way through the stages
+struct PacketState
+{
+    bool go, error;                        // still decoding; the reference's error flag (:273), over the hard bits in both decoders
+    int outLen, dropped;
+    int rate, rdd;                         // the rate the message is laid out at (the setter's, or the one a header-rate entry's header names);
+                                           // the rate the payload's nibbles are decoded at (the header's)
+    bool checkCrc;                         // (rdd and checkCrc: from decodeHeader on)
+    long long packetLength, dataLength, cEnd;   // cEnd: first codeword NOT needed by the bytes
+    unsigned char h0, h1, h2;              // the explicit header: length, coding rate and crc enable, checksum residue
+    int iLen, iRdd, iCrc, iRes, iNeed;     // the report (lorahip_packet_info)
+};
+
+//! which packet a lane works on: lane t of group g of the workgroup, packet p (pc: 0 in its place for a group that has none)
+struct GroupPacket { int g, t; unsigned p, pc; bool have; int nsyms, PPM, rowSyms; unsigned char *out; };
+
+//! interleaver blocks of a message at one rate
+struct RateCounts { int bs, numSymbols, numCodewords; };
+
+/*! Packet identity and the group-uniform early outs (:202 throws, :208 too short). A header-rate entry (a.rdd < 0) starts at 4/8: its
+ * rate is known behind the bodies' first barrier. */
+template <int G>
+__device__ __forceinline__ GroupPacket packetOf(const DecodeArgs &a, const int perBlock, const bool known, PacketState &st)
+{
+    GroupPacket k;
+    k.g = threadIdx.x / G; k.t = threadIdx.x % G;
+    k.p = blockIdx.x * perBlock + k.g;
+    k.have = k.g < perBlock && k.p < a.nPackets;                    // (long slices: fewer packets per workgroup than groups, the rest idle)
+    k.pc = k.have ? k.p : 0;
+    k.nsyms = k.have ? a.nsyms[k.pc] : 0;
+    k.out = a.out + (size_t)k.pc * a.outStride;
+    k.PPM = a.ppm == 0 ? a.sf : a.ppm;                                                       // LoRaDecoder.cpp:201
+    // the row holds the first symStride symbols of a longer packet: whether that is enough is known once the length is (decodeNeeds)
+    k.rowSyms = k.nsyms < a.symStride ? k.nsyms : a.symStride;
+    st.go = k.have && known && !(k.PPM > a.sf || k.nsyms < LORAHIP_N_HDR_SYMBOLS);
+    st.error = false; st.outLen = -1; st.dropped = 0;
+    st.rate = a.rdd < 0 ? LORAHIP_HDR_RDD : a.rdd;
+    st.packetLength = 0; st.dataLength = 0; st.cEnd = 0;
+    st.h0 = 0; st.h1 = 0; st.h2 = 0;
+    st.iLen = -1; st.iRdd = -1; st.iCrc = 0; st.iRes = -1; st.iNeed = -1;                    // "header not reached"
+    return k;
+}
+
+__device__ __forceinline__ RateCounts countsAt(const int nsyms, const int PPM, const int rate)
+{
+    RateCounts n;
+    n.bs = 4 + rate;                                                                         // symbols per interleaver block
+    const int nBlocks = (nsyms + n.bs - 1) / n.bs;
+    n.numSymbols = nBlocks * n.bs;                                                           // :210
+    n.numCodewords = nBlocks * PPM;                                                          // :211
+    return n;
+}
+
+//! where codeword c comes from: row i of the interleaver block whose symbols start at symOff and are coded at R, and its whitening byte
+struct CodewordPlace { int i, symOff, R; bool whole; unsigned white; };
+
+/*! Placement of codeword c < n.numCodewords (diagonal de-interleave :366-381, de-whitening :225-255). The first block is always 4/8 over
+ * 8 symbols unless the whole packet is (then every block is). */
+__device__ __forceinline__ CodewordPlace placeCodeword(const int c, const int PPM, const int rate, const RateCounts &n, const int explicitHdr)
+{
+    const bool hdrBlock = rate != LORAHIP_HDR_RDD;
+    CodewordPlace w;
+    int x;
+    if (hdrBlock && c < PPM) { x = 0; w.i = c; w.symOff = 0; w.R = LORAHIP_HDR_RDD; }
+    else if (hdrBlock) { x = (c - PPM) / PPM; w.i = (c - PPM) - x * PPM; w.symOff = LORAHIP_N_HDR_SYMBOLS + x * n.bs; w.R = rate; }
+    else { x = c / PPM; w.i = c - x * PPM; w.symOff = x * n.bs; w.R = rate; }
+    // with a header block the payload's symbols may end inside a block of `bs`: the reference de-interleaves
+    // (numSymbols - 8) / bs whole blocks and leaves the rest of the codewords zero
+    w.whole = !hdrBlock || c < PPM || (w.symOff + (4 + w.R) <= n.numSymbols);
+    // position in the whitening sequence: codeword index, minus the five header codewords that are not whitened
+    // (with a header block and nothing but it -- exactly 8 symbols -- the reference skips the payload's whitening call)
+    const int pos = explicitHdr ? c - LORAHIP_N_HDR_CODEWORDS : c;
+    w.white = 0;
+    // (the tables end behind the last codeword any length can need: LORAHIP_DEC_MAX_DATA_LENGTH)
+    if (pos >= 0 && (pos >> 1) < LORAHIP_WHITEN_LEN && !(hdrBlock && c >= PPM && n.numSymbols <= LORAHIP_N_HDR_SYMBOLS))
+        w.white = kCodec.white[w.R == 1 ? 1 : 0][pos & 1][pos >> 1] & (0xffu >> (4 - w.R));
+    return w;
+}
+
+/*! The header (:283-311), evaluated by every lane of the group alike: nib[c] is the decoded nibble of header codeword c, st.error what the
+ * hard 4/8 decode of the five found (both only read with an explicit header). */
+__device__ __forceinline__ void decodeHeader(PacketState &st, const DecodeArgs &a, const unsigned char (&nib)[LORAHIP_N_HDR_CODEWORDS], const int numCodewords)
+{
+    st.rdd = st.rate;                                                                        // :215
+    st.checkCrc = a.crcc != 0;
+    if (!st.go) return;
+    const int nbytes = (numCodewords + 1) / 2;
+    if (a.explicitHdr)
+    {
+        st.h0 = (unsigned char)(nib[1] | (nib[0] << 4));                                     // length
+        st.h1 = nib[2];                                                                      // coding rate and crc enable
+        st.h2 = (unsigned char)(nib[4] | (nib[3] << 4));                                     // checksum
+        const unsigned char hb[2] = { st.h0, st.h1 };
+        st.h2 ^= headerChecksum(hb);
+        st.iLen = st.h0; st.iRdd = (st.h1 >> 1) & 0x7; st.iRes = st.h2;
+        if (st.error && a.errorCheck) { st.dropped = 1; st.go = false; }
+        if (st.go)
+        {
+            if (0 == (st.h1 & 1)) st.checkCrc = false;
+            st.rdd = (st.h1 >> 1) & 0x7;
+            if (st.rdd > 4) { st.dropped = 1; st.go = false; }
+            st.packetLength = st.h0;
+            st.dataLength = st.packetLength + ((st.h1 & 1) ? 5 : 3);
+        }
+    }
+    else
+    {
+        st.packetLength = a.dataLength;
+        st.dataLength = a.crcc ? st.packetLength + 2 : st.packetLength;
+        st.iLen = a.dataLength; st.iRdd = st.rate;
+    }
+    if (st.go && st.dataLength > nbytes) { st.dropped = 1; st.go = false; }                  // :313
+}
+
+/*! What the bytes need. Nibbles (:315-361): codeword c -> nibble c (+1 after an explicit header); the first block is 4/8, the rest at the
+ * coding rate the HEADER names; decoded are the first block, the nibble that completes its last byte, and what dataLength bytes need
+ * -- [first payload codeword, st.cEnd); errors anywhere else do not count, exactly as in the reference's loops. symCap / cwCap: the
+ * caps of the packet's rate in the hard plan, in both decoders: the same packets are -2 in both. */
+__device__ __forceinline__ void decodeNeeds(PacketState &st, const DecodeArgs &a, const GroupPacket &k, const int bs, const int symCap, const int cwCap)
+{
+    if (!st.go) return;
+    const int shift = a.explicitHdr ? 1 : 0;
+    st.cEnd = 2 * st.dataLength - shift;
+    const int fill = k.PPM + (((k.PPM + shift) & 1) ? 1 : 0);                                // first block + the odd nibble
+    if (st.cEnd < fill) st.cEnd = fill;
+    // the symbols those codewords are made of: whole interleaver blocks. A packet longer than its row decodes all the same while
+    // they lie inside the row; if not, the caller's rows are too short for this packet (-2: reported, never guessed)
+    const long long nBlocks = (st.cEnd + k.PPM - 1) / k.PPM;
+    const long long needSyms = st.rate != LORAHIP_HDR_RDD ? LORAHIP_N_HDR_SYMBOLS + (nBlocks - 1) * bs : nBlocks * bs;
+    st.iNeed = (int)needSyms;
+    if ((k.nsyms > a.symStride && needSyms > a.symStride) || needSyms > symCap || st.cEnd + 4 > cwCap) { st.outLen = -2; st.go = false; }
+}
+
+//! the nibbles no codeword loop writes: the header's six in front, and zeros behind the decoded ones (the reference's buffer is zeroed)
+template <int G>
+__device__ __forceinline__ void frameNibbles(const PacketState &st, const DecodeArgs &a, const int t, unsigned char *sNib)
+{
+    if (!st.go) return;
+    const int shift = a.explicitHdr ? 1 : 0;
+    if (a.explicitHdr) { sNib[0] = st.h0 & 0xf; sNib[1] = st.h0 >> 4; sNib[2] = st.h1 & 0xf; sNib[3] = 0; sNib[4] = st.h2 & 0xf; sNib[5] = st.h2 >> 4; }
+    for (long long v = st.cEnd + shift + t; v < 2 * (st.dataLength + 1); v += G) sNib[v] = 0;
+}
+
+/*! Behind the nibbles' barrier, st.error the whole group's: the error drop, then the checksum (:367-388): crc = sum over the bytes of
+ * byte * x^(8 (len-1-i)), folded over the lanes, then the two LFSR masks; lane 0 un-masks the packet's two crc bytes in place. */
+template <int G>
+__device__ __forceinline__ void checkPayload(PacketState &st, const DecodeArgs &a, const int t, unsigned char *sNib)
+{
+    if (st.go && st.error && a.errorCheck) { st.dropped = 1; st.go = false; }                // :342, :363
+    if (!(st.go && (a.explicitHdr ? (st.h1 & 1) != 0 : st.checkCrc))) return;
+    const int base = a.explicitHdr ? 3 : 0;
+    const int len = a.explicitHdr ? (int)st.packetLength : a.dataLength;
+    unsigned acc = 0;
+    for (int i = t; i < len; i += G)
+    {
+        const unsigned byte = sNib[2 * (base + i)] | (sNib[2 * (base + i) + 1] << 4);
+        // res_{i+1} = S(res_i) ^ d_i: byte i is shifted by the len-1-i byte steps that follow it
+        acc ^= crcShift(byte, kCodec.xpow[len - 1 - i]);
+    }
+    unsigned crc = groupXor<G>(acc);
+    crc ^= kCodec.lfsr8[len];                                                                // res ^= v after len steps
+    crc ^= (unsigned)kCodec.lfsr8[len + 1] << 8;                                             // ... and one step later, high byte
+    crc &= 0xffff;
+    const unsigned packetCrc = (sNib[2 * (base + len)] | (sNib[2 * (base + len) + 1] << 4)) |
+                               ((sNib[2 * (base + len) + 2] | (sNib[2 * (base + len) + 3] << 4)) << 8);
+    st.iCrc = crc == packetCrc ? 1 : -1;
+    if (a.explicitHdr)
+    {
+        if (crc != packetCrc && st.checkCrc) { st.dropped = 1; st.go = false; }
+    }
+    else if (crc != packetCrc) { st.dropped = 1; st.go = false; }
+    if (st.go && t == 0)
+    {
+        // bytes[len] ^= crc, bytes[len + 1] ^= crc >> 8 (:377-378, :386-387)
+        const unsigned lo = (sNib[2 * (base + len)] | (sNib[2 * (base + len) + 1] << 4)) ^ (crc & 0xff);
+        const unsigned hi = (sNib[2 * (base + len) + 2] | (sNib[2 * (base + len) + 3] << 4)) ^ (crc >> 8);
+        sNib[2 * (base + len)] = lo & 0xf; sNib[2 * (base + len) + 1] = (lo >> 4) & 0xf;
+        sNib[2 * (base + len) + 2] = hi & 0xf; sNib[2 * (base + len) + 3] = (hi >> 4) & 0xf;
+    }
+}
+
+//! behind the last barrier: the bytes out of the nibbles, out_len, dropped and the report. known = false: -3, nothing else of the packet.
+template <int G>
+__device__ __forceinline__ void writePacket(PacketState &st, const DecodeArgs &a, const GroupPacket &k, const unsigned char *sNib, const bool known)
+{
+    int dOfs = 0;
+    if (st.go && a.explicitHdr && !a.hdr) { dOfs = 3; st.dataLength -= 5; }                  // :379
+    // `dataLength -= 5` on a size_t wraps for a header without the crc flag that announces fewer than 2 bytes; the
+    // reference then fails to allocate its output and posts nothing
+    if (st.go && st.dataLength >= 0)
+    {
+        for (long long i = k.t; i < st.dataLength; i += G) k.out[i] = (unsigned char)(sNib[2 * (dOfs + i)] | (sNib[2 * (dOfs + i) + 1] << 4));   // :391-395
+        st.outLen = (int)st.dataLength;
+    }
+    if (k.have && k.t == 0)
+    {
+        a.outLen[k.p] = known ? st.outLen : -3;
+        a.dropped[k.p] = st.dropped;
+        // (error: every lane's own after the header, the group's after the nibbles -- where the decode ended, it is the reference's flag)
+        if (a.info != nullptr) writePacketInfo(a.info, k.p, st.iLen, st.iRdd, st.iCrc, st.iRes, st.error ? 1 : 0, st.iNeed);
+    }
+}
+
+} // namespace
+
 /*! One packet per group of G lanes under the settings in `a` and the caps of THOSE settings; `slice` is the launch's distance between two
  * groups' LDS (>= what the caps need). decodeGroup hands in its kernel arguments, so every setting is a launch-uniform scalar there;
  * decodeGroupCfgs hands in the packet's own entry of the table, the same for every lane of a group (the lanes of a group share p): whatever
@@ -530,50 +754,35 @@ __device__ __forceinline__ void decodeGroupBody(const DecodeArgs a, const Decode
 {
     // per packet: symCap Gray-coded symbols (u16), then the codewords (u8), then the nibbles (u8), 16-byte aligned slices
     extern __shared__ __attribute__((aligned(16))) unsigned char smemDec[];
+    PacketState st;
+    const GroupPacket k = packetOf<G>(a, perBlock, known, st);
+    const int t = k.t, nsyms = k.nsyms, PPM = k.PPM, sf = a.sf;
     int symCap = caps.symCap, cwCap = caps.cwCap;
-    const int g = threadIdx.x / G, t = threadIdx.x % G;
-    unsigned short *sSym = reinterpret_cast<unsigned short *>(smemDec + (size_t)g * slice);
-    unsigned char *sCw = smemDec + (size_t)g * slice + symCap * 2;
+    unsigned short *sSym = reinterpret_cast<unsigned short *>(smemDec + (size_t)k.g * slice);
+    unsigned char *sCw = smemDec + (size_t)k.g * slice + symCap * 2;
     unsigned char *sNib = sCw + cwCap;
-    int iLen = -1, iRdd = -1, iCrc = 0, iRes = -1, iNeed = -1;     // the report (lorahip_packet_info): "header not reached"
-    const unsigned p = blockIdx.x * perBlock + g;
-    const bool have = g < perBlock && p < a.nPackets;               // (long slices: fewer packets per workgroup than groups, the rest idle)
-    const unsigned pc = have ? p : 0;
-    const int nsyms = have ? a.nsyms[pc] : 0;
-    const unsigned short *in = a.syms + (size_t)pc * a.symStride;
-    unsigned char *out = a.out + (size_t)pc * a.outStride;
-    int outLen = -1, dropped = 0;
-
-    const int sf = a.sf;
-    const int PPM = a.ppm == 0 ? sf : a.ppm;                                                 // LoRaDecoder.cpp:201
+    const unsigned short *in = a.syms + (size_t)k.pc * a.symStride;
     // the coding rate of the setter. A header-rate entry (a.rdd < 0) has none: the packet's header names it, behind the first barrier, and
-    // everything from `rate` to `cwLoad` is worked out again there; until then only the Gray-code load runs, which does not depend on it
-    int rate = a.rdd < 0 ? LORAHIP_HDR_RDD : a.rdd;
-    int bs = 4 + rate;                                                                       // symbols per interleaver block
-    int numSymbols = ((nsyms + bs - 1) / bs) * bs;                                           // :210
-    int numCodewords = (numSymbols / bs) * PPM;                                              // :211
-    // the row holds the first symStride symbols of a longer packet: whether that is enough is known once the length is (below)
-    const int rowSyms = nsyms < a.symStride ? nsyms : a.symStride;
-    int symLoad = numSymbols < symCap ? numSymbols : symCap;                                 // what of it this slice holds
-    int cwLoad = numCodewords + 4 < cwCap ? numCodewords + 4 : cwCap;
-    // group-uniform early outs (:202 throws, :208 too short)
-    bool go = have && known && !(PPM > sf || nsyms < LORAHIP_N_HDR_SYMBOLS);
+    // everything from the counts to `cwLoad` is worked out again there; until then only the Gray-code load runs, which does not depend on it
+    RateCounts n = countsAt(nsyms, PPM, st.rate);
+    int symLoad = n.numSymbols < symCap ? n.numSymbols : symCap;                             // what of it this slice holds
+    int cwLoad = n.numCodewords + 4 < cwCap ? n.numCodewords + 4 : cwCap;
 
     // ---- Gray code with rounding to the symbol size (:218-222) --------------------------------------------------------
-    if (go && !a.interleaving && nsyms > a.symStride) { outLen = -2; go = false; }           // every symbol is output: the row must hold them all
+    if (st.go && !a.interleaving && nsyms > a.symStride) { st.outLen = -2; st.go = false; }  // every symbol is output: the row must hold them all
     // header rate: numSymbols is nsyms rounded up to a block of 4..8, so nsyms + 7 covers every rate (zeros behind the row, as always)
-    const int grayLoad = !a.interleaving ? numSymbols : a.rdd < 0 ? (nsyms + 7 < symCap ? nsyms + 7 : symCap) : symLoad;
-    if (go)
+    const int grayLoad = !a.interleaving ? n.numSymbols : a.rdd < 0 ? (nsyms + 7 < symCap ? nsyms + 7 : symCap) : symLoad;
+    if (st.go)
         for (int i = t; i < grayLoad; i += G)
         {
-            unsigned short sym = i < rowSyms ? in[i] : 0;
+            unsigned short sym = i < k.rowSyms ? in[i] : 0;
             sym = (unsigned short)(sym + (1 << (sf - PPM)) / 2);
             sym = (unsigned short)(sym >> (sf - PPM));
             sym = (unsigned short)(sym ^ (sym >> 1));
             if (a.interleaving) sSym[i] = sym;
-            else reinterpret_cast<unsigned short *>(out)[i] = sym;                          // :264-270
+            else reinterpret_cast<unsigned short *>(k.out)[i] = sym;                        // :264-270
         }
-    if (go && !a.interleaving) { outLen = numSymbols; go = false; }
+    if (st.go && !a.interleaving) { st.outLen = n.numSymbols; st.go = false; }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __syncthreads();
 
@@ -586,192 +795,74 @@ __device__ __forceinline__ void decodeGroupBody(const DecodeArgs a, const Decode
     // A field of 5..7 runs at 4/8 into the header stage, which drops it (the error check or :297) -- as it would under every setting.
     if (a.rdd < 0)                                                                           // (group-uniform; no barrier inside)
     {
-        if (go)
+        if (st.go)
         {
             unsigned cw2 = 0;
-            for (int k = 0; k < LORAHIP_N_HDR_SYMBOLS; k++)
+            for (int s = 0; s < LORAHIP_N_HDR_SYMBOLS; s++)
             {
-                int m = 2 - (k < PPM ? k : k - PPM);                                        // 2 - k % PPM (5 <= PPM: a header-rate entry has a header)
+                int m = 2 - (s < PPM ? s : s - PPM);                                        // 2 - s % PPM (5 <= PPM: a header-rate entry has a header)
                 if (m < 0) m += PPM;
-                cw2 |= ((sSym[k] >> m) & 1u) << k;
+                cw2 |= ((sSym[s] >> m) & 1u) << s;
             }
             bool e2 = false, b2 = false;
             const int field = ((decodeHamming84((unsigned char)cw2, e2, b2) & 0xf) >> 1) & 0x7;
-            rate = field > 4 ? LORAHIP_HDR_RDD : field;
+            st.rate = field > 4 ? LORAHIP_HDR_RDD : field;
         }
-        const DecodeCaps cr = decodeCapsAt(sf, a.ppm, rate, 1, a.dataLength, a.symStride);       // (a header-rate entry has a header)
+        const DecodeCaps cr = decodeCapsAt(sf, a.ppm, st.rate, 1, a.dataLength, a.symStride);   // (a header-rate entry has a header)
         symCap = cr.symCap; cwCap = cr.cwCap;
-        sCw = smemDec + (size_t)g * slice + symCap * 2;
+        sCw = smemDec + (size_t)k.g * slice + symCap * 2;
         sNib = sCw + cwCap;
-        bs = 4 + rate;
-        const int nBlocks = (nsyms + bs - 1) / bs;
-        numSymbols = nBlocks * bs;                                                           // :210
-        numCodewords = nBlocks * PPM;                                                        // :211
-        symLoad = numSymbols < symCap ? numSymbols : symCap;
-        cwLoad = numCodewords + 4 < cwCap ? numCodewords + 4 : cwCap;
+        n = countsAt(nsyms, PPM, st.rate);
+        symLoad = n.numSymbols < symCap ? n.numSymbols : symCap;
+        cwLoad = n.numCodewords + 4 < cwCap ? n.numCodewords + 4 : cwCap;
     }
 
-    // ---- diagonal de-interleave (:366-381) + de-whitening (:225-255), one codeword per lane and round ------------------
-    // the first block is always 4/8 over 8 symbols unless the whole packet is (then every block is)
-    const bool hdrBlock = rate != LORAHIP_HDR_RDD;
-    if (go)
+    // ---- de-interleave + de-whitening (placeCodeword), one codeword per lane and round, out of the Gray-coded symbols in LDS ----------
+    if (st.go)
         for (int c = t; c < cwLoad; c += G)
         {
             unsigned cw = 0;
-            if (c < numCodewords)
+            if (c < n.numCodewords)
             {
-                int x, i, symOff, R;
-                if (hdrBlock && c < PPM) { x = 0; i = c; symOff = 0; R = LORAHIP_HDR_RDD; }
-                else if (hdrBlock) { x = (c - PPM) / PPM; i = (c - PPM) - x * PPM; symOff = LORAHIP_N_HDR_SYMBOLS + x * bs; R = rate; }
-                else { x = c / PPM; i = c - x * PPM; symOff = x * bs; R = rate; }
-                // with a header block the payload's symbols may end inside a block of `bs`: the reference de-interleaves
-                // (numSymbols - 8) / bs whole blocks and leaves the rest of the codewords zero
-                // (... and a block whose symbols lie behind the slice is behind what any length can need: left zero, never read)
-                const bool whole = (!hdrBlock || c < PPM || (symOff + (4 + R) <= numSymbols)) && symOff + (4 + R) <= symLoad;
-                if (whole)
-                    for (int k = 0; k < 4 + R; k++)
+                const CodewordPlace w = placeCodeword(c, PPM, st.rate, n, a.explicitHdr);
+                // (a block whose symbols lie behind the slice is behind what any length can need: left zero, never read)
+                if (w.whole && w.symOff + (4 + w.R) <= symLoad)
+                    for (int s = 0; s < 4 + w.R; s++)
                     {
-                        int m = i - (k % PPM);
+                        int m = w.i - (s % PPM);
                         if (m < 0) m += PPM;
-                        cw |= ((sSym[symOff + k] >> m) & 1u) << k;
+                        cw |= ((sSym[w.symOff + s] >> m) & 1u) << s;
                     }
-                // position in the whitening sequence: codeword index, minus the five header codewords that are not whitened
-                // (with a header block and nothing but it -- exactly 8 symbols -- the reference skips the payload's whitening call)
-                const int pos = a.explicitHdr ? c - LORAHIP_N_HDR_CODEWORDS : c;
-                // (the tables end behind the last codeword any length can need: LORAHIP_DEC_MAX_DATA_LENGTH)
-                if (pos >= 0 && (pos >> 1) < LORAHIP_WHITEN_LEN && !(hdrBlock && c >= PPM && numSymbols <= LORAHIP_N_HDR_SYMBOLS))
-                {
-                    const int Rw = (hdrBlock && c < PPM) ? LORAHIP_HDR_RDD : rate;
-                    const unsigned keep = 0xffu >> (4 - Rw);
-                    cw ^= kCodec.white[Rw == 1 ? 1 : 0][pos & 1][pos >> 1] & keep;
-                }
+                cw ^= w.white;
             }
             sCw[c] = (unsigned char)cw;
         }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __syncthreads();
 
-    // ---- header (:283-311), evaluated by every lane of the group alike -------------------------------------------------
-    bool error = false, bad = false;
-    const int nbytes = (numCodewords + 1) / 2;
-    long long packetLength = 0, dataLength = 0;
-    bool checkCrc = a.crcc != 0;
-    int rdd = rate;
-    unsigned char h0 = 0, h1 = 0, h2 = 0;
-    if (go)
-    {
-        if (a.explicitHdr)
-        {
-            h0 = (unsigned char)((decodeHamming84(sCw[1], error, bad) & 0xf) | (decodeHamming84(sCw[0], error, bad) << 4));   // length
-            h1 = decodeHamming84(sCw[2], error, bad) & 0xf;                                      // coding rate and crc enable
-            h2 = (unsigned char)((decodeHamming84(sCw[4], error, bad) & 0xf) | (decodeHamming84(sCw[3], error, bad) << 4));   // checksum
-            const unsigned char hb[2] = { h0, h1 };
-            h2 ^= headerChecksum(hb);
-            iLen = h0; iRdd = (h1 >> 1) & 0x7; iRes = h2;
-            if (error && a.errorCheck) { dropped = 1; go = false; }
-            if (go)
-            {
-                if (0 == (h1 & 1)) checkCrc = false;
-                rdd = (h1 >> 1) & 0x7;
-                if (rdd > 4) { dropped = 1; go = false; }
-                packetLength = h0;
-                dataLength = packetLength + ((h1 & 1) ? 5 : 3);
-            }
-        }
-        else
-        {
-            packetLength = a.dataLength;
-            dataLength = a.crcc ? packetLength + 2 : packetLength;
-            iLen = a.dataLength; iRdd = rate;
-        }
-        if (go && dataLength > nbytes) { dropped = 1; go = false; }                          // :313
-    }
-
-    // ---- nibbles (:315-361): codeword c -> nibble c (+1 after an explicit header); the first block is 4/8, the rest at the
-    // coding rate the HEADER names; decoded are the first block, the nibble that completes its last byte, and what
-    // dataLength bytes need -- errors anywhere else do not count, exactly as in the reference's loops
-    const int c0 = a.explicitHdr ? LORAHIP_N_HDR_CODEWORDS : 0, shift = a.explicitHdr ? 1 : 0;
-    long long cEnd = 0;
-    if (go)
-    {
-        cEnd = 2 * dataLength - shift;                                                       // first codeword NOT needed by the bytes
-        const int fill = PPM + (((PPM + shift) & 1) ? 1 : 0);                               // first block + the odd nibble
-        if (cEnd < fill) cEnd = fill;
-        // the symbols those codewords are made of: whole interleaver blocks. A packet longer than its row decodes all the same while
-        // they lie inside the row; if not, the caller's rows are too short for this packet (-2: reported, never guessed)
-        const long long nBlocks = (cEnd + PPM - 1) / PPM;
-        const long long needSyms = hdrBlock ? LORAHIP_N_HDR_SYMBOLS + (nBlocks - 1) * bs : nBlocks * bs;
-        iNeed = (int)needSyms;
-        if ((nsyms > a.symStride && needSyms > a.symStride) || needSyms > symCap || cEnd + 4 > cwCap) { outLen = -2; go = false; }
-    }
-    if (go)
-    {
-        if (a.explicitHdr) { sNib[0] = h0 & 0xf; sNib[1] = h0 >> 4; sNib[2] = h1 & 0xf; sNib[3] = 0; sNib[4] = h2 & 0xf; sNib[5] = h2 >> 4; }
-        for (int c = c0 + t; c < cEnd; c += G)
+    // ---- header, needs, and the nibbles of the codewords the bytes need: the table FEC --------------------------------------------
+    bool bad = false;
+    unsigned char hn[LORAHIP_N_HDR_CODEWORDS] = { 0, 0, 0, 0, 0 };
+    if (st.go && a.explicitHdr)
+        for (int c = 0; c < LORAHIP_N_HDR_CODEWORDS; c++) hn[c] = decodeHamming84(sCw[c], st.error, bad);
+    decodeHeader(st, a, hn, n.numCodewords);
+    decodeNeeds(st, a, k, n.bs, symCap, cwCap);
+    frameNibbles<G>(st, a, t, sNib);
+    if (st.go)
+        for (int c = (a.explicitHdr ? LORAHIP_N_HDR_CODEWORDS : 0) + t; c < st.cEnd; c += G)
         {
             const unsigned char cw = sCw[c];
-            const unsigned char nib = c < PPM ? decodeHamming84(cw, error, bad) : decodeNibble(cw, rdd, error, bad);
-            sNib[c + shift] = nib & 0xf;
+            const unsigned char nib = c < PPM ? decodeHamming84(cw, st.error, bad) : decodeNibble(cw, st.rdd, st.error, bad);
+            sNib[c + (a.explicitHdr ? 1 : 0)] = nib & 0xf;
         }
-        // the bytes beyond the decoded nibbles are zero in the reference's buffer
-        for (long long v = cEnd + shift + t; v < 2 * (dataLength + 1); v += G) sNib[v] = 0;
-    }
-    error = groupAny<G>(error);
+    st.error = groupAny<G>(st.error);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __syncthreads();
-    if (go && error && a.errorCheck) { dropped = 1; go = false; }                            // :342, :363
 
-    // ---- checksum (:367-388): crc = sum over the bytes of byte * x^(8 (len-1-i)), then the two LFSR masks ---------------
-    int dOfs = 0;
-    if (go && (a.explicitHdr ? (h1 & 1) != 0 : checkCrc))
-    {
-        const int base = a.explicitHdr ? 3 : 0;
-        const int len = a.explicitHdr ? (int)packetLength : a.dataLength;
-        unsigned acc = 0;
-        for (int i = t; i < len; i += G)
-        {
-            const unsigned byte = sNib[2 * (base + i)] | (sNib[2 * (base + i) + 1] << 4);
-            // res_{i+1} = S(res_i) ^ d_i: byte i is shifted by the len-1-i byte steps that follow it
-            acc ^= crcShift(byte, kCodec.xpow[len - 1 - i]);
-        }
-        unsigned crc = groupXor<G>(acc);
-        crc ^= kCodec.lfsr8[len];                                                            // res ^= v after len steps
-        crc ^= (unsigned)kCodec.lfsr8[len + 1] << 8;                                         // ... and one step later, high byte
-        crc &= 0xffff;
-        const unsigned packetCrc = (sNib[2 * (base + len)] | (sNib[2 * (base + len) + 1] << 4)) |
-                                   ((sNib[2 * (base + len) + 2] | (sNib[2 * (base + len) + 3] << 4)) << 8);
-        iCrc = crc == packetCrc ? 1 : -1;
-        if (a.explicitHdr)
-        {
-            if (crc != packetCrc && checkCrc) { dropped = 1; go = false; }
-        }
-        else if (crc != packetCrc) { dropped = 1; go = false; }
-        if (go && t == 0)
-        {
-            // bytes[len] ^= crc, bytes[len + 1] ^= crc >> 8 (:377-378, :386-387)
-            const unsigned lo = (sNib[2 * (base + len)] | (sNib[2 * (base + len) + 1] << 4)) ^ (crc & 0xff);
-            const unsigned hi = (sNib[2 * (base + len) + 2] | (sNib[2 * (base + len) + 3] << 4)) ^ (crc >> 8);
-            sNib[2 * (base + len)] = lo & 0xf; sNib[2 * (base + len) + 1] = (lo >> 4) & 0xf;
-            sNib[2 * (base + len) + 2] = hi & 0xf; sNib[2 * (base + len) + 3] = (hi >> 4) & 0xf;
-        }
-    }
-    if (go && a.explicitHdr && !a.hdr) { dOfs = 3; dataLength -= 5; }                        // :379
+    checkPayload<G>(st, a, t, sNib);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __syncthreads();
-    // `dataLength -= 5` on a size_t wraps for a header without the crc flag that announces fewer than 2 bytes; the
-    // reference then fails to allocate its output and posts nothing
-    if (go && dataLength >= 0)
-    {
-        for (long long i = t; i < dataLength; i += G) out[i] = (unsigned char)(sNib[2 * (dOfs + i)] | (sNib[2 * (dOfs + i) + 1] << 4));   // :391-395
-        outLen = (int)dataLength;
-    }
-    if (have && t == 0)
-    {
-        a.outLen[p] = known ? outLen : -3;
-        a.dropped[p] = dropped;
-        // (error: every lane's own after the header, the group's after the nibbles -- where the decode ended, it is the reference's flag)
-        if (a.info != nullptr) writePacketInfo(a.info, p, iLen, iRdd, iCrc, iRes, error ? 1 : 0, iNeed);
-    }
+    writePacket<G>(st, a, k, sNib, known);
 }
 
 template <int G>
@@ -785,6 +876,13 @@ constexpr int kGroupLdsMax = 160 * 1024;
 
 //! lanes per packet by the symbols of the longest row a launch can meet (a lane per symbol in the widest pass, about as many codewords)
 static int lanesFor(const long rowSyms) { return rowSyms <= 48 ? 8 : rowSyms <= 96 ? 16 : rowSyms <= 200 ? 32 : 64; }
+
+//! packets per workgroup of 256 threads: one per lane group, or as many slices as fit the LDS if that is fewer (0: not even one)
+static int packetsPerBlock(const int lanes, const int slice)
+{
+    const int perBlock = 256 / lanes;
+    return slice * perBlock > kGroupLdsMax ? kGroupLdsMax / slice : perBlock;
+}
 
 //! f(std::integral_constant<int, G>()) for the kernel instance of G = `lanes` lanes per packet
 template <class F>
@@ -845,8 +943,7 @@ DecodeTiling decodePlan(DecodeCfg *cfgs, const size_t nCfgs, const int symStride
         t.slice = slice > t.slice ? slice : t.slice;
     }
     t.lanes = lanesFor(t.symCap);
-    t.perBlock = 256 / t.lanes;
-    if (t.slice * t.perBlock > kGroupLdsMax) t.perBlock = kGroupLdsMax / t.slice;
+    t.perBlock = packetsPerBlock(t.lanes, t.slice);
     return t;
 }
 
@@ -1061,8 +1158,7 @@ EncodeTiling encodePlan(EncodeCfg *cfgs, const size_t nCfgs, const int byteStrid
         t.slice = slice > t.slice ? slice : t.slice;
     }
     t.lanes = lanesFor(rowSyms);
-    t.perBlock = 256 / t.lanes;
-    if (t.slice * t.perBlock > kGroupLdsMax) t.perBlock = kGroupLdsMax / t.slice;
+    t.perBlock = packetsPerBlock(t.lanes, t.slice);
     return t;
 }
 
@@ -1111,14 +1207,21 @@ __global__ void __launch_bounds__(256) decodeGroupCfgs(const DecodeArgs rows, co
     decodeGroupBody<G>(withCfg(rows, e), caps, slice, perBlock, i >= 0);
 }
 
+//! the kernel argument of a table launch, hard or soft, over 1 <= nCfgs <= LORAHIP_DEC_MAX_CFGS entries
+static DecodeCfgTable decodeTableOf(const DecodeCfg *cfgs, const size_t nCfgs, const int *index, const int *table, const int nTable)
+{
+    DecodeCfgTable tab;
+    tab.index = index; tab.table = table; tab.nTable = nTable; tab.nCfgs = int(nCfgs);
+    for (size_t i = 0; i < size_t(LORAHIP_DEC_MAX_CFGS); i++) tab.e[i] = cfgs[i < nCfgs ? i : 0];      // (no entry of the argument block is left unset)
+    return tab;
+}
+
 hipError_t launchDecodeCfgs(const DecodeArgs &rows, const DecodeCfg *cfgs, const size_t nCfgs, const int *index, const int *table, const int nTable,
                             const int variant, hipStream_t stream)
 {
     if (rows.nPackets == 0) return hipSuccess;
     if (nCfgs == 0 || nCfgs > size_t(LORAHIP_DEC_MAX_CFGS)) return hipErrorInvalidValue;
-    DecodeCfgTable tab;
-    tab.index = index; tab.table = table; tab.nTable = nTable; tab.nCfgs = int(nCfgs);
-    for (size_t i = 0; i < size_t(LORAHIP_DEC_MAX_CFGS); i++) tab.e[i] = cfgs[i < nCfgs ? i : 0];      // (no entry of the argument block is left unset)
+    DecodeCfgTable tab = decodeTableOf(cfgs, nCfgs, index, table, nTable);
     const DecodeTiling t = decodePlan(tab.e, nCfgs, rows.symStride);
     if (variant == 1)
     {
@@ -1194,49 +1297,38 @@ hipError_t launchEncodeCfgs(const EncodeArgs &rows, const EncodeCfg *cfgs, const
 /***********************************************************************
  * the soft-decision decoder (lorahip_decode_packets_soft): a symbol is its PPM log-likelihood ratios (positive: bit 1 of the Gray-coded,
  * rounded symbol value), and every FEC nibble is the x in 0..15 whose codeword correlates best with the codeword's LLRs. Behind the hard
- * kernels on purpose: those stay the functions they were. What decodeSoftBody shares with decodeGroupBody is the order of the reference's
- * decisions, the row rule and everything from the checksum on, statement for statement; the `error` flag is still the hard decoders' over
- * the hard bits (llr > 0). The LLRs stay in global memory: a lane gathers the (at most eight) values of its codeword from the symbols of
- * its interleaver block -- the same diagonal the hard kernel walks in LDS -- so a packet's LDS slice holds its nibbles and nothing else,
- * and no configuration outgrows it.
+ * kernels because it needs the encoder's encodeNibble. decodeSoftBody runs the stages decodeGroupBody runs (packetOf .. writePacket, in
+ * front of decodeGroupBody) around its own front end; the `error` flag is still the hard decoders' over the hard bits (llr > 0). The LLRs
+ * stay in global memory: a lane gathers the (at most eight) values of its codeword from the symbols of its interleaver block -- the same
+ * diagonal the hard kernel walks in LDS -- so a packet's LDS slice holds its nibbles and nothing else, and no configuration outgrows it.
  **********************************************************************/
 namespace {
 
 /*! Codeword c of packet row `llr` (PPM floats per symbol, rowSyms symbols present): its hard bits, de-whitened, and in L[0..7] its LLRs with a
  * whitening bit of 1 negating the value. Bits the block does not carry, symbols behind the row, a block that is not whole and codewords
- * behind numCodewords are hard 0 / LLR 0, as decodeGroupBody's zero symbols and zero codewords are. */
-__device__ __forceinline__ unsigned softCodeword(const float *llr, const int rowSyms, const int c, const int PPM, const int rate, const bool hdrBlock,
-                                                 const int numSymbols, const int numCodewords, const int explicitHdr, float (&L)[8])
+ * behind n.numCodewords are hard 0 / LLR 0, as decodeGroupBody's zero symbols and zero codewords are. */
+__device__ __forceinline__ unsigned softCodeword(const float *llr, const int rowSyms, const int c, const int PPM, const int rate, const RateCounts &n,
+                                                 const int explicitHdr, float (&L)[8])
 {
 #pragma unroll
-    for (int k = 0; k < 8; k++) L[k] = 0.0f;
-    if (c >= numCodewords) return 0u;
-    const int bs = 4 + rate;
-    int x, i, symOff, R;
-    if (hdrBlock && c < PPM) { x = 0; i = c; symOff = 0; R = LORAHIP_HDR_RDD; }
-    else if (hdrBlock) { x = (c - PPM) / PPM; i = (c - PPM) - x * PPM; symOff = LORAHIP_N_HDR_SYMBOLS + x * bs; R = rate; }
-    else { x = c / PPM; i = c - x * PPM; symOff = x * bs; R = rate; }
+    for (int s = 0; s < 8; s++) L[s] = 0.0f;
+    if (c >= n.numCodewords) return 0u;
+    const CodewordPlace w = placeCodeword(c, PPM, rate, n, explicitHdr);
     unsigned cw = 0;
-    if (!hdrBlock || c < PPM || symOff + (4 + R) <= numSymbols)
+    if (w.whole)
     {
 #pragma unroll
-        for (int k = 0; k < 8; k++)
+        for (int s = 0; s < 8; s++)
         {
-            int m = i - (k % PPM);
+            int m = w.i - (s % PPM);
             if (m < 0) m += PPM;
-            if (k < 4 + R && symOff + k < rowSyms) L[k] = llr[(size_t)(symOff + k) * PPM + m];
-            cw |= (L[k] > 0.0f ? 1u : 0u) << k;
+            if (s < 4 + w.R && w.symOff + s < rowSyms) L[s] = llr[(size_t)(w.symOff + s) * PPM + m];
+            cw |= (L[s] > 0.0f ? 1u : 0u) << s;
         }
     }
-    const int pos = explicitHdr ? c - LORAHIP_N_HDR_CODEWORDS : c;
-    if (pos >= 0 && (pos >> 1) < LORAHIP_WHITEN_LEN && !(hdrBlock && c >= PPM && numSymbols <= LORAHIP_N_HDR_SYMBOLS))
-    {
-        const int Rw = (hdrBlock && c < PPM) ? LORAHIP_HDR_RDD : rate;
-        const unsigned w = kCodec.white[Rw == 1 ? 1 : 0][pos & 1][pos >> 1] & (0xffu >> (4 - Rw));
-        cw ^= w;
+    cw ^= w.white;
 #pragma unroll
-        for (int k = 0; k < 8; k++) L[k] = ((w >> k) & 1u) ? -L[k] : L[k];
-    }
+    for (int s = 0; s < 8; s++) L[s] = ((w.white >> s) & 1u) ? -L[s] : L[s];
     return cw;
 }
 
@@ -1266,34 +1358,21 @@ __device__ __forceinline__ void decodeSoftBody(const DecodeArgs a, const float *
 {
     // per packet: 16 bytes for the header block's five codewords (hard bits, then soft nibbles), then the nibbles
     extern __shared__ __attribute__((aligned(16))) unsigned char smemDec[];
-    int symCap = caps.symCap, cwCap = caps.cwCap;
-    const int g = threadIdx.x / G, t = threadIdx.x % G;
-    unsigned char *sHdr = smemDec + (size_t)g * slice;
+    PacketState st;
+    const GroupPacket k = packetOf<G>(a, perBlock, known, st);
+    const int t = k.t, PPM = k.PPM;
+    int symCap = caps.symCap, cwCap = caps.cwCap;                   // of the hard plan: they enter the row rule only
+    unsigned char *sHdr = smemDec + (size_t)k.g * slice;
     unsigned char *sNib = sHdr + 16;
-    int iLen = -1, iRdd = -1, iCrc = 0, iRes = -1, iNeed = -1;     // the report (lorahip_packet_info): "header not reached"
-    const unsigned p = blockIdx.x * perBlock + g;
-    const bool have = g < perBlock && p < a.nPackets;
-    const unsigned pc = have ? p : 0;
-    const int nsyms = have ? a.nsyms[pc] : 0;
-    unsigned char *out = a.out + (size_t)pc * a.outStride;
-    int outLen = -1, dropped = 0;
-
-    const int sf = a.sf;
-    const int PPM = a.ppm == 0 ? sf : a.ppm;                                                 // LoRaDecoder.cpp:201
-    const float *llr = llrRows + (size_t)pc * llrStride;
-    int rate = a.rdd < 0 ? LORAHIP_HDR_RDD : a.rdd;
-    int bs = 4 + rate;
-    int numSymbols = ((nsyms + bs - 1) / bs) * bs;                                           // :210
-    int numCodewords = (numSymbols / bs) * PPM;                                              // :211
-    const int rowSyms = nsyms < a.symStride ? nsyms : a.symStride;
-    bool go = have && known && !(PPM > sf || nsyms < LORAHIP_N_HDR_SYMBOLS);                 // :202, :208
+    const float *llr = llrRows + (size_t)k.pc * llrStride;
+    RateCounts n = countsAt(k.nsyms, PPM, st.rate);
 
     // ---- the five header codewords: always the first block at 4/8 over symbols 0..7, never whitened ------------------------
-    if (go && a.explicitHdr)
+    if (st.go && a.explicitHdr)
         for (int c = t; c < LORAHIP_N_HDR_CODEWORDS; c += G)
         {
             float L[8];
-            sHdr[c] = (unsigned char)softCodeword(llr, rowSyms, c, PPM, LORAHIP_HDR_RDD, false, LORAHIP_N_HDR_SYMBOLS, PPM, 1, L);
+            sHdr[c] = (unsigned char)softCodeword(llr, k.rowSyms, c, PPM, LORAHIP_HDR_RDD, countsAt(LORAHIP_N_HDR_SYMBOLS, PPM, LORAHIP_HDR_RDD), 1, L);
             sHdr[8 + c] = (unsigned char)softNibble(L, LORAHIP_HDR_RDD);
         }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
@@ -1302,135 +1381,42 @@ __device__ __forceinline__ void decodeSoftBody(const DecodeArgs a, const float *
     // ---- header rate (LORAHIP_RDD_FROM_HEADER): the soft-decoded codeword 2 names it; from here on a packet of that rate -----------
     if (a.rdd < 0)                                                                           // (group-uniform; no barrier inside)
     {
-        if (go)
+        if (st.go)
         {
             const int field = (sHdr[8 + 2] >> 1) & 0x7;
-            rate = field > 4 ? LORAHIP_HDR_RDD : field;
+            st.rate = field > 4 ? LORAHIP_HDR_RDD : field;
         }
-        const DecodeCaps cr = decodeCapsAt(sf, a.ppm, rate, 1, a.dataLength, a.symStride);
+        const DecodeCaps cr = decodeCapsAt(a.sf, a.ppm, st.rate, 1, a.dataLength, a.symStride);
         symCap = cr.symCap; cwCap = cr.cwCap;
-        bs = 4 + rate;
-        const int nBlocks = (nsyms + bs - 1) / bs;
-        numSymbols = nBlocks * bs;
-        numCodewords = nBlocks * PPM;
-    }
-    const bool hdrBlock = rate != LORAHIP_HDR_RDD;
-
-    // ---- header (:283-311), evaluated by every lane of the group alike: the nibbles soft, the error flag from the hard bits ----------
-    bool error = false, bad = false;
-    const int nbytes = (numCodewords + 1) / 2;
-    long long packetLength = 0, dataLength = 0;
-    bool checkCrc = a.crcc != 0;
-    int rdd = rate;
-    unsigned char h0 = 0, h1 = 0, h2 = 0;
-    if (go)
-    {
-        if (a.explicitHdr)
-        {
-            for (int c = 0; c < LORAHIP_N_HDR_CODEWORDS; c++) (void)decodeHamming84(sHdr[c], error, bad);
-            h0 = (unsigned char)(sHdr[8 + 1] | (sHdr[8 + 0] << 4));                          // length
-            h1 = sHdr[8 + 2];                                                                // coding rate and crc enable
-            h2 = (unsigned char)(sHdr[8 + 4] | (sHdr[8 + 3] << 4));                          // checksum
-            const unsigned char hb[2] = { h0, h1 };
-            h2 ^= headerChecksum(hb);
-            iLen = h0; iRdd = (h1 >> 1) & 0x7; iRes = h2;
-            if (error && a.errorCheck) { dropped = 1; go = false; }
-            if (go)
-            {
-                if (0 == (h1 & 1)) checkCrc = false;
-                rdd = (h1 >> 1) & 0x7;
-                if (rdd > 4) { dropped = 1; go = false; }
-                packetLength = h0;
-                dataLength = packetLength + ((h1 & 1) ? 5 : 3);
-            }
-        }
-        else
-        {
-            packetLength = a.dataLength;
-            dataLength = a.crcc ? packetLength + 2 : packetLength;
-            iLen = a.dataLength; iRdd = rate;
-        }
-        if (go && dataLength > nbytes) { dropped = 1; go = false; }                          // :313
+        n = countsAt(k.nsyms, PPM, st.rate);
     }
 
-    // ---- nibbles (:315-361), a codeword per lane and round, its LLRs gathered from the row ------------------------------------------
-    const int c0 = a.explicitHdr ? LORAHIP_N_HDR_CODEWORDS : 0, shift = a.explicitHdr ? 1 : 0;
-    long long cEnd = 0;
-    if (go)
-    {
-        cEnd = 2 * dataLength - shift;
-        const int fill = PPM + (((PPM + shift) & 1) ? 1 : 0);
-        if (cEnd < fill) cEnd = fill;
-        const long long nBlocks = (cEnd + PPM - 1) / PPM;
-        const long long needSyms = hdrBlock ? LORAHIP_N_HDR_SYMBOLS + (nBlocks - 1) * bs : nBlocks * bs;
-        iNeed = (int)needSyms;
-        // the row rule of decodeGroupBody, on the caps of the hard plan: the same packets are -2 in both decoders
-        if ((nsyms > a.symStride && needSyms > a.symStride) || needSyms > symCap || cEnd + 4 > cwCap) { outLen = -2; go = false; }
-    }
-    if (go)
-    {
-        if (a.explicitHdr) { sNib[0] = h0 & 0xf; sNib[1] = h0 >> 4; sNib[2] = h1 & 0xf; sNib[3] = 0; sNib[4] = h2 & 0xf; sNib[5] = h2 >> 4; }
-        for (int c = c0 + t; c < cEnd; c += G)
+    // ---- header (the nibbles soft, the error flag from the hard bits), needs, and the nibbles of the codewords the bytes need: a
+    // codeword per lane and round, its LLRs gathered from the row, the maximum-likelihood nibble ------------------------------------
+    bool bad = false;
+    unsigned char hn[LORAHIP_N_HDR_CODEWORDS] = { 0, 0, 0, 0, 0 };
+    if (st.go && a.explicitHdr)
+        for (int c = 0; c < LORAHIP_N_HDR_CODEWORDS; c++) { (void)decodeHamming84(sHdr[c], st.error, bad); hn[c] = sHdr[8 + c]; }
+    decodeHeader(st, a, hn, n.numCodewords);
+    decodeNeeds(st, a, k, n.bs, symCap, cwCap);
+    frameNibbles<G>(st, a, t, sNib);
+    if (st.go)
+        for (int c = (a.explicitHdr ? LORAHIP_N_HDR_CODEWORDS : 0) + t; c < st.cEnd; c += G)
         {
             float L[8];
-            const unsigned char cw = (unsigned char)softCodeword(llr, rowSyms, c, PPM, rate, hdrBlock, numSymbols, numCodewords, a.explicitHdr, L);
-            if (c < PPM) (void)decodeHamming84(cw, error, bad);
-            else (void)decodeNibble(cw, rdd, error, bad);
-            sNib[c + shift] = (unsigned char)softNibble(L, c < PPM ? LORAHIP_HDR_RDD : rdd);
+            const unsigned char cw = (unsigned char)softCodeword(llr, k.rowSyms, c, PPM, st.rate, n, a.explicitHdr, L);
+            if (c < PPM) (void)decodeHamming84(cw, st.error, bad);
+            else (void)decodeNibble(cw, st.rdd, st.error, bad);
+            sNib[c + (a.explicitHdr ? 1 : 0)] = (unsigned char)softNibble(L, c < PPM ? LORAHIP_HDR_RDD : st.rdd);
         }
-        for (long long v = cEnd + shift + t; v < 2 * (dataLength + 1); v += G) sNib[v] = 0;
-    }
-    error = groupAny<G>(error);
+    st.error = groupAny<G>(st.error);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __syncthreads();
-    if (go && error && a.errorCheck) { dropped = 1; go = false; }                            // :342, :363
 
-    // ---- checksum (:367-388) and output: decodeGroupBody's, statement for statement ----------------------------------------------------
-    int dOfs = 0;
-    if (go && (a.explicitHdr ? (h1 & 1) != 0 : checkCrc))
-    {
-        const int base = a.explicitHdr ? 3 : 0;
-        const int len = a.explicitHdr ? (int)packetLength : a.dataLength;
-        unsigned acc = 0;
-        for (int i = t; i < len; i += G)
-        {
-            const unsigned byte = sNib[2 * (base + i)] | (sNib[2 * (base + i) + 1] << 4);
-            acc ^= crcShift(byte, kCodec.xpow[len - 1 - i]);
-        }
-        unsigned crc = groupXor<G>(acc);
-        crc ^= kCodec.lfsr8[len];
-        crc ^= (unsigned)kCodec.lfsr8[len + 1] << 8;
-        crc &= 0xffff;
-        const unsigned packetCrc = (sNib[2 * (base + len)] | (sNib[2 * (base + len) + 1] << 4)) |
-                                   ((sNib[2 * (base + len) + 2] | (sNib[2 * (base + len) + 3] << 4)) << 8);
-        iCrc = crc == packetCrc ? 1 : -1;
-        if (a.explicitHdr)
-        {
-            if (crc != packetCrc && checkCrc) { dropped = 1; go = false; }
-        }
-        else if (crc != packetCrc) { dropped = 1; go = false; }
-        if (go && t == 0)
-        {
-            const unsigned lo = (sNib[2 * (base + len)] | (sNib[2 * (base + len) + 1] << 4)) ^ (crc & 0xff);
-            const unsigned hi = (sNib[2 * (base + len) + 2] | (sNib[2 * (base + len) + 3] << 4)) ^ (crc >> 8);
-            sNib[2 * (base + len)] = lo & 0xf; sNib[2 * (base + len) + 1] = (lo >> 4) & 0xf;
-            sNib[2 * (base + len) + 2] = hi & 0xf; sNib[2 * (base + len) + 3] = (hi >> 4) & 0xf;
-        }
-    }
-    if (go && a.explicitHdr && !a.hdr) { dOfs = 3; dataLength -= 5; }                        // :379
+    checkPayload<G>(st, a, t, sNib);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __syncthreads();
-    if (go && dataLength >= 0)
-    {
-        for (long long i = t; i < dataLength; i += G) out[i] = (unsigned char)(sNib[2 * (dOfs + i)] | (sNib[2 * (dOfs + i) + 1] << 4));   // :391-395
-        outLen = (int)dataLength;
-    }
-    if (have && t == 0)
-    {
-        a.outLen[p] = known ? outLen : -3;
-        a.dropped[p] = dropped;
-        if (a.info != nullptr) writePacketInfo(a.info, p, iLen, iRdd, iCrc, iRes, error ? 1 : 0, iNeed);
-    }
+    writePacket<G>(st, a, k, sNib, known);
 }
 
 template <int G>
@@ -1451,14 +1437,11 @@ hipError_t launchDecodeSoft(const DecodeArgs &rows, const float *llr, const long
 {
     if (rows.nPackets == 0) return hipSuccess;
     if (nCfgs == 0 || nCfgs > size_t(LORAHIP_DEC_MAX_CFGS)) return hipErrorInvalidValue;
-    DecodeCfgTable tab;
-    tab.index = index; tab.table = table; tab.nTable = nTable; tab.nCfgs = int(nCfgs);
-    for (size_t i = 0; i < size_t(LORAHIP_DEC_MAX_CFGS); i++) tab.e[i] = cfgs[i < nCfgs ? i : 0];
+    DecodeCfgTable tab = decodeTableOf(cfgs, nCfgs, index, table, nTable);
     // lanes and caps of the hard plan (the caps enter the row rule); the slice is the nibbles' alone
     const DecodeTiling t = decodePlan(tab.e, nCfgs, rows.symStride);
     const int slice = (16 + t.cwCap + 15) & ~15;
-    int perBlock = 256 / t.lanes;
-    if (slice * perBlock > kGroupLdsMax) perBlock = kGroupLdsMax / slice;
+    const int perBlock = packetsPerBlock(t.lanes, slice);
     if (perBlock < 1) return hipErrorInvalidValue;                  // (the entry points bound data_length: cannot happen)
     return withLanes(t.lanes, [&](auto g) { return launchGroup<decodeSoftCfgs<decltype(g)::value>>(rows.nPackets, perBlock, slice, stream, rows, llr, llrStride, tab, slice, perBlock); });
 }

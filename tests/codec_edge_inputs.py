@@ -156,6 +156,21 @@ def e_groups():
     return [(sf, ppm, rdd, explicit, length) for sf, ppm in E_SYMBOL_SIZES for rdd in (1, 2, 3, 4) for explicit in (1, 0) for length in E_LENGTHS]
 
 
+# ---- set R: rows shorter than their packet ---------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def set_r(sf, ppm, rdd, length):
+    """-> (packets (3, S) uint16, need): the packets of test_set_r_rows_shorter_than_the_packet -- an explicit-header packet of `length`
+    bytes + crc, two zero-nibble blocks longer than it needs, clean, with one bit flipped in the last decoded codeword and in the one
+    behind it -- and the symbols (whole interleaver blocks) its announced bytes need"""
+    P = ppm or sf
+    clean, _ = D.build(sf, np.random.default_rng(length).integers(0, 256, length).astype(np.uint8), ppm, rdd, True, True, n_blocks=2)
+    c_end, _ = D.decoded_end(P, True, length + 5)
+    need = D.num_symbols_def(-(-c_end // P) * P, P, rdd)
+    packets = np.stack([clean, D.flip(clean, sf, ppm, rdd, c_end - 1, 0), D.flip(clean, sf, ppm, rdd, c_end, 0)])
+    packets.setflags(write=False)
+    return packets, need
+
+
 # ---- the launch shape, restated from lorahip_codec.hip (decodeCaps, launchDecode, launchDecodeGroup) -----------------------------
 def launch_shape(sf, ppm, rdd, explicit, data_length, stride):
     """-> (lanes per packet G, LDS bytes per packet, packets per workgroup). The tests cannot observe any of the three; this restatement

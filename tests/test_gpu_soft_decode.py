@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import codec_def as D
+import codec_edge_inputs as E
 import codec_hdr_def as H
 import soft_def as S
 import test_gpu_codec_cfgs as T
@@ -237,6 +238,65 @@ def test_uniform_launch_and_every_lane_count(gpu, ctx, cfg):
         got, rep = soft_launch(gpu, ctx, [cfg], rows, nsyms, None, stride=stride)
         assert_equal(got, rep, want, wrep, short, ("uniform", stride))
     assert (want[1] > 0).any()
+
+
+# ---- the hard decoder's crafted edge packets through the soft decoder ------------------------------------------------------------------
+EDGE_STRIDES = (60, 260)                                             # rows that plan 16 and 64 lanes per packet
+EDGE_OUTCOMES = ("header error check", "rdd > 4", ":313", "-2", "crc mismatch", "delivered")
+
+
+def edge_set(stride):
+    """-> cfgs, rows (P, stride * 7) float32, nsyms, index: packets of tests/codec_edge_inputs.py as LLRs that spell their symbols, each of
+    a random magnitude in [0.5, 2] (7.0 behind what the row holds of a packet: never read). Set H at (7, 0, 4) and (9, 7, 1), every header
+    of the lengths 0..6 over a body of 6 bytes, whole and cut to two interleaver blocks (lengths the packet cannot hold), even lengths under
+    crcc + error_check without the header bytes, odd ones under neither with them; set R at (7, 0), 4/4, 4/6 and 4/8, with a length of 200
+    beside its 2, 9 and 40 so that rows of 260 symbols are too short for some as rows of 60 are; the one-bit flips in the five header
+    codewords of set E's (7, 0) 4/8 packet, which neither H nor R holds: the only packets the header's error check drops."""
+    rng = np.random.default_rng(stride)
+    cfgs, packets, index = [], [], []
+    for sf, ppm, rdd in E.H_CONFIGS[:2]:
+        cfgs += [(sf, ppm, rdd, 1, 1, 1, 1, 0, 8), (sf, ppm, rdd, 0, 1, 0, 1, 1, 8)]
+        for n_symbols in (None, 2 * (4 + rdd)):
+            for j, s in enumerate(E.set_h(sf, ppm, rdd, 6, 6, n_symbols)):
+                packets.append((sf, ppm, s)); index.append(len(cfgs) - 2 + (j // 16) % 2)   # (16 headers per length)
+    for rdd in (0, 2, 4):
+        if rdd != 4:
+            cfgs.append((7, 0, rdd, 1, 1, 1, 1, 0, 8))
+        for length in (2, 9, 40, 200):
+            for s in E.set_r(7, 0, rdd, length)[0]:
+                packets.append((7, 0, s)); index.append(0 if rdd == 4 else len(cfgs) - 1)
+    flips, labels, _, _ = E.set_e(7, 0, 4, 1, 1)
+    for s, (kind, c, _) in zip(flips, labels):
+        if kind == "flip" and c < D.N_HDR_CODEWORDS:
+            packets.append((7, 0, s)); index.append(0)
+    rows = np.full((len(packets), stride * 7), 7.0, np.float32)
+    for row, (sf, ppm, s) in zip(rows, packets):
+        llr = S.llr_of_symbols(s[:stride], sf, ppm)
+        row[:llr.size] = (llr * rng.uniform(0.5, 2.0, llr.shape).astype(np.float32)).reshape(-1)
+    return cfgs, rows, np.array([s.size for _, _, s in packets], np.int32), np.array(index, np.int32)
+
+
+def edge_outcomes(cfgs, index, want, wrep):
+    """which packets reach which of EDGE_OUTCOMES, from the definition's results alone"""
+    _, n, d = want
+    ec = np.array([c[5] for c in cfgs])[index]
+    at_header = (d == 1) & (wrep[:, 5] == -1) & (wrep[:, 1] <= 4)       # dropped before the needs were worked out, under a valid rate field
+    by_check = at_header & (wrep[:, 4] == 1) & (ec == 1)
+    return dict(zip(EDGE_OUTCOMES, (by_check, (d == 1) & (wrep[:, 1] > 4), at_header & ~by_check, n == -2, (d == 1) & (wrep[:, 2] == -1), n > 0)))
+
+
+@pytest.mark.parametrize("stride", EDGE_STRIDES)
+def test_crafted_edge_packets_of_the_hard_decoder(gpu, ctx, stride):
+    """Both group decoders run the same header, length, row and checksum stages (lorahip_codec.hip: packetOf .. writePacket), so the packets
+    crafted to reach every branch of them in the hard decoder go through the soft one, as one table launch per row length."""
+    cfgs, rows, nsyms, index = edge_set(stride)
+    assert len(rows) <= 620
+    assert E.launch_shape(7, 0, 4, 1, 8, stride)[0] == {60: 16, 260: 64}[stride]
+    want, wrep, short = expected(cfgs, rows, nsyms, index, stride=stride)
+    for name, hit in edge_outcomes(cfgs, index, want, wrep).items():
+        assert hit.any(), (stride, name)
+    got, rep = soft_launch(gpu, ctx, cfgs, rows, nsyms, index, stride=stride)
+    assert_equal(got, rep, want, wrep, short, ("edges", stride))
 
 
 @pytest.mark.parametrize("explicit", [1, 0])
