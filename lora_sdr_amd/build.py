@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "liblorahip.so")
 SOURCES = ["lorahip_kernels.hip", "lorahip_fast.hip", "lorahip_wide.hip", "lorahip_stream_wide.hip", "lorahip_stream.hip", "lorahip_stream_lanes.hip", "lorahip_stream_pairs.hip", "lorahip_resident.hip", "lorahip_soft.hip", "lorahip_codec.hip", "lorahip_tx.hip", "lorahip_txsched.hip", "lorahip_chan.hip", "lorahip_synth.hip", "lorahip_pfb.hip", "lorahip_psb.hip", "lorahip_resamp.hip", "lorahip_api.cpp", "lorahip_codec_api.cpp", "lorahip_tables.cpp",
            "lorahip_demod.cpp", "lorahip_demod_rounds.cpp", "lorahip_demod_stream.cpp", "lorahip_demod_pipe.cpp", "lorahip_demod_resident.cpp", "lorahip_demod_ports.cpp", "lorahip_mixed.cpp", "lorahip_upload.cpp", "lorahip_rx.cpp", "lorahip_fma_fast.hip", "lorahip_fma_wide.hip"]
-HEADERS = ["lorahip_internal.h", "lorahip_own.h", "lorahip_worker.h", "lorahip_demod_state.h", "lorahip_demod_home.h", "lorahip_device.h", "lorahip_fft.h", "lorahip_fastcore.h", "lorahip_widecore.h", "lorahip_framemachine.h", "lorahip_framestep.h", "lorahip_streamkernel.h", "lorahip_residentproto.h", "lorahip_streamcfg.h", "lorahip_fine.h", "lorahip_mixer.h", "lorahip_pfbfft.h", "lorahip_pfbfft5.h", "lorahip_bank.h", "lorahip_frontend.h", os.path.join("..", "..", "include", "lorahip.h")]
+HEADERS = ["lorahip_internal.h", "lorahip_own.h", "lorahip_worker.h", "lorahip_demod_state.h", "lorahip_demod_home.h", "lorahip_device.h", "lorahip_fft.h", "lorahip_fastcore.h", "lorahip_widecore.h", "lorahip_framemachine.h", "lorahip_framestep.h", "lorahip_framewalk.h", "lorahip_streamkernel.h", "lorahip_residentproto.h", "lorahip_streamcfg.h", "lorahip_fine.h", "lorahip_mixer.h", "lorahip_pfbfft.h", "lorahip_pfbfft5.h", "lorahip_bank.h", "lorahip_frontend.h", os.path.join("..", "..", "include", "lorahip.h")]
 INCLUDED_SOURCES = {"lorahip_fma_fast.hip": ["lorahip_fast.hip"], "lorahip_fma_wide.hip": ["lorahip_wide.hip"]}
 OBJDIR = os.path.join(HERE, "build")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",

@@ -1,5 +1,5 @@
 // C ABI of liblorahip.so: context management, the batch entry points and the
-// LoRaDetector shim (include/lorahip.h). Host-side only; kernels are in lorahip_kernels.hip.
+// LoRaDetector shim (include/lorahip.h). Host-side only; the detect kernels are in lorahip_kernels.hip and lorahip_fast / _wide.hip, the transmit kernels in lorahip_tx.hip.
 #include "lorahip_own.h"
 #include <cmath>
 #include <cstdlib>

@@ -1,19 +1,17 @@
 // Transmit side, scheduled frames: the modulator that takes SF, channel row and start sample PER FRAME and writes each frame's body into
 // (nRows, rowLen) channel rows (lorahip_mod_frames_sched) -- the load generator in front of a synthesiser, a downlink scheduler.
 //
-// The frame is the one modFrames (lorahip_kernels.hip) and modFramesVar (lorahip_tx.hip) walk: the reference's float frequency / phase
-// recurrence statement by statement (LoRaMod.cpp:135-229 on ChirpGenerator.hpp:22-47), one accumulator from 0 through 10 up-chirps, the two
-// sync chirps, 2 1/4 down-chirps and the data chirps, reduced mod 2 pi in double at the end of every chirp. Only that recurrence is serial --
-// three float operations a sample. The sincos of the phase in double, which is nearly all of the work, is independent per sample. So a GROUP
-// of L = 4 / 16 / 64 lanes of a wavefront owns a frame: lane 0 walks a tile of LORAHIP_SCHED_TILE samples and leaves their float32 phases in the
-// group's LDS slice, then the L lanes take the samples of the tile L apart -- consecutive lanes consecutive samples, so the stores coalesce
-// at any start -- evaluate, scale and store. Groups never span a wavefront: wave-level fences order the LDS traffic, as in modFramesVar.
+// The frame is the one modFrames (lorahip_tx.hip) walks, by the same walker (lorahip_framewalk.h): the reference's float frequency / phase
+// recurrence, one accumulator from 0 through 10 up-chirps, the two sync chirps, 2 1/4 down-chirps and the data chirps, reduced mod 2 pi in
+// double at the end of every chirp. Only that recurrence is serial -- three float operations a sample. The sincos of the phase in double,
+// which is nearly all of the work, is independent per sample. So a GROUP of L = 4 / 16 / 64 lanes of a wavefront owns a frame: lane 0
+// walks a tile of LORAHIP_SCHED_TILE samples and leaves their float32 phases in the group's LDS slice, then the L lanes take the samples of
+// the tile L apart -- consecutive lanes consecutive samples, so the stores coalesce at any start -- evaluate, scale and store. Groups never span a wavefront: wave-level fences order the LDS traffic, as in modFrames.
 // L = 64 is one frame per wavefront and no divergence between frames of different SF; with L = 4 / 16 the groups of a wavefront are frames
-// taken in the order given, and the wavefront runs as long as its longest frame.
-//
-// The walk is a THIRD COPY of modFrames' on purpose (lorahip_kernels.hip is stamped into the committed counter measurements, build.py:
-// kernel_digest): tests/test_gpu_mod_sched.py requires every body bit-identical to lorahip_mod_frames' frame for the same symbols.
+// taken in the order given, and the wavefront runs as long as its longest frame. tests/test_gpu_mod_sched.py requires every body
+// bit-identical to lorahip_mod_frames' frame for the same symbols.
 #include "lorahip_internal.h"
+#include "lorahip_framewalk.h"
 
 namespace lorahip {
 
@@ -51,13 +49,10 @@ __global__ void __launch_bounds__(256) modFramesSched(const ModSchedArgs a)
     const unsigned short *mySyms = a.syms + (size_t)fc * a.symStride;
     const float ampl = a.amplOf != nullptr ? a.amplOf[fc] : a.ampl;
     float2 *out = a.iq + (body ? (size_t)row * a.rowStride + start : 0);
-    const float fMin = (float)(-M_PI), fMax = (float)M_PI;                 // ovs = 1   ChirpGenerator.hpp:25-26
-    const float fStep = (float)((2 * M_PI) / N);                           //           :27
-    float phaseAccum = 0.0f;                                               // LoRaMod.cpp:135
-    // the walker's place in the frame: chirp c (LoRaMod.cpp:141-229), sample i of its NN
-    int c = 0, i = 0, NN = N;
-    bool down = false;
-    float f = fMin + 0.0f;                                                 // ChirpGenerator.hpp:28
+    FrameWalk w(N);
+    // the walker's place in the frame: chirp c, sample i of its w.NN. The body ends with the last symbol: no zero chirp is walked
+    int c = 0, i = 0;
+    w.chirp(0, a.sync, mySyms, nsyms);
     for (long long base = 0; base < body; base += T)
     {
         const int n = body - base < T ? int(body - base) : T;
@@ -68,42 +63,24 @@ __global__ void __launch_bounds__(256) modFramesSched(const ModSchedArgs a)
             {
                 // the rest of the tile or of the chirp. A multiple of 16: chirps are N or N / 4 >= 16 samples, so the body, the tiles
                 // (of 64) and every chirp boundary inside a tile are -- the walk is unrolled over 16 samples without a remainder
-                const int m = n - j < NN - i ? n - j : NN - i;
+                const int m = n - j < w.NN - i ? n - j : w.NN - i;
                 for (int k = 0; k < m; k += 16)
                 {
 #pragma unroll
-                    for (int u = 0; u < 16; u++)
-                    {
-                        f += fStep;                                        // :31 / :39
-                        if (f > fMax) f -= (fMax - fMin);
-                        phaseAccum = down ? phaseAccum - f : phaseAccum + f;
-                        sP[j + k + u] = phaseAccum;
-                    }
+                    for (int u = 0; u < 16; u++) sP[j + k + u] = w.next();
                 }
                 j += m; i += m;
-                if (i == NN)
+                if (i == w.NN)
                 {
-                    phaseAccum = (float)((double)phaseAccum - floor((double)phaseAccum / (2 * M_PI)) * 2 * M_PI);   // :45
-                    c++; i = 0; NN = N; down = false;
-                    float f0 = 0.0f;
-                    if (c < 10) {}
-                    else if (c == 10) f0 = (float)((2 * M_PI * ((a.sync >> 4) * 8)) / N);
-                    else if (c == 11) f0 = (float)((2 * M_PI * ((a.sync & 0xf) * 8)) / N);
-                    else if (c < 14) down = true;
-                    else if (c == 14) { down = true; NN = N / 4; }
-                    else if (c < 15 + nsyms) f0 = (float)((2 * M_PI * (int)mySyms[c - 15]) / N);   // (behind the last chirp: nothing is read)
-                    f = fMin + f0;                                         // :28
+                    w.endChirp();
+                    w.chirp(++c, a.sync, mySyms, nsyms);                   // (behind the last chirp: nothing is read)
+                    i = 0;
                 }
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        for (int j = t; j < n; j += L)
-        {
-            double sn, cs;
-            sincos((double)sP[j], &sn, &cs);
-            out[base + j] = make_float2(ampl * (float)cs, ampl * (float)sn);   // std::polar(ampl, phaseAccum)
-        }
+        for (int j = t; j < n; j += L) out[base + j] = polar(ampl, sP[j]);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }

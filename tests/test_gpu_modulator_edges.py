@@ -1,5 +1,5 @@
-"""GPU: the transmit waveform kernels at the edges of their definition -- modFrames (lorahip_kernels.hip), modFramesVar
-(lorahip_tx.hip) and synthSymbols (lorahip_kernels.hip) against tests/modulator_def.py.
+"""GPU: the transmit waveform kernels at the edges of their definition -- modFrames through both its entry points
+(lorahip_mod_frames, lorahip_mod_frames_var) and synthSymbols, all in lorahip_tx.hip -- against tests/modulator_def.py.
 
 The comparison is with what the kernels COMPUTE, the reference's float32 recurrence with cos / sin taken in double and rounded once
 (the definition), not with the reference modulator's own cosf / sinf: tests/test_modulator_cpu.py holds the definition to the

@@ -1,4 +1,4 @@
-"""GPU: the synthetic-input noise (addAwgn and the noise term of synthSymbols, lora_sdr_amd/csrc/lorahip_kernels.hip) is noise.
+"""GPU: the synthetic-input noise (addAwgn and the noise term of synthSymbols, lora_sdr_amd/csrc/lorahip_tx.hip) is noise.
 
 Every symbol-error figure of the project (BASELINE config 5, the loopback test, the channeliser chain tests) is drawn from this
 generator, and nothing bit-exact exists to hold it to. So it is held to closed-form statistics of independent N(0, sigma^2)
@@ -114,7 +114,7 @@ def splitmix64(x):
 
 
 def host_noise(n, seed, first=0):
-    """the generator as lorahip_kernels.hip states it: sample e = Box-Muller in double of the two 32-bit halves of
+    """the generator as lorahip_tx.hip (noiseSample) states it: sample e = Box-Muller in double of the two 32-bit halves of
     splitmix64(seed ^ (e * 0xD1342543DE82EF95 + 0x632BE59BD9B4E019)), rounded to fp32"""
     e = np.arange(first, first + n, dtype=np.uint64)
     with np.errstate(over="ignore"):

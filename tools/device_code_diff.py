@@ -4,7 +4,8 @@ AGPRs, SGPRs, scratch and static LDS bytes on both sides, and whether the code a
 e.g. python tools/device_code_diff.py ../parent . lorahip_wide lorahip_fma_wide lorahip_stream_wide=lorahip_wide
 Each unit is compiled in <tree>/lora_sdr_amd/csrc with the library's flags (build.FLAGS) plus --cuda-device-only -S. A function is the
 text from its `_Z...:` label to `.Lfunc_end<n>:`, comments (`;` to the end of the line) and empty lines dropped, every mangled name
-inside a body replaced by one token; the `.amdhsa_kernel ... .end_amdhsa_kernel` block is taken out of the body and compared by
+inside a body replaced by one token and the function's ordinal taken out of its block labels (`.LBB<ordinal>_<block>`: it changes
+when another function enters or leaves the unit); the `.amdhsa_kernel ... .end_amdhsa_kernel` block is taken out of the body and compared by
 itself; the register, scratch and LDS figures are the compiler's `; Kernel info:` comments after the function. "instr" counts the
 lines of a body that are neither directives nor labels. Functions are matched by mangled name (a function that only one side has is
 listed as such: expected where a unit of the new tree holds part of a parent's). Two texts are compared, nothing else: the script
@@ -16,6 +17,7 @@ sys.path.insert(0, ROOT)
 from lora_sdr_amd.build import FLAGS
 
 MANGLED = re.compile(r"_Z[A-Za-z0-9_.$]+")
+LOCAL = re.compile(r"\.LBB\d+_")                            # a block label carries the function's ordinal in its unit: not code
 INFO = {"vgpr": r"; NumVgprs: (\d+)", "agpr": r"; NumAgprs: (\d+)", "sgpr": r"; TotalNumSgprs: (\d+)", "scratch": r"; ScratchSize: (\d+)", "lds": r"; LDSByteSize: (\d+)"}
 
 
@@ -44,7 +46,7 @@ def functions(path):
             continue
         if not line.strip():
             continue
-        line = MANGLED.sub("<sym>", line)
+        line = LOCAL.sub(".LBB_", MANGLED.sub("<sym>", line))
         if line.strip().startswith(".amdhsa_kernel"):
             in_desc = True
         (desc if in_desc else body).append(line)
