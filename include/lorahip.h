@@ -770,6 +770,11 @@ int lorahip_decode_max_data_length(void);
  *       g(k) = binaryToGray16(uint16((k + ((1 << (sf-ppm)) / 2)) >> (sf-ppm))) & ((1 << ppm) - 1)      (LoRaDecoder.cpp:218-222)
  *       llr[p][s][m] = max{P[k] : bit m of g(k) = 1} - max{P[k] : bit m of g(k) = 0},   m = 0..ppm-1
  * -- the max-log metric on |X|^2, positive = bit 1; one float subtraction of two exact maxima, so independent of any reduction order.
+ * NON-FINITE BINS. Each of the two maxima starts at 0 and a bin enters it only through P[k] > max. A NaN P[k] (a NaN bin, or an
+ * infinite one beside a NaN) therefore never enters; a side no bin was admitted to is +0.0, and a window with no admitted bin on either
+ * side (all bins zero, all P[k] underflowed to zero, or all NaN) has the LLR +0.0. P[k] = +Inf does enter, so an LLR can be +Inf, -Inf or
+ * NaN (Inf - Inf; the NaN's bit pattern is unspecified). sym is found the same way, as lorahip_detect_batch finds it: the first k in
+ * ascending order whose P[k] exceeds every earlier one, from 0 -- and 0 when no bin is admitted.
  * Row p of llr_dev is sym_stride * ppm floats, window s at s * ppm; windows s >= min(nsyms[p], sym_stride) are not evaluated and their
  * entries (and sym_dev's) are left as they were; nsyms[p] < 1: nothing is read or written for the run. ppm = 0 means sf.
  * fine_idx0 / fine_err of a packet are the demodulator's _fineTuneIndex / _finefreqError when its first DATASYMBOLS call begins (both
@@ -784,6 +789,17 @@ int lorahip_soft_symbols(lorahip_ctx *ctx, const float *iq_dev,
                          const float *fine_err_dev,         /* [n_packets] nullable -> 0 */
                          size_t n_packets, int ppm, float *llr_dev, size_t sym_stride,
                          uint16_t *sym_dev /* nullable, [n_packets][sym_stride] */);
+/* What lorahip_soft_symbols launches for n_packets runs (host only, no device work; the launch takes its grid and block from the same
+ * function). SF6-SF10: a run per lane group of a wavefront, runs_per_wavefront = 64 / lanes per window (16, 8, 4, 2, 1); four wavefronts
+ * per workgroup once ceil(n_packets / (4 * runs_per_wavefront)) reaches twice the device's compute units, one below that; workgroups =
+ * ceil(n_packets / (runs_per_wavefront * waves_per_workgroup)). SF11 / SF12: a run per workgroup, runs_per_wavefront = 0,
+ * waves_per_workgroup = 2 / 4, workgroups = n_packets. LORAHIP_E_INVALID (*plan zeroed): a null context, n_packets > 0x7fffffff; a null
+ * plan or a struct_size that is not this struct's. */
+typedef struct lorahip_soft_tiling {
+    size_t struct_size;     /* = sizeof(lorahip_soft_tiling), set by the caller */
+    int32_t runs_per_wavefront, waves_per_workgroup, workgroups, reserved;
+} lorahip_soft_tiling;
+int lorahip_soft_plan(lorahip_ctx *ctx, size_t n_packets, lorahip_soft_tiling *plan);   /* no device work */
 /* THE SOFT DECODER: lorahip_decode_packets_info with rows of LLRs in place of rows of symbols. Packet p under entry e reads symbol s, bit m,
  * at llr_dev[p * llr_stride + s * PPM_e + m] (PPM_e = the entry's ppm, or its sf), s < min(nsyms[p], sym_stride); every other symbol of
  * its blocks is all-zero LLRs, as the hard decoder's are zero symbols. sym_stride * PPM_e <= llr_stride <= 8 * 12 * sym_stride for every
@@ -795,6 +811,10 @@ int lorahip_soft_symbols(lorahip_ctx *ctx, const float *iq_dev,
  *   - Where the reference calls decodeHamming84sx / 74sx / checkParity64 / 54 or passes a 4/4 nibble through, the nibble is the x in 0..15
  *     that maximises M(x) = sum over k = 0..n-1 ascending of (bit k of enc(x) ? +L[k] : -L[k]), accumulated in float from 0.0f in that
  *     order; the smallest x wins ties; enc = the encoder's codeword at the rate that call decodes (n = 4 + rdd; the first block: n = 8).
+ *     Stated as the loop it is, which also settles LLRs that are not finite: x = 0 is the incumbent, and x = 1..15 in ascending order
+ *     replaces it only by M(x) > M(incumbent). A NaN M(x) (a NaN LLR, or +Inf and -Inf contributions meeting) therefore never wins, and a
+ *     NaN M(0) is never replaced: the nibble is 0. The hard bit is llr > 0, so a NaN LLR reads as 0 (and, negated by a whitening bit
+ *     of 1, is still NaN).
  *   - The reference's `error` flag (error_check, fec_error) is still the hard decoders' over the hard bits: the hard codeword is the hard
  *     bits of the LLRs as read, de-interleaved, XOR the whitening bits -- so drops and the report mean what they mean in the hard decoder.
  *   - Header checksum and length, the CRC and its drop, hdr, the outcomes -1 / -2 / -3 (the row rule on the caps of lorahip_decode_plan),

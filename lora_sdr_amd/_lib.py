@@ -71,6 +71,11 @@ class DecodeTiling(C.Structure):
                                                                           "packets_per_workgroup", "reserved")]
 
 
+class SoftTiling(C.Structure):
+    """struct lorahip_soft_tiling"""
+    _fields_ = [("struct_size", C.c_size_t)] + [(n, C.c_int32) for n in ("runs_per_wavefront", "waves_per_workgroup", "workgroups", "reserved")]
+
+
 class PacketRows(C.Structure):
     """struct lorahip_packet_rows"""
     _fields_ = [("struct_size", C.c_size_t), ("syms_dev", C.c_void_p), ("sym_stride", C.c_size_t), ("nsyms_dev", C.c_void_p),
@@ -211,6 +216,7 @@ SIGNATURES = {
                                                   C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lorahip_soft_symbols": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
                                       C.c_void_p]),
+    "lorahip_soft_plan": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "lorahip_decode_packets_soft": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lorahip_decode_packets_soft_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,

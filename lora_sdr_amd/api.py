@@ -280,6 +280,13 @@ class Context(_Handle):
                                              _dptr(sym)), "lorahip_soft_symbols")
         return (llr, sym) if hard else llr
 
+    def soft_plan(self, n_packets):
+        """what soft_symbols launches for n_packets runs (lorahip_soft_plan; no device work): a dict with the fields of struct
+        lorahip_soft_tiling in include/lorahip.h"""
+        t = _lib.SoftTiling(C.sizeof(_lib.SoftTiling))
+        check(self._lib.lorahip_soft_plan(self._h, int(n_packets), C.byref(t)), "lorahip_soft_plan")
+        return dict((f, int(getattr(t, f))) for f, _ in _lib.SoftTiling._fields_ if f not in ("struct_size", "reserved"))
+
     # ------------------------------------------------------------------
     def mod_frame_len(self, nsyms, padding=1):
         return int(self._lib.lorahip_mod_frame_len(self.sf, int(nsyms), int(padding)))

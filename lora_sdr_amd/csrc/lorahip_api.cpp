@@ -398,6 +398,19 @@ int lorahip_soft_symbols(lorahip_ctx *ctx, const float *iq_dev, const int64_t *f
     return LORAHIP_OK;
 }
 
+//! the grid and block lorahip_soft_symbols launches for n_packets runs (host only: the launch takes them from the same functions)
+int lorahip_soft_plan(lorahip_ctx *ctx, const size_t n_packets, lorahip_soft_tiling *plan)
+{
+    if (plan == nullptr || plan->struct_size != sizeof(lorahip_soft_tiling)) return LORAHIP_E_INVALID;
+    *plan = lorahip_soft_tiling();
+    plan->struct_size = sizeof(lorahip_soft_tiling);
+    if (ctx == nullptr || n_packets > 0x7fffffffu) return LORAHIP_E_INVALID;
+    SoftTiling tl;
+    if (!softPlan(ctx->sf, unsigned(n_packets), ctx->cuCount, tl)) return LORAHIP_E_INVALID;
+    plan->runs_per_wavefront = tl.runsPerWave; plan->waves_per_workgroup = tl.waves; plan->workgroups = int32_t(tl.blocks);
+    return LORAHIP_OK;
+}
+
 int lorahip_timer_start(lorahip_ctx *ctx)
 {
     if (ctx == nullptr) return LORAHIP_E_INVALID;

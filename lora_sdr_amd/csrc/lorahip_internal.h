@@ -79,6 +79,15 @@ struct SoftArgs
     int symStride, ppm;         // ppm: 1..sf
 };
 hipError_t launchSoftSymbols(int sf, const SoftArgs &a, const FastTables &ft, hipStream_t stream);
+//! what a soft symbol launch runs on (lorahip_soft_plan; the launches take grid and block from the same functions): runs per wavefront
+//! (0: a run per workgroup), wavefronts per workgroup, workgroups
+struct SoftTiling
+{
+    int runsPerWave, waves;
+    unsigned blocks;
+};
+//! host only; false: no kernel for this sf
+bool softPlan(int sf, unsigned nRuns, int cuCount, SoftTiling &tl);
 
 //! per-channel state of the LoRaDemod block as the streaming kernel keeps it (LoRaDemod.cpp:385-392)
 struct StreamState

@@ -200,20 +200,27 @@ softFast(const SoftArgs a, const FastTables ft)
 }
 
 template <class C>
-static hipError_t launchSoftFast(const SoftArgs &a, const FastTables &ft, hipStream_t stream)
+static SoftTiling planSoftFast(const unsigned nRuns, const int cuCount)
 {
     // four wavefronts share a workgroup's tables; fewer runs than keep two such workgroups on every CU go one wavefront per workgroup,
     // so that a short list of long runs still spreads over the device (a run is walked by ONE lane group, window after window)
+    const unsigned cus = unsigned(cuCount > 0 ? cuCount : 256);
+    const int waves = (nRuns + 4 * C::WPW - 1) / (4 * C::WPW) < 2 * cus ? 1 : 4;
+    const unsigned perBlock = unsigned(waves * C::WPW);
+    return { C::WPW, waves, (nRuns + perBlock - 1) / perBlock };
+}
+
+template <class C>
+static hipError_t launchSoftFast(const SoftArgs &a, const FastTables &ft, hipStream_t stream)
+{
     const auto smemOf = [](const int waves) { return size_t(C::TWN + C::CH_ELEMS) * sizeof(float2) + size_t((waves * C::XW + 1) & ~1) * sizeof(float2) + FineDims<C::LOG2N>::BYTES; };
     static unsigned long long attrDone = 0;
     {
         const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(softFast<C>), smemOf(4), attrDone);
         if (e != hipSuccess) return e;
     }
-    const unsigned cus = unsigned(ft.nBlocksHint > 0 ? ft.nBlocksHint : 256);
-    const int waves = (a.nRuns + 4 * C::WPW - 1) / (4 * C::WPW) < 2 * cus ? 1 : 4;
-    const unsigned perBlock = unsigned(waves * C::WPW);
-    hipLaunchKernelGGL((softFast<C>), dim3((a.nRuns + perBlock - 1) / perBlock), dim3(waves * 64), smemOf(waves), stream, a, ft);
+    const SoftTiling tl = planSoftFast<C>(a.nRuns, ft.nBlocksHint);
+    hipLaunchKernelGGL((softFast<C>), dim3(tl.blocks), dim3(tl.waves * 64), smemOf(tl.waves), stream, a, ft);
     return hipGetLastError();
 }
 
@@ -340,6 +347,13 @@ softWide(const SoftArgs a, const FastTables ft)
 }
 
 template <class C>
+static SoftTiling planSoftWide(const unsigned nRuns)
+{
+    static_assert(C::BLOCK == C::WPWIN * 64, "the workgroup is the window's wavefronts");
+    return { 0, C::WPWIN, nRuns };                        // (the grid is the run count)
+}
+
+template <class C>
 static hipError_t launchSoftWide(const SoftArgs &a, const FastTables &ft, hipStream_t stream)
 {
     const size_t smem = sizeof(typename WideSmem<C>::Stream) + FineDims<C::LOG2N>::BYTES + size_t(C::WPWIN) * 2 * C::LOG2N * sizeof(float);
@@ -348,8 +362,24 @@ static hipError_t launchSoftWide(const SoftArgs &a, const FastTables &ft, hipStr
         const hipError_t e = ensureDynamicLds(reinterpret_cast<const void *>(softWide<C>), smem, attrDone);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((softWide<C>), dim3(a.nRuns), dim3(C::BLOCK), smem, stream, a, ft);
+    const SoftTiling tl = planSoftWide<C>(a.nRuns);
+    hipLaunchKernelGGL((softWide<C>), dim3(tl.blocks), dim3(tl.waves * 64), smem, stream, a, ft);
     return hipGetLastError();
+}
+
+bool softPlan(const int sf, const unsigned nRuns, const int cuCount, SoftTiling &tl)
+{
+    switch (sf)
+    {
+    case 6: tl = planSoftFast<SoftFast6>(nRuns, cuCount); return true;
+    case 7: tl = planSoftFast<SoftFast7>(nRuns, cuCount); return true;
+    case 8: tl = planSoftFast<SoftFast8>(nRuns, cuCount); return true;
+    case 9: tl = planSoftFast<SoftFast9>(nRuns, cuCount); return true;
+    case 10: tl = planSoftFast<SoftFast10>(nRuns, cuCount); return true;
+    case 11: tl = planSoftWide<StreamWide11>(nRuns); return true;
+    case 12: tl = planSoftWide<StreamWide12>(nRuns); return true;
+    default: return false;
+    }
 }
 
 hipError_t launchSoftSymbols(const int sf, const SoftArgs &a, const FastTables &ft, hipStream_t stream)

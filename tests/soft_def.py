@@ -2,14 +2,16 @@
 lorahip_decode_packets_soft), restated in numpy on the primitives of tests/codec_def.py and tests/codec_hdr_def.py. No GPU, no library import.
 
 `llr_def`: per window, P[k] = re*re + im*im in float32; g(k) = gray(uint16((k + half) >> (sf - ppm))) & (2^ppm - 1), the decoder's own
-mapping of a bin to the bits it reads (LoRaDecoder.cpp:218-222); llr[m] = max{P[k]: bit m of g(k) = 1} - max{P[k]: bit m of g(k) = 0}.
+mapping of a bin to the bits it reads (LoRaDecoder.cpp:218-222); llr[m] = max{P[k]: bit m of g(k) = 1} - max{P[k]: bit m of g(k) = 0},
+each maximum starting at 0 and admitting a bin only by P[k] > max (class_max): a NaN P[k] never enters, +Inf does, no admitted bin is +0.0.
 
 `decode_soft_def`: codec_hdr_def.walk, statement for statement, with a symbol replaced by its PPM LLRs (hard bit: llr > 0):
     - symbols behind the row or behind nsyms are all-zero LLRs (walk: zero symbols); bits a block does not carry are 0;
     - the hard codeword is the hard bits de-interleaved, XOR the whitening bits -- walk's own `cw` -- and feeds the `error` flag only;
     - the LLRs of a codeword are de-interleaved alike, a whitening bit of 1 negates;
     - every nibble is soft_nibble(L, rate): the x in 0..15 maximising M(x) = sum over k = 0..3+rate ascending of (bit k of fec_def(x, rate) ?
-      +L[k] : -L[k]), accumulated in float32 from 0 in that order, the smallest x among equals;
+      +L[k] : -L[k]), accumulated in float32 from 0 in that order, the smallest x among equals -- as a loop: x = 0 is the incumbent and
+      x > 0 replaces it only by M(x) > M(incumbent), so a NaN M(x) never wins and a NaN M(0) is never replaced;
     - rdd = -1 reads the rate field from the soft nibble of codeword 2.
 Like walk it knows no out_len = -2."""
 import numpy as np
@@ -30,7 +32,14 @@ def gray_map(sf, ppm):
 def power_def(bins):
     b = np.asarray(bins, np.complex64)
     re, im = b.real.astype(np.float32), b.imag.astype(np.float32)
-    return (re * re + im * im).astype(np.float32)
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        return (re * re + im * im).astype(np.float32)
+
+
+def class_max(P):
+    """(W, n) -> (W,): the maximum that starts at 0 and admits a value only by `value > max` -- NaN never enters, +Inf does, and a row
+    (or a class: n = 0) without an admitted value is +0.0. fmax returns the operand that is not NaN, so from 0 it is that maximum."""
+    return np.fmax.reduce(np.asarray(P, np.float32), axis=1, initial=np.float32(0)).astype(np.float32)
 
 
 def llr_def(bins, sf, ppm):
@@ -39,9 +48,10 @@ def llr_def(bins, sf, ppm):
     P = power_def(bins).reshape(-1, 1 << sf)
     g = gray_map(sf, ppm)
     out = np.zeros((P.shape[0], ppm), np.float32)
-    for m in range(ppm):
-        one = ((g >> np.uint32(m)) & np.uint32(1)).astype(bool)
-        out[:, m] = P[:, one].max(axis=1) - P[:, ~one].max(axis=1)
+    with np.errstate(invalid="ignore"):                                                  # (Inf - Inf is a result here, not an accident)
+        for m in range(ppm):
+            one = ((g >> np.uint32(m)) & np.uint32(1)).astype(bool)
+            out[:, m] = class_max(P[:, one]) - class_max(P[:, ~one])
     return out
 
 
@@ -58,9 +68,14 @@ def soft_nibble(L, rate):
     L = np.asarray(L, np.float32)
     M = np.zeros(16, np.float32)
     code = _CODE[rate]
-    for k in range(4 + rate):
-        M = (M + np.where((code >> np.uint32(k)) & np.uint32(1), L[k], -L[k]).astype(np.float32)).astype(np.float32)
-    return int(np.argmax(M))                                                             # the first maximum: the smallest x
+    with np.errstate(invalid="ignore"):
+        for k in range(4 + rate):
+            M = (M + np.where((code >> np.uint32(k)) & np.uint32(1), L[k], -L[k]).astype(np.float32)).astype(np.float32)
+    best = 0                                                                             # x = 0 is the incumbent ...
+    for x in range(1, 16):
+        if M[x] > M[best]:                                                               # ... replaced only by a greater metric: the smallest x
+            best = x                                                                     # among equals; a NaN never wins, a NaN M(0) stays
+    return best
 
 
 def decode_soft_def(llr, cfg, nsyms=None):

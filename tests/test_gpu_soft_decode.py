@@ -355,3 +355,58 @@ def test_refusals(gpu, ctx):
     off = T.cfg_array([CFGS[0][:4] + (0,) + CFGS[0][5:]])
     assert lib.lorahip_decode_packets_soft(h, off, 1, None, None, 0, p(llr), 16 * 7, 16, p(n), 2, p(out), 48, p(ol), p(ol), None) == -1
     dec._ctx.close()
+
+
+# ---- LLRs that are not finite -----------------------------------------------------------------------------------------------------------
+NF_STRIDE = 40
+NF_CFGS = [(7, 0, 1, 1, 1, 0, 1, 0, 0), (7, 0, 4, 1, 1, 1, 1, 0, 0)]            # 4/5 and 4/8, explicit header, crcc on; error_check off / on
+NF_PLACES = (("header codeword", 2, 3), ("payload codeword", 9, 2), ("header symbol", 3, None), ("payload symbol", 10, None))
+NF_VALUES = ("nan", "+inf", "-inf", "inf of the sent sign")
+
+
+def non_finite_set():
+    """-> rows (P, NF_STRIDE * 7) float32, nsyms, index, payloads, labels: per rate one valid packet as LLRs of magnitude 0.5..2 that spell
+    its symbols, then the same packet with one LLR (symbol s, bit m) -- which lands in one codeword of the header block / of a payload
+    block -- or one whole symbol (a bit of every codeword of its block) overwritten by NaN, +Inf, -Inf, or the infinity of the sign it had"""
+    rng = np.random.default_rng(99)
+    rows, nsyms, index, payloads, labels = [], [], [], [], []
+    for i, cfg in enumerate(NF_CFGS):
+        sf, ppm, rdd = cfg[:3]
+        payload = rng.integers(0, 256, 6, dtype=np.uint8)
+        syms, _ = D.build(sf, payload, ppm, rdd, True, True)
+        assert 10 < syms.size <= NF_STRIDE
+        base = np.zeros((NF_STRIDE, sf), np.float32)
+        base[:syms.size] = S.llr_of_symbols(syms, sf, sf) * rng.uniform(0.5, 2.0, (syms.size, sf)).astype(np.float32)
+        variants = [("untouched", base)]
+        for place, s, m in NF_PLACES:
+            for value in NF_VALUES:
+                llr = base.copy()
+                at = (s, slice(None) if m is None else m)
+                llr[at] = {"nan": np.nan, "+inf": np.inf, "-inf": -np.inf}.get(value, np.float32(np.inf) * np.sign(llr[at]))
+                variants.append((place + ": " + value, llr))
+        for label, llr in variants:
+            rows.append(llr.reshape(-1)); nsyms.append(syms.size); index.append(i); payloads.append(payload); labels.append((cfg[2], label))
+    return np.stack(rows), np.array(nsyms, np.int32), np.array(index, np.int32), payloads, labels
+
+
+def test_llrs_that_are_not_finite_decode_as_the_definition(gpu, ctx):
+    """NaN and infinite LLRs (lorahip_soft_symbols gives them for windows with infinite bins): the nibble rule of include/lorahip.h --
+    x = 0 the incumbent, replaced only by a greater metric, so a NaN metric never wins and a NaN M(0) stays; the hard bit llr > 0"""
+    rows, nsyms, index, payloads, labels = non_finite_set()
+    assert not np.isfinite(rows).all()
+    want, wrep, short = expected(NF_CFGS, rows, nsyms, index, stride=NF_STRIDE)
+    out, n, d = want
+    # the set, judged by the definition alone: the untouched packets decode to their payload; at either rate a touched packet is dropped,
+    # and a touched packet still decodes. (An infinite LLR of the sign that was sent does not help: every x whose codeword agrees in
+    # that bit scores +Inf, they tie, and the smallest wins.)
+    assert not short
+    touched = np.array([label != "untouched" for _, label in labels])
+    for p in np.flatnonzero(~touched):
+        assert n[p] == 6 and d[p] == 0 and np.array_equal(out[p, :6], payloads[p]), labels[p]
+    for rdd in (1, 4):
+        assert (d[touched & np.array([r == rdd for r, _ in labels])] == 1).any(), rdd
+    assert any(n[p] == 6 and np.array_equal(out[p, :6], payloads[p]) for p in np.flatnonzero(touched))
+    got, rep = soft_launch(gpu, ctx, NF_CFGS, rows, nsyms, index, stride=NF_STRIDE)
+    assert_equal(got, rep, want, wrep, short, "not finite, device")
+    got, rep = soft_launch(gpu, ctx, NF_CFGS, rows, nsyms, index, host=True, stride=NF_STRIDE)
+    assert_equal(got, rep, want, wrep, short, "not finite, host")

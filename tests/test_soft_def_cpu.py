@@ -101,3 +101,118 @@ def test_one_codeword_pins_the_tie_and_order_rules():
     f32 = [float(_metric(L4, x, 0, np.float32)) for x in range(16)]
     assert [x for x in range(16) if f32[x] == max(f32)] == [1, 3, 9, 11]
     assert S.soft_nibble(L4, 0) == 1
+
+
+# ---- bins and LLRs that are not finite: the rule of include/lorahip.h, restated by class_max and by soft_nibble's loop ------------------
+def _serial_llr(P, sf, ppm):
+    """the rule written out as the scan it is: both maxima from 0, a bin enters only by P[k] > max"""
+    g = S.gray_map(sf, ppm)
+    out = np.zeros(ppm, np.float32)
+    for m in range(ppm):
+        hi = lo = np.float32(0)
+        for k in range(1 << sf):
+            if (int(g[k]) >> m) & 1:
+                hi = P[k] if P[k] > hi else hi
+            else:
+                lo = P[k] if P[k] > lo else lo
+        with np.errstate(invalid="ignore"):
+            out[m] = hi - lo
+    return out
+
+
+def _same(a, b):
+    """bit for bit, or NaN for NaN"""
+    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
+    return a.shape == b.shape and bool(np.all((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))))
+
+
+def test_llr_of_bins_that_are_not_finite():
+    sf, ppm = 6, 4                      # shift 2, half 2: bins 62, 63 round up to v = 16, whose masked Gray value 8 is not bin 0's
+    N = 1 << sf
+    nan, inf = np.float32(np.nan), np.float32(np.inf)
+    assert int(S.gray_map(sf, ppm)[N - 1]) == 8 and int(S.gray_map(sf, ppm)[0]) == 0
+    rows = np.zeros((7, N), np.complex64)
+    rows[0, 9] = 3 + 4j; rows[0, 40] = 2; rows[0, 11] = complex(np.nan, 0)               # a NaN bin beside finite ones: never enters
+    rows[1, 9] = 3 + 4j; rows[1, 40] = complex(np.inf, 0)                                # +Inf enters: bits of g(40) +Inf, the others -Inf
+    rows[2, 9] = complex(np.inf, 0); rows[2, 40] = complex(0, -np.inf)                   # +Inf on both sides of a bit: NaN there
+    rows[3, :] = complex(np.nan, np.nan)                                                 # all NaN: nothing admitted
+    # row 4: all zero
+    rows[5, :] = complex(np.nan, 1); rows[5, 63] = 2                                     # every bin NaN but the last
+    rows[6, 9] = complex(np.inf, np.nan); rows[6, 40] = 1e-30                            # Inf beside NaN is NaN: out; 1e-60 underflows to 0: not admitted
+    got = S.llr_def(rows, sf, ppm)
+    assert got.dtype == np.float32 and got.shape == (7, ppm)
+    P = S.power_def(rows)
+    for r in range(7):
+        assert _same(got[r], _serial_llr(P[r], sf, ppm)), (r, got[r])
+    g9, g40 = int(S.gray_map(sf, ppm)[9]), int(S.gray_map(sf, ppm)[40])
+    assert (g9, g40) == (3, 15)
+    assert got[0].tolist() == [25 - 0, 25 - 0, 4 - 25, 4 - 25]                           # as if the NaN bin were not there
+    assert got[1].tolist() == [np.inf, np.inf, np.inf, np.inf]
+    assert got[2, :2].tolist() == [np.inf, np.inf] and np.isnan(got[2, 2:]).all()        # bits 0, 1: both bins on side 1, Inf - 0; bits 2, 3: Inf - Inf
+    for r in (3, 4, 6):
+        assert np.array_equal(got[r].view(np.uint32), np.zeros(ppm, np.uint32)), (r, got[r])        # +0.0, not -0.0, not NaN
+    assert got[5].tolist() == [-4, -4, -4, 4]
+    # finite rows: the rule is the plain maximum
+    rng = np.random.default_rng(6)
+    bins = (rng.standard_normal((16, N)) + 1j * rng.standard_normal((16, N))).astype(np.complex64)
+    Pf = S.power_def(bins)
+    for m in range(ppm):
+        one = ((S.gray_map(sf, ppm) >> np.uint32(m)) & 1).astype(bool)
+        assert np.array_equal(S.llr_def(bins, sf, ppm)[:, m], Pf[:, one].max(axis=1) - Pf[:, ~one].max(axis=1))
+
+
+def _nibble_loop(L, rate):
+    """the rule of include/lorahip.h in scalar float32: x = 0 the incumbent, replaced only by M(x) > M(incumbent)"""
+    best, best_m = 0, None
+    for x in range(16):
+        with np.errstate(invalid="ignore"):
+            m = _metric(np.asarray(L, np.float32), x, rate, np.float32)
+        if x == 0 or m > best_m:
+            best, best_m = x, m
+    return best
+
+
+def test_soft_nibble_on_llrs_that_are_not_finite():
+    nan, inf = np.float32(np.nan), np.float32(np.inf)
+    code = lambda x, r: int(D.fec_def(x, r))
+    # a NaN LLR that every codeword reads: every M(x) is NaN, x = 0 stays
+    assert S.soft_nibble(np.array([1, nan, -1, 1, 1, -1, 1, 1], np.float32), 4) == 0
+    # 4/4: bit k of enc(x) is bit k of x. L = (+Inf, 1, -1, 1): M(x) = +Inf for odd x, -Inf for even x: the first odd x
+    assert [code(x, 0) & 15 for x in range(16)] == list(range(16))
+    assert S.soft_nibble(np.array([inf, 1, -1, 1, 0, 0, 0, 0], np.float32), 0) == 1
+    assert S.soft_nibble(np.array([-inf, 1, -1, 1, 0, 0, 0, 0], np.float32), 0) == 0
+    # M(0) = -Inf and a later M(x) NaN: L = (+Inf, +Inf, ...). x = 0: -Inf - Inf = -Inf; x = 1, 2: Inf - Inf = NaN (never win); x = 3: +Inf wins
+    L = np.array([inf, inf, -1, -1, 0, 0, 0, 0], np.float32)
+    with np.errstate(invalid="ignore"):
+        M = [float(_metric(L, x, 0, np.float32)) for x in range(4)]
+    assert M[0] == -np.inf and np.isnan(M[1]) and np.isnan(M[2]) and M[3] == np.inf
+    assert S.soft_nibble(L, 0) == 3
+    # the same with nothing finite to follow: M(0) = -Inf, every other M(x) NaN or -Inf -> 0 stays (argmax would answer the first NaN)
+    L = np.array([inf, -inf, nan, nan, 0, 0, 0, 0], np.float32)
+    with np.errstate(invalid="ignore"):
+        M = np.array([_metric(L, x, 0, np.float32) for x in range(16)])
+    assert np.isnan(M).all()
+    assert S.soft_nibble(L, 0) == 0
+    L = np.array([-inf, -inf, inf, 1, 0, 0, 0, 0], np.float32)       # M(0) = Inf - Inf ... : -(-Inf) - (-Inf) - Inf = NaN at x = 0: never replaced
+    with np.errstate(invalid="ignore"):
+        assert np.isnan(_metric(L, 0, 0, np.float32)) and _metric(L, 4, 0, np.float32) == np.inf
+    assert S.soft_nibble(L, 0) == 0
+    L = np.array([-inf, 2, -3, 5, 0, 0, 0, 0], np.float32)           # M(0) = +Inf - 2 + 3 - 5: every even x is +Inf, none greater: 0
+    assert S.soft_nibble(L, 0) == 0
+    L = np.array([inf, 2, -3, 5, 0, 0, 0, 0], np.float32)            # M(0) = -Inf, M(1) = +Inf
+    assert S.soft_nibble(L, 0) == 1
+    # mixed signs, every rate, random places of NaN / +Inf / -Inf: the vector form is the scalar loop
+    rng = np.random.default_rng(41)
+    seen_nan0 = seen_later = 0
+    for trial in range(400):
+        rate = trial % 5
+        L = rng.standard_normal(8).astype(np.float32) * np.float32(4)
+        for k in rng.choice(8, int(rng.integers(0, 4)), replace=False):
+            L[k] = (nan, inf, -inf)[int(rng.integers(0, 3))]
+        want = _nibble_loop(L, rate)
+        assert S.soft_nibble(L, rate) == want, (trial, L, rate)
+        with np.errstate(invalid="ignore"):
+            M = np.array([_metric(L, x, rate, np.float32) for x in range(16)])
+        seen_nan0 += int(np.isnan(M[0]))
+        seen_later += int(not np.isnan(M[0]) and int(np.argmax(M)) != want)      # a later NaN that argmax would have answered
+    assert seen_nan0 > 10 and seen_later > 10, (seen_nan0, seen_later)           # the draw holds both kinds
